@@ -59,7 +59,35 @@ def parse_args():
     ap.add_argument("--no-also", action="store_true",
                     help="skip the extra frames reported beside the headline (BVH traversal; f64 fidelity mode; BASELINE configs 2, 4, 5)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step computed to DIR/*.npy (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, frame, max_bytes: int = DUMP_MAX_BYTES) -> list[str]:
+    """--dump-outputs: what a caller of the timed path receives from its last step — the gathered (H, W, 3) frame in the
+    render's own precision (f32, or f64 with --precision f64) — as DIR/frame.npy, so that two builds can be compared value
+    for value on the same arguments.  A frame over `max_bytes` is written as a fixed sample instead: frame_sample.npy holds
+    the RGB of pixels drawn without replacement by a seed-0 generator (the same pixels for the same frame size),
+    frame_sample_pixels.npy their row-major pixel indices (float64, exact).  Returns the paths written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(frame.detach().cpu().numpy())
+    if img.nbytes <= max_bytes:
+        path = os.path.join(out_dir, "frame.npy")
+        np.save(path, img)
+        return [path]
+    px = img.reshape(-1, 3)
+    n = (max_bytes - 1024) // (3 * px.itemsize + 8)  # RGB + one float64 index per pixel; 1 KiB for the two .npy headers
+    idx = np.sort(np.random.default_rng(0).choice(len(px), size=n, replace=False))
+    paths = [os.path.join(out_dir, "frame_sample.npy"), os.path.join(out_dir, "frame_sample_pixels.npy")]
+    np.save(paths[0], px[idx])
+    np.save(paths[1], idx.astype(np.float64))
+    return paths
 
 
 def kernel_sources_sha256() -> str:
@@ -189,6 +217,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args)  # does not return (the ranks inherit this process's stdout)
     # stdout carries exactly ONE line, the JSON record: everything else this process (or a library it loads — RCCL prints
@@ -316,6 +346,10 @@ def run(args, json_fd):
     frame_hash = rdist.frame_sha256
 
     frame_sha256 = frame_hash(fg.frame) if rank == 0 else None
+    # here, before the blocks below render other frames into the same buffers
+    if args.dump_outputs and rank == 0:
+        for f in dump_outputs(args.dump_outputs, fg.frame):
+            print(f"bench.py: wrote {f}", file=sys.stderr)
 
     # N > 1: the same frame through the BVH traversal on every rank's shard (the kernel RAYZ_TRAVERSAL_AUTO gives callers; its
     # share is ~60 ms per GPU at N = 8, so the per-step host sync and the gather show here, not on the 1.1 s flat-list share).

@@ -1,5 +1,6 @@
 """The two entry points a user (and the driver) runs: `bench.py` prints one JSON line with the agreed keys, and
 the `rayz <img_w> [out.ppm]` CLI renders the reference's scene to a P3 PPM (src/rayz.zig:12-43)."""
+import hashlib
 import json
 import os
 import subprocess
@@ -13,10 +14,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_json_contract(gpu):
+def test_bench_json_contract(gpu, tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "96", "--spp", "4", "--grid", "4",
-                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5"], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, RAYZ_BENCH_MULTI_ALSO_AT_N1="1"))
+                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, RAYZ_BENCH_MULTI_ALSO_AT_N1="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and len(r.stdout.strip().splitlines()) == 1  # ONE line on stdout: library chatter goes to stderr
@@ -64,6 +65,11 @@ def test_bench_json_contract(gpu):
             assert L["timed"] >= 2 and L["kernel_ms"]["min"] <= L["kernel_ms"]["mean"] <= L["kernel_ms"]["max"], k
     hb = d["roofline"]["hbm"]
     assert hb["algorithmic_bytes"] < hb["workspace_bytes"] * 10 and hb["chunk_sums_per_pixel"] >= 1
+    # --dump-outputs: the timed path's last frame, the very values the line's frame_sha256 was taken over
+    assert sorted(os.listdir(tmp_path / "dump")) == ["frame.npy"]
+    img = np.load(tmp_path / "dump" / "frame.npy")
+    assert img.dtype == np.float32 and img.shape == (54, 96, 3)
+    assert hashlib.sha256(img.tobytes()).hexdigest() == d["frame_sha256"]
 
 
 @pytest.mark.parametrize("world", [2, 3])
