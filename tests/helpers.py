@@ -45,3 +45,13 @@ def assert_images_equal(got, want, what):
         err = np.abs(got.astype(np.float64) - want.astype(np.float64)).max()
         raise AssertionError(f"{what}: {len(bad)} of {got.size} values differ, max |d| {err:.3e}; first at "
                              f"{bad[:5].tolist()}")
+
+
+def check_counters(gst, ost):
+    """Segments are exact.  Box / primitive test counts are work done, not results: the GPU walks the same tree
+    nearer-child-first with both child boxes tested per visit and parks leaves / candidates for a later phase, the
+    oracle walks it left-then-right like the reference; the nearest hit is order-independent, the pruning is not."""
+    assert gst.segments == ost.segments
+    assert 0.3 * ost.node_tests <= gst.node_tests <= 2.0 * ost.node_tests + 64
+    # (+ up to 8 oversized hittables kept out of the GPU's tree and tested once per segment, bvh_build.hpp)
+    assert 0.3 * ost.sphere_tests <= gst.sphere_tests <= 2.0 * ost.sphere_tests + 8 * gst.segments + 64

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import assert_images_equal
+from helpers import assert_images_equal, check_counters
 from rayz_amd import capi, tracer
 
 _P = C.POINTER
@@ -130,16 +130,6 @@ def test_oracle_bvh_traversal_equals_flat_list(oracle):
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------
-def _check_counters(gst, ost):
-    """Segments are exact.  Box / primitive test counts are work done, not results: the GPU walks the same tree
-    nearer-child-first with both child boxes tested per visit and parks leaves / candidates for a later phase, the
-    oracle walks it left-then-right like the reference; the nearest hit is order-independent, the pruning is not."""
-    assert gst.segments == ost.segments
-    assert 0.3 * ost.node_tests <= gst.node_tests <= 2.0 * ost.node_tests + 64
-    # (+ up to 8 oversized hittables kept out of the GPU's tree and tested once per segment, bvh_build.hpp)
-    assert 0.3 * ost.sphere_tests <= gst.sphere_tests <= 2.0 * ost.sphere_tests + 8 * gst.segments + 64
-
-
 def _pair(gpu, oracle, t):
     scene, cam, p = t.scene_desc(), t.camera_desc(), t.params()
     got, gst = gpu.render_host(scene, cam, p)
@@ -155,7 +145,7 @@ def test_gpu_bvh_parity_random_bouncing(gpu, oracle, prec):
     t.set_gpu(render_seed=5, traversal=capi.TRAVERSAL_BVH, precision=prec)
     got, want, gst, ost = _pair(gpu, oracle, t)
     assert_images_equal(got, want, f"BVH randomBouncing precision {prec}")
-    _check_counters(gst, ost)
+    check_counters(gst, ost)
 
 
 @pytest.mark.gpu
@@ -195,7 +185,7 @@ def test_gpu_bvh_parity_10k_and_equals_flat_list(gpu, oracle):
     t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH)
     got, want, gst, ost = _pair(gpu, oracle, t)
     assert_images_equal(got, want, "BVH 10k spheres")
-    _check_counters(gst, ost)
+    check_counters(gst, ost)
     t.set_gpu(traversal=capi.TRAVERSAL_LINEAR)
     flat, fst = gpu.render_host(t.scene_desc(), t.camera_desc(), t.params())
     # the box test is conservative and the nearest hit (with its tie rule) order-independent: the SAME image.  (Until
@@ -314,7 +304,7 @@ def test_gpu_bvh_edge_cases(gpu, oracle):
         t.set_gpu(render_seed=2, traversal=capi.TRAVERSAL_BVH)
         got, want, gst, ost = _pair(gpu, oracle, t)
         assert_images_equal(got, want, f"BVH {name}")
-        _check_counters(gst, ost)
+        check_counters(gst, ost)
     # empty pool: no tree at all, background only
     t = tracer.Tracer.init(48, 40.0, 1.0, 0.0, (0, 0, 0), (0, 0.3, -1), (0, 1, 0), seed=1)
     t.samples_per_px = 2
