@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plane_runs.hpp"
+
 namespace rayz_dev {
 
 #define RAYZ_CONSTANT __attribute__((address_space(4)))
@@ -55,22 +57,35 @@ template <> struct VecOf<double> { typedef d4 type; typedef d2 pair; };
 //   mov-Y   v = (0, vy, 0)   movy: blocks of G: cx[G] cy[G] cz[G] r²[G] vy[G]
 //                            (what randomBouncing makes)
 //   mov-G   any other v      movg[2i] = {cx, cy, cz, r²}, movg[2i+1] = {vx, vy, vz, 0}
+// Inside the static and mov-Y classes, spheres that share one f32 centre height cy (randomBouncing puts its whole grid at
+// y = 0.2) are gathered into PLANE RUNS, which come first in the class's stream and slot order: blocks of G without the
+// cy field, cx[G] cz[G] r²[G] (+ vy[G]); the run's cy is held once, in the stream's head.  Per stream:
+//   [head][plane blocks of run 0, run 1, ...][two spare plane groups][loose blocks, the layout above][two spare groups]
+// The stream's head (kPlaneHeader words) holds its layout: {number of runs, plane_slots = the slots the runs cover, 0, 0},
+// then kMaxPlaneRuns PlaneRun records.  It is read with scalar loads at every scan: a run table in the kernel arguments
+// indexed by the run counter is copied to scratch, and any new argument is loaded once per kernel and held (spilled)
+// across the whole persistent loop.
 // The block layout puts the same field of two neighbouring spheres in one aligned SGPR pair, which is what a
 // v_pk_fma_f32 takes as a single scalar operand.  A "slot" numbers the records stat | movy | movg
 // in that order.  All three are f32 for both precisions (the reject test only filters); the f64
 // copies feed the narrow phase.
+using rayz_plane::kMaxPlaneRuns;
+using rayz_plane::PlaneRun;
+constexpr int kPlaneHeader = 16; // words of layout at the head of the static and mov-Y streams (64 B: blocks stay aligned)
+static_assert(4 * sizeof(uint32_t) + kMaxPlaneRuns * sizeof(PlaneRun) <= kPlaneHeader * sizeof(float), "run table fits the head");
+
 template <class R> struct DevScene {
     typedef typename VecOf<R>::type r4;
-    const float* stat;       // [4 * ns_pad + spare block]   (the scan streams are f32 for both precisions: the reject test
+    const float* stat;       // head, plane runs, loose spheres (above)   (the scan streams are f32 for both precisions: the reject test
                              //                               only filters, the narrow phase decides — DESIGN.md §4.3)
-    const float* movy;       // [5 * ny_pad + spare block]
+    const float* movy;       // head, plane runs, loose spheres
     const f4* movg;
     const d4* slot64;        // [2 * slots] the pool's own f64 values per slot: {cx, cy, cz, r²}, {vx, vy, vz, 0}
     const uint32_t* slot_pool; // [slots] pool index of each slot
     const r4* sph_pool;      // [2 * n_spheres] by POOL index: {cx, cy, cz, r²}, {vx, vy, vz, bits(material)}
     const r4* mat;           // [n_mat] {bits(kind | method << 8), bits(texture), param, 1/param}
     const r4* tex;           // [2 * n_tex] {bits(kind), bits(even), bits(odd), scale}, {r, g, b, 0}
-    uint32_t ns_pad, ny_pad, ng_pad, n_spheres;
+    uint32_t ns_pad, ny_pad, ng_pad, n_spheres; // slots of each class (plane runs and loose spheres together)
     // build-defined triangles (hittable index = n_spheres + i): {v0, bits(material)}, {e1 = v1 - v0, 0}, {e2 = v2 - v0, 0};
     // pool order, padded with degenerate records (e1 = e2 = 0: det = 0, never accepted) like the sphere streams
     const r4* tri;           // [3 * (nt_pad + kTriGroup)]
@@ -374,6 +389,9 @@ __device__ __forceinline__ void tri_accept(R filt, V<R> v0, V<R> e1, V<R> e2, V<
     }
 }
 
+// Slots the plane runs of a static / mov-Y stream cover (its head: see DevScene).
+__device__ __forceinline__ uint32_t plane_slots(const float* stream) { return ((const RAYZ_CONSTANT uint32_t*)stream)[1]; }
+
 // One scan group of a velocity class, held in SGPRs: load() issues the scalar loads, test() runs the
 // reject test of its spheres against 64 rays and sends candidates to the narrow phase.
 template <class R, int CLS> struct ScanGroup;
@@ -414,7 +432,7 @@ template <class R> struct ScanGroup<R, 0> { // static
             out[2 * q + 1] = d.y;
         }
     }
-    template <class SC> static __device__ __forceinline__ int slot0(const SC&) { return 0; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)plane_slots(sc.stat); }
 };
 template <class R> struct ScanGroup<R, 1> { // mov-Y
     typedef typename VecOf<R>::pair pr;
@@ -449,7 +467,7 @@ template <class R> struct ScanGroup<R, 1> { // mov-Y
             out[2 * q + 1] = d.y;
         }
     }
-    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)(sc.ns_pad + plane_slots(sc.movy)); }
 };
 template <class R> struct ScanGroup<R, 2> { // mov-G
     typedef typename VecOf<R>::type r4;
@@ -478,6 +496,74 @@ template <class R> struct ScanGroup<R, 2> { // mov-G
         for (int k = 0; k < G; ++k) out[k] = disc(k, b, time);
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)(sc.ns_pad + sc.ny_pad); }
+};
+
+// Plane-run blocks (static: CLS 3, mov-Y: CLS 4): every sphere of the run has the same cy, so cy·e2y + k2 is ONE value per
+// ray and run, K2, which the run loop (scan_plane_class) puts in the basis's k2 before the run.  p2 = fm(cz, e2z, fm(cx, e2x, K2)):
+// 6 packed FMAs per sphere pair instead of 7 (static), 7 instead of 8 (mov-Y).  The same three roundings as basis_p2, in
+// another order, with the same bounds on the partial sums: the pad E stays.
+template <class R> struct ScanGroup<R, 3> { // static, plane run
+    typedef typename VecOf<R>::pair pr;
+    static constexpr int G = group_size<R>(), H = G / 2;
+    pr cx[H], cz[H], r2[H];
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 3 * i);
+#pragma unroll
+        for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q];
+    }
+    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0])); }
+    __device__ __forceinline__ void opaque() {
+#pragma unroll
+        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
+    }
+    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R) const { // b.k2 = the run's K2
+        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2};
+#pragma unroll
+        for (int q = 0; q < H; ++q) {
+            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
+            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
+            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
+            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
+            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
+            out[2 * q] = d.x;
+            out[2 * q + 1] = d.y;
+        }
+    }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC&) { return 0; }
+};
+template <class R> struct ScanGroup<R, 4> { // mov-Y, plane run
+    typedef typename VecOf<R>::pair pr;
+    static constexpr int G = group_size<R>(), H = G / 2;
+    pr cx[H], cz[H], r2[H], vy[H];
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 4 * i);
+#pragma unroll
+        for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q], vy[q] = p[3 * H + q];
+    }
+    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0]), "s"(vy[0])); }
+    __device__ __forceinline__ void opaque() {
+#pragma unroll
+        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]), "+s"(vy[q]));
+    }
+    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R time) const { // b.k2 = the run's K2
+        const R t2y = time * b.e2y;
+        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2},
+            T2y{t2y, t2y};
+#pragma unroll
+        for (int q = 0; q < H; ++q) {
+            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
+            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
+            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
+            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
+            p2 = __builtin_elementwise_fma(vy[q], T2y, p2);
+            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
+            out[2 * q] = d.x;
+            out[2 * q + 1] = d.y;
+        }
+    }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
 
 // What the scan needs of one ray (one of the NR rays a lane carries).
@@ -552,18 +638,15 @@ __device__ __forceinline__ void group_collect(const DevScene<R>& sc, int first, 
 // group after next, the same for b, then ONE reject branch for the 2·G tests.  (Scalar loads return out of
 // order, so a wave can only wait for all of them — lgkmcnt(0) — hence the explicit order; the sched_barriers
 // keep hipcc from sinking the loads.  The branch costs ≈10 cycles of a wave's time: once per 8 tests, not 4.)
+// scan_blocks tests the stream's slots i0 .. i1 (relative to the class's first slot, ScanGroup::slot0).
 template <class R, int CLS, int NR>
-__device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay<R> (&ray)[NR], R tmin) {
+__device__ __forceinline__ void scan_blocks(const DevScene<R>& sc, const RAYZ_CONSTANT float* base, int i0, int i1,
+                                            ScanRay<R> (&ray)[NR], R tmin) {
     constexpr int G = ScanGroup<float, CLS>::G;
-    if (n == 0) return;
-    // the stream's base as a value of its own: read out of the kernel arguments it is one lane of a 16-register block,
-    // and a spilled block comes back whole (the f64 kernel paid 20 v_readlane per iteration for this one pointer)
-    const RAYZ_CONSTANT float* base = ScanGroup<float, CLS>::stream(sc);
-    if constexpr (sizeof(R) == 8) asm volatile("" : "+s"(base));
     ScanGroup<float, CLS> a, b;
-    a.load(base, 0);
-    b.load(base, G);
-    for (int i = 0; i < n; i += 2 * G) {
+    a.load(base, i0);
+    b.load(base, i0 + G);
+    for (int i = i0; i < i1; i += 2 * G) {
         float da[NR][G], db[NR][G];
         float m = -1.0f;
 #ifdef RAYZ_DEBUG_NOFEED // timing experiment only: never reload (wrong results); values kept opaque to the compiler
@@ -590,6 +673,48 @@ __device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay
             group_collect<R, CLS, NR>(sc, slot0 + i + G, ray, db, tmin);
         }
     }
+}
+template <class R, int CLS, int NR>
+__device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay<R> (&ray)[NR], R tmin) {
+    if (n == 0) return;
+    // the stream's base as a value of its own: read out of the kernel arguments it is one lane of a 16-register block,
+    // and a spilled block comes back whole (the f64 kernel paid 20 v_readlane per iteration for this one pointer)
+    const RAYZ_CONSTANT float* base = ScanGroup<float, CLS>::stream(sc);
+    if constexpr (sizeof(R) == 8) asm volatile("" : "+s"(base));
+    scan_blocks<R, CLS, NR>(sc, base, 0, n, ray, tmin);
+}
+// The static (CLS 0) or mov-Y (CLS 1) class: its plane runs, then its loose spheres.  Per run, K2 = fm(cy, e2y, k2) replaces
+// each ray's k2 (one FMA per ray and run), which is put back before the loose spheres.  The head is read here, every scan
+// (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
+template <class R, int CLS, int NR>
+__device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_class, ScanRay<R> (&ray)[NR], R tmin) {
+    constexpr int P = CLS == 0 ? 3 : 4, G = ScanGroup<float, CLS>::G; // words per plane sphere
+    const RAYZ_CONSTANT float* head = ScanGroup<float, CLS>::stream(sc);
+    asm volatile("" : "+s"(head));
+    const RAYZ_CONSTANT uint32_t* h = (const RAYZ_CONSTANT uint32_t*)head;
+    const int nr = (int)h[0], plane = (int)h[1];
+    if (nr != 0) {
+        const RAYZ_CONSTANT PlaneRun* runs = (const RAYZ_CONSTANT PlaneRun*)(h + 4);
+        float k2[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) k2[r] = ray[r].basis.k2;
+        for (int j = 0; j < nr; ++j) {
+            const float cy = runs[j].cy;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = fm(cy, ray[r].basis.e2y, k2[r]);
+            scan_blocks<R, CLS + 3, NR>(sc, head + kPlaneHeader, (int)runs[j].first, (int)runs[j].end, ray, tmin);
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r) ray[r].basis.k2 = k2[r];
+    }
+    if (n_class > plane) scan_blocks<R, CLS, NR>(sc, head + kPlaneHeader + P * (plane + 2 * G), 0, n_class - plane, ray, tmin);
+}
+// Every sphere class in slot order (the slot order only matters to the candidates' parking order; the acceptance rule
+// decides ties by pool index, so the hit is the same in any order).
+template <class R, int NR> __device__ __forceinline__ void scan_sphere_classes(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
+    scan_plane_class<R, 0, NR>(sc, (int)sc.ns_pad, ray, tmin);
+    scan_plane_class<R, 1, NR>(sc, (int)sc.ny_pad, ray, tmin);
+    scan_class<R, 2, NR>(sc, (int)sc.ng_pad, ray, tmin);
 }
 
 // Triangle stream of the flat list: same ping-pong scalar prefetch, groups of kTriGroup.
@@ -668,9 +793,7 @@ __device__ __forceinline__ void scan_begin(ScanRay<R>& ray, V<R> o, V<R> d, V<R>
     ray.ncand = 0u;
 }
 template <class R, int NR> __device__ __forceinline__ void scan_spheres(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
-    scan_class<R, 0, NR>(sc, (int)sc.ns_pad, ray, tmin);
-    scan_class<R, 1, NR>(sc, (int)sc.ny_pad, ray, tmin);
-    scan_class<R, 2, NR>(sc, (int)sc.ng_pad, ray, tmin);
+    scan_sphere_classes<R, NR>(sc, ray, tmin);
     narrow_flush<R, NR>(sc, ray, tmin);
     scan_triangles<R, NR>(sc, ray, tmin);
 }
@@ -1021,9 +1144,7 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
         RAYZ_FPROF(1)
 #ifdef RAYZ_FLAT_PROFILE
         fiters++;
-        scan_class<R, 0, NR>(A.sc, (int)A.sc.ns_pad, ray, A.tmin);
-        scan_class<R, 1, NR>(A.sc, (int)A.sc.ny_pad, ray, A.tmin);
-        scan_class<R, 2, NR>(A.sc, (int)A.sc.ng_pad, ray, A.tmin);
+        scan_sphere_classes<R, NR>(A.sc, ray, A.tmin);
         RAYZ_FPROF(2)
         narrow_flush<R, NR>(A.sc, ray, A.tmin);
         scan_triangles<R, NR>(A.sc, ray, A.tmin);

@@ -146,6 +146,11 @@ struct NarrowBuffers {
     uint32_t* slot_pool = nullptr;
     d4* bvh_sph64 = nullptr; // leaf order (BVH traversal only)
     uint32_t ns_pad = 0, ny_pad = 0, ng_pad = 0;
+    // slot order of the static (0) and mov-Y (1) classes: plane runs first (rayz_plane::plan_runs), then the loose spheres
+    std::vector<PlaneRun> runs[2];
+    std::vector<std::vector<uint32_t>> run_members[2]; // pool indices of each run
+    std::vector<uint32_t> loose[2];
+    uint32_t plane_slots[2] = {0, 0};
     bool ready = false, bvh_ready = false;
     void release() {
         (void)hipFree(bvh_sph64);
@@ -319,9 +324,14 @@ uint32_t stream_len(size_t n, uint32_t group) { return scan_len(n, group) + 2 * 
 int upload_narrow_body(RayzScene* s) {
     NarrowBuffers& nb = s->narrow;
     classify(s);
-    // slot numbering is shared by both precisions: pad to the larger (f32) group size
-    nb.ns_pad = scan_len(s->cls[0].size(), kStaticGroup);
-    nb.ny_pad = scan_len(s->cls[1].size(), kMovYGroup);
+    // slot numbering is shared by both precisions: pad to the larger (f32) group size.  Static and mov-Y: plane runs,
+    // each padded to whole group pairs, then the loose spheres
+    static_assert(kStaticGroup == kMovYGroup, "one run padding for both classes");
+    for (int c = 0; c < 2; ++c)
+        nb.plane_slots[c] = rayz_plane::plan_runs(s->cls[c], [&](uint32_t pool) { return (float)s->spheres[pool].center[1]; },
+                                                  kStaticGroup, nb.runs[c], nb.run_members[c], nb.loose[c]);
+    nb.ns_pad = nb.plane_slots[0] + scan_len(nb.loose[0].size(), kStaticGroup);
+    nb.ny_pad = nb.plane_slots[1] + scan_len(nb.loose[1].size(), kMovYGroup);
     nb.ng_pad = scan_len(s->cls[2].size(), kMovGGroup);
     const size_t slots = (size_t)nb.ns_pad + nb.ny_pad + nb.ng_pad;
     std::vector<d4> slot64(2 * slots, d4{0, 0, 0, 0});
@@ -332,8 +342,12 @@ int upload_narrow_body(RayzScene* s) {
         slot64[2 * slot + 1] = d4{q.velocity[0], q.velocity[1], q.velocity[2], 0.0};
         slot_pool[slot] = pool;
     };
-    for (size_t k = 0; k < s->cls[0].size(); ++k) place(k, s->cls[0][k]);
-    for (size_t k = 0; k < s->cls[1].size(); ++k) place(nb.ns_pad + k, s->cls[1][k]);
+    const size_t class0[2] = {0, nb.ns_pad};
+    for (int c = 0; c < 2; ++c) { // a run's members fill its first slots; its pads keep slot_pool 0 (never a candidate: r² = -inf)
+        for (size_t j = 0; j < nb.runs[c].size(); ++j)
+            for (size_t k = 0; k < nb.run_members[c][j].size(); ++k) place(class0[c] + nb.runs[c][j].first + k, nb.run_members[c][j][k]);
+        for (size_t k = 0; k < nb.loose[c].size(); ++k) place(class0[c] + nb.plane_slots[c] + k, nb.loose[c][k]);
+    }
     for (size_t k = 0; k < s->cls[2].size(); ++k) place((size_t)nb.ns_pad + nb.ny_pad + k, s->cls[2][k]);
     HIP_TRY(put(&nb.slot64, slot64));
     HIP_TRY(put(&nb.slot_pool, slot_pool));
@@ -358,27 +372,44 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         return r4{(R)q.center[0], (R)q.center[1], (R)q.center[2], (R)pad_radius2_scan<R>(q, b.pad_S)};
     };
     // static / mov-Y streams (f32 for both precisions): blocks of G spheres, SoA inside a block (field f of sphere k of
-    // block g at g·F·G + f·G + k), pad spheres {0, 0, 0, r² = -inf, vy = 0}
+    // block g at g·W·G + f·G + k).  After the head (kPlaneHeader words: layout and run table, rayz_device.hpp), the plane
+    // section — its runs at their slots, W = F − 1 fields (no cy: the run table holds it), two spare groups — then the
+    // loose section, W = F, two spare groups.  Pad spheres {0, (0,) 0, r² = -inf, vy = 0}.
     const float ninf32 = -std::numeric_limits<float>::infinity();
     auto rec32 = [&](uint32_t pool) { // w = the PADDED r² of the conservative filter
         const RayzSphere& q = s->spheres[pool];
         return f4{(float)q.center[0], (float)q.center[1], (float)q.center[2], pad_radius2_scan<R>(q, b.pad_S)};
     };
-    auto blocks = [&](const std::vector<uint32_t>& cls, uint32_t G, uint32_t F, uint32_t scanned) {
-        const uint32_t n = scanned + 2 * G; // the scanned slots + two spare groups
-        std::vector<float> v((size_t)n * F, 0.0f);
-        for (uint32_t k = 0; k < n; ++k) v[(size_t)(k / G) * F * G + 3 * G + k % G] = ninf32;
-        for (size_t k = 0; k < cls.size(); ++k) {
-            const RayzSphere& q = s->spheres[cls[k]];
-            const f4 c = rec32(cls[k]);
-            float* blk = v.data() + (k / G) * F * G + k % G;
-            blk[0] = c.x, blk[G] = c.y, blk[2 * G] = c.z, blk[3 * G] = c.w;
-            if (F == 5) blk[4 * G] = (float)q.velocity[1];
+    auto blocks = [&](int c, uint32_t F, uint32_t class_slots) {
+        const NarrowBuffers& nb = s->narrow;
+        const uint32_t G = group_size<float>(), P = F - 1;
+        const uint32_t n_plane = nb.plane_slots[c] + 2 * G, n_loose = class_slots - nb.plane_slots[c] + 2 * G;
+        std::vector<float> v(kPlaneHeader + (size_t)n_plane * P + (size_t)n_loose * F, 0.0f);
+        const uint32_t head[4] = {(uint32_t)nb.runs[c].size(), nb.plane_slots[c], 0u, 0u}; // the stream's head (rayz_device.hpp)
+        std::memcpy(v.data(), head, sizeof(head));
+        std::memcpy(v.data() + 4, nb.runs[c].data(), nb.runs[c].size() * sizeof(PlaneRun));
+        float* const plane = v.data() + kPlaneHeader;
+        float* const loose = plane + (size_t)n_plane * P;
+        for (uint32_t k = 0; k < n_plane; ++k) plane[(size_t)(k / G) * P * G + 2 * G + k % G] = ninf32;
+        for (uint32_t k = 0; k < n_loose; ++k) loose[(size_t)(k / G) * F * G + 3 * G + k % G] = ninf32;
+        for (size_t j = 0; j < nb.runs[c].size(); ++j)
+            for (size_t m = 0; m < nb.run_members[c][j].size(); ++m) {
+                const uint32_t pool = nb.run_members[c][j][m], k = nb.runs[c][j].first + (uint32_t)m;
+                const f4 r = rec32(pool);
+                float* blk = plane + (size_t)(k / G) * P * G + k % G;
+                blk[0] = r.x, blk[G] = r.z, blk[2 * G] = r.w;
+                if (F == 5) blk[3 * G] = (float)s->spheres[pool].velocity[1];
+            }
+        for (size_t k = 0; k < nb.loose[c].size(); ++k) {
+            const uint32_t pool = nb.loose[c][k];
+            const f4 r = rec32(pool);
+            float* blk = loose + (k / G) * F * G + k % G;
+            blk[0] = r.x, blk[G] = r.y, blk[2 * G] = r.z, blk[3 * G] = r.w;
+            if (F == 5) blk[4 * G] = (float)s->spheres[pool].velocity[1];
         }
         return v;
     };
-    const std::vector<float> stat = blocks(s->cls[0], group_size<float>(), 4, s->narrow.ns_pad),
-                             movy = blocks(s->cls[1], group_size<float>(), 5, s->narrow.ny_pad);
+    const std::vector<float> stat = blocks(0, 4, s->narrow.ns_pad), movy = blocks(1, 5, s->narrow.ny_pad);
     std::vector<f4> movg(2 * (size_t)stream_len(s->cls[2].size(), kMovGGroup), f4{0.0f, 0.0f, 0.0f, 0.0f});
     for (size_t k = 0; k < movg.size(); k += 2) movg[k] = f4{0.0f, 0.0f, 0.0f, ninf32};
     for (size_t k = 0; k < s->cls[2].size(); ++k) {
