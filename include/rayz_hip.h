@@ -262,6 +262,35 @@ int rayz_hip_render(const RayzSceneDesc* scene, const RayzCameraDesc* camera, co
 int rayz_hip_render_f64(const RayzSceneDesc* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
                         double* rgb_out, RayzRenderStats* stats_or_null);
 
+/* ---- progressive rendering: one frame in passes --------------------------------------------------------------
+ * The reference reports progress while it renders (`\rProgress: xx.xx%`, src/renderer.zig:84,98-99); these entry points
+ * render the frame of rayz_hip_render_device in passes of WHOLE chunks of its chunk schedule (rayz_hip_chunk_schedule),
+ * each pass adding its chunk sums to an accumulator in chunk order.  After the last pass the preview is the one-shot frame
+ * bit for bit, for any partition into passes; the preview after n samples is the mean of exactly the first n samples of every
+ * pixel of that frame (not a separate lower-spp render).  A pass needs chunk-sum workspace for its own chunks only.
+ * A handle keeps its scene, camera and params (copied at create), its own copy of the schedule, the device accumulator
+ * (rows_in_shard*width*4 values of the precision) and the cursor.  It uses the scene's workspace: one render in flight per
+ * scene, as everywhere; other renders on the scene may run BETWEEN steps and change nothing of the progressive result.
+ * Progressive passes leave rayz_hip_scene_sync's counters (the scene's last one-shot render) alone.  Destroy the handle
+ * before its scene. */
+typedef struct RayzProgressive RayzProgressive; /* opaque: scene + camera + params + device accumulator + chunk cursor */
+/* Validates as rayz_hip_render_device does (either precision); binds the scene to the default device if it is not bound. */
+int rayz_hip_progressive_create(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                RayzProgressive** out);
+/* One pass, asynchronous on `hip_stream` (NULL: the library's stream): the fewest whole chunks from the cursor that add at
+ * least `min_samples` samples — at least one chunk (min_samples = 0), at most the rest of the frame (UINT32_MAX).  If
+ * `d_preview_or_null` is not NULL it receives the frame so far (DEVICE memory, rows_in_shard*width*3 values, as
+ * rayz_hip_render_device writes).  The entry must match params.precision (RAYZ_ERR_BAD_ARG); stepping a finished render
+ * is RAYZ_ERR_STATE. */
+int rayz_hip_progressive_step(RayzProgressive* pr, uint32_t min_samples, float* d_preview_or_null, void* hip_stream);
+int rayz_hip_progressive_step_f64(RayzProgressive* pr, uint32_t min_samples, double* d_preview_or_null, void* hip_stream);
+/* Samples per pixel and chunks done so far, and the schedule's chunk count: host state, no wait.  `total_or_null` waits for
+ * the passes so far and sums their counters (primary_rays, segments, sphere_tests, node_tests, kernel_ms).  Any pointer may
+ * be NULL. */
+int rayz_hip_progressive_info(const RayzProgressive* pr, uint32_t* samples_done, uint32_t* chunks_done,
+                              uint32_t* n_chunks, RayzRenderStats* total_or_null);
+int rayz_hip_progressive_destroy(RayzProgressive* pr);
+
 /* ---- several GPUs behind ONE call -------------------------------------------------------------------------
  * The reference's caller makes one call, `tracer.render()` (src/rayz.zig:26, src/renderer.zig:72-101).  These
  * entry points give that one call every GPU of the node: the pool is replicated (one scene per device), image

@@ -112,6 +112,13 @@ PROTOTYPES = [
       C.POINTER(RenderStats)]),
     ("rayz_hip_tonemap_u8", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rayz_hip_kat", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]),
+    ("rayz_hip_progressive_create", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(C.c_void_p)]),
+    ("rayz_hip_progressive_step", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_progressive_step_f64", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_progressive_info", C.c_int,
+     [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(RenderStats)]),
+    ("rayz_hip_progressive_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_multi_create", C.c_int,
      [C.POINTER(C.c_int), C.c_int, C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_multi_destroy", C.c_int, [C.c_void_p]),

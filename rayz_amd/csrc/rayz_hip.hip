@@ -789,15 +789,14 @@ int scene_ctx(RayzScene* s, DeviceCtx** out) {
     return RAYZ_OK;
 }
 
-// Launches one render of `p`'s shard on the scene's device.  The caller has selected that device (DeviceScope).
-// A scene supports ONE render in flight: a second call first waits for the previous one (its workspace and
-// counters are reused).
+// The scene's device side for a render of `p` with `cam`: the buffers uploaded (their filter padded for the camera's origin
+// bound) and, when the render walks the BVH, the tree.  A scene supports ONE render in flight: a launch on another stream first
+// waits for the previous one (its workspace and counters are reused, and a re-upload frees buffers it may still read).
 template <class R>
-int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
-                R* d_out, hipStream_t stream) {
-    typedef typename VecOf<R>::type r4;
-    const bool use_bvh = p->traversal == RAYZ_TRAVERSAL_BVH ||
-                         (p->traversal == RAYZ_TRAVERSAL_AUTO && s->spheres.size() + s->triangles.size() > RAYZ_AUTO_BVH_MIN);
+int prepare_scene(RayzScene* s, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p, hipStream_t stream,
+                  bool& use_bvh) {
+    use_bvh = p->traversal == RAYZ_TRAVERSAL_BVH ||
+              (p->traversal == RAYZ_TRAVERSAL_AUTO && s->spheres.size() + s->triangles.size() > RAYZ_AUTO_BVH_MIN);
     if (s->spheres.size() + s->triangles.size() >= (1u << 27))
         return fail(RAYZ_ERR_BAD_ARG, "too many hittables for the device layout");
     if (s->last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream)); // previous render done
@@ -810,30 +809,41 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         if (s->bvh_dev.depth > (uint32_t)kBvhStackDepth)
             return fail(RAYZ_ERR_BAD_ARG, "BVH depth %u exceeds the traversal stack (%d)", s->bvh_dev.depth, kBvhStackDepth);
     }
+    return RAYZ_OK;
+}
 
+// Work items of a launch over `chunks` chunks of a shard of `shard_pixels` pixels: the queue head, its reservations and the
+// place_item arithmetic are u32.
+int check_items(uint64_t shard_pixels, uint64_t chunks) {
+    const uint64_t items = shard_pixels * chunks;
+    if (shard_pixels >= (1ull << 31) || items >= (1ull << 32) - (1ull << 26))
+        return fail(RAYZ_ERR_BAD_ARG, "too many work items (%llu): raise chunk_spp", (unsigned long long)items);
+    return RAYZ_OK;
+}
+
+// Which trace kernel a launch used (scene_sync's measurement-build reports).
+struct LaunchKind {
+    bool two_paths = false, exchange = false;
+};
+
+// One launch of the trace kernel over the chunk WINDOW [c0, c1) of `p`'s shard (prepare_scene done, the device selected):
+// queue entry k · shard_pixels + i sums the samples of chunk c0 + k of the i-th pixel into the scene's workspace, partial[k ·
+// shard_pixels + local pixel] (grown here to the window).  `d_starts` is the device copy of the WHOLE schedule `starts`;
+// p->samples_per_px stays the total, so every sample keeps its stream (pixel · spp + s): a chunk's sum does not depend on the
+// window it is traced in.  The first `reset_bytes` of `counters` are cleared first (the queue head, counters[0], at least);
+// ev0 / ev1 bracket the kernel.
+template <class R>
+int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
+                 bool use_bvh, const std::vector<uint32_t>& starts, const uint32_t* d_starts, uint32_t c0, uint32_t c1,
+                 unsigned long long* counters, size_t reset_bytes, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream,
+                 LaunchKind& kind) {
+    typedef typename VecOf<R>::type r4;
     const uint32_t rows = rayz_hip_shard_rows(p);
     const uint64_t shard_pixels64 = (uint64_t)rows * p->width;
-    std::vector<uint32_t> starts;
-    chunk_schedule(p, starts);
-    const uint32_t chunks_per_px = (uint32_t)starts.size() - 1;
+    const uint32_t chunks_per_px = c1 - c0;
     const uint64_t items64 = shard_pixels64 * chunks_per_px;
-    if (shard_pixels64 >= (1ull << 31) || items64 >= (1ull << 32) - (1ull << 26))
-        return fail(RAYZ_ERR_BAD_ARG, "too many work items (%llu): raise chunk_spp", (unsigned long long)items64);
-    s->last = RayzRenderStats{};
-    s->last.primary_rays = shard_pixels64 * p->samples_per_px;
-    s->last_bvh = use_bvh;
-    s->last_two_paths = false;
-    if (items64 == 0) {
-        s->rendered = false;
-        return RAYZ_OK;
-    }
-    if (!d_out) return fail(RAYZ_ERR_BAD_ARG, "output pointer is null");
-    s->last_stream = stream;
-    if (p->max_bounces == 0) { // bounceRay(ray, 0) is black, src/renderer.zig:104-105
-        HIP_TRY(hipMemsetAsync(d_out, 0, shard_pixels64 * 3 * sizeof(R), stream));
-        s->rendered = false;
-        return RAYZ_OK;
-    }
+    int rc = check_items(shard_pixels64, chunks_per_px);
+    if (rc != RAYZ_OK) return rc;
     const size_t need = (size_t)items64 * sizeof(r4);
     if (need > s->partial_bytes) {
         HIP_TRY(hipStreamSynchronize(stream));
@@ -842,23 +852,6 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         s->partial_bytes = 0;
         HIP_TRY(hipMalloc(&s->partial, need));
         s->partial_bytes = need;
-    }
-    if (!s->counters) HIP_TRY(hipMalloc((void**)&s->counters, 32 * sizeof(unsigned long long)));
-    if (starts != s->chunk_start_host) { // the schedule table, kept on the device until it changes
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (starts.size() > s->chunk_start_cap) {
-            (void)hipFree(s->chunk_start);
-            s->chunk_start = nullptr;
-            s->chunk_start_cap = 0;
-            HIP_TRY(hipMalloc((void**)&s->chunk_start, starts.size() * sizeof(uint32_t)));
-            s->chunk_start_cap = starts.size();
-        }
-        HIP_TRY(hipMemcpy(s->chunk_start, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        s->chunk_start_host = starts;
-    }
-    if (!s->ev0) {
-        HIP_TRY(hipEventCreate(&s->ev0));
-        HIP_TRY(hipEventCreate(&s->ev1));
     }
 
     TraceArgs<R> A{};
@@ -888,18 +881,20 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
     A.sc.bvh_top = 0u; // (bytes: set below, once the launch knows how many records its workgroup keeps in LDS)
     fill_camera<R>(cam, A.cam);
     A.partial = (r4*)s->partial;
-    A.counters = s->counters;
+    A.counters = counters;
     A.seed = p->seed;
     A.tmin = (R)p->tmin;
     A.width = p->width;
     A.height = p->height;
     A.spp = p->samples_per_px;
     A.max_bounces = p->max_bounces;
-    A.chunk_start = s->chunk_start;
+    A.chunk_start = d_starts + c0; // (chunk_bounds indexes the table with the window's own k)
     A.chunks_per_px = chunks_per_px;
     A.chunk_uniform = starts[1]; // the table's uniform prefix (chunk_bounds): chunks of starts[1] samples while the table keeps that stride
     A.chunk_n_uniform = 0;
-    while (A.chunk_n_uniform < chunks_per_px && starts[A.chunk_n_uniform + 1] == (A.chunk_n_uniform + 1) * A.chunk_uniform) A.chunk_n_uniform++;
+    // .. computed from the WINDOW's k, which is the chunk's own index only in a window that starts at chunk 0: later windows read
+    // every chunk's bounds from the table (tools/progressive_bench.py measures what that costs)
+    while (c0 == 0 && A.chunk_n_uniform < chunks_per_px && starts[A.chunk_n_uniform + 1] == (A.chunk_n_uniform + 1) * A.chunk_uniform) A.chunk_n_uniform++;
     A.tile_rows = p->tile_rows ? p->tile_rows : RAYZ_DEFAULT_TILE_ROWS;
     A.shard_index = p->shard_index;
     A.shard_count = p->shard_count ? p->shard_count : 1u;
@@ -1000,15 +995,75 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
     const uint64_t want = (items64 + (two_paths ? 2 : 1) * block - 1) / ((two_paths ? 2 : 1) * block);
     if (grid > want) grid = want;
 
-    s->last_two_paths = two_paths;
-    s->last_exchange = exchange;
-    HIP_TRY(hipMemsetAsync(s->counters, 0, 32 * sizeof(unsigned long long), stream));
-    HIP_TRY(hipEventRecord(s->ev0, stream));
+    kind.two_paths = two_paths;
+    kind.exchange = exchange;
+    HIP_TRY(hipMemsetAsync(counters, 0, reset_bytes, stream));
+    HIP_TRY(hipEventRecord(ev0, stream));
     hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), use_bvh ? bvh_lds : 0, stream, A);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s->ev1, stream));
-    hipLaunchKernelGGL(resolve_kernel<R>, dim3((A.shard_pixels + 255) / 256), dim3(256), 0, stream,
-                       (const r4*)s->partial, d_out, A.shard_pixels, chunks_per_px, A.spp);
+    HIP_TRY(hipEventRecord(ev1, stream));
+    return RAYZ_OK;
+}
+
+
+// Launches one render of `p`'s shard on the scene's device: the trace kernel over every chunk, then resolve_kernel.  The caller
+// has selected that device (DeviceScope).
+template <class R>
+int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
+                R* d_out, hipStream_t stream) {
+    typedef typename VecOf<R>::type r4;
+    bool use_bvh = false;
+    int rc = prepare_scene<R>(s, b, cam, p, stream, use_bvh);
+    if (rc != RAYZ_OK) return rc;
+
+    const uint32_t rows = rayz_hip_shard_rows(p);
+    const uint64_t shard_pixels64 = (uint64_t)rows * p->width;
+    std::vector<uint32_t> starts;
+    chunk_schedule(p, starts);
+    const uint32_t chunks_per_px = (uint32_t)starts.size() - 1;
+    const uint64_t items64 = shard_pixels64 * chunks_per_px;
+    rc = check_items(shard_pixels64, chunks_per_px);
+    if (rc != RAYZ_OK) return rc;
+    s->last = RayzRenderStats{};
+    s->last.primary_rays = shard_pixels64 * p->samples_per_px;
+    s->last_bvh = use_bvh;
+    s->last_two_paths = false;
+    if (items64 == 0) {
+        s->rendered = false;
+        return RAYZ_OK;
+    }
+    if (!d_out) return fail(RAYZ_ERR_BAD_ARG, "output pointer is null");
+    s->last_stream = stream;
+    if (p->max_bounces == 0) { // bounceRay(ray, 0) is black, src/renderer.zig:104-105
+        HIP_TRY(hipMemsetAsync(d_out, 0, shard_pixels64 * 3 * sizeof(R), stream));
+        s->rendered = false;
+        return RAYZ_OK;
+    }
+    if (!s->counters) HIP_TRY(hipMalloc((void**)&s->counters, 32 * sizeof(unsigned long long)));
+    if (starts != s->chunk_start_host) { // the schedule table, kept on the device until it changes
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (starts.size() > s->chunk_start_cap) {
+            (void)hipFree(s->chunk_start);
+            s->chunk_start = nullptr;
+            s->chunk_start_cap = 0;
+            HIP_TRY(hipMalloc((void**)&s->chunk_start, starts.size() * sizeof(uint32_t)));
+            s->chunk_start_cap = starts.size();
+        }
+        HIP_TRY(hipMemcpy(s->chunk_start, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        s->chunk_start_host = starts;
+    }
+    if (!s->ev0) {
+        HIP_TRY(hipEventCreate(&s->ev0));
+        HIP_TRY(hipEventCreate(&s->ev1));
+    }
+    LaunchKind kind;
+    rc = trace_window<R>(s, ctx, b, cam, p, use_bvh, starts, s->chunk_start, 0, chunks_per_px, s->counters,
+                         32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, kind);
+    s->last_two_paths = kind.two_paths;
+    s->last_exchange = kind.exchange;
+    if (rc != RAYZ_OK) return rc;
+    hipLaunchKernelGGL(resolve_kernel<R>, dim3((uint32_t)((shard_pixels64 + 255) / 256)), dim3(256), 0, stream,
+                       (const r4*)s->partial, d_out, (uint32_t)shard_pixels64, chunks_per_px, p->samples_per_px);
     HIP_TRY(hipGetLastError());
     s->rendered = true;
     return RAYZ_OK;
@@ -1189,6 +1244,187 @@ int render_oneshot(const RayzSceneDesc* scene, const RayzCameraDesc* cam, const 
     (void)hipFree(d_out);
     scene_free(s);
     return rc;
+}
+
+// ---- progressive rendering (rayz_hip_progressive_*): the frame in passes of whole chunks ---------------------------------
+// A pass traces a window of chunks [c0, c1) into the scene's workspace and folds the window's chunk sums into the handle's
+// accumulator in chunk order (accumulate_kernel).  The chunk sums do not depend on the window (trace_window), and the fold
+// performs resolve_kernel's additions in resolve_kernel's order, so once every chunk is covered the frame is the one-shot
+// render's, bit for bit, whatever the passes were.
+} // namespace
+
+struct RayzProgressive {
+    RayzScene* scene = nullptr;
+    int device = -1;
+    RayzCameraDesc cam{};
+    RayzRenderParams params{};
+    std::vector<uint32_t> starts;           // the chunk schedule: n_chunks + 1 entries
+    uint32_t* d_starts = nullptr;           // the handle's own device copy (the scene's table follows the scene's last render)
+    void* acc = nullptr;                    // shard_pixels running sums (r4 of the precision)
+    unsigned long long* counters = nullptr; // [0] queue head (cleared per pass), [1..3] summed over the passes
+    uint64_t shard_pixels = 0;
+    uint32_t chunks_done = 0;
+    uint64_t primary_rays = 0;
+    bool bvh = false, traced = false;
+    std::vector<hipEvent_t> pending, spare; // pairs bracketing the trace kernel of every pass not yet summed into kernel_ms
+    double kernel_ms = 0;
+    hipStream_t last_stream = nullptr;
+};
+
+namespace {
+
+int progressive_free(RayzProgressive* pr) {
+    if (!pr) return RAYZ_OK;
+    if (pr->device >= 0) {
+        DeviceScope scope(pr->device);
+        if (pr->last_stream) (void)hipStreamSynchronize(pr->last_stream);
+        (void)hipFree(pr->d_starts);
+        (void)hipFree(pr->acc);
+        (void)hipFree(pr->counters);
+        for (hipEvent_t e : pr->pending) (void)hipEventDestroy(e);
+        for (hipEvent_t e : pr->spare) (void)hipEventDestroy(e);
+    }
+    delete pr;
+    return RAYZ_OK;
+}
+
+int progressive_create(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, RayzProgressive** out) {
+    if (!out) return fail(RAYZ_ERR_BAD_ARG, "out handle pointer is null");
+    *out = nullptr;
+    if (!s) return fail(RAYZ_ERR_STATE, "scene handle is null");
+    if (!p) return fail(RAYZ_ERR_BAD_ARG, "params is null");
+    int rc = check_render_args(s, cam, p, p->precision); // (either precision: the step entry must then match it)
+    if (rc != RAYZ_OK) return rc;
+    const uint64_t shard_pixels = (uint64_t)rayz_hip_shard_rows(p) * p->width;
+    rc = check_items(shard_pixels, 1);
+    if (rc != RAYZ_OK) return rc;
+    DeviceCtx* ctx = nullptr;
+    rc = scene_ctx(s, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    std::vector<uint32_t> starts;
+    chunk_schedule(p, starts);
+    DeviceScope scope(s->device);
+    RayzProgressive* pr = new RayzProgressive();
+    pr->scene = s;
+    pr->device = s->device;
+    pr->cam = *cam;
+    pr->params = *p;
+    pr->shard_pixels = shard_pixels;
+    pr->starts.swap(starts);
+    auto bail = [&](int code) {
+        progressive_free(pr);
+        return code;
+    };
+    const size_t r4_bytes = p->precision == RAYZ_PRECISION_F64 ? sizeof(d4) : sizeof(f4);
+    hipError_t e = hipMalloc((void**)&pr->d_starts, pr->starts.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(pr->d_starts, pr->starts.data(), pr->starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&pr->acc, shard_pixels ? shard_pixels * r4_bytes : 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&pr->counters, 32 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(pr->counters, 0, 32 * sizeof(unsigned long long));
+    if (e != hipSuccess)
+        return bail(fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "progressive handle: %s", hipGetErrorString(e)));
+    *out = pr;
+    return RAYZ_OK;
+}
+
+template <class R>
+int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, void* stream_arg, uint32_t precision) {
+    typedef typename VecOf<R>::type r4;
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (pr->params.precision != precision)
+        return fail(RAYZ_ERR_BAD_ARG, "params.precision %u does not match this entry point", pr->params.precision);
+    const uint32_t n = (uint32_t)pr->starts.size() - 1, c0 = pr->chunks_done;
+    if (c0 >= n) return fail(RAYZ_ERR_STATE, "the progressive render is finished (%u of %u chunks done)", c0, n);
+    // the fewest whole chunks from the cursor that add at least min_samples samples (at least one, at most the rest)
+    const uint64_t want = (uint64_t)pr->starts[c0] + min_samples;
+    uint32_t c1 = (uint32_t)(std::lower_bound(pr->starts.begin() + c0 + 1, pr->starts.end(), want) - pr->starts.begin());
+    if (c1 > n) c1 = n;
+    RayzScene* s = pr->scene;
+    DeviceCtx* ctx = nullptr;
+    int rc = scene_ctx(s, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    DeviceScope scope(s->device);
+    const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    SceneBuffers<R>* b;
+    if constexpr (sizeof(R) == 4) b = &s->f32;
+    else b = &s->f64;
+    bool use_bvh = false;
+    rc = prepare_scene<R>(s, *b, &pr->cam, &pr->params, stream, use_bvh);
+    if (rc != RAYZ_OK) return rc;
+    rc = check_items(pr->shard_pixels, c1 - c0);
+    if (rc != RAYZ_OK) return rc;
+    if (pr->last_stream && pr->last_stream != stream) HIP_TRY(hipStreamSynchronize(pr->last_stream)); // the accumulator's last pass
+    pr->bvh = use_bvh;
+    const uint64_t samples = pr->starts[c1] - pr->starts[c0];
+    if (pr->shard_pixels && pr->params.max_bounces == 0) { // bounceRay(ray, 0) is black, src/renderer.zig:104-105
+        if (d_preview) HIP_TRY(hipMemsetAsync(d_preview, 0, pr->shard_pixels * 3 * sizeof(R), stream));
+        pr->last_stream = stream;
+    } else if (pr->shard_pixels) {
+        if (!s->counters) HIP_TRY(hipMalloc((void**)&s->counters, 32 * sizeof(unsigned long long))); // (the scene's: left alone)
+        while (pr->spare.size() < 2) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e));
+            pr->spare.push_back(e);
+        }
+        const hipEvent_t ev1 = pr->spare.back();
+        pr->spare.pop_back();
+        const hipEvent_t ev0 = pr->spare.back();
+        pr->spare.pop_back();
+        s->last_stream = stream;
+        pr->last_stream = stream;
+        LaunchKind kind;
+        rc = trace_window<R>(s, *ctx, *b, &pr->cam, &pr->params, use_bvh, pr->starts, pr->d_starts, c0, c1, pr->counters,
+                             sizeof(unsigned long long), ev0, ev1, stream, kind);
+        if (rc != RAYZ_OK) {
+            pr->spare.push_back(ev0);
+            pr->spare.push_back(ev1);
+            return rc;
+        }
+        pr->pending.push_back(ev0);
+        pr->pending.push_back(ev1);
+        hipLaunchKernelGGL(accumulate_kernel<R>, dim3((uint32_t)((pr->shard_pixels + 255) / 256)), dim3(256), 0, stream,
+                           (const r4*)s->partial, (r4*)pr->acc, d_preview, (uint32_t)pr->shard_pixels, c1 - c0,
+                           pr->starts[c1], c0 == 0 ? 1u : 0u);
+        HIP_TRY(hipGetLastError());
+        pr->traced = true;
+    }
+    pr->primary_rays += pr->shard_pixels * samples;
+    pr->chunks_done = c1;
+    return RAYZ_OK;
+}
+
+int progressive_info(const RayzProgressive* cpr, uint32_t* samples_done, uint32_t* chunks_done, uint32_t* n_chunks,
+                     RayzRenderStats* total) {
+    if (!cpr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    RayzProgressive* pr = const_cast<RayzProgressive*>(cpr); // (summing the passes' kernel times recycles their events)
+    if (samples_done) *samples_done = pr->starts[pr->chunks_done];
+    if (chunks_done) *chunks_done = pr->chunks_done;
+    if (n_chunks) *n_chunks = (uint32_t)pr->starts.size() - 1;
+    if (!total) return RAYZ_OK;
+    RayzRenderStats st{};
+    st.primary_rays = pr->primary_rays;
+    if (pr->traced) {
+        DeviceScope scope(pr->device);
+        if (pr->last_stream) HIP_TRY(hipStreamSynchronize(pr->last_stream));
+        unsigned long long c[32] = {};
+        HIP_TRY(hipMemcpy(c, pr->counters, sizeof(c), hipMemcpyDeviceToHost));
+        if (pr->bvh && c[31])
+            return fail(RAYZ_ERR_STATE, "trace_kernel_bvh refused to run: its dynamic LDS segment does not start at LDS address 0");
+        for (size_t i = 0; i + 1 < pr->pending.size(); i += 2) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, pr->pending[i], pr->pending[i + 1]));
+            pr->kernel_ms += ms;
+        }
+        pr->spare.insert(pr->spare.end(), pr->pending.begin(), pr->pending.end());
+        pr->pending.clear();
+        const RayzScene* s = pr->scene;
+        st.segments = c[1];
+        st.sphere_tests = pr->bvh ? c[3] : c[1] * (unsigned long long)(s->spheres.size() + s->triangles.size());
+        st.node_tests = pr->bvh ? c[2] : 0;
+        st.kernel_ms = pr->kernel_ms;
+    }
+    *total = st;
+    return RAYZ_OK;
 }
 
 // ---- RCCL, opened at run time ------------------------------------------------------------------------------
@@ -1874,6 +2110,29 @@ int rayz_hip_render_multi(const int* devices, int n_devices, const RayzSceneDesc
 int rayz_hip_render_multi_f64(const int* devices, int n_devices, const RayzSceneDesc* scene, const RayzCameraDesc* cam,
                               const RayzRenderParams* p, double* rgb_out, RayzRenderStats* stats) {
     return guarded([&] { return render_multi_oneshot<double>(devices, n_devices, scene, cam, p, rgb_out, stats); });
+}
+
+// src/renderer.zig:80-97 (the loop nest) in passes, with src/renderer.zig:84,98-99's progress report in reach of the caller
+int rayz_hip_progressive_create(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                RayzProgressive** out) {
+    return guarded([&] { return progressive_create(scene, camera, params, out); });
+}
+
+int rayz_hip_progressive_step(RayzProgressive* pr, uint32_t min_samples, float* d_preview, void* stream) {
+    return guarded([&] { return progressive_step<float>(pr, min_samples, d_preview, stream, RAYZ_PRECISION_F32); });
+}
+
+int rayz_hip_progressive_step_f64(RayzProgressive* pr, uint32_t min_samples, double* d_preview, void* stream) {
+    return guarded([&] { return progressive_step<double>(pr, min_samples, d_preview, stream, RAYZ_PRECISION_F64); });
+}
+
+int rayz_hip_progressive_info(const RayzProgressive* pr, uint32_t* samples_done, uint32_t* chunks_done, uint32_t* n_chunks,
+                              RayzRenderStats* total) {
+    return guarded([&] { return progressive_info(pr, samples_done, chunks_done, n_chunks, total); });
+}
+
+int rayz_hip_progressive_destroy(RayzProgressive* pr) {
+    return guarded([&] { return progressive_free(pr); });
 }
 
 } // extern "C"

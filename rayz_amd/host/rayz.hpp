@@ -8,6 +8,9 @@
 #pragma once
 
 #include "../../include/rayz_hip.h"
+#if defined(__HIP__) // the progressive render (GpuOptions::progress) needs device memory for its frame; CPU-only builds lack it
+#include <hip/hip_runtime_api.h>
+#endif
 
 #include <cmath>
 #include <cstdint>
@@ -323,6 +326,9 @@ struct GpuOptions {
     uint32_t chunk_spp = 0;
     uint32_t tile_rows = 0, shard_index = 0, shard_count = 0;
     std::vector<int> devices; // empty: the default device; else render() drives all of these (one kept RayzMulti, rayz_hip_multi_render)
+    // one device only (ignored when `devices` lists more than one): render in passes of about 1/100 of the frame (rayz_hip_progressive_*, the same
+    // image) and print the reference's progress line to stderr after each, src/renderer.zig:84,98-99
+    bool progress = false;
 };
 
 static const double ASPECT_RATIO = 16.0 / 9.0; // src/renderer.zig:16
@@ -446,6 +452,18 @@ struct Tracer {
         RayzRenderParams p = params(seed);
         p.shard_index = 0, p.shard_count = 1; // a Tracer owns a whole image
         const size_t n = img.h * img.w;
+        if (gpu.progress && gpu.devices.size() <= 1) {
+            if (gpu.precision == RAYZ_PRECISION_F32) {
+                std::vector<float> rgb(n * 3);
+                renderProgressive(sd, cd, p, rgb.data(), sizeof(float));
+                for (size_t i = 0; i < n; ++i) img.pixels[i] = V3{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]};
+            } else {
+                std::vector<double> rgb(n * 3);
+                renderProgressive(sd, cd, p, rgb.data(), sizeof(double));
+                for (size_t i = 0; i < n; ++i) img.pixels[i] = V3{rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]};
+            }
+            return (size_t)stats.primary_rays;
+        }
         int rc = RAYZ_OK;
         const bool multi = !gpu.devices.empty();
         RayzMulti* mh = nullptr;
@@ -482,6 +500,44 @@ struct Tracer {
         }
         if (rc != RAYZ_OK) throw GpuRenderFailed(rc, rayz_hip_last_error());
         return (size_t)stats.primary_rays;
+    }
+
+    // render() with gpu.progress: the same frame through a progressive handle, in passes of about 1/100 of the samples (whole
+    // chunks), each followed by the reference's `\rProgress: xx.xx%` (src/renderer.zig:84); ends with its 100.00% line (:98-99).
+    // `rgb` receives the frame (host, width*height*3 values of `elem` bytes).
+    void renderProgressive(const RayzSceneDesc& sd, const RayzCameraDesc& cd, const RayzRenderParams& p, void* rgb, size_t elem) {
+#if defined(__HIP__)
+        RayzScene* scene = nullptr;
+        RayzProgressive* pr = nullptr;
+        void* d_rgb = nullptr;
+        const size_t bytes = img.h * img.w * 3 * elem;
+        auto done = [&](int rc, const std::string& msg) {
+            if (pr) rayz_hip_progressive_destroy(pr);
+            if (scene) rayz_hip_scene_destroy(scene);
+            if (d_rgb) (void)hipFree(d_rgb);
+            if (rc != RAYZ_OK) throw GpuRenderFailed(rc, msg);
+        };
+        int rc = gpu.devices.empty() ? rayz_hip_scene_create(&sd, &scene) : rayz_hip_scene_create_on(gpu.devices[0], &sd, &scene);
+        if (rc == RAYZ_OK) rc = rayz_hip_progressive_create(scene, &cd, &p, &pr);
+        if (rc != RAYZ_OK) return done(rc, rayz_hip_last_error());
+        if (hipMalloc(&d_rgb, bytes ? bytes : 16) != hipSuccess) return done(RAYZ_ERR_OOM, "hipMalloc(frame) failed");
+        const uint32_t spp = p.samples_per_px, pass = (spp + 99) / 100;
+        uint32_t samples = 0, chunks = 0, n_chunks = 1;
+        // (every pass writes the frame so far into d_rgb: the last one leaves the frame there)
+        while (rc == RAYZ_OK && chunks < n_chunks) {
+            rc = p.precision == RAYZ_PRECISION_F64 ? rayz_hip_progressive_step_f64(pr, pass, (double*)d_rgb, nullptr)
+                                                   : rayz_hip_progressive_step(pr, pass, (float*)d_rgb, nullptr);
+            if (rc == RAYZ_OK) rc = rayz_hip_progressive_info(pr, &samples, &chunks, &n_chunks, &stats); // (waits for the pass)
+            if (rc == RAYZ_OK && chunks < n_chunks) std::fprintf(stderr, "\rProgress: %.2f%%", 100.0 * samples / spp);
+        }
+        if (rc != RAYZ_OK) return done(rc, rayz_hip_last_error());
+        std::fprintf(stderr, "\rProgress: 100.00%%\n");
+        if (hipMemcpy(rgb, d_rgb, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(RAYZ_ERR_HIP, "hipMemcpy(frame) failed");
+        done(RAYZ_OK, "");
+#else
+        (void)sd, (void)cd, (void)p, (void)rgb, (void)elem;
+        throw GpuRenderFailed(RAYZ_ERR_STATE, "GpuOptions::progress needs a HIP build of the host mirror");
+#endif
     }
 };
 

@@ -5,7 +5,10 @@
 // Extras the reference does not have (environment variables, so the positional interface stays the
 // reference's): RAYZ_SPP, RAYZ_BOUNCES, RAYZ_SEED, RAYZ_GRID (half-width of the sphere grid, 11 in the
 // reference), RAYZ_PRECISION=f32|f64, RAYZ_TRAVERSAL=linear|bvh|auto (default auto), RAYZ_DEVICES=0,1,...
-// (render on several GPUs of the node through rayz_hip_render_multi; default: device 0).
+// (render on several GPUs of the node through rayz_hip_render_multi; default: device 0), RAYZ_PROGRESS=1 (render in
+// passes of about 1/100 of the frame through rayz_hip_progressive_* and print the reference's `\rProgress: xx.xx%` to
+// stderr after each, src/renderer.zig:84,98-99; the same image and rate line.  Single device only: a RAYZ_DEVICES list
+// of more than one ordinal renders in one call, without progress).
 #include "rayz.hpp"
 
 #include <chrono>
@@ -49,6 +52,8 @@ int main(int argc, char** argv) {
             q = next + 1;
         }
     }
+
+    if ((e = std::getenv("RAYZ_PROGRESS")) && std::string(e) == "1") tracer.gpu.progress = true;
 
     if (rayz_hip_init(tracer.gpu.devices.empty() ? 0 : tracer.gpu.devices[0]) != RAYZ_OK) {
         std::fprintf(stderr, "error: GpuRenderFailed: %s\n", rayz_hip_last_error());

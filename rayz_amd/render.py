@@ -68,6 +68,10 @@ class DeviceScene:
         rc = fn(self._h, C.byref(camera), C.byref(params), C.c_void_p(out_ptr), C.c_void_p(stream))
         capi.check(self._lib, rc, "rayz_hip_render_device")
 
+    def progressive(self, camera: capi.CameraDesc, params: capi.RenderParams) -> "Progressive":
+        """The frame of `render_into(camera, params, ...)` in passes of whole chunks (`rayz_hip_progressive_create`)."""
+        return Progressive(self, camera, params)
+
     def sync(self) -> capi.RenderStats:
         st = capi.RenderStats()
         capi.check(self._lib, self._lib.rayz_hip_scene_sync(self._h, C.byref(st)), "rayz_hip_scene_sync")
@@ -76,6 +80,66 @@ class DeviceScene:
     def close(self) -> None:
         if self._h:
             self._lib.rayz_hip_scene_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Progressive:
+    """One frame rendered in passes (`rayz_hip_progressive_*`): every `step` adds whole chunks of the chunk schedule and may
+    write the frame so far; the last one writes the one-shot frame bit for bit.  Close it before its scene."""
+
+    def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams):
+        self._lib = scene._lib
+        self._scene = scene  # (kept alive: the handle renders on it)
+        self._h = C.c_void_p()
+        self.f64 = params.precision == capi.PRECISION_F64
+        capi.check(self._lib, self._lib.rayz_hip_progressive_create(scene._h, C.byref(camera), C.byref(params),
+                                                                    C.byref(self._h)), "rayz_hip_progressive_create")
+
+    def step(self, min_samples: int = 0, out_ptr: int = 0, stream: int = 0) -> None:
+        """One pass of at least `min_samples` samples per pixel (0: one chunk; 0xFFFFFFFF: the rest), asynchronous on `stream`;
+        `out_ptr` (device memory, optional) receives the frame so far."""
+        fn = self._lib.rayz_hip_progressive_step_f64 if self.f64 else self._lib.rayz_hip_progressive_step
+        capi.check(self._lib, fn(self._h, min_samples, C.c_void_p(out_ptr or None), C.c_void_p(stream or None)),
+                   "rayz_hip_progressive_step")
+
+    def _info(self, total: bool = False):
+        s, c, n = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        st = capi.RenderStats() if total else None
+        capi.check(self._lib, self._lib.rayz_hip_progressive_info(self._h, C.byref(s), C.byref(c), C.byref(n),
+                                                                  C.byref(st) if total else None),
+                   "rayz_hip_progressive_info")
+        return s.value, c.value, n.value, st
+
+    @property
+    def samples_done(self) -> int:
+        return self._info()[0]
+
+    @property
+    def chunks_done(self) -> int:
+        return self._info()[1]
+
+    @property
+    def n_chunks(self) -> int:
+        return self._info()[2]
+
+    @property
+    def done(self) -> bool:
+        _, c, n, _ = self._info()
+        return c == n
+
+    def stats(self) -> capi.RenderStats:
+        """Counters summed over the passes so far (waits for them)."""
+        return self._info(total=True)[3]
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.rayz_hip_progressive_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
