@@ -382,9 +382,15 @@ typedef enum RayzKatOp {
     RAYZ_KAT_SCAN_DISCS = 9   /* one 4-sphere block of the flat list's scan streams, as the SCAN LOOP evaluates it (packed FMAs,
                                  two spheres per instruction; the values are f32 for both precisions):
                                  in: cx[0..3] cy[4..7] cz[8..11] radius[12..15] (padded and squared by the library as the scene
-                                     upload does) vy[16..19] origin[20..22] dir[23..25] time[26] class[27] (0 static, 1 y-moving)
-                                 out: r2 - p1^2 - p2^2 per sphere [0..3] (>= 0: candidate), the same value from the
-                                      general-velocity form the BVH leaves use [4..7]     src/geom.zig:40-50, DESIGN.md 4.3 */
+                                     upload does) vy[16..19] origin[20..22] dir[23..25] time[26] class[27]: 0 static, 1 y-moving
+                                     (the loose forms, ScanGroup<float, 0 / 1>), 2 static, 3 y-moving PLANE RUN (the run forms,
+                                     ScanGroup<float, 3 / 4>: the run's height is cy[4], K2 = fm(cy, e2y, k2) as the run loop
+                                     computes it; the four cy must be one f32 value, bit for bit); any other class, or a plane-run
+                                     record whose cy differ in f32, is RAYZ_ERR_BAD_ARG; want_r2[32] (0 or 1, RAYZ_ERR_BAD_ARG
+                                     otherwise): 1 returns the padded r2 below, for any class
+                                 out: r2 - p1^2 - p2^2 per sphere [0..3] (>= 0: candidate; the plane form for classes 2 / 3), the
+                                      same value from the general-velocity form the BVH leaves use [4..7], the padded r2 (f32) the
+                                      library used [8..11] if want_r2, else 0              src/geom.zig:40-50, DESIGN.md 4.3 */
 } RayzKatOp;
 #define RAYZ_KAT_IN_STRIDE 48
 #define RAYZ_KAT_OUT_STRIDE 12

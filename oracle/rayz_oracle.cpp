@@ -1502,7 +1502,9 @@ template <class R> static void katB(uint32_t op, const double* a, double* r) {
     }
     case RAYZ_KAT_CHECKER: r[0] = (double)checkerParity<R>(v3(0), (R)a[3]); break;
     case RAYZ_KAT_SCAN_DISCS: { // the flat list's reject test on a block of 4 spheres: sphereFilter, the ONE form mode B has
+                                // (classes 2 / 3, the plane runs, are 0 / 1 here: tests/plane_filter_mirror.cpp restates the run form)
         const V<R> o = v3(20), d = v3(23);
+        const bool movy = a[27] == 1.0 || a[27] == 3.0;
         const V<R> udk = unit(d);
         const Basis<float> b = makeBasis<float>(V<float>{(float)udk.x, (float)udk.y, (float)udk.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
         const float ft = (float)(R)a[26];
@@ -1511,12 +1513,14 @@ template <class R> static void katB(uint32_t op, const double* a, double* r) {
         for (int k = 0; k < 4; ++k) {
             q[k].center[0] = a[k], q[k].center[1] = a[4 + k], q[k].center[2] = a[8 + k];
             q[k].radius = a[12 + k];
-            q[k].velocity[1] = a[27] != 0.0 ? a[16 + k] : 0.0;
+            q[k].velocity[1] = movy ? a[16 + k] : 0.0;
             S = std::max(S, norm3(q[k].center) + norm3(q[k].velocity) + std::fabs(q[k].radius));
         }
         for (int k = 0; k < 4; ++k) {
             const V<float> c{(float)a[k], (float)a[4 + k], (float)a[8 + k]}, v{0.0f, (float)q[k].velocity[1], 0.0f};
-            r[k] = r[4 + k] = (double)sphereFilter<float>(b, ft, c, v, padRadius2Scan<R>(q[k], S));
+            const float r2 = padRadius2Scan<R>(q[k], S);
+            r[k] = r[4 + k] = (double)sphereFilter<float>(b, ft, c, v, r2);
+            r[8 + k] = a[32] != 0.0 ? (double)r2 : 0.0;
         }
         break;
     }
@@ -1604,7 +1608,7 @@ static void katA(uint32_t op, const double* a, double* r) {
     case RAYZ_KAT_SCAN_DISCS: { // the reference's own discriminant (src/geom.zig:40-50) for the four spheres: sign only
         const V3 o = v3(a + 20), d = v3(a + 23);
         for (int k = 0; k < 4; ++k) {
-            const V3 c{a[k], a[4 + k] + (a[27] != 0.0 ? a[16 + k] * a[26] : 0.0), a[8 + k]};
+            const V3 c{a[k], a[4 + k] + (a[27] == 1.0 || a[27] == 3.0 ? a[16 + k] * a[26] : 0.0), a[8 + k]};
             const V3 oc = c.sub(o);
             const double aa = d.dot(d), hb = d.dot(oc), cc = oc.dot(oc) - a[12 + k] * a[12 + k];
             r[k] = r[4 + k] = hb * hb - aa * cc;
@@ -1625,11 +1629,26 @@ static void katA(uint32_t op, const double* a, double* r) {
     default: break;
     }
 }
+// The library's argument checks of a record (rayz_hip_kat): SCAN_DISCS takes class 0 - 3, want_r2 0 or 1, and a plane-run
+// class (2, 3) one f32 height for its four spheres, bit for bit.
+static bool katRecordOk(uint32_t op, const double* a) {
+    auto bits32 = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; };
+    if (op != RAYZ_KAT_SCAN_DISCS) return true;
+    const double cls = a[27];
+    if (!(cls == 0.0 || cls == 1.0 || cls == 2.0 || cls == 3.0)) return false;
+    if (!(a[32] == 0.0 || a[32] == 1.0)) return false;
+    if (cls >= 2.0)
+        for (int k = 1; k < 4; ++k)
+            if (bits32((float)a[4 + k]) != bits32((float)a[4])) return false;
+    return true;
+}
 } // namespace
 extern "C" {
 
 int rayz_oracle_kat_b(uint32_t op, uint32_t precision, const double* in, uint32_t n, double* out) {
     if (op > RAYZ_KAT_SCAN_DISCS || precision > RAYZ_PRECISION_F64 || (n && (!in || !out))) return RAYZ_ERR_BAD_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!katRecordOk(op, in + (size_t)i * RAYZ_KAT_IN_STRIDE)) return RAYZ_ERR_BAD_ARG;
     for (uint32_t i = 0; i < n; ++i) {
         double* r = out + (size_t)i * RAYZ_KAT_OUT_STRIDE;
         std::fill(r, r + RAYZ_KAT_OUT_STRIDE, 0.0);
@@ -1640,6 +1659,8 @@ int rayz_oracle_kat_b(uint32_t op, uint32_t precision, const double* in, uint32_
 }
 int rayz_oracle_kat_a(uint32_t op, const double* in, uint32_t n, double* out) {
     if (op > RAYZ_KAT_SCAN_DISCS || (n && (!in || !out))) return RAYZ_ERR_BAD_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!katRecordOk(op, in + (size_t)i * RAYZ_KAT_IN_STRIDE)) return RAYZ_ERR_BAD_ARG;
     for (uint32_t i = 0; i < n; ++i) {
         double* r = out + (size_t)i * RAYZ_KAT_OUT_STRIDE;
         std::fill(r, r + RAYZ_KAT_OUT_STRIDE, 0.0);

@@ -683,6 +683,8 @@ __device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay
     if constexpr (sizeof(R) == 8) asm volatile("" : "+s"(base));
     scan_blocks<R, CLS, NR>(sc, base, 0, n, ray, tmin);
 }
+// A plane run's K2 for one ray: cy·e2y + k2 in ONE rounding (the run loop below and RAYZ_KAT_SCAN_DISCS classes 2 / 3).
+__device__ __forceinline__ float plane_run_k2(float cy, float e2y, float k2) { return fm(cy, e2y, k2); }
 // The static (CLS 0) or mov-Y (CLS 1) class: its plane runs, then its loose spheres.  Per run, K2 = fm(cy, e2y, k2) replaces
 // each ray's k2 (one FMA per ray and run), which is put back before the loose spheres.  The head is read here, every scan
 // (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
@@ -701,7 +703,7 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
         for (int j = 0; j < nr; ++j) {
             const float cy = runs[j].cy;
 #pragma unroll
-            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = fm(cy, ray[r].basis.e2y, k2[r]);
+            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = plane_run_k2(cy, ray[r].basis.e2y, k2[r]);
             scan_blocks<R, CLS + 3, NR>(sc, head + kPlaneHeader, (int)runs[j].first, (int)runs[j].end, ray, tmin);
         }
 #pragma unroll
@@ -2786,22 +2788,25 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
         break;
     }
     case 9: { // SCAN_DISCS: one block of the flat list's scan, THROUGH the packed-FMA form the scan loop runs
-              // (ScanGroup<float, cls>::discs: two spheres per v_pk_fma_f32), plus the general-velocity form of the BVH
+              // (ScanGroup<float, CLS>::discs: two spheres per v_pk_fma_f32), plus the general-velocity form of the BVH
               // leaves on the same spheres: cx[4] cy[4] cz[4] radius[4] vy[4] o(3) d(3) time cls (+ padded r²[4] at 28, from the
-              // host) -> disc[4] leaf_disc[4]
+              // host) want_r2 -> disc[4] leaf_disc[4] r²[4] (if want_r2, else 0).  cls (checked by the host): 0 static, 1 mov-Y (the loose forms), 2 static,
+              // 3 mov-Y plane run (the run forms, cy[4] the run's height, K2 put in the basis as scan_plane_class does)
         const V<R> o = v3(20), d = v3(23);
         const V<R> ud = unit(d);
         const RayBasis<float> b = make_basis<float>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
         const float ft = (float)(R)a[26];
+        const int cls = (int)a[27];
+        const bool movy = cls == 1 || cls == 3;
         float out4[4];
-        if (a[27] == 0.0) {
+        if (cls == 0) {
             ScanGroup<float, 0> g;
             for (int q = 0; q < 2; ++q) {
                 g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cy[q] = f2{(float)a[4 + 2 * q], (float)a[5 + 2 * q]};
                 g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]}, g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
             }
             g.discs(out4, b, ft);
-        } else {
+        } else if (cls == 1) {
             ScanGroup<float, 1> g;
             for (int q = 0; q < 2; ++q) {
                 g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cy[q] = f2{(float)a[4 + 2 * q], (float)a[5 + 2 * q]};
@@ -2809,13 +2814,32 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
                 g.vy[q] = f2{(float)a[16 + 2 * q], (float)a[17 + 2 * q]};
             }
             g.discs(out4, b, ft);
+        } else {
+            RayBasis<float> bk = b;
+            bk.k2 = plane_run_k2((float)a[4], b.e2y, b.k2);
+            if (cls == 2) {
+                ScanGroup<float, 3> g;
+                for (int q = 0; q < 2; ++q) {
+                    g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
+                    g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
+                }
+                g.discs(out4, bk, ft);
+            } else {
+                ScanGroup<float, 4> g;
+                for (int q = 0; q < 2; ++q) {
+                    g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
+                    g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]}, g.vy[q] = f2{(float)a[16 + 2 * q], (float)a[17 + 2 * q]};
+                }
+                g.discs(out4, bk, ft);
+            }
         }
         for (int k = 0; k < 4; ++k) {
             r[k] = (double)out4[k];
-            const float vy = a[27] == 0.0 ? 0.0f : (float)a[16 + k];
+            const float vy = movy ? (float)a[16 + k] : 0.0f;
             const float p1 = fm(0.0f, ft * b.e1z, fm(0.0f, ft * b.e1x, basis_p1<float>(b, (float)a[k], (float)a[8 + k])));
             const float p2 = fm(0.0f, ft * b.e2z, fm(vy, ft * b.e2y, fm(0.0f, ft * b.e2x, basis_p2<float>(b, (float)a[k], (float)a[4 + k], (float)a[8 + k]))));
             r[4 + k] = (double)basis_disc<float>(p1, p2, (float)a[28 + k]);
+            r[8 + k] = a[32] != 0.0 ? (double)(float)a[28 + k] : 0.0;
         }
         break;
     }

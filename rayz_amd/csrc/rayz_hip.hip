@@ -1946,12 +1946,23 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
                 }
             }
             if (op == RAYZ_KAT_SCAN_DISCS) { // the padded squares the scan streams would hold for these four spheres
+                const double cls = a[27];
+                if (!(cls == 0.0 || cls == 1.0 || cls == 2.0 || cls == 3.0))
+                    return fail(RAYZ_ERR_BAD_ARG, "record %u: class = %g is not 0, 1, 2 or 3", i, cls);
+                if (!(a[32] == 0.0 || a[32] == 1.0)) return fail(RAYZ_ERR_BAD_ARG, "record %u: want_r2 = %g is not 0 or 1", i, a[32]);
+                if (cls >= 2.0) { // a plane run: one f32 height, bit for bit (+0 and -0 are two runs), as plan_runs groups them
+                    const uint32_t h = rayz_plane::bits32((float)a[4]);
+                    for (int k = 1; k < 4; ++k)
+                        if (rayz_plane::bits32((float)a[4 + k]) != h)
+                            return fail(RAYZ_ERR_BAD_ARG, "record %u: plane-run class %g with cy[%d] = %.9g != cy[0] = %.9g in f32", i, cls, k,
+                                        (double)(float)a[4 + k], (double)(float)a[4]);
+                }
                 double S = norm3(a + 20);
                 RayzSphere q[4] = {};
                 for (int k = 0; k < 4; ++k) {
                     q[k].center[0] = a[k], q[k].center[1] = a[4 + k], q[k].center[2] = a[8 + k];
                     q[k].radius = a[12 + k];
-                    q[k].velocity[1] = a[27] != 0.0 ? a[16 + k] : 0.0;
+                    q[k].velocity[1] = cls == 1.0 || cls == 3.0 ? a[16 + k] : 0.0;
                     S = std::max(S, norm3(q[k].center) + norm3(q[k].velocity) + std::fabs(q[k].radius));
                 }
                 for (int k = 0; k < 4; ++k)

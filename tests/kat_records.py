@@ -217,3 +217,51 @@ def random_scan_blocks(rng, n):
     rec[:, 0:4], rec[:, 4:8], rec[:, 8:12], rec[:, 12:16], rec[:, 16:20] = f32r(cx), f32r(cy), f32r(cz), f32r(r), f32r(vy)
     rec[:, 20:23], rec[:, 23:26], rec[:, 26], rec[:, 27] = f32r(o), f32r(d), uniforms(rng, n), cls
     return rec
+
+
+def random_plane_blocks(rng, n):
+    """Blocks of four spheres of ONE plane run (RAYZ_KAT_SCAN_DISCS classes 2 and 3): as random_scan_blocks, but the four share
+    one f32 height, drawn from the heights where the run form can go wrong: small positive ones (randomBouncing's grid),
+    negative ones, +0.0 and -0.0, and ~3e4 with the ray origins near it.  A quarter of the rays graze the plane
+    (|d.y| < 1e-3 |d|), a quarter start AT the run's height and look horizontally (d.y = 0); the rest are aimed near
+    one sphere of the block.  Half the blocks are y-moving (class 3).  Every record asks for the padded r² (want_r2 = 1)."""
+    rec = blank(n)
+    kind = rng.integers(0, 6, n)
+    cy = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4],
+                   [rng.uniform(0.15, 1.0, n), -rng.uniform(0.1, 20.0, n), np.zeros(n), np.full(n, -0.0),
+                    3.0e4 + rng.uniform(-50, 50, n)], rng.uniform(-3.0, 3.0, n))
+    cy = f32r(cy)
+    cx, cz = rng.uniform(-50, 50, (n, 4)), rng.uniform(-50, 50, (n, 4))
+    r = rng.uniform(0.15, 1.0, (n, 4))
+    cls = np.where(rng.random(n) < 0.5, 2.0, 3.0)
+    vy = rng.uniform(-0.5, 0.5, (n, 4)) * (cls == 3.0)[:, None]
+    time = uniforms(rng, n)
+    o = np.stack([rng.uniform(-20, 20, n), cy + rng.uniform(-6, 6, n), rng.uniform(-20, 20, n)], 1)
+    k = rng.integers(0, 4, n)
+    at = np.arange(n)
+    tgt = np.stack([cx[at, k], cy + vy[at, k] * time, cz[at, k]], 1)
+    aim = tgt + unit(rng.normal(size=(n, 3))) * (r[at, k] * rng.uniform(0, 3.0, n))[:, None]
+    d = (aim - o) * rng.uniform(0.2, 3.0, (n, 1))
+    ray = rng.integers(0, 4, n)
+    graze = ray == 1
+    d[graze, 1] = rng.choice([-1.0, 1.0], graze.sum()) * rng.uniform(0, 1e-3, graze.sum()) * np.linalg.norm(d[graze], axis=1)
+    level = ray == 2
+    o[level, 1] = cy[level]
+    d[level, 1] = 0.0
+    rec[:, 0:4], rec[:, 4:8], rec[:, 8:12], rec[:, 12:16], rec[:, 16:20] = f32r(cx), f32r(cy)[:, None], f32r(cz), f32r(r), f32r(vy)
+    rec[:, 20:23], rec[:, 23:26], rec[:, 26], rec[:, 27] = f32r(o), f32r(d), time, cls
+    rec[:, 32] = 1.0
+    return rec
+
+
+def scan_pad_r2(rec, precision):
+    """The padded r² the library puts in a SCAN_DISCS record (rayz_hip.hip: pad_radius2_scan, S = the larger of |o| and the
+    block's |c| + |v| + r): E = 32u (f32) or 40u (f64) times (|c| + |v| + r + S), (r + E)² rounded UP to f32."""
+    norm = lambda x, y, z: np.sqrt(x * x + y * y + z * z)  # noqa: E731  (the library's norm3, in its order)
+    vy = np.where(((rec[:, 27] == 1) | (rec[:, 27] == 3))[:, None], rec[:, 16:20], 0.0)
+    cn = norm(rec[:, 0:4], rec[:, 4:8], rec[:, 8:12]) + norm(0.0, vy, 0.0) + np.abs(rec[:, 12:16])
+    S = np.maximum(norm(rec[:, 20], rec[:, 21], rec[:, 22]), cn.max(1))
+    E = (32.0 if precision == 0 else 40.0) * 5.9604644775390625e-08 * (cn + S[:, None])
+    v = (np.abs(rec[:, 12:16]) + E) ** 2
+    f = v.astype(np.float32)
+    return np.where(f.astype(np.float64) < v, np.nextafter(f, np.float32(np.inf)), f).astype(np.float64)

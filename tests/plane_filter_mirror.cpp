@@ -3,6 +3,9 @@
 //   layout <spheres>               -> the plane runs of the static and mov-Y classes (rayz_plane::plan_runs)
 //   audit <spheres> <rays> <S> <f64>  -> the plane-form f32 filter against the f64 discriminant for every (ray, sphere) pair
 //   pairs <spheres> <rays> <S> <f64>  -> the same for ray i against sphere i only
+//   discs <records> <f64>          -> per RAYZ_KAT_SCAN_DISCS record of class 2 / 3 (a plane run: the run's height cy[4]), the
+//                                     plane-form value of its four spheres and the value of a pad slot (r² = -inf) at their
+//                                     place: 8 raw f32 on stdout.  The record carries the library's padded r² at [28..31].
 // spheres: rows of 7 doubles (cx cy cz vx vy vz r); rays: rows of 7 doubles (ox oy oz dx dy dz time).
 #include <cmath>
 #include <cstdio>
@@ -62,8 +65,42 @@ static float pad_r2(const double* s, double S, bool f64_rays) {
     return f;
 }
 
+// The plane form of a block as the device runs it for a plane run (rayz_device.hpp: scan_plane_class puts K2 in the basis,
+// ScanGroup<float, 3 / 4>::discs), from a KAT record: the ray as kat_kernel narrows it (unit(d) in R, then f32).
+static int discs(const char* path, bool f64_rays) {
+    const std::vector<double> rec = read_rows(path);
+    for (size_t i = 0; i + 48 <= rec.size(); i += 48) {
+        const double* a = &rec[i];
+        if (a[27] != 2.0 && a[27] != 3.0) return 3;
+        float ud[3];
+        if (f64_rays) {
+            double u64[3];
+            unit<double>(a + 23, u64);
+            for (int j = 0; j < 3; ++j) ud[j] = (float)u64[j];
+        } else {
+            unit<float>(a + 23, ud);
+        }
+        const float o[3] = {(float)a[20], (float)a[21], (float)a[22]}, ft = (float)a[26];
+        const Basis b = make_basis(ud, o);
+        const float K2 = fm((float)a[4], b.e2y, b.k2);
+        float out[8];
+        for (int k = 0; k < 4; ++k) {
+            const float cx = (float)a[k], cz = (float)a[8 + k], vy = (float)a[16 + k];
+            float p1 = fm(cx, b.e1x, b.k1), p2 = fm(cx, b.e2x, K2);
+            p1 = fm(cz, b.e1z, p1);
+            p2 = fm(cz, b.e2z, p2);
+            if (a[27] == 3.0) p2 = fm(vy, ft * b.e2y, p2);
+            out[k] = fm(-p1, p1, fm(-p2, p2, (float)a[28 + k]));
+            out[4 + k] = fm(-p1, p1, fm(-p2, p2, -INFINITY));
+        }
+        std::fwrite(out, sizeof(float), 8, stdout);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
+    if (std::string(argv[1]) == "discs") return argc < 4 ? 2 : discs(argv[2], std::atoi(argv[3]) != 0);
     const std::vector<double> sph = read_rows(argv[2]);
     const size_t ns = sph.size() / 7;
     std::vector<uint32_t> cls[2];

@@ -91,6 +91,64 @@ def axis_scene(seed):
     return t
 
 
+def plane_scene(seed):
+    """Third generator: plane runs, which the two above never form (at most 40 spheres, random heights).  1 to 6
+    heights (+0, -0, negative or positive), 40 / 63 / 64 / 65 / 100 / 257 spheres each, static or y-moving per height,
+    among loose, generally moving spheres and a ground sphere; random materials; a camera that may sit at a run's height
+    and look horizontally along it."""
+    rng = np.random.default_rng(seed)
+    n_h = int(rng.integers(1, 7))
+    hs = [float(rng.choice([0.0, -0.0, float(rng.uniform(-2.5, -0.1)), float(rng.uniform(0.1, 3.0))])) for _ in range(n_h)]
+    level = rng.random() < 0.4
+    if level:
+        h = hs[int(rng.integers(0, n_h))]
+        look_from, look_at = np.array([-14.0, h, float(rng.uniform(-1, 1))]), np.array([10.0, h, float(rng.uniform(-1, 1))])
+    else:
+        look_from, look_at = rng.uniform(-8, 8, 3) + np.array([0, 6.0, 0]), rng.uniform(-1, 1, 3)
+    t = tracer.Tracer.init(int(rng.integers(24, 48)), float(rng.uniform(25, 60)), float(rng.uniform(4, 12)),
+                           float(rng.choice([0.0, 0.0, 1.0])), look_from, look_at, (0, 1, 0), seed=seed)
+    P = t.pool
+    tex = [P.add_solid_texture(rng.uniform(0.05, 0.95, 3)) for _ in range(3)]
+    tex.append(P.add_checker_texture(float(rng.uniform(0.2, 1.0)), tex[0], tex[1]))
+    mats = [P.add_diffuse(int(rng.choice(tex)), int(rng.integers(0, 3))) for _ in range(3)]
+    mats += [P.add_metallic(int(rng.choice(tex)), float(rng.choice([0.0, rng.uniform(0, 1)]))), P.add_dielectric(1.5)]
+    rows = [((0.0, -1004.0, 0.0), 1000.0, (0.0, 0.0, 0.0))]
+    for h in hs:
+        movy = rng.random() < 0.5
+        spread = float(rng.uniform(3, 9))
+        for _ in range(int(rng.choice([40, 63, 64, 65, 100, 257]))):
+            v = (0.0, float(rng.uniform(0.05, 0.6) * rng.choice([-1, 1])), 0.0) if movy else (0.0, 0.0, 0.0)
+            rows.append(((float(rng.uniform(-spread, spread)), h, float(rng.uniform(-spread, spread))), float(rng.uniform(0.1, 0.6)), v))
+    for _ in range(int(rng.integers(0, 20))):
+        cls = rng.integers(0, 3)
+        v = (0, 0, 0) if cls == 0 else ((0, float(rng.uniform(-1, 1)), 0) if cls == 1 else tuple(rng.uniform(-1, 1, 3)))
+        rows.append((tuple(rng.uniform((-6, -2.5, -6), (6, 3, 6))), float(rng.uniform(0.2, 0.9)), v))
+    for k in rng.permutation(len(rows)):
+        c, r, v = rows[k]
+        P.add_sphere(c, r, int(rng.choice(mats)), velocity=v)
+    t.samples_per_px = int(rng.integers(1, 8))
+    t.max_bounces = int(rng.integers(2, 12))
+    t.set_gpu(render_seed=int(rng.integers(0, 2 ** 62)), chunk_spp=int(rng.choice([0, 1, 16])))
+    return t
+
+
+@pytest.mark.parametrize("seed", range(300, 308))
+def test_plane_scene_parity(gpu, oracle, seed):
+    """Flat list == oracle mode B and == the BVH frame, bit for bit, segments equal, in both precisions."""
+    t = plane_scene(seed)
+    for prec in (capi.PRECISION_F32, capi.PRECISION_F64):
+        t.set_gpu(traversal=capi.TRAVERSAL_LINEAR, precision=prec)
+        scene, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+        got, gst = gpu.render_host(scene, cam, p)
+        want, ost = oracle.render_b(scene, cam, p)
+        assert_images_equal(got, want, f"plane scene {seed} precision {prec}")
+        assert gst.segments == ost.segments
+        t.set_gpu(traversal=capi.TRAVERSAL_BVH)
+        got_b, bst = gpu.render_host(t.scene_desc(), t.camera_desc(), t.params())
+        assert_images_equal(got_b, got, f"plane scene {seed} precision {prec}: BVH vs flat list")
+        assert bst.segments == gst.segments
+
+
 @pytest.mark.parametrize("seed", range(200, 208))
 def test_axis_scene_parity(gpu, oracle, seed):
     t = axis_scene(seed)

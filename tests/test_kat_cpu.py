@@ -278,3 +278,73 @@ def test_scan_block_filter_is_conservative_against_the_reference_discriminant(or
         dist = np.linalg.norm(oc - (oc * dd).sum(2, keepdims=True) * dd, axis=2)
         clear = dist > 1.05 * rec[:, 12:16] + 1e-3 * np.linalg.norm(oc, axis=2)
         assert clear.mean() > 0.3 and (b[:, :4][clear] < 0).all()
+
+
+def _bad_scan_records():
+    """SCAN_DISCS records the argument checks must refuse, each with the reason: a class that is not 0 - 3, a want_r2 that
+    is not 0 or 1, and plane-run records (classes 2, 3) whose four heights are not one f32 value bit for bit."""
+    rec = K.random_plane_blocks(np.random.default_rng(3), 4)
+    bad = []
+    for want in (2.0, 0.5, -1.0, float("nan")):
+        r = rec.copy()
+        r[1, 32] = want
+        bad.append((f"want_r2 {want}", r))
+    for cls in (4.0, -1.0, 0.5, 2.5, float("nan"), float("inf"), 1e30):
+        r = rec.copy()
+        r[:, 27] = cls
+        bad.append((f"class {cls}", r))
+    for cls in (2.0, 3.0):
+        for k, cy, run in ((1, 0.5, 0.25), (3, 0.25 + 2.0 ** -20, 0.25), (2, -0.0, 0.0), (0, 0.0, -0.0)):
+            r = rec.copy()
+            r[:, 27], r[:, 4:8] = cls, run
+            r[2, 4 + k] = cy  # one sphere of one record off the run's height (+0 vs -0: two runs)
+            bad.append((f"class {cls} cy[{k}] = {cy}", r))
+    return bad
+
+
+def test_scan_discs_argument_checks_on_the_oracle(oracle):
+    """The oracle refuses what rayz_hip_kat refuses (tests/test_plane_runs_gpu.py holds the library to the same list), and
+    accepts every class 0 - 3 and plane-run heights that differ in f64 but are one f32 value."""
+    import ctypes as C
+
+    lib = oracle.load()
+    D = C.POINTER(C.c_double)
+
+    def rcs(rec):
+        rec = np.ascontiguousarray(rec)
+        out = np.zeros((len(rec), capi.KAT_OUT_STRIDE))
+        return (lib.rayz_oracle_kat_b(capi.KAT_SCAN_DISCS, F32, rec.ctypes.data_as(D), len(rec), out.ctypes.data_as(D)),
+                lib.rayz_oracle_kat_a(capi.KAT_SCAN_DISCS, rec.ctypes.data_as(D), len(rec), out.ctypes.data_as(D)))
+
+    for why, rec in _bad_scan_records():
+        assert rcs(rec) == (capi.ERR_BAD_ARG, capi.ERR_BAD_ARG), why
+    rec = K.random_plane_blocks(np.random.default_rng(4), 8)
+    for cls in (0.0, 1.0, 2.0, 3.0):
+        rec[:, 27] = cls
+        assert rcs(rec) == (capi.OK, capi.OK), cls
+    rec[:, 4:8] = 0.7 + np.array([0.0, 1e-12, -1e-12, 3e-9])  # one f32 height, four f64 ones
+    assert rcs(rec) == (capi.OK, capi.OK)
+
+
+@pytest.mark.parametrize("prec", [F32, F64])
+def test_scan_discs_plane_classes_on_the_oracle(oracle, prec):
+    """Mode B has one filter form: classes 2 / 3 give what 0 / 1 give, bit for bit; out[8..11] is the padded r² the library's
+    rule gives (restated in numpy), for every class; mode A's discriminant moves a class-3 sphere with its vy as class 1's."""
+    rng = np.random.default_rng(17)
+    plane = K.random_plane_blocks(rng, 100_000)
+    loose = plane.copy()
+    loose[:, 27] -= 2
+    b, b0 = oracle.kat_b(capi.KAT_SCAN_DISCS, plane, prec), oracle.kat_b(capi.KAT_SCAN_DISCS, loose, prec)
+    assert np.array_equal(b, b0)
+    assert np.array_equal(oracle.kat_a(capi.KAT_SCAN_DISCS, plane), oracle.kat_a(capi.KAT_SCAN_DISCS, loose))
+    for rec in (plane, K.random_scan_blocks(rng, 100_000)):
+        rec[:, 32] = 1.0
+        got = oracle.kat_b(capi.KAT_SCAN_DISCS, rec, prec)
+        assert np.array_equal(got[:, 8:12], K.scan_pad_r2(rec, prec))
+        assert (got[:, 8:12] > rec[:, 12:16] ** 2).all()
+        rec[:, 32] = 0.0  # without want_r2 the record gives what it gave before the flag existed: zeros in [8..11]
+        off = oracle.kat_b(capi.KAT_SCAN_DISCS, rec, prec)
+        assert np.array_equal(off[:, :8], got[:, :8]) and (off[:, 8:12] == 0).all()
+    a = oracle.kat_a(capi.KAT_SCAN_DISCS, plane)[:, :4]
+    assert 0.1 < (a >= 0).mean() < 0.6
+    assert (b[:, :4][a >= 0] >= 0).all()  # mode B's filter is conservative on the plane blocks too

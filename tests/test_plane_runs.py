@@ -168,3 +168,64 @@ def test_plane_loops_issue_one_packed_fma_less_per_sphere_pair(tmp_path):
                 per_pair.append(pk)
     # static plane, static loose, mov-Y plane, mov-Y loose (slot order); per group: 6·G/2, 7·G/2, 7·G/2, 8·G/2
     assert per_pair[:4] == [2 * 6 * G // 2, 2 * 7 * G // 2, 2 * 7 * G // 2, 2 * 8 * G // 2], per_pair
+
+
+def _groups(spec, rng):
+    """Sphere rows for [(class, cy, members), ...] (class 0 static, 1 mov-Y), shuffled into one pool order."""
+    rows = []
+    for cls, cy, n in spec:
+        s = np.zeros((n, 7))
+        s[:, 0], s[:, 1], s[:, 2], s[:, 6] = rng.uniform(-9, 9, n), cy, rng.uniform(-9, 9, n), 0.3
+        s[:, 4] = rng.uniform(0.1, 0.5, n) * cls
+        rows.append(s)
+    sph = np.concatenate(rows)
+    return sph[rng.permutation(len(sph))]
+
+
+def test_run_layout_keeps_the_four_largest_groups(mirror, tmp_path):
+    """More than four qualifying heights: the four largest groups become runs, a tie in size goes to the smaller cy BITS
+    (+0 before a positive height before -0 before a negative one), the runs are laid out in ascending cy (+0 before -0),
+    groups of 63 and the groups left over stay loose."""
+    rng = np.random.default_rng(2)
+    cases = [  # (class, [(cy, members)]), the runs wanted in layout order
+        (0, [(1.5, 64), (-0.5, 64), (2.5, 90), (0.5, 80), (3.5, 70)], [(0.5, 80), (1.5, 64), (2.5, 90), (3.5, 70)]),
+        (0, [(0.25, 100), (-2.0, 65), (0.75, 64), (1.25, 72), (3.0, 64), (4.0, 63), (-0.0, 65)],
+         [(-2.0, 65), (-0.0, 65), (0.25, 100), (1.25, 72)]),
+        (1, [(-0.0, 64), (0.0, 64), (5.0, 64), (-5.0, 64), (6.0, 64)], [(0.0, 64), (-0.0, 64), (5.0, 64), (6.0, 64)]),
+    ]
+    bits = lambda x: int(np.float32(x).view(np.uint32))  # noqa: E731
+    for c, spec, want in cases:
+        sph = _groups([(c, cy, n) for cy, n in spec], rng)
+        cl = _run(mirror, tmp_path, "layout", _write(tmp_path, "s.bin", sph))["classes"][c]
+        # (the run's height as its members hold it: the layout's JSON prints -0 as an integer)
+        got = [(bits(sph[r["members"][0], 1]), len(r["members"])) for r in cl["runs"]]
+        assert got == [(bits(cy), n) for cy, n in want], (spec, got)
+        at = 0
+        for r in cl["runs"]:
+            assert r["first"] == at and r["end"] - r["first"] == -(-len(r["members"]) // (2 * G)) * 2 * G
+            at = r["end"]
+        assert len(cl["loose"]) == sum(n for _, n in spec) - sum(n for _, n in want)
+
+
+def test_mirror_plane_form_is_conservative_on_plane_blocks(mirror, tmp_path, oracle):
+    """The mirror's plane form (tests/test_plane_runs_gpu.py holds the device to it bit for bit), from the padded r² the
+    oracle returns for the record, passes every sphere whose f64 discriminant (mode A) is >= 0; pad slots never pass."""
+    import kat_records as K
+
+    rec = K.random_plane_blocks(np.random.default_rng(21), 100_000)
+    a = oracle.kat_a(capi.KAT_SCAN_DISCS, rec)[:, :4]
+    for prec in (capi.PRECISION_F32, capi.PRECISION_F64):
+        r = rec.copy()
+        r[:, 28:32] = oracle.kat_b(capi.KAT_SCAN_DISCS, rec, prec)[:, 8:12]
+        m = mirror_discs(mirror, tmp_path, r, prec)
+        assert (m[:, :4][a >= 0] >= 0).all(), int((m[:, :4][a >= 0] < 0).sum())
+        assert not (m[:, 4:] >= 0).any()
+        assert 0.1 < (m[:, :4] >= 0).mean() < 0.6
+
+
+def mirror_discs(mirror, tmp_path, rec, prec):
+    """The mirror's `discs` command: (n, 8) f32 = the plane form of the record's four spheres, then a pad slot's value."""
+    p = _write(tmp_path, "rec.bin", rec)
+    r = subprocess.run([mirror, "discs", str(p), str(int(prec == capi.PRECISION_F64))], capture_output=True, timeout=900)
+    assert r.returncode == 0, r.stderr
+    return np.frombuffer(r.stdout, dtype=np.float32).reshape(-1, 8)
