@@ -13,6 +13,14 @@ library's one default, include/rayz_hip.h; no data-path collective while tracing
 framebuffer tiles per step ("strong" scaling: the frame is fixed, per-GPU work shrinks with N).  Rank 0 prints one JSON
 line.  The line carries `frame_sha256` of the gathered frame: the image does not depend on N, so the N = 1 line and every
 N > 1 line of the same command must carry the same hash.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, check and hash the frame, write it with
+--dump-outputs, print the line.  --full adds what takes renders of its own, after the timed region (about 70 s more at
+the default size): the frames beside the headline (`also`: the BVH, the f64 fidelity mode, the C ABI's multi-device
+entry, BASELINE configs 2, 4 and 5; at N > 1 the BVH block) and the CPU baseline.  --no-also and --no-cpu-baseline
+leave one of the two out of a --full run.
+
+    python bench.py --full
 """
 from __future__ import annotations
 
@@ -55,9 +63,11 @@ def parse_args():
     ap.add_argument("--render-seed", type=int, default=1)
     ap.add_argument("--traversal", choices=["linear", "bvh"], default="linear")
     ap.add_argument("--precision", choices=["f32", "f64"], default="f32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also render the extra frames reported beside the headline (`also`) and time the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the extra frames reported beside the headline (BVH traversal; f64 fidelity mode; BASELINE configs 2, 4, 5)")
+                    help="with --full: skip the extra frames reported beside the headline (BVH traversal; f64 fidelity mode; BASELINE configs 2, 4, 5)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the frame the last timed step computed to DIR/*.npy (see dump_outputs)")
@@ -356,9 +366,9 @@ def run(args, json_fd):
     # Bit-identical to the flat list, so its gathered frame must hash to the headline's.  Same barrier + max-over-ranks timing.
     also_multi = None
     # (RAYZ_BENCH_MULTI_ALSO_AT_N1=1: the test suite's hook — the development pool has one GPU per box, so the block below runs at
-    #  N = 1 there, collectives skipped, to keep this code from meeting its first execution on the driver's scaling run)
+    #  N = 1 there, collectives skipped, to keep this code from meeting its first execution on a real multi-GPU run; --full only)
     multi_also = world > 1 or os.environ.get("RAYZ_BENCH_MULTI_ALSO_AT_N1") == "1"
-    if multi_also and args.traversal == "linear" and args.precision == "f32" and not args.no_also:
+    if args.full and multi_also and args.traversal == "linear" and args.precision == "f32" and not args.no_also:
         t.set_gpu(render_seed=args.render_seed, traversal=capi.TRAVERSAL_BVH, precision=capi.PRECISION_F32, tmin=1e-3)
         pb = rdist.shard_params(t.params(), rank, world)
         kb, gb, sb = [], [], []
@@ -397,9 +407,9 @@ def run(args, json_fd):
     # N = 1 only, after the timed region: the same frame through the reference's own accelerator (BVH traversal), and
     # the f64 fidelity mode (the reference's scalar type and tmin, src/vec.zig:4-8, src/renderer.zig:107) through both —
     # reported beside the headline, which stays the f32 flat hit list BASELINE.json names.  All of them at the headline's own
-    # samples per pixel.
+    # samples per pixel.  --full only.
     also = None
-    if world == 1 and args.traversal == "linear" and args.precision == "f32" and not args.no_also:
+    if args.full and world == 1 and args.traversal == "linear" and args.precision == "f32" and not args.no_also:
         also, frames = {}, {}
 
         def velocity_classes(sd_):
@@ -647,7 +657,7 @@ def run(args, json_fd):
             out["also"] = also
         if also_multi:
             out.setdefault("also", {}).update({("bvh_traversal" if world > 1 else "multi_gpu_bvh_block_at_n1"): also_multi["bvh_traversal"]})
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(t, args.cpu_seconds)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

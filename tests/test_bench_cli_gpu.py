@@ -1,5 +1,6 @@
-"""The two entry points a user (and the driver) runs: `bench.py` prints one JSON line with the agreed keys, and
-the `rayz <img_w> [out.ppm]` CLI renders the reference's scene to a P3 PPM (src/rayz.zig:12-43)."""
+"""The two entry points a user runs: `bench.py` prints one JSON line with the agreed keys (a plain run the
+headline alone, `--full` the frames beside it and the CPU baseline as well), and the `rayz <img_w> [out.ppm]` CLI renders the
+reference's scene to a P3 PPM (src/rayz.zig:12-43)."""
 import hashlib
 import json
 import os
@@ -16,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract(gpu, tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "96", "--spp", "4", "--grid", "4",
-                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--dump-outputs", str(tmp_path / "dump")],
+                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.5", "--dump-outputs", str(tmp_path / "dump"), "--full"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, RAYZ_BENCH_MULTI_ALSO_AT_N1="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -82,7 +83,7 @@ def test_bench_ranks_on_one_gpu_print_the_same_frame_hash(gpu, world):
     one = subprocess.run([sys.executable, *base, "--gpus", "1", "--no-also"], capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
-    two = subprocess.run([sys.executable, *base, "--gpus", str(world)], capture_output=True, text=True, timeout=600,
+    two = subprocess.run([sys.executable, *base, "--gpus", str(world), "--full"], capture_output=True, text=True, timeout=600,
                          env=dict(os.environ, RAYZ_BENCH_TEST_SHARED_GPU="1"))
     assert two.returncode == 0, two.stderr[-3000:]
     lines = [l for l in two.stdout.splitlines() if l.startswith("{")]
@@ -95,6 +96,29 @@ def test_bench_ranks_on_one_gpu_print_the_same_frame_hash(gpu, world):
     assert abs(sum(pr["segments"]) - d1["config"]["segments_per_sample"] * 96 * 54 * 4) < 0.5  # the shards' segments add up to the frame's
     b = d2["also"]["bvh_traversal"]
     assert b["frame_sha256"] == d1["frame_sha256"] and b["value"] > 0 and len(b["per_rank"]["kernel_ms"]["all"]) == world
+
+
+def test_bench_plain_run_prints_the_headline_alone(gpu, tmp_path):
+    """Without --full the line carries the headline and nothing that takes renders of its own: no `also` frames (not even
+    with the N > 1 BVH block's test hook set), no CPU baseline.  Its frame, hash and dump are those of a --full run."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--width", "96", "--spp", "4", "--grid", "4", "--steps", "2", "--warmup", "1"]
+    env = dict(os.environ, RAYZ_BENCH_MULTI_ALSO_AT_N1="1")
+    r = subprocess.run([*base, "--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(r.stdout.strip().splitlines()) == 1
+    d = json.loads(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "frame_sha256", "roofline", "per_rank"):
+        assert k in d, k
+    assert "also" not in d and "cpu_baseline" not in d
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["value"] - 96 * 54 * 4 * 2 / (d["ms_per_step"] * 2e-3) / 1e6) < 1e-6 * d["value"] + 1e-9
+    full = subprocess.run([*base, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], capture_output=True,
+                          text=True, timeout=600, env=env)
+    assert full.returncode == 0, full.stderr[-2000:]
+    f = json.loads(full.stdout)
+    assert "also" in f and "cpu_baseline" not in f and f["frame_sha256"] == d["frame_sha256"] and f["metric"] == d["metric"]
+    plain_img, full_img = np.load(tmp_path / "plain" / "frame.npy"), np.load(tmp_path / "full" / "frame.npy")
+    assert np.array_equal(plain_img, full_img) and hashlib.sha256(plain_img.tobytes()).hexdigest() == d["frame_sha256"]
 
 
 def test_cli_renders_reference_scene(gpu, tmp_path):
