@@ -396,6 +396,67 @@ typedef enum RayzKatOp {
 #define RAYZ_KAT_OUT_STRIDE 12
 int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n_records, double* out);
 
+/* ---- ray queries: "what does this ray hit?" ------------------------------------------------------------------
+ * The reference's other interface, `BVH.findHit(hittables, ray, tmin, tmax) -> ?Hit` (src/hit.zig:181-217, the sphere test
+ * src/geom.zig:33-66, the record `Hit.init` src/hit.zig:25-41), on a batch of rays held in DEVICE memory, against a scene created
+ * with rayz_hip_scene_create: the render's own scan or BVH walk, reject test, f64 narrow phase and tie rule (nearest, ties to the
+ * larger hittable index), with the root accepted in [tmin, tmax] — both ends inclusive, as in the reference.
+ * Hittables are numbered spheres first, then triangles.  Added in ABI 5 (additive: no existing symbol changed).
+ * Queries leave rayz_hip_scene_sync's counters alone and change nothing of a progressive handle stepped between them; a scene
+ * still has ONE render or query in flight (a query on another stream first waits for the scene's last launch). */
+typedef enum RayzQueryKind {
+    RAYZ_QUERY_NEAREST = 0, /* the `findHit` result: hittable, t, point, normal, front_face, material, albedo */
+    RAYZ_QUERY_ANY = 1      /* occlusion: is there a root in [tmin, tmax]?  A lane's BVH walk ends at the first one */
+} RayzQueryKind;
+
+typedef struct RayzQueryParams {
+    uint32_t n_rays;    /* 0: a no-op that returns RAYZ_OK */
+    uint32_t kind;      /* RayzQueryKind */
+    uint32_t precision; /* RayzPrecision: the type of the rays and of the R outputs.  F32 holds rays in f32 and decides candidates in
+                           f64 on the pool's spheres; F64 is f64 throughout (as renders) */
+    uint32_t traversal; /* RayzTraversal.  AUTO uses RAYZ_AUTO_BVH_MIN, a crossover measured for PATH TRACING, not for queries */
+    double tmin;        /* the same for every ray (a NaN is RAYZ_ERR_BAD_ARG) */
+} RayzQueryParams;
+
+/* Where the results go: DEVICE memory, each pointer optional (NULL = not written).  R = float or double by the precision.
+ * NEAREST writes every field it is given; ANY writes `hit` only.  On a miss: index and material -1, t +inf, point, normal and
+ * albedo 0, front_face 0. */
+typedef struct RayzQueryOutputs {
+    int32_t* index;     /* n: hittable index, or -1 */
+    void* t;            /* n R */
+    void* point;        /* 3n R: o + t·d as shade computes it */
+    void* normal;       /* 3n R: unit outward normal, flipped to face the ray (Hit.init) */
+    uint8_t* front_face;/* n: 1 if the ray hit the outside */
+    int32_t* material;  /* n: MaterialHandle.idx, or -1 */
+    void* albedo;       /* 3n R: texture_value at the point; (1, 1, 1) for a dielectric */
+    uint8_t* hit;       /* n: 1 if a root lies in [tmin, tmax] (either kind) */
+} RayzQueryOutputs;
+
+/* A batch of rays: `d_rays` is DEVICE memory, n_rays x 8 values of the precision, {ox, oy, oz, time, dx, dy, dz, tmax} per ray.
+ * Refused with RAYZ_ERR_BAD_ARG: a NaN or infinite origin, direction or time, an origin component beyond RAYZ_QUERY_MAX_ORIGIN,
+ * a zero direction, a NaN tmax, a time outside [0, 1] (the BVH's moving-sphere boxes enclose the centre over [0, 1] only,
+ * Sphere.boundingBox).  tmax < tmin is allowed: a miss.
+ * BLOCKING PART: a small reduction kernel over the batch finds max |origin|, the time range and the refusals, and the host waits for
+ * those few values (the scan's reject radii and the BVH's f32 boxes are padded for a bound on every ray origin, DESIGN.md §4.3 /
+ * §4.8: the scene's buffers are rebuilt if they were padded for less).  The query itself then runs asynchronously on
+ * `hip_stream` (NULL: the library's stream); rayz_hip_query_sync waits for it.  `d_rays` and the outputs must stay allocated
+ * until then.
+ * PADDING IS NEVER SHRUNK: a batch whose origins lie farther out than the scene's and the cameras' own bound widens the scene's
+ * reject radii and boxes for good (for twice that bound), so later renders and queries on the scene test more candidates and
+ * boxes — the same images, more work.  A caller that queries from far away and then renders again keeps a second scene. */
+#define RAYZ_QUERY_MAX_ORIGIN 1e9 /* largest |origin component| a query accepts: the padding stays finite in f32 */
+int rayz_hip_scene_query(RayzScene* scene, const RayzQueryParams* query, const void* d_rays, const RayzQueryOutputs* outputs,
+                         void* hip_stream);
+/* The camera form: one ray per pixel of the shard `params` describes, camera_ray_no_rng — `getRay(px, py, null)`: the pixel's
+ * centre, the lens centre, time 0, tmax +inf — a G-buffer.  Output entry = local row · width + column (rows_in_shard x width),
+ * as renders store pixels.  Reads width, height, shard_index, shard_count, tile_rows, precision, traversal and tmin of
+ * `params`; ignores samples_per_px, max_bounces, seed and chunk_spp.  Kind NEAREST.  Asynchronous, nothing blocks. */
+int rayz_hip_scene_query_camera(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                const RayzQueryOutputs* outputs, void* hip_stream);
+/* Waits for the scene's last query and returns its counters: primary_rays = segments = rays, node_tests and sphere_tests as
+ * renders count them (flat list: rays x hittables), kernel_ms = the query kernel's HIP-event time. */
+int rayz_hip_query_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
+
 #ifdef __cplusplus
 }
 #endif

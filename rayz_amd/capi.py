@@ -34,6 +34,7 @@ MAT_DIFFUSE, MAT_METALLIC, MAT_DIELECTRIC = 0, 1, 2
 DIFFUSE_UNIT_SPHERE, DIFFUSE_UNIT_SPHERE_SURFACE, DIFFUSE_HEMISPHERE = 0, 1, 2
 PRECISION_F32, PRECISION_F64 = 0, 1
 TRAVERSAL_LINEAR, TRAVERSAL_BVH, TRAVERSAL_AUTO = 0, 1, 2
+QUERY_NEAREST, QUERY_ANY = 0, 1
 
 D3 = C.c_double * 3
 
@@ -80,9 +81,20 @@ class RenderStats(C.Structure):
                 ("node_tests", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class QueryParams(C.Structure):
+    _fields_ = [("n_rays", C.c_uint32), ("kind", C.c_uint32), ("precision", C.c_uint32), ("traversal", C.c_uint32),
+                ("tmin", C.c_double)]
+
+
+class QueryOutputs(C.Structure):
+    _fields_ = [("index", C.c_void_p), ("t", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p),
+                ("front_face", C.c_void_p), ("material", C.c_void_p), ("albedo", C.c_void_p), ("hit", C.c_void_p)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
+assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -137,6 +149,11 @@ PROTOTYPES = [
     ("rayz_hip_render_multi_f64", C.c_int,
      [C.POINTER(C.c_int), C.c_int, C.POINTER(SceneDesc), C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,
       C.POINTER(RenderStats)]),
+    ("rayz_hip_scene_query", C.c_int,
+     [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p]),
+    ("rayz_hip_scene_query_camera", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(QueryOutputs), C.c_void_p]),
+    ("rayz_hip_query_sync", C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
 ]
 
 

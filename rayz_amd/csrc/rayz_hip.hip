@@ -286,6 +286,13 @@ struct RayzScene {
     hipStream_t last_stream = nullptr;
     bool rendered = false, last_bvh = false, last_two_paths = false, last_exchange = false;
     RayzRenderStats last{};
+    // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
+    unsigned long long* q_counters = nullptr; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
+                                              // [kQueryBoundBase + k·kQueryBoundStride] the bound check's four words
+    hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
+    hipStream_t q_stream = nullptr;
+    bool queried = false, q_bvh = false;
+    RayzRenderStats q_last{};
 };
 
 namespace {
@@ -792,16 +799,16 @@ int scene_ctx(RayzScene* s, DeviceCtx** out) {
 // The scene's device side for a render of `p` with `cam`: the buffers uploaded (their filter padded for the camera's origin
 // bound) and, when the render walks the BVH, the tree.  A scene supports ONE render in flight: a launch on another stream first
 // waits for the previous one (its workspace and counters are reused, and a re-upload frees buffers it may still read).
+// (ray queries pass their own origin bound `S`: the largest |origin| of the batch, rayz_hip_scene_query)
 template <class R>
-int prepare_scene(RayzScene* s, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p, hipStream_t stream,
-                  bool& use_bvh) {
-    use_bvh = p->traversal == RAYZ_TRAVERSAL_BVH ||
-              (p->traversal == RAYZ_TRAVERSAL_AUTO && s->spheres.size() + s->triangles.size() > RAYZ_AUTO_BVH_MIN);
+int prepare_scene_bound(RayzScene* s, SceneBuffers<R>& b, double S, uint32_t traversal, hipStream_t stream, bool& use_bvh) {
+    use_bvh = traversal == RAYZ_TRAVERSAL_BVH ||
+              (traversal == RAYZ_TRAVERSAL_AUTO && s->spheres.size() + s->triangles.size() > RAYZ_AUTO_BVH_MIN);
     if (s->spheres.size() + s->triangles.size() >= (1u << 27))
         return fail(RAYZ_ERR_BAD_ARG, "too many hittables for the device layout");
     if (s->last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream)); // previous render done
     if (s->origin_bound < 0) s->origin_bound = scene_origin_bound(s);
-    int rc = upload<R>(s, b, std::max(s->origin_bound, camera_origin_bound(cam)));
+    int rc = upload<R>(s, b, std::max(s->origin_bound, S));
     if (rc != RAYZ_OK) return rc;
     if (use_bvh) {
         rc = upload_bvh<R>(s, b);
@@ -810,6 +817,12 @@ int prepare_scene(RayzScene* s, SceneBuffers<R>& b, const RayzCameraDesc* cam, c
             return fail(RAYZ_ERR_BAD_ARG, "BVH depth %u exceeds the traversal stack (%d)", s->bvh_dev.depth, kBvhStackDepth);
     }
     return RAYZ_OK;
+}
+
+template <class R>
+int prepare_scene(RayzScene* s, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p, hipStream_t stream,
+                  bool& use_bvh) {
+    return prepare_scene_bound<R>(s, b, camera_origin_bound(cam), p->traversal, stream, use_bvh);
 }
 
 // Work items of a launch over `chunks` chunks of a shard of `shard_pixels` pixels: the queue head, its reservations and the
@@ -1201,8 +1214,11 @@ int scene_free(RayzScene* s) {
         (void)hipFree(s->partial);
         (void)hipFree(s->counters);
         (void)hipFree(s->chunk_start);
+        (void)hipFree(s->q_counters);
         if (s->ev0) (void)hipEventDestroy(s->ev0);
         if (s->ev1) (void)hipEventDestroy(s->ev1);
+        if (s->q_ev0) (void)hipEventDestroy(s->q_ev0);
+        if (s->q_ev1) (void)hipEventDestroy(s->q_ev1);
     }
     delete s;
     return RAYZ_OK;
@@ -1700,6 +1716,226 @@ int render_multi_oneshot(const int* devices, int n, const RayzSceneDesc* scene, 
     return rc;
 }
 
+// ---- ray queries (rayz_hip_scene_query*) ---------------------------------------------------------------
+// query_key (rayz_device.hpp) and its inverse on the host: an order-preserving u64 of a double
+unsigned long long query_key_host(double x) {
+    unsigned long long b;
+    std::memcpy(&b, &x, 8);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+double query_unkey_host(unsigned long long k) {
+    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+    double x;
+    std::memcpy(&x, &b, 8);
+    return x;
+}
+
+// What every query entry checks before touching a device.
+int check_query_args(RayzScene* s, uint32_t kind, uint32_t precision, uint32_t traversal, double tmin) {
+    if (!s) return fail(RAYZ_ERR_BAD_ARG, "scene handle is null");
+    if (kind > RAYZ_QUERY_ANY) return fail(RAYZ_ERR_BAD_ARG, "bad query kind %u", kind);
+    if (precision > RAYZ_PRECISION_F64) return fail(RAYZ_ERR_BAD_ARG, "bad precision %u", precision);
+    if (traversal > RAYZ_TRAVERSAL_AUTO) return fail(RAYZ_ERR_BAD_ARG, "bad traversal %u", traversal);
+    if (!(tmin == tmin)) return fail(RAYZ_ERR_BAD_ARG, "tmin is NaN");
+    return RAYZ_OK;
+}
+
+// The bound check of a batch: max |origin|, time range and refusals (query_bounds_kernel), read back — the one wait of a query.
+constexpr uint32_t kQueryBoundBase = 32, kQueryCounterWords = kQueryBoundBase + 4 * kQueryBoundStride;
+template <class R> int query_bounds(RayzScene* s, const DeviceCtx& ctx, const R* rays, uint32_t n, hipStream_t stream, double& S) {
+    unsigned long long init[4 * kQueryBoundStride] = {};
+    init[0] = query_key_host(0.0);
+    init[kQueryBoundStride] = query_key_host(std::numeric_limits<double>::infinity());
+    init[2 * kQueryBoundStride] = query_key_host(-std::numeric_limits<double>::infinity());
+    unsigned long long* words = s->q_counters + kQueryBoundBase;
+    HIP_TRY(hipMemcpyAsync(words, init, sizeof(init), hipMemcpyHostToDevice, stream));
+    const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx.num_cu * 2, (n + 255) / 256));
+    hipLaunchKernelGGL(query_bounds_kernel<R>, dim3(blocks), dim3(256), 0, stream, rays, n, words);
+    HIP_TRY(hipGetLastError());
+    unsigned long long got[4 * kQueryBoundStride] = {};
+    HIP_TRY(hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const unsigned long long flags = got[3 * kQueryBoundStride];
+    if (flags & 1u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a NaN or infinite origin, direction or time");
+    if (flags & 8u) return fail(RAYZ_ERR_BAD_ARG, "query rays: an origin component beyond RAYZ_QUERY_MAX_ORIGIN (%g)", (double)RAYZ_QUERY_MAX_ORIGIN);
+    if (flags & 2u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a zero direction");
+    if (flags & 4u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a NaN tmax");
+    const double tlo = query_unkey_host(got[kQueryBoundStride]), thi = query_unkey_host(got[2 * kQueryBoundStride]);
+    if (tlo < 0.0 || thi > 1.0)
+        return fail(RAYZ_ERR_BAD_ARG, "query rays: time %g outside [0, 1] (the BVH's moving-sphere boxes cover [0, 1] only)",
+                    tlo < 0.0 ? tlo : thi);
+    S = query_unkey_host(got[0]) * (1.0 + 1e-6); // (the norm is rounded in f64: a relative margin far above its error)
+    return RAYZ_OK;
+}
+
+// One query launch: rays (or the camera form when rays == NULL, `cam` / `p` then describe it) on the scene's device.
+template <class R>
+int query_impl(RayzScene* s, const DeviceCtx& ctx, uint32_t kind, uint32_t traversal, double tmin, uint32_t n, const R* rays,
+               const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzQueryOutputs* out, hipStream_t stream) {
+    SceneBuffers<R>* bp;
+    if constexpr (sizeof(R) == 4) bp = &s->f32;
+    else bp = &s->f64;
+    SceneBuffers<R>& b = *bp;
+    if (s->last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream)); // one launch in flight per scene
+    if (!s->q_counters) {
+        HIP_TRY(hipMalloc((void**)&s->q_counters, kQueryCounterWords * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(s->q_counters, 0, kQueryCounterWords * sizeof(unsigned long long)));
+    }
+    if (!s->q_ev0) {
+        HIP_TRY(hipEventCreate(&s->q_ev0));
+        HIP_TRY(hipEventCreate(&s->q_ev1));
+    }
+    double S = 0;
+    int rc = rays ? query_bounds<R>(s, ctx, rays, n, stream, S) : RAYZ_OK;
+    if (rc != RAYZ_OK) return rc;
+    if (!rays) S = camera_origin_bound(cam);
+    bool use_bvh = false;
+    rc = prepare_scene_bound<R>(s, b, S, traversal, stream, use_bvh);
+    if (rc != RAYZ_OK) return rc;
+
+    QueryArgs<R> A{};
+    A.sc.stat = b.stat;
+    A.sc.movy = b.movy;
+    A.sc.movg = b.movg;
+    A.sc.slot64 = s->narrow.slot64;
+    A.sc.slot_pool = s->narrow.slot_pool;
+    A.sc.sph_pool = b.sph_pool;
+    A.sc.mat = b.mat;
+    A.sc.tex = b.tex;
+    A.sc.ns_pad = s->narrow.ns_pad;
+    A.sc.ny_pad = s->narrow.ny_pad;
+    A.sc.ng_pad = s->narrow.ng_pad;
+    A.sc.n_spheres = (uint32_t)s->spheres.size();
+    A.sc.tri = b.tri;
+    A.sc.nt_pad = b.nt_pad;
+    A.sc.n_triangles = (uint32_t)s->triangles.size();
+    A.sc.bvh_nodes = (const f4*)b.bvh_nodes;
+    for (int k = 0; k < 3; ++k) A.sc.bvh_glo[k] = b.grid.glo[k], A.sc.bvh_cell[k] = b.grid.cell[k];
+    A.sc.bvh_leaf = b.bvh_leaf;
+    A.sc.bvh_sph64 = s->narrow.bvh_sph64;
+    A.sc.bvh_n_nodes = use_bvh ? b.bvh_n_inner : 0u;
+    A.sc.bvh_leaf_stride = b.bvh_leaf_stride;
+    A.sc.bvh_n_big_leaves = use_bvh ? b.n_big_leaves : 0u;
+    for (int k = 0; k < 4; ++k) A.sc.bvh_big[k] = b.big_desc[k];
+    A.sc.bvh_top = 0u;
+    if (cam) fill_camera<R>(cam, A.cam);
+    A.rays = rays;
+    A.tmin = (R)tmin;
+    A.n = n;
+    A.kind = kind;
+    if (!rays) {
+        const uint32_t rows = rayz_hip_shard_rows(p);
+        A.width = p->width;
+        A.tile_rows = p->tile_rows ? p->tile_rows : RAYZ_DEFAULT_TILE_ROWS;
+        A.shard_index = p->shard_index;
+        A.shard_count = p->shard_count ? p->shard_count : 1u;
+        A.tiled_pixels = p->width % 8 == 0 ? (uint32_t)((uint64_t)(rows / 8 * 8) * p->width) : 0u;
+    }
+    A.counters = s->q_counters;
+    A.index = out->index;
+    A.t = (R*)out->t;
+    A.point = (R*)out->point;
+    A.normal = (R*)out->normal;
+    A.front = out->front_face;
+    A.material = out->material;
+    A.albedo = (R*)out->albedo;
+    A.hit = out->hit;
+
+    typedef void (*Kernel)(const QueryArgs<R>);
+    Kernel kernel = query_kernel<R>;
+    int block = 256, blocks_per_cu = 0;
+    size_t lds = 0;
+    if (use_bvh) {
+        // the render's LDS layout (trace_window): top | stacks | oversized hittables' records, the top shortened should the
+        // request be refused
+        kernel = b.quantized ? query_kernel_bvh<R, true> : query_kernel_bvh<R, false>;
+        block = (int)kBvhWg;
+        const size_t stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kBvhWg * sizeof(uint32_t);
+        const size_t fixed = stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0);
+        const size_t rec_bytes = b.quantized ? 32 : 64;
+        uint32_t top_records = b.bvh_top;
+        size_t top_bytes = 0;
+        for (;;) {
+            top_bytes = (size_t)top_records * rec_bytes;
+            lds = top_bytes + fixed;
+            hipError_t e = hipSuccess;
+            if (lds > 64 * 1024) e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, block, lds);
+            if (e == hipSuccess && blocks_per_cu >= 1) break;
+            (void)hipGetLastError();
+            if (top_records == 0)
+                return fail(RAYZ_ERR_HIP, "the query kernel cannot be launched with %zu bytes of LDS: %s", lds,
+                            e == hipSuccess ? "no workgroup fits a CU" : hipGetErrorString(e));
+            const uint32_t step = (uint32_t)(8192 / rec_bytes);
+            top_records = top_records > step ? top_records - step : 0u;
+        }
+        A.bvh_top_words = (uint32_t)(top_bytes / sizeof(uint32_t));
+        A.bvh_big_words = (uint32_t)((top_bytes + stack_bytes) / sizeof(uint32_t));
+        A.sc.bvh_top = (uint32_t)top_bytes;
+    }
+    uint64_t grid = (n + (uint64_t)block - 1) / block;
+    if (use_bvh) grid = std::min<uint64_t>(grid, (uint64_t)ctx.num_cu * std::max(1, blocks_per_cu));
+    s->last_stream = stream;
+    s->q_stream = stream;
+    s->q_bvh = use_bvh;
+    s->q_last = RayzRenderStats{};
+    s->q_last.primary_rays = s->q_last.segments = n;
+    HIP_TRY(hipMemsetAsync(s->q_counters, 0, 4 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipEventRecord(s->q_ev0, stream));
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), lds, stream, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->q_ev1, stream));
+    s->queried = true;
+    return RAYZ_OK;
+}
+
+template <class R>
+int scene_query(RayzScene* s, const RayzQueryParams* q, const void* rays, const RayzQueryOutputs* out, void* stream_arg) {
+    if (!q) return fail(RAYZ_ERR_BAD_ARG, "query params is null");
+    DeviceCtx* ctx = nullptr;
+    int rc = scene_ctx(s, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    DeviceScope scope(s->device);
+    const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    return query_impl<R>(s, *ctx, q->kind, q->traversal, q->tmin, q->n_rays, (const R*)rays, nullptr, nullptr, out, stream);
+}
+
+template <class R>
+int scene_query_camera(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzQueryOutputs* out,
+                       void* stream_arg) {
+    const uint32_t rows = rayz_hip_shard_rows(p);
+    const uint64_t pixels = (uint64_t)rows * p->width;
+    if (pixels >= (1ull << 31)) return fail(RAYZ_ERR_BAD_ARG, "camera query of %llu pixels", (unsigned long long)pixels);
+    if (pixels == 0) return RAYZ_OK;
+    DeviceCtx* ctx = nullptr;
+    int rc = scene_ctx(s, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    DeviceScope scope(s->device);
+    const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    return query_impl<R>(s, *ctx, RAYZ_QUERY_NEAREST, p->traversal, p->tmin, (uint32_t)pixels, nullptr, cam, p, out, stream);
+}
+
+int query_sync(RayzScene* s, RayzRenderStats* stats) {
+    if (!s) return fail(RAYZ_ERR_BAD_ARG, "scene handle is null");
+    if (!s->queried) {
+        if (stats) *stats = s->q_last;
+        return RAYZ_OK;
+    }
+    DeviceScope scope(s->device);
+    HIP_TRY(hipStreamSynchronize(s->q_stream));
+    unsigned long long c[32] = {};
+    HIP_TRY(hipMemcpy(c, s->q_counters, sizeof(c), hipMemcpyDeviceToHost));
+    if (s->q_bvh && c[31]) return fail(RAYZ_ERR_STATE, "query_kernel_bvh refused to run: its dynamic LDS segment does not start at LDS address 0");
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, s->q_ev0, s->q_ev1));
+    s->q_last.sphere_tests = s->q_bvh ? c[3] : s->q_last.segments * (unsigned long long)(s->spheres.size() + s->triangles.size());
+    s->q_last.node_tests = s->q_bvh ? c[2] : 0;
+    s->q_last.kernel_ms = ms;
+    s->queried = false;
+    if (stats) *stats = s->q_last;
+    return RAYZ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2144,6 +2380,40 @@ int rayz_hip_progressive_info(const RayzProgressive* pr, uint32_t* samples_done,
 
 int rayz_hip_progressive_destroy(RayzProgressive* pr) {
     return guarded([&] { return progressive_free(pr); });
+}
+
+int rayz_hip_scene_query(RayzScene* s, const RayzQueryParams* q, const void* d_rays, const RayzQueryOutputs* out, void* stream) {
+    // every argument is checked before the first HIP call
+    if (!q) return fail(RAYZ_ERR_BAD_ARG, "query params is null");
+    int rc = check_query_args(s, q->kind, q->precision, q->traversal, q->tmin);
+    if (rc != RAYZ_OK) return rc;
+    if (!out) return fail(RAYZ_ERR_BAD_ARG, "outputs is null");
+    if (q->n_rays == 0) return RAYZ_OK;
+    if (!d_rays) return fail(RAYZ_ERR_BAD_ARG, "rays is null");
+    return guarded([&] {
+        return q->precision == RAYZ_PRECISION_F64 ? scene_query<double>(s, q, d_rays, out, stream)
+                                                  : scene_query<float>(s, q, d_rays, out, stream);
+    });
+}
+
+int rayz_hip_scene_query_camera(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzQueryOutputs* out,
+                                void* stream) {
+    if (!p) return fail(RAYZ_ERR_BAD_ARG, "params is null");
+    int rc = check_query_args(s, RAYZ_QUERY_NEAREST, p->precision, p->traversal, p->tmin);
+    if (rc != RAYZ_OK) return rc;
+    if (!cam) return fail(RAYZ_ERR_BAD_ARG, "camera is null");
+    if (!out) return fail(RAYZ_ERR_BAD_ARG, "outputs is null");
+    if (!p->width || !p->height) return fail(RAYZ_ERR_BAD_ARG, "width and height must be > 0");
+    const uint32_t sc = p->shard_count ? p->shard_count : 1;
+    if (p->shard_index >= sc) return fail(RAYZ_ERR_BAD_ARG, "shard_index %u >= shard_count %u", p->shard_index, sc);
+    return guarded([&] {
+        return p->precision == RAYZ_PRECISION_F64 ? scene_query_camera<double>(s, cam, p, out, stream)
+                                                  : scene_query_camera<float>(s, cam, p, out, stream);
+    });
+}
+
+int rayz_hip_query_sync(RayzScene* s, RayzRenderStats* stats) {
+    return guarded([&] { return query_sync(s, stats); });
 }
 
 } // extern "C"

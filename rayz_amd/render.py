@@ -13,9 +13,14 @@ import numpy as np
 from . import capi
 
 
+_default_device = None  # the ordinal of the last successful init(): where a scene created without a device is bound
+
+
 def init(device: int = 0) -> None:
+    global _default_device
     lib = capi.load()
     capi.check(lib, lib.rayz_hip_init(device), f"rayz_hip_init({device})")
+    _default_device = device
 
 
 def debug_set(knob: int, value: int = -1) -> None:
@@ -49,6 +54,48 @@ def render_host(scene: capi.SceneDesc, camera: capi.CameraDesc, params: capi.Ren
     return out, st
 
 
+QUERY_OUTPUTS = ("index", "t", "point", "normal", "front_face", "material", "albedo")
+
+
+class QueryResult:
+    """The outputs of a query as torch tensors on the scene's device (None where not requested): index, material (int32),
+    t (R), point / normal / albedo (..., 3) of R, front_face and hit (uint8).  Written asynchronously: call
+    DeviceScene.query_sync() (or synchronise the stream) before reading them on the host."""
+
+    _VEC = ("point", "normal", "albedo")
+
+    def __init__(self):
+        for k in QUERY_OUTPUTS + ("hit",):
+            setattr(self, k, None)
+
+    @classmethod
+    def _alloc(cls, shape, dtype, device, outputs):
+        import torch
+
+        r = cls()
+        for k in outputs:
+            if k not in QUERY_OUTPUTS + ("hit",):
+                raise ValueError(f"unknown query output {k!r}; choose from {QUERY_OUTPUTS + ('hit',)}")
+            if k in ("index", "material"):
+                t = torch.empty(shape, dtype=torch.int32, device=device)
+            elif k in ("front_face", "hit"):
+                t = torch.empty(shape, dtype=torch.uint8, device=device)
+            elif k in cls._VEC:
+                t = torch.empty(tuple(shape) + (3,), dtype=dtype, device=device)
+            else:
+                t = torch.empty(shape, dtype=dtype, device=device)
+            setattr(r, k, t)
+        return r
+
+    def _outputs(self) -> capi.QueryOutputs:
+        o = capi.QueryOutputs()
+        for k in QUERY_OUTPUTS + ("hit",):
+            t = getattr(self, k)
+            if t is not None and t.numel():
+                setattr(o, k, t.data_ptr())
+        return o
+
+
 class DeviceScene:
     """A pool resident in HBM (`rayz_hip_scene_create`; `device` binds it to that HIP ordinal now)."""
 
@@ -60,6 +107,26 @@ class DeviceScene:
         else:
             rc = self._lib.rayz_hip_scene_create_on(device, C.byref(scene), C.byref(self._h))
         capi.check(self._lib, rc, "rayz_hip_scene_create")
+        self._device = device
+        self._inflight = None  # (rays, outputs) of the last query: kept alive until query_sync (the kernel may still use them)
+
+    @property
+    def device(self) -> int:
+        """The HIP ordinal the scene lives on (a scene created without one: the default device of init())."""
+        d = self._device if self._device is not None else _default_device
+        if d is None:
+            raise capi.RayzHipError("no device: call render.init() first")
+        return d
+
+    def _query_prologue(self, stream: int):
+        """Before a query: the previous one is waited for (its tensors released), and — on the library's own stream, which does not
+        order itself after torch's — torch's work on the scene's device is finished, so the rays and outputs are in place."""
+        import torch
+
+        if self._inflight is not None:
+            self.query_sync()
+        if not stream:
+            torch.cuda.synchronize(self.device)
 
     def render_into(self, camera: capi.CameraDesc, params: capi.RenderParams, out_ptr: int, stream: int = 0) -> None:
         """Asynchronous on `stream` (a hipStream_t as int, 0 = the library's stream); `out_ptr` is device memory."""
@@ -77,10 +144,81 @@ class DeviceScene:
         capi.check(self._lib, self._lib.rayz_hip_scene_sync(self._h, C.byref(st)), "rayz_hip_scene_sync")
         return st
 
+    # ---- ray queries (`findHit`, include/rayz_hip.h: rayz_hip_scene_query*) ----
+    def query(self, rays, tmin: float = 1e-3, kind: str = "nearest", traversal: int = capi.TRAVERSAL_AUTO,
+              outputs=QUERY_OUTPUTS, stream: int = 0) -> "QueryResult":
+        """What each ray hits: `rays` is a torch tensor on the scene's device, (n, 8) {ox, oy, oz, time, dx, dy, dz, tmax},
+        float32 or float64 (which selects the precision).  kind "nearest" fills the requested `outputs` (any of QUERY_OUTPUTS),
+        "any" only `hit`.  Blocks for the bound check of the batch; the query itself is asynchronous on `stream` (0: the library's
+        stream, after torch's work on the device has finished; another stream must itself be ordered after the rays' producer).
+        The rays (their contiguous copy) and the outputs are kept alive by the scene until query_sync() or the next query."""
+        import torch
+
+        if not isinstance(rays, torch.Tensor) or not rays.is_cuda:
+            raise ValueError("rays must be a torch tensor in GPU memory")
+        if rays.device.index != self.device:
+            raise ValueError(f"rays are on cuda:{rays.device.index}, the scene on cuda:{self.device}")
+        if rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"rays must be (n, 8), got {tuple(rays.shape)}")
+        if rays.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"rays must be float32 or float64, got {rays.dtype}")
+        if kind not in ("nearest", "any"):
+            raise ValueError(f"kind must be 'nearest' or 'any', got {kind!r}")
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        if kind == "any":
+            outputs = ("hit",)
+        res = QueryResult._alloc((n,), rays.dtype, rays.device, outputs)
+        self._query_prologue(stream)
+        q = capi.QueryParams(n_rays=n, kind=capi.QUERY_ANY if kind == "any" else capi.QUERY_NEAREST,
+                             precision=capi.PRECISION_F64 if rays.dtype == torch.float64 else capi.PRECISION_F32,
+                             traversal=traversal, tmin=tmin)
+        rc = self._lib.rayz_hip_scene_query(self._h, C.byref(q), C.c_void_p(rays.data_ptr() if n else None),
+                                            C.byref(res._outputs()), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_scene_query")
+        self._inflight = (rays, res)
+        return res
+
+    def gbuffer(self, camera: capi.CameraDesc, params: capi.RenderParams, outputs=QUERY_OUTPUTS,
+                stream: int = 0) -> "QueryResult":
+        """The camera form: one lens-centre ray per pixel of `params`' shard (getRay(px, py, null)), results shaped
+        (rows_in_shard, width, ...) on the scene's device.  Asynchronous on `stream`; the outputs are kept alive by the scene until
+        query_sync() or the next query."""
+        import torch
+
+        rows = shard_rows(params)
+        dtype = torch.float64 if params.precision == capi.PRECISION_F64 else torch.float32
+        res = QueryResult._alloc((rows, params.width), dtype, torch.device("cuda", self.device), outputs)
+        self._query_prologue(stream)
+        rc = self._lib.rayz_hip_scene_query_camera(self._h, C.byref(camera), C.byref(params), C.byref(res._outputs()),
+                                                   C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_scene_query_camera")
+        self._inflight = (None, res)
+        return res
+
+    def pick(self, camera: capi.CameraDesc, params: capi.RenderParams, px: int, py: int) -> int:
+        """The hittable under pixel (px, py) of the frame `params` describes (-1: background): the camera form on the one-row
+        shard that holds row py (tile_rows 1, shard_count = height), so the ray is exactly that pixel's G-buffer ray.  Blocks."""
+        if not (0 <= px < params.width and 0 <= py < params.height):
+            raise ValueError(f"pixel ({px}, {py}) outside {params.width}x{params.height}")
+        p = capi.RenderParams.from_buffer_copy(params)
+        p.tile_rows, p.shard_count, p.shard_index = 1, params.height, py
+        r = self.gbuffer(camera, p, outputs=("index",))
+        self.query_sync()
+        return int(r.index[0, px].item())
+
+    def query_sync(self) -> capi.RenderStats:
+        """Waits for the last query on the scene; its counters (rayz_hip_query_sync)."""
+        st = capi.RenderStats()
+        capi.check(self._lib, self._lib.rayz_hip_query_sync(self._h, C.byref(st)), "rayz_hip_query_sync")
+        self._inflight = None
+        return st
+
     def close(self) -> None:
         if self._h:
-            self._lib.rayz_hip_scene_destroy(self._h)
+            self._lib.rayz_hip_scene_destroy(self._h)  # (waits for the scene's last launch)
             self._h = C.c_void_p()
+        self._inflight = None
 
     def __del__(self):
         try:
