@@ -434,7 +434,7 @@ typedef struct RayzQueryOutputs {
 
 /* A batch of rays: `d_rays` is DEVICE memory, n_rays x 8 values of the precision, {ox, oy, oz, time, dx, dy, dz, tmax} per ray.
  * Refused with RAYZ_ERR_BAD_ARG: a NaN or infinite origin, direction or time, an origin component beyond RAYZ_QUERY_MAX_ORIGIN,
- * a zero direction, a NaN tmax, a time outside [0, 1] (the BVH's moving-sphere boxes enclose the centre over [0, 1] only,
+ * a zero direction, a direction whose largest |component| lies outside [RAYZ_QUERY_MIN_DIR, RAYZ_QUERY_MAX_DIR], a NaN tmax, a time outside [0, 1] (the BVH's moving-sphere boxes enclose the centre over [0, 1] only,
  * Sphere.boundingBox).  tmax < tmin is allowed: a miss.
  * BLOCKING PART: a small reduction kernel over the batch finds max |origin|, the time range and the refusals, and the host waits for
  * those few values (the scan's reject radii and the BVH's f32 boxes are padded for a bound on every ray origin, DESIGN.md §4.3 /
@@ -445,6 +445,14 @@ typedef struct RayzQueryOutputs {
  * reject radii and boxes for good (for twice that bound), so later renders and queries on the scene test more candidates and
  * boxes — the same images, more work.  A caller that queries from far away and then renders again keeps a second scene. */
 #define RAYZ_QUERY_MAX_ORIGIN 1e9 /* largest |origin component| a query accepts: the padding stays finite in f32 */
+/* The accepted scale of a direction, 2^-32 <= max_k |d_k| <= 2^32.  `findHit` does not depend on the scale of d (d·2^k with
+ * tmin, tmax·2^-k is the same hit at t·2^-k), but the arithmetic does: beyond about 2^58 (F32: unit(d)'s d·d and the triangle
+ * test's det² overflow f32) and below about 2^-56 (the BVH's 1/d_k is capped at 2^64; F32: d·d underflows), and for F64 beyond
+ * the ±2^100 hold on d_k in front of the f32 box test, true hits are lost without an error.  The range keeps a factor of at least
+ * 2^16 to the first lost hit of every piece (measured on the CPU restatement: tests/test_query_exact_cpu.py).  This refusal, in
+ * ABI 5 as the others, rejects only inputs that gave wrong answers before. */
+#define RAYZ_QUERY_MIN_DIR 2.3283064365386962890625e-10 /* 2^-32 */
+#define RAYZ_QUERY_MAX_DIR 4294967296.0                 /* 2^32 */
 int rayz_hip_scene_query(RayzScene* scene, const RayzQueryParams* query, const void* d_rays, const RayzQueryOutputs* outputs,
                          void* hip_stream);
 /* The camera form: one ray per pixel of the shard `params` describes, camera_ray_no_rng — `getRay(px, py, null)`: the pixel's

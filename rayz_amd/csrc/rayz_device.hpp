@@ -3074,7 +3074,9 @@ void query_kernel_bvh(const QueryArgs<R> A) {
 
 // The bound check in front of a query (rayz_hip_scene_query): max |origin| (f64), the smallest and largest time, and flags —
 // 1: a NaN or infinite origin, direction or time; 2: a zero direction; 4: a NaN tmax; 8: an origin component beyond
-// RAYZ_QUERY_MAX_ORIGIN (tested before the norm is formed, so the norm cannot overflow).  out[0], out[kQueryBoundStride],
+// RAYZ_QUERY_MAX_ORIGIN (tested before the norm is formed, so the norm cannot overflow); 16: a non-zero direction whose largest
+// |component| lies outside [RAYZ_QUERY_MIN_DIR, RAYZ_QUERY_MAX_DIR] (include/rayz_hip.h: beyond that range the query arithmetic
+// loses true hits).  out[0], out[kQueryBoundStride],
 // out[2 kQueryBoundStride] hold order-preserving u64 keys (query_key) for atomicMax / atomicMin, out[3 kQueryBoundStride] the
 // flags: one 128-byte line each, so that the four words' atomics do not queue behind one another.  A workgroup reduces in LDS first
 // and sends ONE atomic per word (same-address atomics serialise: one per wave cost ≈0.2 ms on a 2·10^6-ray batch).  The host
@@ -3098,6 +3100,8 @@ template <class R> __global__ __launch_bounds__(256) void query_bounds_kernel(co
         if (dx == 0.0 && dy == 0.0 && dz == 0.0) flags |= 2ull;
         if (tx != tx) flags |= 4ull;
         if (finite && !near) flags |= 8ull;
+        const double dm = __builtin_fmax(__builtin_fabs(dx), __builtin_fmax(__builtin_fabs(dy), __builtin_fabs(dz)));
+        if (finite && dm != 0.0 && (dm < RAYZ_QUERY_MIN_DIR || dm > RAYZ_QUERY_MAX_DIR)) flags |= 16ull;
         if (finite && near) {
             const unsigned long long k = query_key(__builtin_sqrt(ox * ox + oy * oy + oz * oz));
             omax = k > omax ? k : omax;

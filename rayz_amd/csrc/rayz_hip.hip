@@ -1759,6 +1759,9 @@ template <class R> int query_bounds(RayzScene* s, const DeviceCtx& ctx, const R*
     if (flags & 1u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a NaN or infinite origin, direction or time");
     if (flags & 8u) return fail(RAYZ_ERR_BAD_ARG, "query rays: an origin component beyond RAYZ_QUERY_MAX_ORIGIN (%g)", (double)RAYZ_QUERY_MAX_ORIGIN);
     if (flags & 2u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a zero direction");
+    if (flags & 16u)
+        return fail(RAYZ_ERR_BAD_ARG, "query rays: a direction whose largest component lies outside [2^-32, 2^32] "
+                                      "(RAYZ_QUERY_MIN_DIR, RAYZ_QUERY_MAX_DIR)");
     if (flags & 4u) return fail(RAYZ_ERR_BAD_ARG, "query rays: a NaN tmax");
     const double tlo = query_unkey_host(got[kQueryBoundStride]), thi = query_unkey_host(got[2 * kQueryBoundStride]);
     if (tlo < 0.0 || thi > 1.0)
