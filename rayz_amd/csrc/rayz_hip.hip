@@ -284,7 +284,8 @@ struct RayzScene {
     unsigned long long* counters = nullptr; // [0] queue head, [1] segments
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipStream_t last_stream = nullptr;
-    bool rendered = false, last_bvh = false, last_two_paths = false, last_exchange = false;
+    bool rendered = false, last_bvh = false;
+    int last_experiment = 0; // the last render's BvhLaunchPlan::experiment (0: a product kernel)
     RayzRenderStats last{};
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
     unsigned long long* q_counters = nullptr; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
@@ -834,22 +835,73 @@ int check_items(uint64_t shard_pixels, uint64_t chunks) {
     return RAYZ_OK;
 }
 
-// Which trace kernel a launch used (scene_sync's measurement-build reports).
-struct LaunchKind {
-    bool two_paths = false, exchange = false;
+// What a trace launch runs.  trace_window fills it for the product kernels; with a BVH, experiment_override may then swap in a
+// retired kernel with its own workgroup and LDS needs.
+template <class R> struct BvhLaunchPlan {
+    void (*kernel)(const TraceArgs<R>);
+    int block;               // threads per workgroup
+    size_t stack_bytes;      // LDS: the per-lane traversal stacks, after the tree's top
+    size_t extra_lds_bytes;  // LDS: behind the oversized hittables' records (no product kernel has any)
+    uint32_t top_records;    // records of the tree's top the workgroup keeps in LDS, at most
+    uint32_t items_per_lane; // work items a lane holds at a time (sizes the grid)
+    int experiment;          // 0: a product kernel; else which retired kernel (scene_sync reports by it)
 };
+
+// The retired experiment kernels' host side (trace_kernel_bvh2: two paths per lane; trace_kernel_bvhx: walker / shader waves —
+// DESIGN.md §6): only a -DRAYZ_EXPERIMENTS build contains it.  The product build has these hooks instead: nothing to override or
+// report, and the refusals of the retired kernels' knobs.
+#ifdef RAYZ_EXPERIMENTS
+#include "experiments/launch.hpp"
+#else
+template <class R> int experiment_override(BvhLaunchPlan<R>&, TraceArgs<R>&, const RayzScene*, const SceneBuffers<R>&, const RayzRenderParams*) { return RAYZ_OK; }
+template <class R> void experiment_lds_placed(TraceArgs<R>&, uint32_t) {}
+inline int experiment_sync(int, const unsigned long long*) { return RAYZ_OK; }
+inline int experiment_knob_check(uint32_t knob, long long value) {
+    if (knob == RAYZ_DEBUG_BVH_KERNEL) {
+        if (value != 1) return fail(RAYZ_ERR_BAD_ARG, "BVH_KERNEL %lld: this build holds the one-path kernel only (the retired two-path "
+                                                      "experiment needs -DRAYZ_EXPERIMENTS)", value);
+        return RAYZ_OK;
+    }
+    if (knob == RAYZ_DEBUG_BVH2_KEEP) return fail(RAYZ_ERR_BAD_ARG, "BVH2_KEEP: the two-path kernel is not in this build (-DRAYZ_EXPERIMENTS)");
+    return fail(RAYZ_ERR_BAD_ARG, "BVHX: the exchange kernel is not in this build (-DRAYZ_EXPERIMENTS)");
+}
+#endif
+
+// The LDS request of a launch: `top_records` records of the tree's top (rec_bytes each) in front of `fixed_bytes` (stacks |
+// oversized hittables' records | ..).  The top was sized for kBvhLdsBudget, which this driver stack accepts; should a stack refuse
+// the request (hipFuncSetAttribute fails, or the occupancy query finds room for no workgroup), the launch keeps a SHORTER PREFIX
+// of the top instead of failing every BVH launch — the walk works with any prefix (records beyond it are read from global
+// memory), only slower.  Returns with the prefix kept in top_records, the bytes to ask for in `lds` and the workgroups a CU holds.
+// (A kernel without dynamic LDS, fixed_bytes = 0 and no top, passes with whatever the occupancy query says.)
+template <class K>
+int request_lds(K kernel, const char* what, int block, size_t rec_bytes, size_t fixed_bytes, uint32_t& top_records, size_t& lds, int& blocks_per_cu) {
+    for (;;) {
+        lds = (size_t)top_records * rec_bytes + fixed_bytes;
+        hipError_t e = hipSuccess;
+        if (lds > 64 * 1024) // a workgroup that asks for more than 64 KB of LDS has to say so first
+            e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, block, lds);
+        if (e == hipSuccess && (blocks_per_cu >= 1 || lds == 0)) return RAYZ_OK;
+        (void)hipGetLastError(); // (clear the sticky error of the refused request)
+        if (top_records == 0)
+            return fail(RAYZ_ERR_HIP, "the %s kernel cannot be launched with %zu bytes of LDS: %s", what, lds,
+                        e == hipSuccess ? "no workgroup fits a CU" : hipGetErrorString(e));
+        const uint32_t step = (uint32_t)(8192 / rec_bytes); // give back 8 KB of the top per try
+        top_records = top_records > step ? top_records - step : 0u;
+    }
+}
 
 // One launch of the trace kernel over the chunk WINDOW [c0, c1) of `p`'s shard (prepare_scene done, the device selected):
 // queue entry k · shard_pixels + i sums the samples of chunk c0 + k of the i-th pixel into the scene's workspace, partial[k ·
 // shard_pixels + local pixel] (grown here to the window).  `d_starts` is the device copy of the WHOLE schedule `starts`;
 // p->samples_per_px stays the total, so every sample keeps its stream (pixel · spp + s): a chunk's sum does not depend on the
 // window it is traced in.  The first `reset_bytes` of `counters` are cleared first (the queue head, counters[0], at least);
-// ev0 / ev1 bracket the kernel.
+// ev0 / ev1 bracket the kernel; `experiment` returns BvhLaunchPlan::experiment.
 template <class R>
 int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
                  bool use_bvh, const std::vector<uint32_t>& starts, const uint32_t* d_starts, uint32_t c0, uint32_t c1,
                  unsigned long long* counters, size_t reset_bytes, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream,
-                 LaunchKind& kind) {
+                 int& experiment) {
     typedef typename VecOf<R>::type r4;
     const uint32_t rows = rayz_hip_shard_rows(p);
     const uint64_t shard_pixels64 = (uint64_t)rows * p->width;
@@ -915,104 +967,49 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     A.tiled_pixels = p->width % 8 == 0 ? (uint32_t)((uint64_t)(rows / 8 * 8) * p->width) : 0u; // whole 8x8 tiles of the local rows (place_item)
     A.total_items = (uint32_t)items64;
     A.queue_grab = (uint32_t)std::max(1ll, tuning(RAYZ_DEBUG_QUEUE_GRAB, kQueueGrab));
-    // Which walk: one path per lane (trace_kernel_bvh).  The two-paths-per-lane form (trace_kernel_bvh2, f32 only: same image,
-    // 19 % slower) is a retired experiment: only a -DRAYZ_EXPERIMENTS build contains it (RAYZ_DEBUG_BVH_KERNEL = 2).
-#ifdef RAYZ_EXPERIMENTS
-    const bool two_paths = use_bvh && sizeof(R) == 4 && tuning(RAYZ_DEBUG_BVH_KERNEL, 1) == 2;
-    // .. and the walker / shader-wave form (trace_kernel_bvhx, f32 only): round 4's experiment, RAYZ_DEBUG_BVH_KERNEL = 3
-    const bool exchange = use_bvh && sizeof(R) == 4 && tuning(RAYZ_DEBUG_BVH_KERNEL, 1) == 3;
-#else
-    const bool two_paths = false, exchange = false;
-#endif
     // scheduling thresholds of the BVH kernel (no effect on results; rayz_hip_debug_set refuses values outside 1 .. 64 lanes)
     A.bvh_keep = (uint32_t)tuning(RAYZ_DEBUG_BVH_KEEP, kBvhKeepActive | (kBvhKeepStepping << 8));
-#ifdef RAYZ_EXPERIMENTS
-    if (two_paths)
-        A.bvh_keep = (uint32_t)tuning(RAYZ_DEBUG_BVH2_KEEP, kBvh2Service | (kBvh2Blocked << 8) | (kBvh2Swap << 16) | (kBvhKeepStepping << 24));
-#endif
 
-    const int block = (use_bvh && !two_paths) ? (int)kBvhWg : 256;
-    int blocks_per_cu = 0;
-    // the BVH kernel's LDS stack holds one entry per tree level below the root (nearer child first: the stack never
-    // holds more than one entry per level); sized from THIS tree, so a shallow tree does not cap the occupancy
-    // (+ one guard row under entry 0: a lane that has popped its sentinel reads ahead at index −1)
-    size_t bvh_stack_bytes = use_bvh ? ((size_t)s->bvh_dev.depth + 3) * block * sizeof(uint32_t) : 0;
-    size_t x_bytes = 0; // the exchange kernel's slot area (after the oversized hittables' records); only its walker waves have stacks
-#ifdef RAYZ_EXPERIMENTS
-    if (exchange) {
-        const long long xk = tuning(RAYZ_DEBUG_BVHX, -1);
-        const uint32_t ns = xk < 0 ? 24u : (uint32_t)(xk & 0xff), xmin = xk < 0 ? 12u : (uint32_t)((xk >> 8) & 0xff),
-                       xbatch = xk < 0 ? 48u : (uint32_t)((xk >> 16) & 0xff), xpat = xk < 0 ? 8u : (uint32_t)((xk >> 24) & 0xff),
-                       xprio = xk < 0 ? 0x6eu : (uint32_t)((xk >> 32) & 0xff); // shader | walker box steps << 2 | leaf / root phases << 4 | exchange << 6
-        A.x_slots = ns;
-        A.x_cfg = xmin | (xbatch << 8) | (xpat << 16) | (xprio << 24);
-        bvh_stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kXWalkerLanes * sizeof(uint32_t);
-        x_bytes = bvhx_exchange_bytes(ns);
-        if (p->max_bounces >= (1u << 30)) return fail(RAYZ_ERR_BAD_ARG, "the exchange kernel packs flags into the segment count: max_bounces < 2^30");
+    BvhLaunchPlan<R> plan{};
+    plan.kernel = trace_kernel<R, 1>;
+    plan.block = 256;
+    plan.items_per_lane = 1;
+    if (use_bvh) {
+        plan.kernel = b.quantized ? trace_kernel_bvh<R, true> : trace_kernel_bvh<R, false>;
+        plan.block = (int)kBvhWg;
+        // the BVH kernel's LDS stack holds one entry per tree level below the root (nearer child first: the stack never
+        // holds more than one entry per level); sized from THIS tree, so a shallow tree does not cap the occupancy
+        // (+ one guard row under entry 0: a lane that has popped its sentinel reads ahead at index −1)
+        plan.stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kBvhWg * sizeof(uint32_t);
+        // the tree's top: first in LDS.  The scene numbered b.bvh_top records breadth-first for this kernel's workgroup
+        plan.top_records = b.bvh_top;
+        rc = experiment_override<R>(plan, A, s, b, p); // (the product build: nothing)
+        if (rc != RAYZ_OK) return rc;
     }
-#endif
-    // the tree's top: first in LDS.  The scene numbered b.bvh_top records breadth-first for the one-path kernel's workgroup;
-    // a kernel whose workgroup has less LDS to spare (two paths per lane: three 256-thread workgroups per CU) keeps a prefix
-    uint32_t top_records = use_bvh ? b.bvh_top : 0u;
-    if (two_paths) top_records = std::min<uint32_t>(top_records, b.quantized ? 512u : 256u);
-    if (exchange) { // what the walkers' stacks and the slots leave of the budget
-        const size_t fixed = bvh_stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0) + x_bytes;
-        const size_t room = fixed < kBvhLdsBudget ? kBvhLdsBudget - fixed : 0;
-        top_records = std::min<uint32_t>(top_records, (uint32_t)(room / (b.quantized ? 32 : 64)));
-        const long long cap = tuning(RAYZ_DEBUG_BVH_TOP, -1);
-        if (cap >= 0) top_records = std::min<uint32_t>(top_records, (uint32_t)cap);
-    }
-    typedef void (*Kernel)(const TraceArgs<R>);
-    Kernel kernel = trace_kernel<R, 1>;
-    if (use_bvh) kernel = b.quantized ? trace_kernel_bvh<R, true> : trace_kernel_bvh<R, false>;
-#ifdef RAYZ_EXPERIMENTS
-    if (two_paths) {
-        if constexpr (sizeof(R) == 4) kernel = b.quantized ? trace_kernel_bvh2<float, true> : trace_kernel_bvh2<float, false>;
-    }
-    if (exchange) {
-        if constexpr (sizeof(R) == 4) kernel = b.quantized ? trace_kernel_bvhx<true> : trace_kernel_bvhx<false>;
-    }
-#endif
+    experiment = plan.experiment;
     // The LDS request: top | stacks | oversized hittables' records (+ RAYZ_DEBUG_LDS_PAD unused bytes: an occupancy experiment —
-    // fewer workgroups per CU, the same code).  The top was sized for kBvhLdsBudget, which this driver stack accepts; should a
-    // stack refuse the request (hipFuncSetAttribute fails, or the occupancy query finds room for no workgroup), the launch keeps
-    // a SHORTER PREFIX of the top instead of failing every BVH render — the walk works with any prefix (records beyond it are
-    // read from global memory), only slower.
+    // fewer workgroups per CU, the same code), the top shortened should the request be refused (request_lds)
+    const size_t big_bytes = use_bvh && b.n_big_leaves ? kBvhBigLdsBytes : 0;
+    const size_t bvh_fixed = use_bvh ? plan.stack_bytes + big_bytes + plan.extra_lds_bytes + (size_t)tuning(RAYZ_DEBUG_LDS_PAD, 0) : 0;
     const size_t rec_bytes = b.quantized ? 32 : 64;
-    const size_t bvh_fixed = use_bvh ? bvh_stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0) + x_bytes + (size_t)tuning(RAYZ_DEBUG_LDS_PAD, 0) : 0;
-    size_t bvh_top_bytes = 0, bvh_lds = 0;
-    for (;;) {
-        bvh_top_bytes = (size_t)top_records * rec_bytes;
-        bvh_lds = bvh_top_bytes + bvh_fixed;
-        hipError_t e = hipSuccess;
-        if (use_bvh && bvh_lds > 64 * 1024) // a workgroup that asks for more than 64 KB of LDS has to say so first
-            e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bvh_lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, block, use_bvh ? bvh_lds : 0);
-        if (e == hipSuccess && (blocks_per_cu >= 1 || !use_bvh)) break;
-        (void)hipGetLastError(); // (clear the sticky error of the refused request)
-        if (!use_bvh || top_records == 0)
-            return fail(RAYZ_ERR_HIP, "the trace kernel cannot be launched with %zu bytes of LDS: %s", bvh_lds,
-                        e == hipSuccess ? "no workgroup fits a CU" : hipGetErrorString(e));
-        const uint32_t step = (uint32_t)(8192 / rec_bytes); // give back 8 KB of the top per try
-        top_records = top_records > step ? top_records - step : 0u;
-    }
+    size_t bvh_lds = 0;
+    int blocks_per_cu = 0;
+    rc = request_lds(plan.kernel, "trace", plan.block, rec_bytes, bvh_fixed, plan.top_records, bvh_lds, blocks_per_cu);
+    if (rc != RAYZ_OK) return rc;
+    const size_t bvh_top_bytes = (size_t)plan.top_records * rec_bytes;
     A.bvh_top_words = (uint32_t)(bvh_top_bytes / sizeof(uint32_t));
-    A.bvh_big_words = (uint32_t)((bvh_top_bytes + bvh_stack_bytes) / sizeof(uint32_t));
+    A.bvh_big_words = (uint32_t)((bvh_top_bytes + plan.stack_bytes) / sizeof(uint32_t));
     A.sc.bvh_top = (uint32_t)bvh_top_bytes; // the walk compares byte offsets
-#ifdef RAYZ_EXPERIMENTS
-    A.x_words = (uint32_t)((bvh_top_bytes + bvh_stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0)) / sizeof(uint32_t));
-#endif
+    experiment_lds_placed<R>(A, (uint32_t)((bvh_top_bytes + plan.stack_bytes + big_bytes) / sizeof(uint32_t)));
     if (blocks_per_cu < 1) blocks_per_cu = 1;
     uint64_t grid = (uint64_t)ctx.num_cu * blocks_per_cu;
-    // (a lane of the two-path kernel holds two items)
-    const uint64_t want = (items64 + (two_paths ? 2 : 1) * block - 1) / ((two_paths ? 2 : 1) * block);
+    const uint64_t per_block = (uint64_t)plan.items_per_lane * plan.block;
+    const uint64_t want = (items64 + per_block - 1) / per_block;
     if (grid > want) grid = want;
 
-    kind.two_paths = two_paths;
-    kind.exchange = exchange;
     HIP_TRY(hipMemsetAsync(counters, 0, reset_bytes, stream));
     HIP_TRY(hipEventRecord(ev0, stream));
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(block), use_bvh ? bvh_lds : 0, stream, A);
+    hipLaunchKernelGGL(plan.kernel, dim3((uint32_t)grid), dim3(plan.block), bvh_lds, stream, A);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, stream));
     return RAYZ_OK;
@@ -1040,7 +1037,7 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
     s->last = RayzRenderStats{};
     s->last.primary_rays = shard_pixels64 * p->samples_per_px;
     s->last_bvh = use_bvh;
-    s->last_two_paths = false;
+    s->last_experiment = 0;
     if (items64 == 0) {
         s->rendered = false;
         return RAYZ_OK;
@@ -1069,11 +1066,8 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         HIP_TRY(hipEventCreate(&s->ev0));
         HIP_TRY(hipEventCreate(&s->ev1));
     }
-    LaunchKind kind;
     rc = trace_window<R>(s, ctx, b, cam, p, use_bvh, starts, s->chunk_start, 0, chunks_per_px, s->counters,
-                         32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, kind);
-    s->last_two_paths = kind.two_paths;
-    s->last_exchange = kind.exchange;
+                         32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, s->last_experiment);
     if (rc != RAYZ_OK) return rc;
     hipLaunchKernelGGL(resolve_kernel<R>, dim3((uint32_t)((shard_pixels64 + 255) / 256)), dim3(256), 0, stream,
                        (const r4*)s->partial, d_out, (uint32_t)shard_pixels64, chunks_per_px, p->samples_per_px);
@@ -1146,32 +1140,8 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
                          100.0 * c[6] / tot, 100.0 * c[7] / tot, 100.0 * c[8] / tot);
         }
 #endif
-#ifdef RAYZ_BVH_PROFILE // measurement build only: per-phase wave time and lane occupancy of the BVH kernels
-        if (s->last_bvh && s->last_exchange) {
-            const double wt = (double)(c[4] + c[5] + c[6]), stt = (double)(c[12] + c[13] + c[14]);
-            std::fprintf(stderr, "bvhx walkers (share of wave time): exchange %.1f%% | idle (nobody walks) %.1f%% | rounds %.1f%%; per exchange: %.0f ticks; "
-                                 "at the start of a run of rounds: %.1f lanes walking, %.1f lanes hold a path; runs of rounds %.3g, exchanges %.3g\n",
-                         100.0 * c[4] / wt, 100.0 * c[5] / wt, 100.0 * c[6] / wt, (double)c[4] / (double)(c[7] ? c[7] : 1), (double)c[8] / (double)(c[10] ? c[10] : 1),
-                         (double)c[9] / (double)(c[10] ? c[10] : 1), (double)c[10], (double)c[7]);
-            std::fprintf(stderr, "bvhx shaders (share of wave time): idle, nothing finished %.1f%% | waiting for a batch %.1f%% | pass %.1f%% (%.0f ticks per pass); "
-                                 "%.1f paths per pass, %.1f finished slots seen; passes %.3g\n",
-                         100.0 * c[12] / stt, 100.0 * c[13] / stt, 100.0 * c[14] / stt, (double)c[14] / (double)(c[15] ? c[15] : 1),
-                         (double)c[16] / (double)(c[15] ? c[15] : 1), (double)c[17] / (double)(c[15] ? c[15] : 1), (double)c[15]);
-        } else
-        if (s->last_bvh && s->last_two_paths) {
-            const double tot = (double)(c[4] + c[5] + c[6] + c[7] + c[8]);
-            auto per = [&](int k) { return (double)c[9 + k] / (double)(c[10 + k] ? c[10 + k] : 1); };
-            std::fprintf(stderr,
-                         "bvh2 phases (share of wave time | mean lanes): service %.1f%% %.1f | swap %.1f%% %.1f | N %.1f%% %.1f | L %.1f%% %.1f | "
-                         "C %.1f%% %.1f\n",
-                         100.0 * c[4] / tot, per(0), 100.0 * c[5] / tot, per(2), 100.0 * c[6] / tot, per(4), 100.0 * c[7] / tot, per(6),
-                         100.0 * c[8] / tot, per(8));
-            const double it = (double)(c[14] ? c[14] : 1);
-            std::fprintf(stderr, "  box steps: lanes per wave-step — stepping %.1f | parked at a leaf %.1f | walker idle %.1f; wave-steps per segment "
-                                 "%.2f; service passes %.3g, swaps %.3g, leaf phases %.3g\n",
-                         per(4), (double)c[19] / it, (double)c[20] / it, it / (double)(c[1] ? c[1] : 1), (double)c[10], (double)c[12], (double)c[16]);
-        } else
-        if (s->last_bvh) {
+#ifdef RAYZ_BVH_PROFILE // measurement build only: per-phase wave time and lane occupancy of the BVH kernel
+        if (s->last_bvh && !s->last_experiment) {
             const double tot = (double)(c[4] + c[5] + c[6] + c[7] + c[8]);
             std::fprintf(stderr,
                          "bvh phases (share of wave time | mean active lanes): refill %.1f%% | N %.1f%% %.1f | L %.1f%% %.1f | C %.1f%% "
@@ -1188,8 +1158,10 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
                          100.0 * (double)c[19] / (double)(c[5] ? c[5] : 1), (double)c[19] / it);
         }
 #endif
-        if (s->last_bvh && c[31] == 2)
-            return fail(RAYZ_ERR_STATE, "the exchange kernel gave up waiting for a hand-over between its waves (bounded wait, no result)");
+        if (s->last_experiment) { // a retired kernel ran: its phase profile (measurement builds) and its abort flag
+            const int rc = experiment_sync(s->last_experiment, c);
+            if (rc != RAYZ_OK) return rc;
+        }
         if (s->last_bvh && c[31])
             return fail(RAYZ_ERR_STATE, "trace_kernel_bvh refused to run: its dynamic LDS segment does not start at LDS address 0");
         float ms = 0;
@@ -1388,9 +1360,9 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
         pr->spare.pop_back();
         s->last_stream = stream;
         pr->last_stream = stream;
-        LaunchKind kind;
+        int experiment = 0; // (the passes' counters are not reported)
         rc = trace_window<R>(s, *ctx, *b, &pr->cam, &pr->params, use_bvh, pr->starts, pr->d_starts, c0, c1, pr->counters,
-                             sizeof(unsigned long long), ev0, ev1, stream, kind);
+                             sizeof(unsigned long long), ev0, ev1, stream, experiment);
         if (rc != RAYZ_OK) {
             pr->spare.push_back(ev0);
             pr->spare.push_back(ev1);
@@ -1854,24 +1826,11 @@ int query_impl(RayzScene* s, const DeviceCtx& ctx, uint32_t kind, uint32_t trave
         kernel = b.quantized ? query_kernel_bvh<R, true> : query_kernel_bvh<R, false>;
         block = (int)kBvhWg;
         const size_t stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kBvhWg * sizeof(uint32_t);
-        const size_t fixed = stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0);
         const size_t rec_bytes = b.quantized ? 32 : 64;
         uint32_t top_records = b.bvh_top;
-        size_t top_bytes = 0;
-        for (;;) {
-            top_bytes = (size_t)top_records * rec_bytes;
-            lds = top_bytes + fixed;
-            hipError_t e = hipSuccess;
-            if (lds > 64 * 1024) e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, block, lds);
-            if (e == hipSuccess && blocks_per_cu >= 1) break;
-            (void)hipGetLastError();
-            if (top_records == 0)
-                return fail(RAYZ_ERR_HIP, "the query kernel cannot be launched with %zu bytes of LDS: %s", lds,
-                            e == hipSuccess ? "no workgroup fits a CU" : hipGetErrorString(e));
-            const uint32_t step = (uint32_t)(8192 / rec_bytes);
-            top_records = top_records > step ? top_records - step : 0u;
-        }
+        const int rc = request_lds(kernel, "query", block, rec_bytes, stack_bytes + (b.n_big_leaves ? kBvhBigLdsBytes : 0), top_records, lds, blocks_per_cu);
+        if (rc != RAYZ_OK) return rc;
+        const size_t top_bytes = (size_t)top_records * rec_bytes;
         A.bvh_top_words = (uint32_t)(top_bytes / sizeof(uint32_t));
         A.bvh_big_words = (uint32_t)((top_bytes + stack_bytes) / sizeof(uint32_t));
         A.sc.bvh_top = (uint32_t)top_bytes;
@@ -1960,30 +1919,10 @@ int rayz_hip_debug_set(uint32_t knob, long long value) {
                 return fail(RAYZ_ERR_BAD_ARG, "BVH_KEEP 0x%llx: both thresholds must be 1 .. 64 lanes", (unsigned long long)value);
             break;
         case RAYZ_DEBUG_BVH_KERNEL:
-#ifdef RAYZ_EXPERIMENTS
-            if (value < 1 || value > 3) return fail(RAYZ_ERR_BAD_ARG, "BVH_KERNEL %lld: 1, 2 or 3", value);
-#else
-            if (value != 1) return fail(RAYZ_ERR_BAD_ARG, "BVH_KERNEL %lld: this build holds the one-path kernel only (the retired two-path "
-                                                          "experiment needs -DRAYZ_EXPERIMENTS)", value);
-#endif
-            break;
-        case RAYZ_DEBUG_BVH2_KEEP: // service | blocked << 8 | swap << 16 | keep_stepping << 24
-#ifdef RAYZ_EXPERIMENTS
-            if (value >> 32 || !lane_count(value & 0xff) || !lane_count((value >> 8) & 0xff) || !lane_count((value >> 16) & 0xff) ||
-                !lane_count((value >> 24) & 0xff))
-                return fail(RAYZ_ERR_BAD_ARG, "BVH2_KEEP 0x%llx: every threshold must be 1 .. 64 lanes", (unsigned long long)value);
-#else
-            return fail(RAYZ_ERR_BAD_ARG, "BVH2_KEEP: the two-path kernel is not in this build (-DRAYZ_EXPERIMENTS)");
-#endif
-            break;
-        case RAYZ_DEBUG_BVHX: { // slots | exchange threshold << 8 | minimum batch << 16 | patience << 24 | priority << 32
-#ifdef RAYZ_EXPERIMENTS
-            const long long ns = value & 0xff;
-            if (value >> 40 || ns < 4 || ns > 64 || (ns & 1) || !lane_count((value >> 8) & 0xff) || !lane_count((value >> 16) & 0xff))
-                return fail(RAYZ_ERR_BAD_ARG, "BVHX 0x%llx: slots even 4 .. 64, thresholds 1 .. 64 lanes", (unsigned long long)value);
-#else
-            return fail(RAYZ_ERR_BAD_ARG, "BVHX: the exchange kernel is not in this build (-DRAYZ_EXPERIMENTS)");
-#endif
+        case RAYZ_DEBUG_BVH2_KEEP:
+        case RAYZ_DEBUG_BVHX: { // the retired kernels' knobs: checked in experiments/launch.hpp, refused by the product build
+            const int rc = experiment_knob_check(knob, value);
+            if (rc != RAYZ_OK) return rc;
             break;
         }
         case RAYZ_DEBUG_CHUNK_CAP:

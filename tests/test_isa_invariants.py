@@ -118,3 +118,6 @@ def test_experiments_build_still_compiles(tmp_path):
                     os.path.join(ROOT, "rayz_amd", "csrc", "rayz_hip.hip")], check=True, capture_output=True, timeout=600)
     text = asm.read_text()
     assert "trace_kernel_bvh2" in text and "trace_kernel_bvhx" in text
+    # .. and they stay out of the product's device header (their sources: rayz_amd/csrc/experiments/), so the move does not quietly revert
+    header = open(os.path.join(ROOT, "rayz_amd", "csrc", "rayz_device.hpp")).read()
+    assert "void trace_kernel_bvh2(" not in header and "void trace_kernel_bvhx(" not in header

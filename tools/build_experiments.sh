@@ -6,6 +6,8 @@
 set -e
 cd "$(dirname "$0")/.."
 S=${1:-4}; shift || true
+# (with fewer than 4 shader waves every launch of the exchange kernel ends in its 2^22-poll abort after a long stall)
+case "$S" in 4|5|6) ;; *) echo "build_experiments.sh: shader waves must be 4, 5 or 6 (got '$S')" >&2; exit 2 ;; esac
 mkdir -p variants
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-gpu-flush-denormals-to-zero -fhip-fp32-correctly-rounded-divide-sqrt \
       -DRAYZ_EXPERIMENTS -DRAYZ_BVHX_SHADERS=$S "$@" -shared -o variants/lib_experiments_s$S.so rayz_amd/csrc/rayz_hip.hip rayz_amd/host/rayz_host.cpp
