@@ -209,7 +209,9 @@ typedef enum RayzDebugKnob {
                                      shader's minimum batch << 16 | its patience << 24 | its priority << 32 */
     RAYZ_DEBUG_CHUNK_CAP = 11,    /* -DRAYZ_EXPERIMENTS builds only, refused otherwise — it CHANGES the image's summation tree (the one knob that
                                      does; tools/chunk_cap_sweep.py): largest chunk of the automatic schedule */
-    RAYZ_DEBUG_KNOBS = 12
+    RAYZ_DEBUG_DENOISE_LDS_STRIDE = 12, /* denoiser: the largest stride whose level stages tile + halo in LDS — 0 (every level reads its taps from
+                                     global memory), 1, 2 or 4; the same image either way */
+    RAYZ_DEBUG_KNOBS = 13
 } RayzDebugKnob;
 int rayz_hip_debug_set(uint32_t knob, long long value);
 
@@ -464,6 +466,50 @@ int rayz_hip_scene_query_camera(RayzScene* scene, const RayzCameraDesc* camera, 
 /* Waits for the scene's last query and returns its counters: primary_rays = segments = rays, node_tests and sphere_tests as
  * renders count them (flat list: rays x hittables), kernel_ms = the query kernel's HIP-event time. */
 int rayz_hip_query_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
+
+/* ---- denoising: a G-buffer-guided à-trous filter for low-spp frames -------------------------------------------------
+ * BUILD-DEFINED (the reference has no denoiser): an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) on a WHOLE f32
+ * frame in DEVICE memory, guided by the G-buffer a rayz_hip_scene_query_camera call of F32 precision filled for the same camera
+ * and frame size.  The arithmetic is a contract, DESIGN.md §4.11 (+ - x, explicit FMAs, correctly rounded divides, comparisons;
+ * no transcendental), restated bit for bit on the CPU by tests/denoise_mirror.cpp.  Added in ABI 5 (additive: no existing symbol
+ * changed); it changes no image any other entry point produces.
+ * Limits of this version: whole frames only (rows of a shard are not image neighbours: gather first); f32 only; the guides are
+ * FIRST-HIT guides, so what a metallic or dielectric surface reflects or refracts is filtered as if it were painted on it. */
+typedef struct RayzDenoiser RayzDenoiser; /* opaque: packed guides + two colour buffers for one frame size on one device */
+
+#define RAYZ_DENOISE_ALBEDO 0x1u      /* demodulate: filter c / max(albedo, 2^-8) and multiply it back in (needs gbuffer->albedo) */
+#define RAYZ_DENOISE_DEFAULT_LEVELS 5u
+#define RAYZ_DENOISE_DEFAULT_NORMAL_POWER_LOG2 6u
+#define RAYZ_DENOISE_DEFAULT_SIGMA_COLOR 0.5  /* the sigmas: picked on the CPU restatement; parameters, not contract */
+#define RAYZ_DENOISE_DEFAULT_SIGMA_PLANE 0.25
+#define RAYZ_DENOISE_MAX_PIXELS 1073741824u /* 2^30: the largest width*height a handle accepts (RAYZ_ERR_BAD_ARG beyond) */
+
+typedef struct RayzDenoiseParams {
+    uint32_t levels;            /* 1..8 levels of stride 1, 2, 4, ..; 0 = RAYZ_DENOISE_DEFAULT_LEVELS */
+    uint32_t normal_power_log2; /* the normal weight max(0, n_p.n_q) is squared this many times, 0..16 (taken as given: 0 = not squared) */
+    uint32_t flags;             /* RAYZ_DENOISE_ALBEDO or 0 */
+    uint32_t _pad;
+    double sigma_color;         /* > 0; +inf switches the colour term off exactly.  Used as f32; its f32 square must be > 0 */
+    double sigma_plane;         /* > 0: the sine of the angle out of the centre pixel's tangent plane at which a tap's weight reaches 0 */
+} RayzDenoiseParams;
+
+/* device < 0: the default device (RAYZ_ERR_NO_DEVICE before rayz_hip_init); otherwise creates that device's context if needed.
+ * RAYZ_ERR_BAD_ARG: a zero size, or width*height > RAYZ_DENOISE_MAX_PIXELS. */
+int rayz_hip_denoiser_create(int device, uint32_t width, uint32_t height, RayzDenoiser** out);
+/* d_rgb_in, d_rgb_out: DEVICE memory, height*width*3 floats, packed RGB as renders write it; d_rgb_out == d_rgb_in is allowed.
+ * `gbuffer`: index, normal and point are required, albedo unless RAYZ_DENOISE_ALBEDO is off; the other fields are ignored.
+ * params == NULL: all defaults.  Asynchronous on `hip_stream` (NULL: the library's stream of the handle's device); the inputs
+ * must stay allocated until the run has finished.  One run in flight per handle: a run first makes its stream wait, on the
+ * device, for the handle's previous run (through an event of the handle's own, so the previous run's stream may have been
+ * destroyed by then; _destroy waits the same way).
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): levels > 8, normal_power_log2 > 16, a sigma that is
+ * not positive (NaN included), unknown flag bits, a missing required pointer.  RAYZ_ERR_STATE: a bad handle. */
+int rayz_hip_denoiser_run(RayzDenoiser* dn, const RayzDenoiseParams* params, const float* d_rgb_in,
+                          const RayzQueryOutputs* gbuffer, float* d_rgb_out, void* hip_stream);
+/* Waits for the handle's last run and returns its HIP-event times: *levels_or_null = L, the levels it ran; ms_or_null[0] = the
+ * pack pass, ms_or_null[1 + l] = level l, for as many of the L + 1 entries as `capacity` holds.  RAYZ_ERR_STATE before any run. */
+int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);
+int rayz_hip_denoiser_destroy(RayzDenoiser* dn);
 
 #ifdef __cplusplus
 }

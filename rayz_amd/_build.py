@@ -41,7 +41,8 @@ def _stale(target: str, sources: list[str]) -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     lib_src = [os.path.join(CSRC, "rayz_hip.hip"), os.path.join(HOST, "rayz_host.cpp")]
     deps = lib_src + [
-        os.path.join(CSRC, "rayz_device.hpp"), os.path.join(CSRC, "plane_runs.hpp"), os.path.join(CSRC, "bvh_build.hpp"), os.path.join(HOST, "rayz.hpp"),
+        os.path.join(CSRC, "rayz_device.hpp"), os.path.join(CSRC, "plane_runs.hpp"), os.path.join(CSRC, "bvh_build.hpp"), os.path.join(CSRC, "denoise.hpp"),
+        os.path.join(HOST, "rayz.hpp"),
         # (compiled only with -DRAYZ_EXPERIMENTS, but files rayz_hip.hip can include: an edit must not leave a stale library)
         *(os.path.join(CSRC, "experiments", f) for f in ("bvh2_kernel.hpp", "bvhx_kernel.hpp", "launch.hpp")),
         os.path.join(ROOT, "include", "rayz_hip.h"), os.path.join(ROOT, "include", "rayz_host.h"),

@@ -17,7 +17,8 @@ MAX_DEVICES = 64
 GATHER_RCCL, GATHER_PEER_COPY = 0, 1
 GATHER_ALLOW_DUPLICATE_DEVICES = 0x100  # flag bit, peer-copy only (tests on a one-GPU box)
 (DEBUG_QUEUE_GRAB, DEBUG_BVH_KEEP, DEBUG_BVH_PEEL, DEBUG_BVH_TOP, DEBUG_BVH_KERNEL, DEBUG_BVH2_KEEP,
- DEBUG_LDS_PAD, DEBUG_BVH_TOP_ORDER, DEBUG_BVH_NODES, DEBUG_BVH_SPLIT, DEBUG_BVHX, DEBUG_CHUNK_CAP) = range(12)
+ DEBUG_LDS_PAD, DEBUG_BVH_TOP_ORDER, DEBUG_BVH_NODES, DEBUG_BVH_SPLIT, DEBUG_BVHX, DEBUG_CHUNK_CAP,
+ DEBUG_DENOISE_LDS_STRIDE) = range(13)
 (KAT_REFRACT, KAT_REFLECTANCE, KAT_GET_RAY, KAT_BOX_HIT, KAT_SPHERE_HIT, KAT_SCATTER, KAT_CHECKER, KAT_BACKGROUND,
  KAT_TRIANGLE_HIT, KAT_SCAN_DISCS) = range(10)
 KAT_IN_STRIDE, KAT_OUT_STRIDE = 48, 12
@@ -35,6 +36,8 @@ DIFFUSE_UNIT_SPHERE, DIFFUSE_UNIT_SPHERE_SURFACE, DIFFUSE_HEMISPHERE = 0, 1, 2
 PRECISION_F32, PRECISION_F64 = 0, 1
 TRAVERSAL_LINEAR, TRAVERSAL_BVH, TRAVERSAL_AUTO = 0, 1, 2
 QUERY_NEAREST, QUERY_ANY = 0, 1
+DENOISE_ALBEDO = 1
+DENOISE_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 0.5, "sigma_plane": 0.25}
 
 D3 = C.c_double * 3
 
@@ -91,10 +94,15 @@ class QueryOutputs(C.Structure):
                 ("front_face", C.c_void_p), ("material", C.c_void_p), ("albedo", C.c_void_p), ("hit", C.c_void_p)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_plane", C.c_double)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
-assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64
+assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -154,6 +162,11 @@ PROTOTYPES = [
     ("rayz_hip_scene_query_camera", C.c_int,
      [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(QueryOutputs), C.c_void_p]),
     ("rayz_hip_query_sync", C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
+    ("rayz_hip_denoiser_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("rayz_hip_denoiser_run", C.c_int,
+     [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p]),
+    ("rayz_hip_denoiser_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]),
+    ("rayz_hip_denoiser_destroy", C.c_int, [C.c_void_p]),
 ]
 
 

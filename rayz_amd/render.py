@@ -287,6 +287,81 @@ class Progressive:
             pass
 
 
+class Denoiser:
+    """A G-buffer-guided à-trous filter for whole float32 frames of one size (`rayz_hip_denoiser_*`):
+    `run(frame, scene.gbuffer(camera, params))` returns the filtered frame.  `device` None: the default device of init()."""
+
+    def __init__(self, width: int, height: int, device: int | None = None):
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        self.width, self.height = int(width), int(height)
+        capi.check(self._lib, self._lib.rayz_hip_denoiser_create(-1 if device is None else device, self.width, self.height,
+                                                                 C.byref(self._h)), "rayz_hip_denoiser_create")
+        self._device = device if device is not None else _default_device
+        self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
+
+    def run(self, rgb, gbuffer: "QueryResult", out=None, stream: int = 0, **params):
+        """Filters `rgb` ((height, width, 3) float32 on the handle's device) guided by `gbuffer` (index, normal, point and — unless
+        flags drops DENOISE_ALBEDO — albedo of a float32 camera query of the same frame) into `out` (default: a new tensor;
+        `out=rgb` filters in place).  `params`: the fields of RayzDenoiseParams (levels, normal_power_log2, flags, sigma_color,
+        sigma_plane); unnamed ones take capi.DENOISE_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
+        work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
+        import torch
+
+        unknown = set(params) - set(capi.DENOISE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown denoise parameter(s) {sorted(unknown)}; choose from {sorted(capi.DENOISE_DEFAULTS)}")
+        prm = capi.DenoiseParams(**{**capi.DENOISE_DEFAULTS, **params})
+        frame = (self.height, self.width, 3)
+        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
+        tensors = [("rgb", rgb, torch.float32, frame)]
+        for k in need:
+            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
+                            frame[:2] if k == "index" else frame))
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=torch.device("cuda", self._device))
+        tensors.append(("out", out, torch.float32, frame))
+        for name, t, dtype, shape in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"{name} must be a torch tensor in GPU memory")
+            if t.device.index != self._device:
+                raise ValueError(f"{name} is on cuda:{t.device.index}, the denoiser on cuda:{self._device}")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if not stream:
+            torch.cuda.synchronize(self._device)
+        o = capi.QueryOutputs()
+        for k in need:
+            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        rc = self._lib.rayz_hip_denoiser_run(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
+                                             C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_denoiser_run")
+        self._inflight = (rgb, gbuffer, out)
+        return out
+
+    def timing(self):
+        """Waits for the last run; its HIP-event times in ms: (pack pass, [level 0, level 1, ..]) (`rayz_hip_denoiser_timing`)."""
+        n, ms = C.c_uint32(), (C.c_float * 9)()
+        capi.check(self._lib, self._lib.rayz_hip_denoiser_timing(self._h, C.byref(n), ms, 9), "rayz_hip_denoiser_timing")
+        return ms[0], [ms[1 + l] for l in range(n.value)]
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.rayz_hip_denoiser_destroy(self._h)  # (waits for the handle's last run)
+            self._h = C.c_void_p()
+        self._inflight = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MultiScene:
     """The pool replicated on several GPUs of the node (`rayz_hip_multi_create`): one call renders the whole frame —
     rows dealt to the devices in interleaved tiles, one RCCL gather (or peer copies) to devices[0], host output."""
