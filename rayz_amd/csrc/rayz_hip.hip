@@ -27,7 +27,9 @@
 #include <atomic>
 #include <new>
 #include <queue>
+#include <memory>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 using namespace rayz_dev;
@@ -94,6 +96,82 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
+// The owners of everything this file allocates on a device.  Both are move-only and remember the HIP ordinal that was current
+// when they allocated: reset() and the destructor free with that device selected, whatever the calling thread's is.
+// DevBuf<T>: one hipMalloc allocation of capacity() elements (DevBuf<char>: bytes).
+template <class T> class DevBuf {
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+    int dev_ = -1;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr), cap_ = std::exchange(o.cap_, 0), dev_ = o.dev_;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (!p_) return;
+        DeviceScope scope(dev_);
+        (void)hipFree(p_);
+        p_ = nullptr, cap_ = 0;
+    }
+    hipError_t alloc(size_t n) { // (no elements: 16 bytes all the same, so that get() is a pointer a kernel may be handed)
+        reset();
+        hipError_t e = hipGetDevice(&dev_);
+        if (e == hipSuccess) e = hipMalloc((void**)&p_, n ? n * sizeof(T) : 16);
+        if (e == hipSuccess) cap_ = n;
+        else p_ = nullptr;
+        return e;
+    }
+    hipError_t upload(const std::vector<T>& v) {
+        const hipError_t e = alloc(v.size());
+        return e == hipSuccess && !v.empty() ? hipMemcpy(p_, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) : e;
+    }
+    // Grow-only: frees first, so the caller has waited for whatever may still use the old allocation.
+    hipError_t grow(size_t n) { return p_ && n <= cap_ ? hipSuccess : alloc(n); }
+    size_t capacity() const { return cap_; }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+};
+typedef DevBuf<char> DevBytes;
+
+class DevEvent {
+    hipEvent_t ev_ = nullptr;
+    int dev_ = -1;
+
+public:
+    DevEvent() = default;
+    DevEvent(DevEvent&& o) noexcept { *this = std::move(o); }
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        if (this != &o) {
+            reset();
+            ev_ = std::exchange(o.ev_, nullptr), dev_ = o.dev_;
+        }
+        return *this;
+    }
+    ~DevEvent() { reset(); }
+    void reset() {
+        if (!ev_) return;
+        DeviceScope scope(dev_);
+        (void)hipEventDestroy(ev_);
+        ev_ = nullptr;
+    }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        reset();
+        hipError_t e = hipGetDevice(&dev_);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_, flags);
+        if (e != hipSuccess) ev_ = nullptr;
+        return e;
+    }
+    operator hipEvent_t() const { return ev_; }
+};
+
 #define HIP_TRY(expr)                                                                                       \
     do {                                                                                                    \
         hipError_t e_ = (expr);                                                                             \
@@ -105,47 +183,26 @@ struct DeviceScope {
 // Device copy of the scene in one precision: scan streams + pool-indexed shading tables.
 template <class R> struct SceneBuffers {
     typedef typename VecOf<R>::type r4;
-    float* stat = nullptr;  // blocks of G = 4 spheres: cx[G] cy[G] cz[G] r²[G]   (scan streams: f32 for both precisions)
-    float* movy = nullptr;  // blocks of G: cx[G] cy[G] cz[G] r²[G] vy[G]
-    f4* movg = nullptr;
-    r4* sph_pool = nullptr;
-    r4* mat = nullptr;
-    r4* tex = nullptr;
-    r4* tri = nullptr;
-    u4* bvh_nodes = nullptr; // BVH traversal only (f32 planes or 16-bit plane indices, for both precisions: the box test only culls)
-    bool quantized = false;  // .. which: DevScene::bvh_nodes
-    r4* bvh_leaf = nullptr;
+    DevBuf<float> stat;    // blocks of G = 4 spheres: cx[G] cy[G] cz[G] r²[G]   (scan streams: f32 for both precisions)
+    DevBuf<float> movy;    // blocks of G: cx[G] cy[G] cz[G] r²[G] vy[G]
+    DevBuf<f4> movg;
+    DevBuf<r4> sph_pool, mat, tex, tri;
+    DevBuf<u4> bvh_nodes;   // BVH traversal only (f32 planes or 16-bit plane indices, for both precisions: the box test only culls)
+    bool quantized = false; // .. which: DevScene::bvh_nodes
+    DevBuf<r4> bvh_leaf;
     uint32_t nt_pad = 0, bvh_leaf_stride = 2, bvh_n_inner = 0;
     uint32_t n_big_leaves = 0, big_desc[4] = {0, 0, 0, 0};
     uint32_t bvh_top = 0; // inner-node records the BVH kernel copies to LDS
     rayz_bvh::PlaneGrid grid; // the grid the node records' 16-bit plane indices live on (f32 planes: origin 0, cell 1)
     double pad_S = 0; // the origin bound S the filter radii of these buffers were padded for
     bool ready = false, bvh_ready = false;
-    void release() {
-        (void)hipFree(tri);
-        (void)hipFree(bvh_nodes);
-        (void)hipFree(bvh_leaf);
-        tri = bvh_leaf = nullptr;
-        bvh_nodes = nullptr;
-        bvh_ready = false;
-        (void)hipFree(stat);
-        (void)hipFree(movy);
-        (void)hipFree(movg);
-        (void)hipFree(sph_pool);
-        (void)hipFree(mat);
-        (void)hipFree(tex);
-        sph_pool = mat = tex = nullptr;
-        movg = nullptr;
-        stat = movy = nullptr;
-        ready = false;
-    }
 };
 
 // The pool's own f64 records in slot order (narrow phase) + slot → pool index; shared by both precisions.
 struct NarrowBuffers {
-    d4* slot64 = nullptr;
-    uint32_t* slot_pool = nullptr;
-    d4* bvh_sph64 = nullptr; // leaf order (BVH traversal only)
+    DevBuf<d4> slot64;
+    DevBuf<uint32_t> slot_pool;
+    DevBuf<d4> bvh_sph64; // leaf order (BVH traversal only)
     uint32_t ns_pad = 0, ny_pad = 0, ng_pad = 0;
     // slot order of the static (0) and mov-Y (1) classes: plane runs first (rayz_plane::plan_runs), then the loose spheres
     std::vector<PlaneRun> runs[2];
@@ -153,16 +210,6 @@ struct NarrowBuffers {
     std::vector<uint32_t> loose[2];
     uint32_t plane_slots[2] = {0, 0};
     bool ready = false, bvh_ready = false;
-    void release() {
-        (void)hipFree(bvh_sph64);
-        bvh_sph64 = nullptr;
-        bvh_ready = false;
-        (void)hipFree(slot64);
-        (void)hipFree(slot_pool);
-        slot64 = nullptr;
-        slot_pool = nullptr;
-        ready = false;
-    }
 };
 
 uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
@@ -179,12 +226,15 @@ uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 // each, nothing left to balance with), with 64 at 94 %; the whole frame on ONE GPU changes by +1.0 % (flat list) / −1.2 % (BVH).
 // The price is partial sums: 18 per pixel instead of 8 at 1024 spp.  Depends on the full frame's size, never on the shard or
 // the GPU count: the image is the same for every deal.
+uint64_t pow2floor(uint64_t v) { // the largest power of two <= max(v, 1)
+    uint64_t r = 1;
+    while (r <= v / 2) r *= 2;
+    return r;
+}
+bool uniform_chunks(const RayzRenderParams* p) {
+    return p->chunk_spp != 0 || (uint64_t)p->width * p->height < (1ull << 19) || p->samples_per_px < 64;
+}
 uint32_t auto_chunk(uint64_t pixels, uint32_t spp) {
-    auto pow2floor = [](uint64_t v) {
-        uint64_t r = 1;
-        while (r <= v / 2) r *= 2;
-        return r;
-    };
     const uint64_t share = pixels >= (1ull << 32) ? 256 : (pixels * spp) >> 24;
     long long cap = (long long)pow2floor(std::min<uint64_t>(256, std::max<uint64_t>(64, share)));
 #ifdef RAYZ_EXPERIMENTS // tools/chunk_cap_sweep.py only: CHANGES the summation tree (the oracle does not follow it)
@@ -196,23 +246,17 @@ void chunk_schedule(const RayzRenderParams* p, std::vector<uint32_t>& starts) {
     const uint32_t spp = p->samples_per_px;
     starts.clear();
     starts.push_back(0);
-    const bool uniform = p->chunk_spp != 0 || (uint64_t)p->width * p->height < (1ull << 19) || spp < 64;
-    if (uniform) {
+    if (uniform_chunks(p)) {
         const uint32_t c = p->chunk_spp ? p->chunk_spp : 16u;
         for (uint64_t s0 = c; s0 < spp; s0 += c) starts.push_back((uint32_t)s0);
         starts.push_back(spp);
         return;
     }
-    auto pow2floor = [](uint32_t v) {
-        uint32_t r = 1;
-        while (r <= v / 2) r *= 2;
-        return r;
-    };
     const uint32_t C = auto_chunk((uint64_t)p->width * p->height, spp);
     uint32_t at = 0, rem = spp;
     while (rem >= 2 * C) at += C, rem -= C, starts.push_back(at);
     while (rem > 16) {
-        const uint32_t c = std::max(16u, pow2floor(rem / 2));
+        const uint32_t c = std::max(16u, (uint32_t)pow2floor(rem / 2));
         at += c, rem -= c, starts.push_back(at);
     }
     if (rem) starts.push_back(at + rem);
@@ -223,18 +267,12 @@ void chunk_schedule(const RayzRenderParams* p, std::vector<uint32_t>& starts) {
 constexpr uint64_t kMaxChunksPerPx = 1ull << 20;
 uint64_t chunk_count(const RayzRenderParams* p) {
     const uint64_t spp = p->samples_per_px;
-    const bool uniform = p->chunk_spp != 0 || (uint64_t)p->width * p->height < (1ull << 19) || spp < 64;
-    if (uniform) {
+    if (uniform_chunks(p)) {
         const uint64_t c = p->chunk_spp ? p->chunk_spp : 16u;
         return (spp + c - 1) / c;
     }
     // the automatic schedule, counted exactly by chunk_schedule's own rule (the full chunks in closed form, the halving
     // tail by its ≤ 10 steps): `spp / 256 + 8` undercounted tails of 256 .. 511 samples by one (spp = 497: 10 chunks)
-    auto pow2floor = [](uint64_t v) {
-        uint64_t r = 1;
-        while (r <= v / 2) r *= 2;
-        return r;
-    };
     const uint64_t C = auto_chunk((uint64_t)p->width * p->height, (uint32_t)spp);
     uint64_t n = spp >= 2 * C ? (spp - 2 * C) / C + 1 : 0, rem = spp - n * C;
     while (rem > 16) rem -= std::max<uint64_t>(16, pow2floor(rem / 2)), ++n;
@@ -277,27 +315,36 @@ struct RayzScene {
     bool bvh_built = false;
     rayz_bvh::FlatBvh bvh_dev;    // the tree the GPU walks: the same build with the oversized hittables kept out (bvh_build.hpp)
     bool bvh_dev_built = false;
-    void* partial = nullptr; // chunk sums, grow-only
-    size_t partial_bytes = 0;
-    uint32_t* chunk_start = nullptr; // device copy of the chunk schedule of the last render
-    size_t chunk_start_cap = 0;
+    DevBytes partial;               // chunk sums, grow-only
+    DevBuf<uint32_t> chunk_start;   // device copy of the chunk schedule of the last render, grow-only
     std::vector<uint32_t> chunk_start_host;
-    unsigned long long* counters = nullptr; // [0] queue head, [1] segments
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevBuf<unsigned long long> counters; // [0] queue head, [1] segments
+    DevEvent ev0, ev1;
     hipStream_t last_stream = nullptr;
     bool rendered = false, last_bvh = false;
     int last_experiment = 0; // the last render's BvhLaunchPlan::experiment (0: a product kernel)
     RayzRenderStats last{};
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
-    unsigned long long* q_counters = nullptr; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
-                                              // [kQueryBoundBase + k·kQueryBoundStride] the bound check's four words
-    hipEvent_t q_ev0 = nullptr, q_ev1 = nullptr;
+    DevBuf<unsigned long long> q_counters; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
+                                           // [kQueryBoundBase + k·kQueryBoundStride] the bound check's four words
+    DevEvent q_ev0, q_ev1;
     hipStream_t q_stream = nullptr;
     bool queried = false, q_bvh = false;
     RayzRenderStats q_last{};
+    // The members free themselves; what is left is to wait for the scene's last launch first.
+    ~RayzScene() {
+        if (device < 0 || !last_stream) return;
+        DeviceScope scope(device);
+        (void)hipStreamSynchronize(last_stream);
+    }
 };
 
 namespace {
+
+template <class R> SceneBuffers<R>& buffers_of(RayzScene& s) {
+    if constexpr (sizeof(R) == 4) return s.f32;
+    else return s.f64;
+}
 
 // Every scattered ray starts at a hit point: on a sphere (|p| ≤ |c| + |v| + r, t ∈ [0,1)) or on a triangle.
 double scene_origin_bound(const RayzScene* s) {
@@ -305,13 +352,6 @@ double scene_origin_bound(const RayzScene* s) {
     for (const RayzSphere& q : s->spheres) S = std::max(S, norm3(q.center) + norm3(q.velocity) + std::fabs(q.radius));
     for (const RayzTriangle& q : s->triangles) S = std::max({S, norm3(q.v0), norm3(q.v1), norm3(q.v2)});
     return S * (1.0 + 1e-3);
-}
-
-template <class T> hipError_t put(T** dst, const std::vector<T>& v) {
-    const size_t bytes = v.size() * sizeof(T);
-    hipError_t e = hipMalloc((void**)dst, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    return bytes ? hipMemcpy(*dst, v.data(), bytes, hipMemcpyHostToDevice) : hipSuccess;
 }
 
 // velocity class of a pool sphere: 0 static, 1 v = (0, vy, 0), 2 anything else
@@ -358,17 +398,17 @@ int upload_narrow_body(RayzScene* s) {
         for (size_t k = 0; k < nb.loose[c].size(); ++k) place(class0[c] + nb.plane_slots[c] + k, nb.loose[c][k]);
     }
     for (size_t k = 0; k < s->cls[2].size(); ++k) place((size_t)nb.ns_pad + nb.ny_pad + k, s->cls[2][k]);
-    HIP_TRY(put(&nb.slot64, slot64));
-    HIP_TRY(put(&nb.slot_pool, slot_pool));
+    HIP_TRY(nb.slot64.upload(slot64));
+    HIP_TRY(nb.slot_pool.upload(slot_pool));
     nb.ready = true;
     return RAYZ_OK;
 }
 
-// A failed upload leaves nothing behind: the partly filled buffer set is released, so a retry starts clean.
+// A failed upload leaves nothing behind: the partly filled buffer set is replaced by a fresh one, so a retry starts clean.
 int upload_narrow(RayzScene* s) {
     if (s->narrow.ready) return RAYZ_OK;
     const int rc = upload_narrow_body(s);
-    if (rc != RAYZ_OK) s->narrow.release();
+    if (rc != RAYZ_OK) s->narrow = NarrowBuffers{};
     return rc;
 }
 
@@ -435,7 +475,7 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         tri[3 * k + 1] = r4{(R)(q.v1[0] - q.v0[0]), (R)(q.v1[1] - q.v0[1]), (R)(q.v1[2] - q.v0[2]), R(0)};
         tri[3 * k + 2] = r4{(R)(q.v2[0] - q.v0[0]), (R)(q.v2[1] - q.v0[1]), (R)(q.v2[2] - q.v0[2]), R(0)};
     }
-    HIP_TRY(put(&b.tri, tri));
+    HIP_TRY(b.tri.upload(tri));
     std::vector<r4> sph_pool, mat, tex;
     for (uint32_t i = 0; i < s->spheres.size(); ++i) {
         const RayzSphere& q = s->spheres[i];
@@ -450,12 +490,12 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         tex.push_back(r4{Bits<R>::from(t.kind), Bits<R>::from(t.even), Bits<R>::from(t.odd), (R)t.scale});
         tex.push_back(r4{(R)t.color[0], (R)t.color[1], (R)t.color[2], R(0)});
     }
-    HIP_TRY(put(&b.stat, stat));
-    HIP_TRY(put(&b.movy, movy));
-    HIP_TRY(put(&b.movg, movg));
-    HIP_TRY(put(&b.sph_pool, sph_pool));
-    HIP_TRY(put(&b.mat, mat));
-    HIP_TRY(put(&b.tex, tex));
+    HIP_TRY(b.stat.upload(stat));
+    HIP_TRY(b.movy.upload(movy));
+    HIP_TRY(b.movg.upload(movg));
+    HIP_TRY(b.sph_pool.upload(sph_pool));
+    HIP_TRY(b.mat.upload(mat));
+    HIP_TRY(b.tex.upload(tex));
     b.ready = true;
     return RAYZ_OK;
 }
@@ -466,10 +506,10 @@ template <class R> int upload(RayzScene* s, SceneBuffers<R>& b, double S) {
     if (b.ready && b.pad_S >= S) return RAYZ_OK;
     const bool again = b.ready;
     if (again) HIP_TRY(hipDeviceSynchronize());
-    b.release();
+    b = SceneBuffers<R>{}; // (every field: what the BVH upload fills is rebuilt with the tree, bvh_ready being false again)
     b.pad_S = again ? 2.0 * S : S;
     const int rc = upload_body<R>(s, b);
-    if (rc != RAYZ_OK) b.release();
+    if (rc != RAYZ_OK) b = SceneBuffers<R>{};
     return rc;
 }
 
@@ -516,7 +556,7 @@ template <class R> int upload_bvh_body(RayzScene* s, SceneBuffers<R>& b) {
                 sph64.push_back(d4{0, 0, 0, 0});
             }
         }
-        HIP_TRY(put(&s->narrow.bvh_sph64, sph64));
+        HIP_TRY(s->narrow.bvh_sph64.upload(sph64));
         s->narrow.bvh_ready = true;
     }
     if (b.bvh_ready) return RAYZ_OK;
@@ -640,8 +680,8 @@ template <class R> int upload_bvh_body(RayzScene* s, SceneBuffers<R>& b) {
             leaf.push_back(r4{(R)(q.v2[0] - q.v0[0]), (R)(q.v2[1] - q.v0[1]), (R)(q.v2[2] - q.v0[2]), R(0)});
         }
     }
-    HIP_TRY(put(&b.bvh_nodes, nodes));
-    HIP_TRY(put(&b.bvh_leaf, leaf));
+    HIP_TRY(b.bvh_nodes.upload(nodes));
+    HIP_TRY(b.bvh_leaf.upload(leaf));
     b.bvh_ready = true;
     return RAYZ_OK;
 }
@@ -650,15 +690,10 @@ template <class R> int upload_bvh(RayzScene* s, SceneBuffers<R>& b) {
     if (b.bvh_ready && s->narrow.bvh_ready) return RAYZ_OK;
     const int rc = upload_bvh_body<R>(s, b);
     if (rc != RAYZ_OK) { // drop the partly built BVH buffers (the scan streams stay valid)
-        (void)hipFree(b.bvh_nodes);
-        (void)hipFree(b.bvh_leaf);
-        b.bvh_nodes = nullptr;
-        b.bvh_leaf = nullptr;
+        b.bvh_nodes.reset();
+        b.bvh_leaf.reset();
         b.bvh_ready = false;
-        if (!s->narrow.bvh_ready) {
-            (void)hipFree(s->narrow.bvh_sph64);
-            s->narrow.bvh_sph64 = nullptr;
-        }
+        if (!s->narrow.bvh_ready) s->narrow.bvh_sph64.reset();
     }
     return rc;
 }
@@ -911,13 +946,9 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     int rc = check_items(shard_pixels64, chunks_per_px);
     if (rc != RAYZ_OK) return rc;
     const size_t need = (size_t)items64 * sizeof(r4);
-    if (need > s->partial_bytes) {
+    if (need > s->partial.capacity()) {
         HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(s->partial);
-        s->partial = nullptr;
-        s->partial_bytes = 0;
-        HIP_TRY(hipMalloc(&s->partial, need));
-        s->partial_bytes = need;
+        HIP_TRY(s->partial.grow(need));
     }
 
     TraceArgs<R> A{};
@@ -936,7 +967,7 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     A.sc.tri = b.tri;
     A.sc.nt_pad = b.nt_pad;
     A.sc.n_triangles = (uint32_t)s->triangles.size();
-    A.sc.bvh_nodes = (const f4*)b.bvh_nodes;
+    A.sc.bvh_nodes = (const f4*)b.bvh_nodes.get();
     for (int k = 0; k < 3; ++k) A.sc.bvh_glo[k] = b.grid.glo[k], A.sc.bvh_cell[k] = b.grid.cell[k];
     A.sc.bvh_leaf = b.bvh_leaf;
     A.sc.bvh_sph64 = s->narrow.bvh_sph64;
@@ -946,7 +977,7 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     for (int k = 0; k < 4; ++k) A.sc.bvh_big[k] = b.big_desc[k];
     A.sc.bvh_top = 0u; // (bytes: set below, once the launch knows how many records its workgroup keeps in LDS)
     fill_camera<R>(cam, A.cam);
-    A.partial = (r4*)s->partial;
+    A.partial = (r4*)s->partial.get();
     A.counters = counters;
     A.seed = p->seed;
     A.tmin = (R)p->tmin;
@@ -1050,28 +1081,22 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         s->rendered = false;
         return RAYZ_OK;
     }
-    if (!s->counters) HIP_TRY(hipMalloc((void**)&s->counters, 32 * sizeof(unsigned long long)));
+    if (!s->counters) HIP_TRY(s->counters.alloc(32));
     if (starts != s->chunk_start_host) { // the schedule table, kept on the device until it changes
         HIP_TRY(hipStreamSynchronize(stream));
-        if (starts.size() > s->chunk_start_cap) {
-            (void)hipFree(s->chunk_start);
-            s->chunk_start = nullptr;
-            s->chunk_start_cap = 0;
-            HIP_TRY(hipMalloc((void**)&s->chunk_start, starts.size() * sizeof(uint32_t)));
-            s->chunk_start_cap = starts.size();
-        }
+        HIP_TRY(s->chunk_start.grow(starts.size()));
         HIP_TRY(hipMemcpy(s->chunk_start, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         s->chunk_start_host = starts;
     }
     if (!s->ev0) {
-        HIP_TRY(hipEventCreate(&s->ev0));
-        HIP_TRY(hipEventCreate(&s->ev1));
+        HIP_TRY(s->ev0.create());
+        HIP_TRY(s->ev1.create());
     }
     rc = trace_window<R>(s, ctx, b, cam, p, use_bvh, starts, s->chunk_start, 0, chunks_per_px, s->counters,
                          32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, s->last_experiment);
     if (rc != RAYZ_OK) return rc;
     hipLaunchKernelGGL(resolve_kernel<R>, dim3((uint32_t)((shard_pixels64 + 255) / 256)), dim3(256), 0, stream,
-                       (const r4*)s->partial, d_out, (uint32_t)shard_pixels64, chunks_per_px, p->samples_per_px);
+                       (const r4*)s->partial.get(), d_out, (uint32_t)shard_pixels64, chunks_per_px, p->samples_per_px);
     HIP_TRY(hipGetLastError());
     s->rendered = true;
     return RAYZ_OK;
@@ -1095,31 +1120,31 @@ int render_device(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParam
     rc = scene_ctx(s, &ctx);
     if (rc != RAYZ_OK) return rc;
     DeviceScope scope(s->device);
-    SceneBuffers<R>* b;
-    if constexpr (sizeof(R) == 4) b = &s->f32;
-    else b = &s->f64;
-    return render_impl<R>(s, *ctx, *b, cam, p, d_out, stream ? (hipStream_t)stream : ctx->stream);
+    return render_impl<R>(s, *ctx, buffers_of<R>(*s), cam, p, d_out, stream ? (hipStream_t)stream : ctx->stream);
 }
 
-int scene_new(const RayzSceneDesc* scene, int device, RayzScene** out) {
+// (a handle is built in a unique_ptr and released to the caller at the end: an exception on the way, which guarded() reports,
+// takes the half-built handle with it)
+int scene_new(const RayzSceneDesc* scene, int device, std::unique_ptr<RayzScene>& out) {
+    const int rc = validate_scene(scene);
+    if (rc != RAYZ_OK) return rc;
+    auto s = std::make_unique<RayzScene>();
+    s->spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
+    s->materials.assign(scene->materials, scene->materials + scene->n_materials);
+    s->textures.assign(scene->textures, scene->textures + scene->n_textures);
+    s->triangles.assign(scene->triangles, scene->triangles + scene->n_triangles);
+    s->device = device;
+    out = std::move(s);
+    return RAYZ_OK;
+}
+
+int scene_create(const RayzSceneDesc* scene, int device, RayzScene** out) {
     if (!out) return fail(RAYZ_ERR_BAD_ARG, "out handle pointer is null");
     *out = nullptr;
-    int rc = validate_scene(scene);
-    if (rc != RAYZ_OK) return rc;
-    RayzScene* s = new (std::nothrow) RayzScene();
-    if (!s) return fail(RAYZ_ERR_OOM, "host allocation failed");
-    try {
-        s->spheres.assign(scene->spheres, scene->spheres + scene->n_spheres);
-        s->materials.assign(scene->materials, scene->materials + scene->n_materials);
-        s->textures.assign(scene->textures, scene->textures + scene->n_textures);
-        s->triangles.assign(scene->triangles, scene->triangles + scene->n_triangles);
-    } catch (...) {
-        delete s;
-        return fail(RAYZ_ERR_OOM, "host allocation failed");
-    }
-    s->device = device;
-    *out = s;
-    return RAYZ_OK;
+    std::unique_ptr<RayzScene> s;
+    const int rc = scene_new(scene, device, s);
+    *out = s.release();
+    return rc;
 }
 
 int scene_sync(RayzScene* s, RayzRenderStats* stats) {
@@ -1177,23 +1202,7 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
 }
 
 int scene_free(RayzScene* s) {
-    if (!s) return RAYZ_OK;
-    if (s->device >= 0) {
-        DeviceScope scope(s->device);
-        if (s->last_stream) (void)hipStreamSynchronize(s->last_stream);
-        s->f32.release();
-        s->f64.release();
-        s->narrow.release();
-        (void)hipFree(s->partial);
-        (void)hipFree(s->counters);
-        (void)hipFree(s->chunk_start);
-        (void)hipFree(s->q_counters);
-        if (s->ev0) (void)hipEventDestroy(s->ev0);
-        if (s->ev1) (void)hipEventDestroy(s->ev1);
-        if (s->q_ev0) (void)hipEventDestroy(s->q_ev0);
-        if (s->q_ev1) (void)hipEventDestroy(s->q_ev1);
-    }
-    delete s;
+    delete s; // (~RayzScene waits for the scene's last launch)
     return RAYZ_OK;
 }
 
@@ -1213,25 +1222,20 @@ int render_oneshot(const RayzSceneDesc* scene, const RayzCameraDesc* cam, const 
         if (rc != RAYZ_OK) return rc;
         device = 0;
     }
-    RayzScene* s = nullptr;
-    rc = scene_new(scene, device, &s);
+    std::unique_ptr<RayzScene> s;
+    rc = scene_new(scene, device, s);
     if (rc != RAYZ_OK) return rc;
     DeviceScope scope(device);
     const size_t n = (size_t)rayz_hip_shard_rows(p) * p->width * 3;
-    R* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_out, n ? n * sizeof(R) : 16);
-    if (e != hipSuccess) {
-        scene_free(s);
-        return fail(RAYZ_ERR_OOM, "hipMalloc(output): %s", hipGetErrorString(e));
-    }
-    rc = render_device<R>(s, cam, p, d_out, nullptr, precision);
-    if (rc == RAYZ_OK) rc = scene_sync(s, stats);
+    DevBuf<R> d_out; // (declared after the scene: freed first, as ever)
+    hipError_t e = d_out.alloc(n);
+    if (e != hipSuccess) return fail(RAYZ_ERR_OOM, "hipMalloc(output): %s", hipGetErrorString(e));
+    rc = render_device<R>(s.get(), cam, p, d_out.get(), nullptr, precision);
+    if (rc == RAYZ_OK) rc = scene_sync(s.get(), stats);
     if (rc == RAYZ_OK && n) {
         e = hipMemcpy(out, d_out, n * sizeof(R), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RAYZ_ERR_HIP, "hipMemcpy(output): %s", hipGetErrorString(e));
     }
-    (void)hipFree(d_out);
-    scene_free(s);
     return rc;
 }
 
@@ -1248,31 +1252,26 @@ struct RayzProgressive {
     RayzCameraDesc cam{};
     RayzRenderParams params{};
     std::vector<uint32_t> starts;           // the chunk schedule: n_chunks + 1 entries
-    uint32_t* d_starts = nullptr;           // the handle's own device copy (the scene's table follows the scene's last render)
-    void* acc = nullptr;                    // shard_pixels running sums (r4 of the precision)
-    unsigned long long* counters = nullptr; // [0] queue head (cleared per pass), [1..3] summed over the passes
+    DevBuf<uint32_t> d_starts;              // the handle's own device copy (the scene's table follows the scene's last render)
+    DevBytes acc;                           // shard_pixels running sums (r4 of the precision)
+    DevBuf<unsigned long long> counters;    // [0] queue head (cleared per pass), [1..3] summed over the passes
     uint64_t shard_pixels = 0;
     uint32_t chunks_done = 0;
     uint64_t primary_rays = 0;
     bool bvh = false, traced = false;
-    std::vector<hipEvent_t> pending, spare; // pairs bracketing the trace kernel of every pass not yet summed into kernel_ms
+    std::vector<DevEvent> pending, spare;   // pairs bracketing the trace kernel of every pass not yet summed into kernel_ms
     double kernel_ms = 0;
     hipStream_t last_stream = nullptr;
+    ~RayzProgressive() { // the accumulator's last pass has finished before the members go
+        if (device < 0 || !last_stream) return;
+        DeviceScope scope(device);
+        (void)hipStreamSynchronize(last_stream);
+    }
 };
 
 namespace {
 
 int progressive_free(RayzProgressive* pr) {
-    if (!pr) return RAYZ_OK;
-    if (pr->device >= 0) {
-        DeviceScope scope(pr->device);
-        if (pr->last_stream) (void)hipStreamSynchronize(pr->last_stream);
-        (void)hipFree(pr->d_starts);
-        (void)hipFree(pr->acc);
-        (void)hipFree(pr->counters);
-        for (hipEvent_t e : pr->pending) (void)hipEventDestroy(e);
-        for (hipEvent_t e : pr->spare) (void)hipEventDestroy(e);
-    }
     delete pr;
     return RAYZ_OK;
 }
@@ -1293,26 +1292,21 @@ int progressive_create(RayzScene* s, const RayzCameraDesc* cam, const RayzRender
     std::vector<uint32_t> starts;
     chunk_schedule(p, starts);
     DeviceScope scope(s->device);
-    RayzProgressive* pr = new RayzProgressive();
+    auto pr = std::make_unique<RayzProgressive>();
     pr->scene = s;
     pr->device = s->device;
     pr->cam = *cam;
     pr->params = *p;
     pr->shard_pixels = shard_pixels;
     pr->starts.swap(starts);
-    auto bail = [&](int code) {
-        progressive_free(pr);
-        return code;
-    };
     const size_t r4_bytes = p->precision == RAYZ_PRECISION_F64 ? sizeof(d4) : sizeof(f4);
-    hipError_t e = hipMalloc((void**)&pr->d_starts, pr->starts.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(pr->d_starts, pr->starts.data(), pr->starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&pr->acc, shard_pixels ? shard_pixels * r4_bytes : 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&pr->counters, 32 * sizeof(unsigned long long));
+    hipError_t e = pr->d_starts.upload(pr->starts);
+    if (e == hipSuccess) e = pr->acc.alloc(shard_pixels * r4_bytes);
+    if (e == hipSuccess) e = pr->counters.alloc(32);
     if (e == hipSuccess) e = hipMemset(pr->counters, 0, 32 * sizeof(unsigned long long));
     if (e != hipSuccess)
-        return bail(fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "progressive handle: %s", hipGetErrorString(e)));
-    *out = pr;
+        return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "progressive handle: %s", hipGetErrorString(e));
+    *out = pr.release();
     return RAYZ_OK;
 }
 
@@ -1334,11 +1328,9 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
     if (rc != RAYZ_OK) return rc;
     DeviceScope scope(s->device);
     const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
-    SceneBuffers<R>* b;
-    if constexpr (sizeof(R) == 4) b = &s->f32;
-    else b = &s->f64;
+    SceneBuffers<R>& b = buffers_of<R>(*s);
     bool use_bvh = false;
-    rc = prepare_scene<R>(s, *b, &pr->cam, &pr->params, stream, use_bvh);
+    rc = prepare_scene<R>(s, b, &pr->cam, &pr->params, stream, use_bvh);
     if (rc != RAYZ_OK) return rc;
     rc = check_items(pr->shard_pixels, c1 - c0);
     if (rc != RAYZ_OK) return rc;
@@ -1349,30 +1341,30 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
         if (d_preview) HIP_TRY(hipMemsetAsync(d_preview, 0, pr->shard_pixels * 3 * sizeof(R), stream));
         pr->last_stream = stream;
     } else if (pr->shard_pixels) {
-        if (!s->counters) HIP_TRY(hipMalloc((void**)&s->counters, 32 * sizeof(unsigned long long))); // (the scene's: left alone)
+        if (!s->counters) HIP_TRY(s->counters.alloc(32)); // (the scene's: left alone)
         while (pr->spare.size() < 2) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            pr->spare.push_back(e);
+            DevEvent e;
+            HIP_TRY(e.create());
+            pr->spare.push_back(std::move(e));
         }
-        const hipEvent_t ev1 = pr->spare.back();
+        DevEvent ev1 = std::move(pr->spare.back());
         pr->spare.pop_back();
-        const hipEvent_t ev0 = pr->spare.back();
+        DevEvent ev0 = std::move(pr->spare.back());
         pr->spare.pop_back();
         s->last_stream = stream;
         pr->last_stream = stream;
         int experiment = 0; // (the passes' counters are not reported)
-        rc = trace_window<R>(s, *ctx, *b, &pr->cam, &pr->params, use_bvh, pr->starts, pr->d_starts, c0, c1, pr->counters,
+        rc = trace_window<R>(s, *ctx, b, &pr->cam, &pr->params, use_bvh, pr->starts, pr->d_starts, c0, c1, pr->counters,
                              sizeof(unsigned long long), ev0, ev1, stream, experiment);
         if (rc != RAYZ_OK) {
-            pr->spare.push_back(ev0);
-            pr->spare.push_back(ev1);
+            pr->spare.push_back(std::move(ev0));
+            pr->spare.push_back(std::move(ev1));
             return rc;
         }
-        pr->pending.push_back(ev0);
-        pr->pending.push_back(ev1);
+        pr->pending.push_back(std::move(ev0));
+        pr->pending.push_back(std::move(ev1));
         hipLaunchKernelGGL(accumulate_kernel<R>, dim3((uint32_t)((pr->shard_pixels + 255) / 256)), dim3(256), 0, stream,
-                           (const r4*)s->partial, (r4*)pr->acc, d_preview, (uint32_t)pr->shard_pixels, c1 - c0,
+                           (const r4*)s->partial.get(), (r4*)pr->acc.get(), d_preview, (uint32_t)pr->shard_pixels, c1 - c0,
                            pr->starts[c1], c0 == 0 ? 1u : 0u);
         HIP_TRY(hipGetLastError());
         pr->traced = true;
@@ -1404,7 +1396,7 @@ int progressive_info(const RayzProgressive* cpr, uint32_t* samples_done, uint32_
             HIP_TRY(hipEventElapsedTime(&ms, pr->pending[i], pr->pending[i + 1]));
             pr->kernel_ms += ms;
         }
-        pr->spare.insert(pr->spare.end(), pr->pending.begin(), pr->pending.end());
+        for (DevEvent& e : pr->pending) pr->spare.push_back(std::move(e));
         pr->pending.clear();
         const RayzScene* s = pr->scene;
         st.segments = c[1];
@@ -1487,41 +1479,36 @@ __global__ __launch_bounds__(256) void unshard_kernel(const T* __restrict__ gath
 // One scene per device + the buffers of the gather; everything is driven by the calling host thread.
 struct RayzMulti {
     std::vector<int> devices;
-    std::vector<RayzScene*> scenes;
-    std::vector<ncclComm_t> comms; // RAYZ_GATHER_RCCL
-    std::vector<void*> tile;       // per device: this device's rows, grow-only
-    std::vector<void*> tile8;      // per device: the same rows tone-mapped to u8 (render_u8 only)
-    std::vector<size_t> tile_have, tile8_have;
-    std::vector<hipEvent_t> done;  // per device: tile ready (peer-copy transport)
-    void* gathered = nullptr; // root: [n][max_rows][row bytes]
-    void* frame = nullptr;    // root: the assembled frame
-    size_t gathered_bytes = 0, frame_bytes = 0;
+    // one entry per device, from construction on
+    std::vector<std::unique_ptr<RayzScene>> scenes;
+    std::vector<ncclComm_t> comms; // RAYZ_GATHER_RCCL (else null)
+    std::vector<DevBytes> tile;    // this device's rows, grow-only
+    std::vector<DevBytes> tile8;   // the same rows tone-mapped to u8 (render_u8 only)
+    std::vector<DevEvent> done;    // tile ready (peer-copy transport)
+    DevBytes gathered; // root: [n][max_rows][row bytes]
+    DevBytes frame;    // root: the assembled frame
     uint32_t transport = RAYZ_GATHER_RCCL;
     int rccl_version = 0;
     std::vector<RayzRenderStats> last_dev; // per device: counters of the last frame (rayz_hip_multi_device_stats)
-    hipEvent_t g0 = nullptr, g1 = nullptr; // on the root's stream: its own tile done / frame assembled
+    DevEvent g0, g1; // on the root's stream: its own tile done / frame assembled
     double last_gather_ms = 0, last_frame_ms = 0;
+    RayzMulti(const int* d, int n) : devices(d, d + n), scenes(n), comms(n, nullptr), tile(n), tile8(n), done(n) {}
+    // Device by device: the scene (it waits for the device's last render), the communicator, the buffers; the root's own follow.
+    ~RayzMulti() {
+        for (size_t i = 0; i < devices.size(); ++i) {
+            scenes[i].reset();
+            if (comms[i]) {
+                DeviceScope scope(devices[i]);
+                (void)g_rccl.CommDestroy(comms[i]);
+            }
+            tile[i].reset(), tile8[i].reset(), done[i].reset();
+        }
+    }
 };
 
 namespace {
 
 int multi_free(RayzMulti* m) {
-    if (!m) return RAYZ_OK;
-    for (size_t i = 0; i < m->devices.size(); ++i) {
-        if (i < m->scenes.size()) scene_free(m->scenes[i]); // waits for the device's last render
-        DeviceScope scope(m->devices[i]);
-        if (i < m->comms.size() && m->comms[i]) (void)g_rccl.CommDestroy(m->comms[i]);
-        if (i < m->tile.size()) (void)hipFree(m->tile[i]);
-        if (i < m->tile8.size()) (void)hipFree(m->tile8[i]);
-        if (i < m->done.size() && m->done[i]) (void)hipEventDestroy(m->done[i]);
-    }
-    if (!m->devices.empty()) {
-        DeviceScope scope(m->devices[0]);
-        (void)hipFree(m->gathered);
-        (void)hipFree(m->frame);
-        if (m->g0) (void)hipEventDestroy(m->g0);
-        if (m->g1) (void)hipEventDestroy(m->g1);
-    }
     delete m;
     return RAYZ_OK;
 }
@@ -1539,13 +1526,60 @@ int check_device_list(const int* devices, int n, bool dup_ok) {
     return RAYZ_OK;
 }
 
-int grow(void** buf, size_t* have, size_t need) {
-    if (need <= *have) return RAYZ_OK;
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(buf, need));
-    *have = need;
+int multi_create(const int* devices, int n_devices, const RayzSceneDesc* scene, uint32_t transport, RayzMulti** out) {
+    if (!out) return fail(RAYZ_ERR_BAD_ARG, "out handle pointer is null");
+    *out = nullptr;
+    const bool dup_ok = (transport & RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES) != 0;
+    transport &= ~(uint32_t)RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES;
+    if (transport > RAYZ_GATHER_PEER_COPY) return fail(RAYZ_ERR_BAD_ARG, "bad gather transport %u", transport);
+    if (dup_ok && transport != RAYZ_GATHER_PEER_COPY)
+        return fail(RAYZ_ERR_BAD_ARG, "RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES needs the peer-copy transport (RCCL refuses a device twice)");
+    int rc = check_device_list(devices, n_devices, dup_ok);
+    if (rc != RAYZ_OK) return rc;
+    rc = validate_scene(scene);
+    if (rc != RAYZ_OK) return rc;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        for (int i = 0; i < n_devices; ++i) {
+            rc = ensure_ctx(devices[i]);
+            if (rc != RAYZ_OK) return rc;
+        }
+        if (transport == RAYZ_GATHER_RCCL) {
+            rc = rccl_load();
+            if (rc != RAYZ_OK) return rc;
+        }
+    }
+    auto m = std::make_unique<RayzMulti>(devices, n_devices);
+    m->transport = transport;
+    for (int i = 0; i < n_devices; ++i) {
+        rc = scene_new(scene, devices[i], m->scenes[i]);
+        if (rc != RAYZ_OK) return rc;
+    }
+    if (transport == RAYZ_GATHER_RCCL) {
+        ncclResult_t r = g_rccl.CommInitAll(m->comms.data(), n_devices, m->devices.data());
+        if (r != ncclSuccess) {
+            m->comms.assign(n_devices, nullptr); // (whatever the failed call left there is no communicator to destroy)
+            return fail(RAYZ_ERR_HIP, "ncclCommInitAll(%d devices): %s", n_devices, g_rccl.GetErrorString(r));
+        }
+        (void)g_rccl.GetVersion(&m->rccl_version);
+    } else {
+        for (int i = 0; i < n_devices; ++i) {
+            DeviceScope scope(devices[i]);
+            hipError_t e = m->done[i].create(hipEventDisableTiming);
+            if (e != hipSuccess) return fail(RAYZ_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e));
+            if (i > 0) { // the root pulls nothing; sources push into the root's buffer
+                int can = 0;
+                (void)hipDeviceCanAccessPeer(&can, devices[i], devices[0]);
+                if (can) {
+                    e = hipDeviceEnablePeerAccess(devices[0], 0);
+                    if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+                        return fail(RAYZ_ERR_HIP, "hipDeviceEnablePeerAccess(%d -> %d): %s", devices[i], devices[0], hipGetErrorString(e));
+                    (void)hipGetLastError();
+                }
+            }
+        }
+    }
+    *out = m.release();
     return RAYZ_OK;
 }
 
@@ -1582,33 +1616,28 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
     // 1. every device traces its rows (asynchronous: the launches of all devices overlap)
     std::vector<DeviceCtx*> ctx(n, nullptr);
     for (uint32_t i = 0; i < n; ++i) {
-        rc = scene_ctx(m->scenes[i], &ctx[i]);
+        rc = scene_ctx(m->scenes[i].get(), &ctx[i]);
         if (rc != RAYZ_OK) return rc;
         DeviceScope scope(m->devices[i]);
         HIP_TRY(hipStreamSynchronize(ctx[i]->stream)); // the previous frame's gather has left the tiles
-        rc = grow(&m->tile[i], &m->tile_have[i], tile_bytes ? tile_bytes : 16);
-        if (rc == RAYZ_OK && to_u8) rc = grow(&m->tile8[i], &m->tile8_have[i], tile8_bytes ? tile8_bytes : 16);
-        if (rc != RAYZ_OK) return rc;
+        HIP_TRY(m->tile[i].grow(tile_bytes ? tile_bytes : 16));
+        if (to_u8) HIP_TRY(m->tile8[i].grow(tile8_bytes ? tile8_bytes : 16));
     }
     {
         DeviceScope scope(m->devices[0]);
-        rc = grow(&m->gathered, &m->gathered_bytes, (size_t)n * send_bytes ? (size_t)n * send_bytes : 16);
-        if (rc == RAYZ_OK) rc = grow(&m->frame, &m->frame_bytes, frame_bytes);
-        if (rc != RAYZ_OK) return rc;
+        HIP_TRY(m->gathered.grow((size_t)n * send_bytes ? (size_t)n * send_bytes : 16));
+        HIP_TRY(m->frame.grow(frame_bytes));
     }
     for (uint32_t i = 0; i < n; ++i) {
         DeviceScope scope(m->devices[i]);
         q.shard_index = i;
-        SceneBuffers<R>* b;
-        if constexpr (sizeof(R) == 4) b = &m->scenes[i]->f32;
-        else b = &m->scenes[i]->f64;
-        rc = render_impl<R>(m->scenes[i], *ctx[i], *b, cam, &q, (R*)m->tile[i], ctx[i]->stream);
+        rc = render_impl<R>(m->scenes[i].get(), *ctx[i], buffers_of<R>(*m->scenes[i]), cam, &q, (R*)m->tile[i].get(), ctx[i]->stream);
         if (rc != RAYZ_OK) return rc;
         if constexpr (to_u8) { // writePPM's transform before the gather: the tiles travel as u8, 4x smaller (src/image.zig:35-38)
             const size_t ne = (size_t)rayz_hip_shard_rows(&q) * row_elems;
             if (ne) {
                 hipLaunchKernelGGL(tonemap_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, ctx[i]->stream,
-                                   (const float*)m->tile[i], (uint8_t*)m->tile8[i], ne);
+                                   (const float*)m->tile[i].get(), (uint8_t*)m->tile8[i].get(), ne);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -1619,12 +1648,12 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
     {
         DeviceScope scope(m->devices[0]);
         if (!m->g0) {
-            HIP_TRY(hipEventCreate(&m->g0));
-            HIP_TRY(hipEventCreate(&m->g1));
+            HIP_TRY(m->g0.create());
+            HIP_TRY(m->g1.create());
         }
         HIP_TRY(hipEventRecord(m->g0, ctx[0]->stream));
     }
-    auto src = [&](uint32_t i) { return to_u8 ? m->tile8[i] : m->tile[i]; };
+    auto src = [&](uint32_t i) { return to_u8 ? m->tile8[i].get() : m->tile[i].get(); };
     if (m->transport == RAYZ_GATHER_RCCL) {
         NCCL_TRY(g_rccl.GroupStart());
         for (uint32_t i = 0; i < n; ++i) {
@@ -1638,7 +1667,7 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
     } else { // peer copies, each on its source device's stream; the root's stream waits for all of them
         for (uint32_t i = 0; i < n; ++i) {
             DeviceScope scope(m->devices[i]);
-            HIP_TRY(hipMemcpyPeerAsync((char*)m->gathered + (size_t)i * send_bytes, m->devices[0], src(i), m->devices[i], send_bytes,
+            HIP_TRY(hipMemcpyPeerAsync(m->gathered.get() + (size_t)i * send_bytes, m->devices[0], src(i), m->devices[i], send_bytes,
                                        ctx[i]->stream));
             HIP_TRY(hipEventRecord(m->done[i], ctx[i]->stream));
         }
@@ -1650,7 +1679,7 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
         DeviceScope scope(m->devices[0]);
         const size_t ne = (size_t)p->height * row_elems;
         hipLaunchKernelGGL(unshard_kernel<T>, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, ctx[0]->stream,
-                           (const T*)m->gathered, (T*)m->frame, p->height, (uint32_t)row_elems, q.tile_rows, n, max_rows);
+                           (const T*)m->gathered.get(), (T*)m->frame.get(), p->height, (uint32_t)row_elems, q.tile_rows, n, max_rows);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(m->g1, ctx[0]->stream));
         HIP_TRY(hipMemcpyAsync(out, m->frame, frame_bytes, hipMemcpyDeviceToHost, ctx[0]->stream));
@@ -1665,7 +1694,7 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
     m->last_dev.assign(n, RayzRenderStats{});
     for (uint32_t i = 0; i < n; ++i) {
         RayzRenderStats st{};
-        rc = scene_sync(m->scenes[i], &st);
+        rc = scene_sync(m->scenes[i].get(), &st);
         if (rc != RAYZ_OK) return rc;
         m->last_dev[i] = st;
         tot.primary_rays += st.primary_rays;
@@ -1681,12 +1710,11 @@ int multi_render(RayzMulti* m, const RayzCameraDesc* cam, const RayzRenderParams
 template <class T>
 int render_multi_oneshot(const int* devices, int n, const RayzSceneDesc* scene, const RayzCameraDesc* cam, const RayzRenderParams* p,
                          T* out, RayzRenderStats* stats) {
-    RayzMulti* m = nullptr;
-    int rc = rayz_hip_multi_create(devices, n, scene, RAYZ_GATHER_RCCL, &m);
+    RayzMulti* raw = nullptr;
+    const int rc = multi_create(devices, n, scene, RAYZ_GATHER_RCCL, &raw);
     if (rc != RAYZ_OK) return rc;
-    rc = multi_render<T>(m, cam, p, out, stats);
-    multi_free(m);
-    return rc;
+    const std::unique_ptr<RayzMulti> m(raw);
+    return multi_render<T>(m.get(), cam, p, out, stats);
 }
 
 // ---- ray queries (rayz_hip_scene_query*) ---------------------------------------------------------------
@@ -1720,7 +1748,7 @@ template <class R> int query_bounds(RayzScene* s, const DeviceCtx& ctx, const R*
     init[0] = query_key_host(0.0);
     init[kQueryBoundStride] = query_key_host(std::numeric_limits<double>::infinity());
     init[2 * kQueryBoundStride] = query_key_host(-std::numeric_limits<double>::infinity());
-    unsigned long long* words = s->q_counters + kQueryBoundBase;
+    unsigned long long* words = s->q_counters.get() + kQueryBoundBase;
     HIP_TRY(hipMemcpyAsync(words, init, sizeof(init), hipMemcpyHostToDevice, stream));
     const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx.num_cu * 2, (n + 255) / 256));
     hipLaunchKernelGGL(query_bounds_kernel<R>, dim3(blocks), dim3(256), 0, stream, rays, n, words);
@@ -1748,18 +1776,15 @@ template <class R> int query_bounds(RayzScene* s, const DeviceCtx& ctx, const R*
 template <class R>
 int query_impl(RayzScene* s, const DeviceCtx& ctx, uint32_t kind, uint32_t traversal, double tmin, uint32_t n, const R* rays,
                const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzQueryOutputs* out, hipStream_t stream) {
-    SceneBuffers<R>* bp;
-    if constexpr (sizeof(R) == 4) bp = &s->f32;
-    else bp = &s->f64;
-    SceneBuffers<R>& b = *bp;
+    SceneBuffers<R>& b = buffers_of<R>(*s);
     if (s->last_stream && s->last_stream != stream) HIP_TRY(hipStreamSynchronize(s->last_stream)); // one launch in flight per scene
     if (!s->q_counters) {
-        HIP_TRY(hipMalloc((void**)&s->q_counters, kQueryCounterWords * sizeof(unsigned long long)));
+        HIP_TRY(s->q_counters.alloc(kQueryCounterWords));
         HIP_TRY(hipMemset(s->q_counters, 0, kQueryCounterWords * sizeof(unsigned long long)));
     }
     if (!s->q_ev0) {
-        HIP_TRY(hipEventCreate(&s->q_ev0));
-        HIP_TRY(hipEventCreate(&s->q_ev1));
+        HIP_TRY(s->q_ev0.create());
+        HIP_TRY(s->q_ev1.create());
     }
     double S = 0;
     int rc = rays ? query_bounds<R>(s, ctx, rays, n, stream, S) : RAYZ_OK;
@@ -1785,7 +1810,7 @@ int query_impl(RayzScene* s, const DeviceCtx& ctx, uint32_t kind, uint32_t trave
     A.sc.tri = b.tri;
     A.sc.nt_pad = b.nt_pad;
     A.sc.n_triangles = (uint32_t)s->triangles.size();
-    A.sc.bvh_nodes = (const f4*)b.bvh_nodes;
+    A.sc.bvh_nodes = (const f4*)b.bvh_nodes.get();
     for (int k = 0; k < 3; ++k) A.sc.bvh_glo[k] = b.grid.glo[k], A.sc.bvh_cell[k] = b.grid.cell[k];
     A.sc.bvh_leaf = b.bvh_leaf;
     A.sc.bvh_sph64 = s->narrow.bvh_sph64;
@@ -1906,10 +1931,17 @@ struct RayzDenoiser {
     uint32_t magic = 0;
     int device = -1;
     uint32_t width = 0, height = 0;
-    dn4 *ga = nullptr, *gb = nullptr, *mod = nullptr, *col[2] = {nullptr, nullptr}; // n_pixels records each
-    hipEvent_t ev[10] = {}; // ev[0]: the run starts; ev[1]: packed; ev[2 + l]: level l done
+    DevBuf<dn4> ga, gb, mod, col[2]; // n_pixels records each
+    DevEvent ev[10];         // ev[0]: the run starts; ev[1]: packed; ev[2 + l]: level l done
     int last_ev = -1;        // the last event recorded, of a failed run too: what the next run and destroy wait for (-1: none yet)
     uint32_t levels_run = 0; // levels of the last COMPLETE run (0: none, or the last run failed half-way: no timing)
+    ~RayzDenoiser() {
+        if (last_ev >= 0) { // (waits on the handle's own event, never on the caller's stream, which may be gone by now)
+            DeviceScope scope(device);
+            (void)hipEventSynchronize(ev[last_ev]);
+        }
+        magic = 0;
+    }
 };
 
 namespace {
@@ -1920,15 +1952,6 @@ constexpr uint32_t kDenoiseFlags = RAYZ_DENOISE_ALBEDO;
 int denoiser_free(RayzDenoiser* dn) {
     if (!dn) return RAYZ_OK;
     if (dn->magic != kDenoiserMagic) return fail(RAYZ_ERR_STATE, "not a denoiser handle");
-    if (dn->device >= 0) {
-        DeviceScope scope(dn->device);
-        // (waits on the handle's own event, never on the caller's stream, which may be gone by now)
-        if (dn->last_ev >= 0) (void)hipEventSynchronize(dn->ev[dn->last_ev]);
-        for (hipEvent_t e : dn->ev)
-            if (e) (void)hipEventDestroy(e);
-        (void)hipFree(dn->ga), (void)hipFree(dn->gb), (void)hipFree(dn->mod), (void)hipFree(dn->col[0]), (void)hipFree(dn->col[1]);
-    }
-    dn->magic = 0;
     delete dn;
     return RAYZ_OK;
 }
@@ -1950,19 +1973,15 @@ int denoiser_create(int device, uint32_t width, uint32_t height, RayzDenoiser** 
         }
     }
     DeviceScope scope(device);
-    RayzDenoiser* dn = new RayzDenoiser();
+    auto dn = std::make_unique<RayzDenoiser>();
     dn->magic = kDenoiserMagic, dn->device = device, dn->width = width, dn->height = height;
-    const size_t bytes = (size_t)width * height * sizeof(dn4);
     hipError_t e = hipSuccess;
-    for (dn4** b : {&dn->ga, &dn->gb, &dn->mod, &dn->col[0], &dn->col[1]})
-        if (e == hipSuccess) e = hipMalloc((void**)b, bytes);
-    for (hipEvent_t& ev : dn->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) {
-        denoiser_free(dn);
-        return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "denoiser buffers: %s", hipGetErrorString(e));
-    }
-    *out = dn;
+    for (DevBuf<dn4>* b : {&dn->ga, &dn->gb, &dn->mod, &dn->col[0], &dn->col[1]})
+        if (e == hipSuccess) e = b->alloc((size_t)width * height);
+    for (DevEvent& ev : dn->ev)
+        if (e == hipSuccess) e = ev.create();
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "denoiser buffers: %s", hipGetErrorString(e));
+    *out = dn.release();
     return RAYZ_OK;
 }
 
@@ -2132,7 +2151,7 @@ uint32_t rayz_hip_chunk_schedule(const RayzRenderParams* p, uint32_t* starts, ui
 }
 
 int rayz_hip_scene_create(const RayzSceneDesc* scene, RayzScene** out) {
-    return guarded([&] { return scene_new(scene, -1, out); });
+    return guarded([&] { return scene_create(scene, -1, out); });
 }
 
 int rayz_hip_scene_create_on(int device, const RayzSceneDesc* scene, RayzScene** out) {
@@ -2143,7 +2162,7 @@ int rayz_hip_scene_create_on(int device, const RayzSceneDesc* scene, RayzScene**
             const int rc = ensure_ctx(device);
             if (rc != RAYZ_OK) return rc;
         }
-        return scene_new(scene, device, out);
+        return scene_create(scene, device, out);
     });
 }
 
@@ -2294,20 +2313,18 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
             }
         }
         DeviceScope scope(device);
-        double *d_in = nullptr, *d_out = nullptr;
+        DevBuf<double> d_in, d_out;
         const size_t in_bytes = host.size() * sizeof(double), out_bytes = (size_t)n * RAYZ_KAT_OUT_STRIDE * sizeof(double);
-        hipError_t e = hipMalloc((void**)&d_in, in_bytes);
-        if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
+        hipError_t e = d_in.alloc(host.size());
+        if (e == hipSuccess) e = d_out.alloc((size_t)n * RAYZ_KAT_OUT_STRIDE);
         if (e == hipSuccess) e = hipMemcpyAsync(d_in, host.data(), in_bytes, hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) {
-            if (precision == RAYZ_PRECISION_F32) hipLaunchKernelGGL(kat_kernel<float>, dim3((n + 63) / 64), dim3(64), 0, stream, op, d_in, n, d_out);
-            else hipLaunchKernelGGL(kat_kernel<double>, dim3((n + 63) / 64), dim3(64), 0, stream, op, d_in, n, d_out);
+            if (precision == RAYZ_PRECISION_F32) hipLaunchKernelGGL(kat_kernel<float>, dim3((n + 63) / 64), dim3(64), 0, stream, op, d_in.get(), n, d_out.get());
+            else hipLaunchKernelGGL(kat_kernel<double>, dim3((n + 63) / 64), dim3(64), 0, stream, op, d_in.get(), n, d_out.get());
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_in);
-        (void)hipFree(d_out);
         if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "rayz_hip_kat: %s", hipGetErrorString(e));
         return (int)RAYZ_OK;
     });
@@ -2315,79 +2332,7 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
 
 // ---- several devices behind one call ----------------------------------------------------------------------
 int rayz_hip_multi_create(const int* devices, int n_devices, const RayzSceneDesc* scene, uint32_t transport, RayzMulti** out) {
-    return guarded([&] {
-        if (!out) return fail(RAYZ_ERR_BAD_ARG, "out handle pointer is null");
-        *out = nullptr;
-        const bool dup_ok = (transport & RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES) != 0;
-        transport &= ~(uint32_t)RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES;
-        if (transport > RAYZ_GATHER_PEER_COPY) return fail(RAYZ_ERR_BAD_ARG, "bad gather transport %u", transport);
-        if (dup_ok && transport != RAYZ_GATHER_PEER_COPY)
-            return fail(RAYZ_ERR_BAD_ARG, "RAYZ_GATHER_ALLOW_DUPLICATE_DEVICES needs the peer-copy transport (RCCL refuses a device twice)");
-        int rc = check_device_list(devices, n_devices, dup_ok);
-        if (rc != RAYZ_OK) return rc;
-        rc = validate_scene(scene);
-        if (rc != RAYZ_OK) return rc;
-        {
-            std::lock_guard<std::mutex> lock(g_mu);
-            for (int i = 0; i < n_devices; ++i) {
-                rc = ensure_ctx(devices[i]);
-                if (rc != RAYZ_OK) return rc;
-            }
-            if (transport == RAYZ_GATHER_RCCL) {
-                rc = rccl_load();
-                if (rc != RAYZ_OK) return rc;
-            }
-        }
-        RayzMulti* m = new RayzMulti();
-        m->transport = transport;
-        m->devices.assign(devices, devices + n_devices);
-        m->tile.assign(n_devices, nullptr);
-        m->tile8.assign(n_devices, nullptr);
-        m->tile_have.assign(n_devices, 0);
-        m->tile8_have.assign(n_devices, 0);
-        m->done.assign(n_devices, nullptr);
-        for (int i = 0; i < n_devices; ++i) {
-            RayzScene* s = nullptr;
-            rc = scene_new(scene, devices[i], &s);
-            if (rc != RAYZ_OK) {
-                multi_free(m);
-                return rc;
-            }
-            m->scenes.push_back(s);
-        }
-        auto bail = [&](int code) {
-            multi_free(m);
-            return code;
-        };
-        if (transport == RAYZ_GATHER_RCCL) {
-            m->comms.assign(n_devices, nullptr);
-            ncclResult_t r = g_rccl.CommInitAll(m->comms.data(), n_devices, m->devices.data());
-            if (r != ncclSuccess) {
-                m->comms.clear();
-                return bail(fail(RAYZ_ERR_HIP, "ncclCommInitAll(%d devices): %s", n_devices, g_rccl.GetErrorString(r)));
-            }
-            (void)g_rccl.GetVersion(&m->rccl_version);
-        } else {
-            for (int i = 0; i < n_devices; ++i) {
-                DeviceScope scope(devices[i]);
-                hipError_t e = hipEventCreateWithFlags(&m->done[i], hipEventDisableTiming);
-                if (e != hipSuccess) return bail(fail(RAYZ_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)));
-                if (i > 0) { // the root pulls nothing; sources push into the root's buffer
-                    int can = 0;
-                    (void)hipDeviceCanAccessPeer(&can, devices[i], devices[0]);
-                    if (can) {
-                        e = hipDeviceEnablePeerAccess(devices[0], 0);
-                        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
-                            return bail(fail(RAYZ_ERR_HIP, "hipDeviceEnablePeerAccess(%d -> %d): %s", devices[i], devices[0],
-                                             hipGetErrorString(e)));
-                        (void)hipGetLastError();
-                    }
-                }
-            }
-        }
-        *out = m;
-        return (int)RAYZ_OK;
-    });
+    return guarded([&] { return multi_create(devices, n_devices, scene, transport, out); });
 }
 
 int rayz_hip_multi_destroy(RayzMulti* m) {
