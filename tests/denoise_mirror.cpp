@@ -1,6 +1,9 @@
 // A plain C++ restatement of the à-trous denoiser's arithmetic contract; it includes no library header.  §4.11
 // fixes the order of every operation, so a restatement of it necessarily has the shape of the device's dn_tap: what makes it a check
-// and not a copy is that it is held, independently of the device, to the hand-derived known answers of tests/test_denoise_cpu.py.
+// and not a copy is that it is held, independently of the device, to the hand-derived known answers of tests/test_denoise_cpu.py: the
+// 0-or-1-weight answers there, the exact rational cases of tests/denoise_cases.py (proper-fraction wn, wz and wc, worked out in
+// Fractions and rounded once) and, on general guides, a float64 statement of §4.11 written from its text (tests/denoise_f64.py)
+// within a derived rounding bound that every listed misreading of §4.11 exceeds.
 // Built by tests/denoise_ref.py with `g++ -O2 -ffp-contract=off` (so the compiler fuses nothing: an FMA happens exactly where fmaf is written) as a shared object; the tests hold the GPU to it bit for bit.
 //
 // §4.11 in short.  Per pixel: radiance c, index, unit normal n, point P, albedo a; bg := index < 0.

@@ -1,11 +1,20 @@
 """The à-trous denoiser without a GPU: hand-derived known answers on the CPU restatement
-(tests/denoise_mirror.cpp, which the GPU tests hold the kernels to bit for bit), the C ABI's refusals, and the quality condition —
-a denoised 4-spp frame of the oracle is nearer to its 256-spp frame than the noisy one."""
+(tests/denoise_mirror.cpp, which the GPU tests hold the kernels to bit for bit) — with weights of 0 and 1 first, then the exact
+rational cases of tests/denoise_cases.py, whose weights are proper fractions, and a float64 statement of §4.11 on general guides
+(tests/denoise_f64.py) that the mirror must stay within a derived bound of and every listed misreading must leave — then the
+C ABI's refusals, and the quality condition — a denoised 4-spp frame of the oracle is nearer to its 256-spp frame than the noisy one."""
 import ctypes as C
+import functools
+import itertools
+import os
+from concurrent.futures import ThreadPoolExecutor
+from fractions import Fraction as F
 
 import numpy as np
 import pytest
 
+import denoise_cases
+import denoise_f64
 import denoise_ref
 import query_reference as qr
 from rayz_amd import capi, tracer
@@ -179,6 +188,150 @@ def test_demodulation_returns_the_albedo_edges_exactly():
     albedo_bg = np.full_like(albedo, 0.5)
     const = np.full((h, w, 3), 0.75, np.float32)
     assert np.array_equal(run(const, index_bg, normal, point, albedo_bg, levels=2), const)
+
+
+# ---- exact answers with weights that are neither 0 nor 1 (tests/denoise_cases.py) ----------------------------------------------
+CASES = {c.name: c for c in denoise_cases.cases()}
+
+
+def test_the_rational_evaluator_gives_the_closed_forms_written_by_hand():
+    """denoise_cases.exact() is §4.11 in Fractions; every case's `hand` is the closed form of its comment with literal weights.  They
+    must agree as rationals, before any rounding.  Two of them once more as bare numbers (base case, L = 3, k = 1): wn = 1/4;
+    out_A = w / (9/64 + w) with w = 3/128·1/4·1/4·1/4 = 3/8192, i.e. 3 / (1152 + 3) = 1/385; out_B = c / (c + w') with c = 9/64·1/16 =
+    1152/131072 and w' = 3/128·1/4·49/64·1/4 = 147/131072, i.e. 1152/1299 = 384/433.  And the 3x3 frame's centre pixel (and 7 of the
+    other 8) has nine pairwise different, nonzero weights."""
+    for c in CASES.values():
+        if c.general:
+            assert denoise_cases.exact(c) == c.hand, c.name
+    b = CASES["base-row-L3-k1"]
+    assert b.hand[(0, 0)] == [F(1, 385)] * 3 and b.hand[(0, 8)] == [F(384, 433)] * 3
+    wts = {}
+    denoise_cases.exact(CASES["nine-weights-3x3"], wts)
+    assert len(wts) == 9 and len(set(wts[(1, 1)])) == 9 and 0 not in wts[(1, 1)]
+    assert sum(len(set(v)) == 9 and 0 not in v for v in wts.values()) >= 8
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_the_mirror_gives_the_rational_answer_bit_for_bit(name):
+    """Every hit pixel of every case of tests/denoise_cases.py (each derived there): the mirror's f32 equals the rational S / W rounded
+    once (then ×m, exact).  No NaN of the background may have reached a hit."""
+    c = CASES[name]
+    c.check(run(c.rgb, c.index, c.normal, c.point, c.albedo, **c.params), "mirror")
+
+
+def test_a_zero_normal_makes_nan_at_its_own_pixel_only():
+    """§4.11 promises W > 0 for unit normals only.  A hit with the normal (0,0,0): its own W is 0 and its output 0/0 = NaN; as a
+    NEIGHBOUR its weight is an honest 0 with finite e_q, so no other pixel's W or S changes (denoise_cases.zero_normal derives every
+    value: W_p = A(x)·A(y) - k·k of the missing tap).  Recorded behaviour, one level: a second level would read the NaN."""
+    c = CASES["zero-normal-5x5"]
+    out = run(c.rgb, c.index, c.normal, c.point, None, **c.params)
+    assert np.isnan(out[2, 2]).all() and np.isnan(out).sum() == 3
+    c.check(out, "mirror")
+    assert out[0, 0, 0] == np.float32((1 / 4 * 3 / 8) / (121 / 256 - 1 / 256))  # I = (0,1) seen from (0,0): k[1]·k[0] / (A(0)^2 - k[2]^2)
+
+
+# ---- the float64 reference on general guides ------------------------------------------------------------------------------------
+F64_SIZES = ((63, 65, 6365), (131, 77, 5))  # (width, height, seed of synthetic())
+F64_LEVELS = (1, 3, 5, 8)
+F64_STATES = [dict(flags=f, sigma_color=sc, sigma_plane=0.3) for f, sc in itertools.product((denoise_ref.ALBEDO, 0), (0.4, INF))] + [
+    {k: denoise_ref.DEFAULTS[k] for k in ("flags", "sigma_color", "sigma_plane")}]
+F64_COMBOS = [dict(st, normal_power_log2=k) for k in (0, 6) for st in F64_STATES]
+EXCLUDED_CAP = 0.001
+POOL = max(1, min(8, os.cpu_count() or 1))
+
+
+@functools.lru_cache(maxsize=None)
+def f64_inputs(size):
+    w, h, seed = F64_SIZES[size]
+    return denoise_cases.synthetic(w, h, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def f64_config(size, combo):
+    """(mirror results, reference results with bound) for levels F64_LEVELS: computed once, shared, never changed."""
+    inp, prm = f64_inputs(size), F64_COMBOS[combo]
+    mir = denoise_ref.denoise(*inp, levels=8, each_level=True, threads=1, **prm)
+    ref = denoise_f64.denoise_f64(*inp, levels=8, want_levels=F64_LEVELS, bound=True, **prm)
+    return {L: mir[L - 1] for L in F64_LEVELS}, ref
+
+
+def _tag(size, combo, L):
+    p = F64_COMBOS[combo]
+    return f"{F64_SIZES[size][0]}x{F64_SIZES[size][1]} L={L} flags={p['flags']} sc={p['sigma_color']} sp={p['sigma_plane']} k={p['normal_power_log2']}"
+
+
+def test_the_mirror_is_within_the_derived_bound_of_the_f64_reference():
+    """synthetic() guides at 63x65 and 131x77; 1, 3, 5, 8 levels; the four (flag, sigma_color) states at sigma_plane 0.3 and the
+    defaults; normal_power_log2 0 and 6: 80 configurations.  Tolerance, per value: denoise_f64's bound — derived in that module's
+    docstring from the rounding count of a tap, |δout| <= Σ_q |δw_q|·|e_q − out| / W plus the propagated input error and the 50
+    roundings of the sums, every quantity the f64 reference's own, DOUBLED for the second-order terms the first-order propagation
+    drops.  The relative error of wn grows 2^k-fold under the squarings (2^6·3u ≈ 1.1e-5 at k = 6), which is why k stops at 6 here.
+    Pixels whose reference W is below 2^-20 at some level are excluded; at most 0.1 % of a frame may be (measured: none — a hit's
+    centre tap alone gives W >= 9/64·(n.n)^64 ≈ 0.14 for the unit normals of these guides).  The measured errors are printed and
+    recorded in DESIGN.md §3; they are not thresholds."""
+    jobs = list(itertools.product(range(len(F64_SIZES)), range(len(F64_COMBOS))))
+    with ThreadPoolExecutor(POOL) as pool:
+        list(pool.map(lambda a: f64_config(*a), jobs))
+    worst = (0.0, 0.0, "")
+    for size, combo in jobs:
+        mir, ref = f64_config(size, combo)
+        for L in F64_LEVELS:
+            out, bound, excluded = ref[L]
+            assert np.isfinite(out).all() and np.isfinite(bound).all(), _tag(size, combo, L)
+            assert excluded.mean() <= EXCLUDED_CAP, (_tag(size, combo, L), int(excluded.sum()))
+            err = np.abs(mir[L].astype(np.float64) - out)
+            keep = ~excluded[..., None] & np.ones(3, bool)
+            ratio = float((err[keep] / bound[keep]).max())
+            print(f"mirror vs f64: {_tag(size, combo, L)}: max |err| {err[keep].max():.3e}, max err/bound {ratio:.4f}, excluded {int(excluded.sum())}")
+            worst = max(worst, (ratio, float(err[keep].max()), _tag(size, combo, L)))
+            assert (err[keep] <= bound[keep]).all(), (_tag(size, combo, L), ratio)
+    print(f"mirror vs f64, worst: err/bound {worst[0]:.4f} (|err| {worst[1]:.3e}) at {worst[2]}")
+
+
+def test_every_misreading_of_the_f64_reference_is_rejected():
+    """Each of denoise_f64.MISREADINGS, switched into the f64 reference, must differ from the MIRROR by more than the bound of the
+    test above (the reference-as-written's, at the same configuration) at some value of some configuration — were mirror and kernel
+    to adopt that misreading together, the test above would fail by the same margin.  Run at 63x65 over all 40 configurations there
+    (the larger frame adds time, not cases).  A misreading that a configuration cannot show (4^l at one level, the colour term at
+    sigma_color = +inf, the floor without demodulation, wn^(k+1) at k = 0) is simply not caught THERE; the condition is one catch.
+    `bg_weighted_zero` changes no value on a finite frame (it adds 0 to W and fma(0, e_q, S) = S), so it alone runs on the same
+    guides with a NaN sky: the mirror keeps every hit pixel within the bound of the reference, the misreading turns hits to NaN."""
+    size = 0
+    inp = f64_inputs(size)
+    hit = inp[1] >= 0
+    sky = list(inp)
+    sky[0] = inp[0].copy()
+    sky[0][~hit] = np.nan
+
+    def one(combo):
+        prm = F64_COMBOS[combo]
+        mir, ref = f64_config(size, combo)
+        mir_sky = denoise_ref.denoise(*sky, levels=8, each_level=True, threads=1, **prm)
+        rows = {}
+        for name in denoise_f64.MISREADINGS:
+            on_sky = name == "bg_weighted_zero"
+            got = denoise_f64.denoise_f64(*(sky if on_sky else inp), levels=8, want_levels=F64_LEVELS, misread=name, **prm)
+            for L in F64_LEVELS:
+                out, bound, excluded = ref[L]
+                keep = hit & ~excluded
+                m = mir_sky[L - 1] if on_sky else mir[L]
+                if on_sky:  # the mirror itself is unharmed by the sky's NaN, to the same bound
+                    assert (np.abs(m[keep].astype(np.float64) - out[keep]) <= bound[keep]).all(), (name, _tag(size, combo, L))
+                with np.errstate(invalid="ignore"):
+                    ratio = np.abs(m[keep].astype(np.float64) - got[L][keep]) / bound[keep]
+                rows[(name, L)] = float("inf") if np.isnan(ratio).any() else float(ratio.max())  # a NaN is outside any tolerance
+        return rows
+
+    with ThreadPoolExecutor(POOL) as pool:
+        rows = list(pool.map(one, range(len(F64_COMBOS))))
+    for name in denoise_f64.MISREADINGS:
+        for combo, r in enumerate(rows):
+            for L in F64_LEVELS:
+                print(f"misreading {name}: {_tag(size, combo, L)}: max |misread - mirror| / bound {r[(name, L)]:.4g}")
+        caught = [r[(name, L)] for r in rows for L in F64_LEVELS if r[(name, L)] > 1]
+        print(f"misreading {name}: caught in {len(caught)} of {len(rows) * len(F64_LEVELS)} configurations; smallest catch {min(caught, default=0):.4g} x bound, "
+              f"largest {max(caught, default=0):.4g} x bound")
+        assert caught, f"the misreading {name} stays within the tolerance of the mirror on every input"
 
 
 # ---- the C ABI's refusals: every one decided before the handle is looked at, none touches a device ---------------------------

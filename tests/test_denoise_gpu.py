@@ -1,7 +1,9 @@
 """The à-trous denoiser on the GPU (rayz_hip_denoiser_*, `render.Denoiser`): every value of every frame equals the CPU restatement of
 DESIGN.md §4.11 (tests/denoise_mirror.cpp) bit for bit — synthetic guides at sizes that are no multiple of a tile and smaller than a
 halo, every level count, both flag states, the colour term on and off, in place and out of place, every staging form of the levels,
-and real G-buffers with rendered 4-spp frames; plus stream ordering after a progressive preview and repeatability on one handle."""
+and real G-buffers with rendered 4-spp frames; plus stream ordering after a progressive preview and repeatability on one handle.
+Two comparisons do not go through the mirror: the exact rational cases of tests/denoise_cases.py, bit for bit, and the float64
+statement of §4.11 (tests/denoise_f64.py) within its derived bound."""
 import ctypes as C
 import itertools
 
@@ -9,7 +11,10 @@ import numpy as np
 import pytest
 import torch
 
+import denoise_cases
+import denoise_f64
 import denoise_ref
+from denoise_cases import synthetic
 from helpers import assert_images_equal
 from rayz_amd import capi, render, tracer
 
@@ -19,35 +24,6 @@ INF = float("inf")
 BVH = capi.TRAVERSAL_BVH
 STAGING = (-1, 0, 1, 2, 4)  # RAYZ_DEBUG_DENOISE_LDS_STRIDE: the built-in choice; no level staged in LDS; strides up to 1 / 2 / 4 staged
 SMALL = [(1, 1), (1, 7), (7, 1), (5, 3), (63, 65), (257, 130)]  # (width, height)
-
-
-def synthetic(w, h, seed):
-    """Guides that exercise every branch of a tap: regions with their own base normal (so wn is 0 across some borders and near 1
-    inside), normals and points perturbed pixel by pixel, blocks of background (their normal and point 0, as a query writes them),
-    pairs of pixels that share one point exactly (d2 == 0), an albedo with channels below the 2^-8 floor, and a noisy colour."""
-    rng = np.random.default_rng(seed)
-    gx, gy = np.meshgrid(np.arange(w), np.arange(h))
-    region = ((gx // 9) + 2 * (gy // 7)) % 5
-    base = rng.normal(size=(5, 3))
-    base /= np.linalg.norm(base, axis=1, keepdims=True)
-    normal = base[region] + rng.normal(scale=0.08, size=(h, w, 3))
-    normal /= np.linalg.norm(normal, axis=2, keepdims=True)
-    point = np.stack([gx * 0.05, gy * 0.05, region * 0.3], axis=2) + rng.normal(scale=0.004, size=(h, w, 3))
-    if w > 1:
-        same = rng.random((h, w - 1)) < 0.05
-        point[:, 1:][same] = point[:, :-1][same]
-    index = rng.integers(0, 400, (h, w)).astype(np.int32)
-    bg = ((gx // 11 + gy // 5) % 4 == 0) | (rng.random((h, w)) < 0.03)
-    index[bg] = -1
-    normal[bg] = 0
-    point[bg] = 0
-    albedo = rng.random((h, w, 3))
-    albedo[rng.random((h, w, 3)) < 0.05] = 0.001
-    albedo[bg] = 0
-    rgb = np.abs(albedo * (0.8 + 0.4 * np.sin(gx * 0.11 + gy * 0.07))[..., None] + rng.normal(scale=0.3, size=(h, w, 3)))
-    rgb[bg] = (0.5, 0.7, 1.0) + rng.normal(scale=0.1, size=(int(bg.sum()), 3))
-    f = lambda a: np.ascontiguousarray(a, dtype=np.float32)  # noqa: E731
-    return f(rgb), index, f(normal), f(point), f(albedo)
 
 
 def to_gbuffer(index, normal, point, albedo):
@@ -65,7 +41,7 @@ def gpu_run(dn, rgb, g, in_place, staging=-1, **prm):
         render.debug_set(capi.DEBUG_DENOISE_LDS_STRIDE, -1)
     torch.cuda.synchronize()
     if not in_place:
-        assert np.array_equal(x.cpu().numpy(), rgb), "an out-of-place run changed its input"
+        assert np.array_equal(x.cpu().numpy().view(np.uint32), rgb.view(np.uint32)), "an out-of-place run changed its input"
     return out.cpu().numpy()
 
 
@@ -113,6 +89,59 @@ def test_device_equals_the_mirror_at_1920x1080(gpu):
         for levels in range(1, 9):
             got = gpu_run(dn, rgb, g, next(place), staging=next(staging), levels=levels, flags=flag, sigma_color=sc)
             assert_images_equal(got, want[levels - 1], f"1920x1080 L={levels} flags={flag} sigma_color={sc}")
+    dn.close()
+
+
+def test_device_gives_the_rational_answers_bit_for_bit(gpu):
+    """Every case of tests/denoise_cases.py (two hits 2^L apart with proper-fraction weights, L = 1..8; column, diagonal, stride 1;
+    wn underflowing, back-facing, d2 == 0, u clamped; demodulation with the floor; nine different weights in a 3x3 frame) under every
+    staging setting, out of place and in place, held to the RATIONAL expectation (Fractions, rounded once) directly — not to the
+    mirror.  The NaN of the background pixels must not reach a hit."""
+    handles = {}
+    for c in denoise_cases.cases():
+        if c.name.startswith("zero-normal"):
+            continue  # what §4.11 does not promise has its own test below
+        h, w = c.index.shape
+        dn = handles.get((w, h)) or handles.setdefault((w, h), render.Denoiser(w, h))
+        g = to_gbuffer(c.index, c.normal, c.point, c.albedo if c.albedo is not None else np.zeros_like(c.normal))
+        for st, in_place in itertools.product(STAGING, (False, True)):
+            c.check(gpu_run(dn, c.rgb, g, in_place, staging=st, **c.params), f"device staging={st} in_place={in_place}")
+    for dn in handles.values():
+        dn.close()
+
+
+def test_a_zero_normal_makes_nan_at_its_own_pixel_only(gpu):
+    """The device on the input of test_denoise_cpu.py's test of the same name: a hit whose normal is (0,0,0) gets 0/0 = NaN at its own
+    pixel after one level; every other pixel has the rational value derived in denoise_cases.zero_normal, as the mirror has."""
+    c = next(c for c in denoise_cases.cases() if c.name.startswith("zero-normal"))
+    h, w = c.index.shape
+    dn = render.Denoiser(w, h)
+    g = to_gbuffer(c.index, c.normal, c.point, np.zeros_like(c.normal))
+    for st in (-1, 0):
+        out = gpu_run(dn, c.rgb, g, False, staging=st, **c.params)
+        assert np.isnan(out[2, 2]).all() and np.isnan(out).sum() == 3
+        c.check(out, f"device staging={st}")
+    dn.close()
+
+
+@pytest.mark.parametrize("w,h,seed", [(63, 65, 6365), (131, 77, 5)])
+def test_device_is_within_the_derived_bound_of_the_f64_reference(gpu, w, h, seed):
+    """The device against tests/denoise_f64.py DIRECTLY, within the per-value bound derived in that module (and used, with the same
+    exclusion cap, by test_denoise_cpu.py): 1, 5 and 8 levels with the default parameters and with one state without demodulation.
+    Redundant with device == mirror by design: this comparison survives an edit of the mirror."""
+    inp = synthetic(w, h, seed)
+    g = to_gbuffer(*inp[1:])
+    dn = render.Denoiser(w, h)
+    levels = (1, 5, 8)
+    for prm in (dict(), dict(flags=0, sigma_color=0.4, sigma_plane=0.3)):
+        ref = denoise_f64.denoise_f64(*inp, **{**denoise_ref.DEFAULTS, **prm, "levels": 8}, want_levels=levels, bound=True)
+        for L in levels:
+            out, bound, excluded = ref[L]
+            assert excluded.mean() <= 0.001, (L, int(excluded.sum()))
+            got = gpu_run(dn, inp[0], g, False, levels=L, **prm).astype(np.float64)
+            err = np.abs(got - out)[~excluded]
+            print(f"device vs f64: {w}x{h} L={L} {prm}: max |err| {err.max():.3e}, max err/bound {(err / bound[~excluded]).max():.4f}")
+            assert (err <= bound[~excluded]).all(), (w, h, L, prm, float((err / bound[~excluded]).max()))
     dn.close()
 
 
