@@ -293,6 +293,67 @@ int rayz_hip_progressive_info(const RayzProgressive* pr, uint32_t* samples_done,
                               uint32_t* n_chunks, RayzRenderStats* total_or_null);
 int rayz_hip_progressive_destroy(RayzProgressive* pr);
 
+/* ---- noise estimate: "is this pixel done?" -----------------------------------------------------------------------------
+ * BUILD-DEFINED (the reference reports progress towards a sample count only, src/renderer.zig:84,98-99).  A progressive handle
+ * that TRACKS noise keeps, beside its accumulator, the second moment of every pixel's chunk sums (three f64 per pixel in a 32-byte
+ * record, folded in chunk order, so the same bits for any partition into passes).  The chunk sums of a pixel are independent sums
+ * of iid samples, so their spread is an unbiased estimate of the variance of the pixel's mean: `var`, channels summed.  `rel2` is
+ * var / max(|mean|^2, mean_floor^2) — the squared relative error of the pixel — and a pixel is UNCONVERGED iff
+ * !(rel2 <= rel_error^2), so a NaN counts as unconverged.  Before the second chunk there is no estimate: var = rel2 = +inf.
+ * With few chunks the estimate itself is noisy (K - 1 degrees of freedom).  The arithmetic is a contract, DESIGN.md §4.12 (f64,
+ * + - x /, comparisons; no FMA, no sqrt), restated bit for bit by tests/noise_ref.py.  Tracking changes no image.  Added in ABI 5
+ * (additive: no existing symbol changed). */
+#define RAYZ_NOISE_DEFAULT_REL_ERROR 0.05  /* parameters, not contract */
+#define RAYZ_NOISE_DEFAULT_MEAN_FLOOR 0.02 /* pixels darker than this (|mean RGB|) are held to the absolute error rel_error x mean_floor */
+typedef struct RayzNoiseParams {
+    double rel_error;  /* > 0 (and its square > 0): the relative standard error of the pixel mean at which a pixel counts as converged */
+    double mean_floor; /* > 0 (and its square > 0) */
+} RayzNoiseParams;
+
+typedef struct RayzNoiseSummary {
+    uint64_t pixels;      /* pixels of the handle's shard */
+    uint64_t unconverged; /* of those, pixels with !(rel2 <= rel_error^2) */
+    double max_rel2;      /* the largest rel2 (a NaN anywhere surfaces here as a NaN; +inf before the second chunk) */
+    double mean_var;      /* (sum of the finite var) / pixels; 0 for an empty shard */
+    uint32_t samples_done;/* N: samples per pixel the estimate covers */
+    uint32_t chunks_done; /* K: chunks the estimate covers */
+} RayzNoiseSummary;
+
+/* Makes `pr` a tracked handle: allocates the moment state (rows_in_shard*width*32 bytes).  Only before the first step
+ * (RAYZ_ERR_STATE afterwards); a second call before the first step is RAYZ_OK and does nothing.  An untracked handle runs
+ * exactly what it ran before this entry point existed. */
+int rayz_hip_progressive_track_noise(RayzProgressive* pr);
+/* Evaluates the estimate for the samples done so far.  `d_var_or_null`, `d_rel2_or_null`: DEVICE memory, rows_in_shard*width
+ * floats each (the f64 values rounded once), written asynchronously on `hip_stream` (NULL: the library's stream), which the call
+ * orders after the handle's last pass on the device.  With `summary_or_null` the call waits for the few summary values and fills
+ * it; without it nothing blocks: the outputs are complete once `hip_stream` has been waited for (rayz_hip_progressive_info with
+ * `total_or_null` also waits for the handle's last evaluation, as does destroying the handle).  p_or_null == NULL: the defaults.  RAYZ_ERR_BAD_ARG (checked first, before any device work): a
+ * rel_error or mean_floor that is not positive (NaN included) or whose square is not; RAYZ_ERR_STATE: an untracked handle. */
+int rayz_hip_progressive_noise(RayzProgressive* pr, const RayzNoiseParams* p_or_null, float* d_var_or_null, float* d_rel2_or_null,
+                               RayzNoiseSummary* summary_or_null, void* hip_stream);
+/* The moment state itself, for tests and tools: rows_in_shard*width*4 doubles {Q_r, Q_g, Q_b, 0} copied to DEVICE memory `d_q`
+ * on `hip_stream`, ordered after the handle's last pass.  Blocks until the copy is done. */
+int rayz_hip_progressive_noise_state(RayzProgressive* pr, double* d_q, void* hip_stream);
+/* Render until converged: steps a tracked handle with `min_samples_per_pass` (as rayz_hip_progressive_step) and evaluates after
+ * every pass, until unconverged <= max_unconverged_fraction * pixels or the schedule ends — both are RAYZ_OK;
+ * last_summary_or_null->chunks_done (against rayz_hip_progressive_info's n_chunks) and ->unconverged tell which.  It stops at
+ * pass boundaries only, so the frame in `d_preview_or_null` is the mean of the first samples_done samples of every pixel, and
+ * the one-shot frame bit for bit once the schedule has ended.  Blocks.  max_unconverged_fraction must lie in [0, 1].  A shard
+ * without pixels has nothing unconverged: it stops after its first pass. */
+int rayz_hip_progressive_run_until(RayzProgressive* pr, const RayzNoiseParams* p_or_null, double max_unconverged_fraction,
+                                   uint32_t min_samples_per_pass, float* d_preview_or_null, RayzNoiseSummary* last_summary_or_null,
+                                   void* hip_stream);
+int rayz_hip_progressive_run_until_f64(RayzProgressive* pr, const RayzNoiseParams* p_or_null, double max_unconverged_fraction,
+                                       uint32_t min_samples_per_pass, double* d_preview_or_null, RayzNoiseSummary* last_summary_or_null,
+                                       void* hip_stream);
+/* Known answers, as rayz_hip_kat: runs the two kernels on caller chunk sums — HOST buffers, chunk_sums[(k*n_pixels + i)*3 + ch]
+ * (narrowed to `precision` as a scene is), chunk_sizes[k] > 0 samples in chunk k — as a tracked handle would have folded them
+ * (chunk 0 as a first pass, the rest as a second), on the default device; no scene needed.  Outputs (HOST, each optional):
+ * q_out n_pixels*3, var_out and rel2_out n_pixels doubles (the f64 values), the summary as rayz_hip_progressive_noise fills it. */
+int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint32_t* chunk_sizes, uint32_t n_pixels,
+                       uint32_t n_chunks, const RayzNoiseParams* p_or_null, double* q_out, double* var_out, double* rel2_out,
+                       RayzNoiseSummary* summary_or_null);
+
 /* ---- several GPUs behind ONE call -------------------------------------------------------------------------
  * The reference's caller makes one call, `tracer.render()` (src/rayz.zig:26, src/renderer.zig:72-101).  These
  * entry points give that one call every GPU of the node: the pool is replicated (one scene per device), image

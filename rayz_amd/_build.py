@@ -42,6 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     lib_src = [os.path.join(CSRC, "rayz_hip.hip"), os.path.join(HOST, "rayz_host.cpp")]
     deps = lib_src + [
         os.path.join(CSRC, "rayz_device.hpp"), os.path.join(CSRC, "plane_runs.hpp"), os.path.join(CSRC, "bvh_build.hpp"), os.path.join(CSRC, "denoise.hpp"),
+        os.path.join(CSRC, "noise.hpp"),
         os.path.join(HOST, "rayz.hpp"),
         # (compiled only with -DRAYZ_EXPERIMENTS, but files rayz_hip.hip can include: an edit must not leave a stale library)
         *(os.path.join(CSRC, "experiments", f) for f in ("bvh2_kernel.hpp", "bvhx_kernel.hpp", "launch.hpp")),

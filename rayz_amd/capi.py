@@ -38,6 +38,7 @@ TRAVERSAL_LINEAR, TRAVERSAL_BVH, TRAVERSAL_AUTO = 0, 1, 2
 QUERY_NEAREST, QUERY_ANY = 0, 1
 DENOISE_ALBEDO = 1
 DENOISE_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 0.5, "sigma_plane": 0.25}
+NOISE_DEFAULTS = {"rel_error": 0.05, "mean_floor": 0.02}
 
 D3 = C.c_double * 3
 
@@ -99,10 +100,20 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_double), ("sigma_plane", C.c_double)]
 
 
+class NoiseParams(C.Structure):
+    _fields_ = [("rel_error", C.c_double), ("mean_floor", C.c_double)]
+
+
+class NoiseSummary(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("unconverged", C.c_uint64), ("max_rel2", C.c_double), ("mean_var", C.c_double),
+                ("samples_done", C.c_uint32), ("chunks_done", C.c_uint32)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
+assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -139,6 +150,17 @@ PROTOTYPES = [
     ("rayz_hip_progressive_info", C.c_int,
      [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(RenderStats)]),
     ("rayz_hip_progressive_destroy", C.c_int, [C.c_void_p]),
+    ("rayz_hip_progressive_track_noise", C.c_int, [C.c_void_p]),
+    ("rayz_hip_progressive_noise", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.c_void_p, C.POINTER(NoiseSummary), C.c_void_p]),
+    ("rayz_hip_progressive_noise_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_progressive_run_until", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_double, C.c_uint32, C.c_void_p, C.POINTER(NoiseSummary), C.c_void_p]),
+    ("rayz_hip_progressive_run_until_f64", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_double, C.c_uint32, C.c_void_p, C.POINTER(NoiseSummary), C.c_void_p]),
+    ("rayz_hip_noise_kat", C.c_int,
+     [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(NoiseParams),
+      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(NoiseSummary)]),
     ("rayz_hip_multi_create", C.c_int,
      [C.POINTER(C.c_int), C.c_int, C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_multi_destroy", C.c_int, [C.c_void_p]),

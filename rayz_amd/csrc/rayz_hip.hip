@@ -9,6 +9,7 @@
 #include "rayz_device.hpp"
 #include "bvh_build.hpp"
 #include "denoise.hpp"
+#include "noise.hpp"
 
 #include <rccl/rccl.h> // types and prototypes only: the library is opened with dlopen at the first multi-device call
 
@@ -1262,10 +1263,18 @@ struct RayzProgressive {
     std::vector<DevEvent> pending, spare;   // pairs bracketing the trace kernel of every pass not yet summed into kernel_ms
     double kernel_ms = 0;
     hipStream_t last_stream = nullptr;
-    ~RayzProgressive() { // the accumulator's last pass has finished before the members go
-        if (device < 0 || !last_stream) return;
+    // noise tracking (rayz_hip_progressive_track_noise): absent from an untracked handle
+    bool tracked = false;
+    DevBuf<d4> q;                           // shard_pixels records {Q_r, Q_g, Q_b, 0}
+    DevBuf<unsigned long long> nz_summary;  // [0] unconverged pixels, [1] max rel2 (bit pattern): cleared per evaluation
+    DevBuf<double> nz_block_sum;            // Σ finite var per block of noise_eval_kernel
+    DevEvent pass_done;                     // recorded behind every pass: what an evaluation on another stream waits for
+    hipStream_t noise_stream = nullptr;     // the stream of the last evaluation (it reads acc and q: the next pass waits for it)
+    ~RayzProgressive() { // the accumulator's last pass, and the last evaluation, have finished before the members go
+        if (device < 0) return;
         DeviceScope scope(device);
-        (void)hipStreamSynchronize(last_stream);
+        if (last_stream) (void)hipStreamSynchronize(last_stream);
+        if (noise_stream && noise_stream != last_stream) (void)hipStreamSynchronize(noise_stream);
     }
 };
 
@@ -1335,6 +1344,7 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
     rc = check_items(pr->shard_pixels, c1 - c0);
     if (rc != RAYZ_OK) return rc;
     if (pr->last_stream && pr->last_stream != stream) HIP_TRY(hipStreamSynchronize(pr->last_stream)); // the accumulator's last pass
+    if (pr->noise_stream && pr->noise_stream != stream) HIP_TRY(hipStreamSynchronize(pr->noise_stream)); // .. and its last reader
     pr->bvh = use_bvh;
     const uint64_t samples = pr->starts[c1] - pr->starts[c0];
     if (pr->shard_pixels && pr->params.max_bounces == 0) { // bounceRay(ray, 0) is black, src/renderer.zig:104-105
@@ -1363,12 +1373,18 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
         }
         pr->pending.push_back(std::move(ev0));
         pr->pending.push_back(std::move(ev1));
-        hipLaunchKernelGGL(accumulate_kernel<R>, dim3((uint32_t)((pr->shard_pixels + 255) / 256)), dim3(256), 0, stream,
-                           (const r4*)s->partial.get(), (r4*)pr->acc.get(), d_preview, (uint32_t)pr->shard_pixels, c1 - c0,
-                           pr->starts[c1], c0 == 0 ? 1u : 0u);
+        if (pr->tracked)
+            hipLaunchKernelGGL(accumulate_moments_kernel<R>, dim3((uint32_t)((pr->shard_pixels + 255) / 256)), dim3(256), 0, stream,
+                               (const r4*)s->partial.get(), (r4*)pr->acc.get(), pr->q.get(), d_preview, pr->d_starts.get() + c0,
+                               (uint32_t)pr->shard_pixels, c1 - c0, pr->starts[c1], c0 == 0 ? 1u : 0u);
+        else
+            hipLaunchKernelGGL(accumulate_kernel<R>, dim3((uint32_t)((pr->shard_pixels + 255) / 256)), dim3(256), 0, stream,
+                               (const r4*)s->partial.get(), (r4*)pr->acc.get(), d_preview, (uint32_t)pr->shard_pixels, c1 - c0,
+                               pr->starts[c1], c0 == 0 ? 1u : 0u);
         HIP_TRY(hipGetLastError());
         pr->traced = true;
     }
+    if (pr->tracked && pr->shard_pixels) HIP_TRY(hipEventRecord(pr->pass_done, stream));
     pr->primary_rays += pr->shard_pixels * samples;
     pr->chunks_done = c1;
     return RAYZ_OK;
@@ -1384,6 +1400,10 @@ int progressive_info(const RayzProgressive* cpr, uint32_t* samples_done, uint32_
     if (!total) return RAYZ_OK;
     RayzRenderStats st{};
     st.primary_rays = pr->primary_rays;
+    if (pr->noise_stream) { // .. and for the last evaluation: what a caller of rayz_hip_progressive_noise without a summary waits with
+        DeviceScope scope(pr->device);
+        HIP_TRY(hipStreamSynchronize(pr->noise_stream));
+    }
     if (pr->traced) {
         DeviceScope scope(pr->device);
         if (pr->last_stream) HIP_TRY(hipStreamSynchronize(pr->last_stream));
@@ -1405,6 +1425,214 @@ int progressive_info(const RayzProgressive* cpr, uint32_t* samples_done, uint32_
         st.kernel_ms = pr->kernel_ms;
     }
     *total = st;
+    return RAYZ_OK;
+}
+
+// ---- the noise estimate of a tracked handle (kernels: noise.hpp) ------------------------------------------------
+int noise_params(const RayzNoiseParams* in, double& tau2, double& floor2) {
+    const RayzNoiseParams p = in ? *in : RayzNoiseParams{RAYZ_NOISE_DEFAULT_REL_ERROR, RAYZ_NOISE_DEFAULT_MEAN_FLOOR};
+    tau2 = p.rel_error * p.rel_error, floor2 = p.mean_floor * p.mean_floor; // (f64, rounded once each: what the kernel compares with)
+    if (!(p.rel_error > 0) || !(tau2 > 0)) return fail(RAYZ_ERR_BAD_ARG, "noise rel_error %g: must be positive (and its square)", p.rel_error);
+    if (!(p.mean_floor > 0) || !(floor2 > 0)) return fail(RAYZ_ERR_BAD_ARG, "noise mean_floor %g: must be positive (and its square)", p.mean_floor);
+    return RAYZ_OK;
+}
+
+int progressive_track_noise(RayzProgressive* pr) {
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (pr->tracked) return RAYZ_OK;
+    if (pr->chunks_done) return fail(RAYZ_ERR_STATE, "noise tracking starts before the first step (%u chunks done)", pr->chunks_done);
+    DeviceScope scope(pr->device);
+    const size_t r4_bytes = pr->params.precision == RAYZ_PRECISION_F64 ? sizeof(d4) : sizeof(f4);
+    const uint32_t blocks = noise_blocks(pr->shard_pixels);
+    hipError_t e = pr->q.alloc(pr->shard_pixels);
+    if (e == hipSuccess) e = pr->nz_summary.alloc(2);
+    if (e == hipSuccess) e = pr->nz_block_sum.alloc(blocks);
+    if (e == hipSuccess) e = pr->pass_done.create(hipEventDisableTiming);
+    // +0 everywhere: what an evaluation before the first pass — or of a render whose passes trace nothing (max_bounces = 0) — reads
+    if (e == hipSuccess && pr->shard_pixels) e = hipMemset(pr->q, 0, pr->shard_pixels * sizeof(d4));
+    if (e == hipSuccess && pr->shard_pixels) e = hipMemset(pr->acc, 0, pr->shard_pixels * r4_bytes);
+    if (e != hipSuccess) {
+        pr->q.reset();
+        return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "noise state: %s", hipGetErrorString(e));
+    }
+    pr->tracked = true;
+    return RAYZ_OK;
+}
+
+// Launches noise_eval_kernel on `stream` and, with `summary`, waits for it and fills the summary.  `acc`, `q`: `pixels` records.
+template <class R>
+int noise_eval(const void* acc, const d4* q, float* d_var, float* d_rel2, double* d_var64, double* d_rel264, unsigned long long* d_summary,
+               double* d_block_sum, uint64_t pixels, uint32_t chunks_done, uint32_t samples_done, double floor2, double tau2,
+               RayzNoiseSummary* summary, hipStream_t stream) {
+    typedef typename VecOf<R>::type r4;
+    const uint32_t blocks = noise_blocks(pixels);
+    if (pixels) {
+        HIP_TRY(hipMemsetAsync(d_summary, 0, 2 * sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL(noise_eval_kernel<R>, dim3(blocks), dim3(256), 0, stream, (const r4*)acc, q, d_var, d_rel2, d_var64, d_rel264,
+                           d_summary, d_block_sum, (uint32_t)pixels, chunks_done, samples_done, floor2, tau2);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!summary) return RAYZ_OK;
+    RayzNoiseSummary out{};
+    out.pixels = pixels, out.samples_done = samples_done, out.chunks_done = chunks_done;
+    if (pixels) {
+        unsigned long long two[2] = {0, 0};
+        std::vector<double> part(blocks);
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpy(two, d_summary, sizeof(two), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(part.data(), d_block_sum, blocks * sizeof(double), hipMemcpyDeviceToHost));
+        double sum = 0.0;
+        for (const double x : part) sum = sum + x; // block order
+        out.unconverged = two[0];
+        std::memcpy(&out.max_rel2, &two[1], sizeof(double));
+        out.mean_var = sum / (double)pixels;
+    }
+    *summary = out;
+    return RAYZ_OK;
+}
+
+int progressive_noise(RayzProgressive* pr, const RayzNoiseParams* params, float* d_var, float* d_rel2, RayzNoiseSummary* summary,
+                      void* stream_arg) {
+    double tau2 = 0, floor2 = 0;
+    int rc = noise_params(params, tau2, floor2);
+    if (rc != RAYZ_OK) return rc;
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
+    DeviceCtx* ctx = nullptr;
+    rc = scene_ctx(pr->scene, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    DeviceScope scope(pr->device);
+    const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    if (pr->noise_stream && pr->noise_stream != stream) HIP_TRY(hipStreamSynchronize(pr->noise_stream)); // one evaluation owns the summary
+    if (pr->last_stream && pr->last_stream != stream && pr->shard_pixels) HIP_TRY(hipStreamWaitEvent(stream, pr->pass_done, 0));
+    pr->noise_stream = stream;
+    const uint32_t K = pr->chunks_done, N = pr->starts[K];
+    if (pr->params.precision == RAYZ_PRECISION_F64)
+        return noise_eval<double>(pr->acc.get(), pr->q, d_var, d_rel2, nullptr, nullptr, pr->nz_summary, pr->nz_block_sum, pr->shard_pixels, K,
+                                  N, floor2, tau2, summary, stream);
+    return noise_eval<float>(pr->acc.get(), pr->q, d_var, d_rel2, nullptr, nullptr, pr->nz_summary, pr->nz_block_sum, pr->shard_pixels, K, N,
+                             floor2, tau2, summary, stream);
+}
+
+int progressive_noise_state(RayzProgressive* pr, double* d_q, void* stream_arg) {
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
+    if (!pr->shard_pixels) return RAYZ_OK;
+    if (!d_q) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
+    DeviceCtx* ctx = nullptr;
+    const int rc = scene_ctx(pr->scene, &ctx);
+    if (rc != RAYZ_OK) return rc;
+    DeviceScope scope(pr->device);
+    const hipStream_t stream = stream_arg ? (hipStream_t)stream_arg : ctx->stream;
+    if (pr->noise_stream && pr->noise_stream != stream) HIP_TRY(hipStreamSynchronize(pr->noise_stream));
+    if (pr->last_stream && pr->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, pr->pass_done, 0));
+    pr->noise_stream = stream; // (a reader of q, as an evaluation is)
+    HIP_TRY(hipMemcpyAsync(d_q, pr->q, pr->shard_pixels * sizeof(d4), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (an accessor for tests and tools: it blocks)
+    return RAYZ_OK;
+}
+
+template <class R>
+int progressive_run_until(RayzProgressive* pr, const RayzNoiseParams* params, double max_fraction, uint32_t min_samples, R* d_preview,
+                          RayzNoiseSummary* last, void* stream_arg, uint32_t precision) {
+    double tau2 = 0, floor2 = 0;
+    int rc = noise_params(params, tau2, floor2);
+    if (rc != RAYZ_OK) return rc;
+    if (!(max_fraction >= 0.0 && max_fraction <= 1.0))
+        return fail(RAYZ_ERR_BAD_ARG, "max_unconverged_fraction %g: must lie in [0, 1]", max_fraction);
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
+    const uint32_t n = (uint32_t)pr->starts.size() - 1;
+    RayzNoiseSummary sm{};
+    for (;;) {
+        rc = progressive_step<R>(pr, min_samples, d_preview, stream_arg, precision);
+        if (rc != RAYZ_OK) return rc;
+        rc = progressive_noise(pr, params, nullptr, nullptr, &sm, stream_arg);
+        if (rc != RAYZ_OK) return rc;
+        if ((double)sm.unconverged <= max_fraction * (double)sm.pixels || pr->chunks_done >= n) break;
+    }
+    if (last) *last = sm;
+    return RAYZ_OK;
+}
+
+int noise_kat(uint32_t precision, const double* sums, const uint32_t* sizes, uint32_t n_pixels, uint32_t n_chunks,
+              const RayzNoiseParams* params, double* q_out, double* var_out, double* rel2_out, RayzNoiseSummary* summary) {
+    double tau2 = 0, floor2 = 0;
+    int rc = noise_params(params, tau2, floor2);
+    if (rc != RAYZ_OK) return rc;
+    if (precision > RAYZ_PRECISION_F64) return fail(RAYZ_ERR_BAD_ARG, "bad precision %u", precision);
+    if (!n_chunks) return fail(RAYZ_ERR_BAD_ARG, "n_chunks is 0");
+    if (!sizes || (n_pixels && !sums)) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
+    if ((uint64_t)n_pixels * n_chunks > (1ull << 28)) return fail(RAYZ_ERR_BAD_ARG, "n_pixels x n_chunks = %llu: more than 2^28 chunk sums",
+                                                                   (unsigned long long)n_pixels * n_chunks);
+    std::vector<uint32_t> starts(n_chunks + 1, 0);
+    for (uint32_t k = 0; k < n_chunks; ++k) {
+        if (!sizes[k] || (uint64_t)starts[k] + sizes[k] > UINT32_MAX)
+            return fail(RAYZ_ERR_BAD_ARG, "chunk_sizes[%u] = %u: a chunk holds at least one sample, and all of them at most 2^32 - 1", k, sizes[k]);
+        starts[k + 1] = starts[k] + sizes[k];
+    }
+    int device;
+    hipStream_t stream;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        device = g_default;
+        if (device < 0) return fail(RAYZ_ERR_NO_DEVICE, "rayz_hip_init has not succeeded");
+        stream = g_ctx[device].stream;
+    }
+    if (!n_pixels) {
+        if (summary) *summary = RayzNoiseSummary{0, 0, 0.0, 0.0, starts[n_chunks], n_chunks};
+        return RAYZ_OK;
+    }
+    const bool f64 = precision == RAYZ_PRECISION_F64;
+    const size_t items = (size_t)n_pixels * n_chunks, r4_bytes = f64 ? sizeof(d4) : sizeof(f4);
+    std::vector<char> host(items * r4_bytes); // the chunk-sum records a trace pass would have left
+    for (size_t i = 0; i < items; ++i) {
+        if (f64) reinterpret_cast<d4*>(host.data())[i] = d4{sums[3 * i], sums[3 * i + 1], sums[3 * i + 2], 0.0};
+        else reinterpret_cast<f4*>(host.data())[i] = f4{(float)sums[3 * i], (float)sums[3 * i + 1], (float)sums[3 * i + 2], 0.0f};
+    }
+    DeviceScope scope(device);
+    DevBytes d_partial, d_acc;
+    DevBuf<d4> d_q;
+    DevBuf<uint32_t> d_starts;
+    DevBuf<double> d_var, d_rel2, d_block_sum;
+    DevBuf<unsigned long long> d_summary;
+    const uint32_t blocks = noise_blocks(n_pixels);
+    hipError_t e = d_partial.alloc(host.size());
+    if (e == hipSuccess) e = d_acc.alloc(n_pixels * r4_bytes);
+    if (e == hipSuccess) e = d_q.alloc(n_pixels);
+    if (e == hipSuccess) e = d_starts.upload(starts);
+    if (e == hipSuccess) e = d_var.alloc(n_pixels);
+    if (e == hipSuccess) e = d_rel2.alloc(n_pixels);
+    if (e == hipSuccess) e = d_block_sum.alloc(blocks);
+    if (e == hipSuccess) e = d_summary.alloc(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_partial, host.data(), host.size(), hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RAYZ_ERR_OOM : RAYZ_ERR_HIP, "rayz_hip_noise_kat: %s", hipGetErrorString(e));
+    // the fold as two passes: chunk 0 from +0, then the rest onto acc and q
+    for (uint32_t pass = 0; pass < (n_chunks > 1 ? 2u : 1u); ++pass) {
+        const uint32_t c0 = pass, c1 = pass ? n_chunks : 1;
+        const char* src = d_partial.get() + (size_t)c0 * n_pixels * r4_bytes;
+        if (f64)
+            hipLaunchKernelGGL(accumulate_moments_kernel<double>, dim3(blocks), dim3(256), 0, stream, (const d4*)src, (d4*)d_acc.get(), d_q.get(),
+                               (double*)nullptr, d_starts.get() + c0, n_pixels, c1 - c0, starts[c1], pass ? 0u : 1u);
+        else
+            hipLaunchKernelGGL(accumulate_moments_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const f4*)src, (f4*)d_acc.get(), d_q.get(),
+                               (float*)nullptr, d_starts.get() + c0, n_pixels, c1 - c0, starts[c1], pass ? 0u : 1u);
+        HIP_TRY(hipGetLastError());
+    }
+    RayzNoiseSummary sm{};
+    rc = f64 ? noise_eval<double>(d_acc.get(), d_q, nullptr, nullptr, d_var, d_rel2, d_summary, d_block_sum, n_pixels, n_chunks, starts[n_chunks],
+                                  floor2, tau2, &sm, stream)
+             : noise_eval<float>(d_acc.get(), d_q, nullptr, nullptr, d_var, d_rel2, d_summary, d_block_sum, n_pixels, n_chunks, starts[n_chunks],
+                                 floor2, tau2, &sm, stream);
+    if (rc != RAYZ_OK) return rc; // (noise_eval has waited for the stream)
+    if (q_out) {
+        std::vector<d4> q(n_pixels);
+        HIP_TRY(hipMemcpy(q.data(), d_q, n_pixels * sizeof(d4), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n_pixels; ++i) q_out[3 * i] = q[i].x, q_out[3 * i + 1] = q[i].y, q_out[3 * i + 2] = q[i].z;
+    }
+    if (var_out) HIP_TRY(hipMemcpy(var_out, d_var, n_pixels * sizeof(double), hipMemcpyDeviceToHost));
+    if (rel2_out) HIP_TRY(hipMemcpy(rel2_out, d_rel2, n_pixels * sizeof(double), hipMemcpyDeviceToHost));
+    if (summary) *summary = sm;
     return RAYZ_OK;
 }
 
@@ -2402,6 +2630,38 @@ int rayz_hip_progressive_step_f64(RayzProgressive* pr, uint32_t min_samples, dou
 int rayz_hip_progressive_info(const RayzProgressive* pr, uint32_t* samples_done, uint32_t* chunks_done, uint32_t* n_chunks,
                               RayzRenderStats* total) {
     return guarded([&] { return progressive_info(pr, samples_done, chunks_done, n_chunks, total); });
+}
+
+int rayz_hip_progressive_track_noise(RayzProgressive* pr) {
+    return guarded([&] { return progressive_track_noise(pr); });
+}
+
+int rayz_hip_progressive_noise(RayzProgressive* pr, const RayzNoiseParams* p, float* d_var, float* d_rel2, RayzNoiseSummary* summary,
+                               void* stream) {
+    return guarded([&] { return progressive_noise(pr, p, d_var, d_rel2, summary, stream); });
+}
+
+int rayz_hip_progressive_noise_state(RayzProgressive* pr, double* d_q, void* stream) {
+    return guarded([&] { return progressive_noise_state(pr, d_q, stream); });
+}
+
+int rayz_hip_progressive_run_until(RayzProgressive* pr, const RayzNoiseParams* p, double max_unconverged_fraction,
+                                   uint32_t min_samples_per_pass, float* d_preview, RayzNoiseSummary* last, void* stream) {
+    return guarded([&] {
+        return progressive_run_until<float>(pr, p, max_unconverged_fraction, min_samples_per_pass, d_preview, last, stream, RAYZ_PRECISION_F32);
+    });
+}
+
+int rayz_hip_progressive_run_until_f64(RayzProgressive* pr, const RayzNoiseParams* p, double max_unconverged_fraction,
+                                       uint32_t min_samples_per_pass, double* d_preview, RayzNoiseSummary* last, void* stream) {
+    return guarded([&] {
+        return progressive_run_until<double>(pr, p, max_unconverged_fraction, min_samples_per_pass, d_preview, last, stream, RAYZ_PRECISION_F64);
+    });
+}
+
+int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint32_t* chunk_sizes, uint32_t n_pixels, uint32_t n_chunks,
+                       const RayzNoiseParams* p, double* q_out, double* var_out, double* rel2_out, RayzNoiseSummary* summary) {
+    return guarded([&] { return noise_kat(precision, chunk_sums, chunk_sizes, n_pixels, n_chunks, p, q_out, var_out, rel2_out, summary); });
 }
 
 int rayz_hip_progressive_destroy(RayzProgressive* pr) {

@@ -329,6 +329,10 @@ struct GpuOptions {
     // one device only (ignored when `devices` lists more than one): render in passes of about 1/100 of the frame (rayz_hip_progressive_*, the same
     // image) and print the reference's progress line to stderr after each, src/renderer.zig:84,98-99
     bool progress = false;
+    // one device only, as `progress`: render until converged (rayz_hip_progressive_run_until) — passes of about 1/16 of the samples until
+    // at most `until_fraction` of the pixels exceed the relative standard error `until_rel_error`, or samples_per_px is reached; 0: off.
+    // render() refuses the combination with more than one device, and leaves where it stopped in Tracer::until_summary.
+    double until_rel_error = 0.0, until_fraction = 0.01;
 };
 
 static const double ASPECT_RATIO = 16.0 / 9.0; // src/renderer.zig:16
@@ -343,6 +347,7 @@ struct Tracer {
     MemPool pool;
     GpuOptions gpu;
     RayzRenderStats stats{};
+    RayzNoiseSummary until_summary{}; // where the last render() with gpu.until_rel_error stopped (rayz_hip_progressive_run_until)
     // Several GPUs (gpu.devices): the per-device scenes and the RCCL communicators (`ncclCommInitAll`: tens of
     // milliseconds per device) are kept across render() calls and rebuilt only when the pool or the device list changes,
     // instead of paying rayz_hip_render_multi's create + destroy per frame.  Shared by copies of the Tracer.
@@ -452,7 +457,9 @@ struct Tracer {
         RayzRenderParams p = params(seed);
         p.shard_index = 0, p.shard_count = 1; // a Tracer owns a whole image
         const size_t n = img.h * img.w;
-        if (gpu.progress && gpu.devices.size() <= 1) {
+        if (gpu.until_rel_error > 0.0 && gpu.devices.size() > 1)
+            throw GpuRenderFailed(RAYZ_ERR_BAD_ARG, "render until converged runs on one device: not with a list of several");
+        if ((gpu.progress || gpu.until_rel_error > 0.0) && gpu.devices.size() <= 1) {
             if (gpu.precision == RAYZ_PRECISION_F32) {
                 std::vector<float> rgb(n * 3);
                 renderProgressive(sd, cd, p, rgb.data(), sizeof(float));
@@ -523,6 +530,20 @@ struct Tracer {
         if (hipMalloc(&d_rgb, bytes ? bytes : 16) != hipSuccess) return done(RAYZ_ERR_OOM, "hipMalloc(frame) failed");
         const uint32_t spp = p.samples_per_px, pass = (spp + 99) / 100;
         uint32_t samples = 0, chunks = 0, n_chunks = 1;
+        if (gpu.until_rel_error > 0.0) { // render until converged: the library's own loop, one evaluation per pass
+            const RayzNoiseParams np{gpu.until_rel_error, RAYZ_NOISE_DEFAULT_MEAN_FLOOR};
+            RayzNoiseSummary sm{};
+            rc = rayz_hip_progressive_track_noise(pr);
+            if (rc == RAYZ_OK)
+                rc = p.precision == RAYZ_PRECISION_F64
+                         ? rayz_hip_progressive_run_until_f64(pr, &np, gpu.until_fraction, (spp + 15) / 16, (double*)d_rgb, &sm, nullptr)
+                         : rayz_hip_progressive_run_until(pr, &np, gpu.until_fraction, (spp + 15) / 16, (float*)d_rgb, &sm, nullptr);
+            if (rc == RAYZ_OK) rc = rayz_hip_progressive_info(pr, &samples, &chunks, &n_chunks, &stats);
+            if (rc != RAYZ_OK) return done(rc, rayz_hip_last_error());
+            until_summary = sm;
+            if (hipMemcpy(rgb, d_rgb, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(RAYZ_ERR_HIP, "hipMemcpy(frame) failed");
+            return done(RAYZ_OK, "");
+        }
         // (every pass writes the frame so far into d_rgb: the last one leaves the frame there)
         while (rc == RAYZ_OK && chunks < n_chunks) {
             rc = p.precision == RAYZ_PRECISION_F64 ? rayz_hip_progressive_step_f64(pr, pass, (double*)d_rgb, nullptr)

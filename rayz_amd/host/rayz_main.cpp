@@ -8,13 +8,29 @@
 // (render on several GPUs of the node through rayz_hip_render_multi; default: device 0), RAYZ_PROGRESS=1 (render in
 // passes of about 1/100 of the frame through rayz_hip_progressive_* and print the reference's `\rProgress: xx.xx%` to
 // stderr after each, src/renderer.zig:84,98-99; the same image and rate line.  Single device only: a RAYZ_DEVICES list
-// of more than one ordinal renders in one call, without progress).
+// of more than one ordinal renders in one call, without progress).  And one optional argument anywhere on the line:
+// `--until <rel_error>` renders until converged (rayz_hip_progressive_run_until: passes of about 1/16 of RAYZ_SPP until at
+// most 1 % of the pixels exceed that relative standard error, or RAYZ_SPP is reached) and prints, after the rate line, the
+// samples per pixel it stopped at and the unconverged fraction.  Without it the output is what it always was.
 #include "rayz.hpp"
 
 #include <chrono>
 #include <cstdlib>
 
 int main(int argc, char** argv) {
+    double until = 0.0;
+    for (int i = 1; i < argc; ++i) { // take `--until <rel_error>` out of the line: the rest is the reference's interface
+        if (std::string(argv[i]) != "--until") continue;
+        char* uend = nullptr;
+        if (i + 1 < argc) until = std::strtod(argv[i + 1], &uend);
+        if (i + 1 >= argc || !(until > 0.0) || (uend && *uend)) {
+            std::fprintf(stderr, "error: --until needs a positive relative error\n");
+            return 2;
+        }
+        for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+        argc -= 2;
+        break;
+    }
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <img_w> [out.ppm]\n", argv[0]); // the reference panics on `.?`, src/rayz.zig:16
         return 2;
@@ -55,6 +71,12 @@ int main(int argc, char** argv) {
 
     if ((e = std::getenv("RAYZ_PROGRESS")) && std::string(e) == "1") tracer.gpu.progress = true;
 
+    if (until > 0.0 && tracer.gpu.devices.size() > 1) {
+        std::fprintf(stderr, "error: --until renders on one device: not with a RAYZ_DEVICES list of several\n");
+        return 2;
+    }
+    tracer.gpu.until_rel_error = until;
+
     if (rayz_hip_init(tracer.gpu.devices.empty() ? 0 : tracer.gpu.devices[0]) != RAYZ_OK) {
         std::fprintf(stderr, "error: GpuRenderFailed: %s\n", rayz_hip_last_error());
         return 1;
@@ -70,6 +92,11 @@ int main(int argc, char** argv) {
     const double durr = std::chrono::duration<double>(std::chrono::steady_clock::now() - st).count();
     std::fprintf(stderr, "Finished render (%.2fs): %.2f rps and %.2f us per ray\n", durr, rays_traced / durr,
                  1e6 * durr / rays_traced); // src/rayz.zig:30-34
+    if (until > 0.0) {
+        const RayzNoiseSummary& sm = tracer.until_summary;
+        std::fprintf(stderr, "Stopped at %u of %zu samples per pixel: %.2f%% of the pixels above %g relative error\n", sm.samples_done,
+                     (size_t)tracer.samples_per_px, sm.pixels ? 100.0 * (double)sm.unconverged / (double)sm.pixels : 0.0, until);
+    }
 
     if (argc > 2) {
         FILE* f = std::fopen(argv[2], "w");

@@ -135,9 +135,10 @@ class DeviceScene:
         rc = fn(self._h, C.byref(camera), C.byref(params), C.c_void_p(out_ptr), C.c_void_p(stream))
         capi.check(self._lib, rc, "rayz_hip_render_device")
 
-    def progressive(self, camera: capi.CameraDesc, params: capi.RenderParams) -> "Progressive":
-        """The frame of `render_into(camera, params, ...)` in passes of whole chunks (`rayz_hip_progressive_create`)."""
-        return Progressive(self, camera, params)
+    def progressive(self, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False) -> "Progressive":
+        """The frame of `render_into(camera, params, ...)` in passes of whole chunks (`rayz_hip_progressive_create`);
+        `track_noise` makes it a tracked handle (`Progressive.noise`, `Progressive.render_until`)."""
+        return Progressive(self, camera, params, track_noise=track_noise)
 
     def sync(self) -> capi.RenderStats:
         st = capi.RenderStats()
@@ -231,13 +232,91 @@ class Progressive:
     """One frame rendered in passes (`rayz_hip_progressive_*`): every `step` adds whole chunks of the chunk schedule and may
     write the frame so far; the last one writes the one-shot frame bit for bit.  Close it before its scene."""
 
-    def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams):
+    def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False):
         self._lib = scene._lib
         self._scene = scene  # (kept alive: the handle renders on it)
         self._h = C.c_void_p()
         self.f64 = params.precision == capi.PRECISION_F64
+        self.shape = (shard_rows(params), params.width)  # of the handle's shard
+        self._inflight = None  # the tensors of the last noise() / render_until(): kept alive until the next call or close()
         capi.check(self._lib, self._lib.rayz_hip_progressive_create(scene._h, C.byref(camera), C.byref(params),
                                                                     C.byref(self._h)), "rayz_hip_progressive_create")
+        if track_noise:
+            self.track_noise()
+
+    def track_noise(self) -> None:
+        """`rayz_hip_progressive_track_noise`: keep the chunk sums' second moments (before the first step only)."""
+        capi.check(self._lib, self._lib.rayz_hip_progressive_track_noise(self._h), "rayz_hip_progressive_track_noise")
+
+    @staticmethod
+    def _noise_params(rel_error, mean_floor) -> capi.NoiseParams:
+        d = capi.NOISE_DEFAULTS
+        return capi.NoiseParams(d["rel_error"] if rel_error is None else rel_error, d["mean_floor"] if mean_floor is None else mean_floor)
+
+    def _stream_prologue(self, stream: int) -> None:
+        import torch
+
+        if not stream:  # the library's stream does not order itself after torch's
+            torch.cuda.synchronize(self._scene.device)
+
+    def noise(self, rel_error: float | None = None, mean_floor: float | None = None, var: bool = False, rel2: bool = False,
+              summary: bool = True, stream: int = 0):
+        """The noise estimate of the samples done so far (`rayz_hip_progressive_noise`).  Returns
+        (summary, var, rel2): a capi.NoiseSummary (None with summary=False: then nothing blocks) and, where asked for, float32 torch
+        tensors shaped (rows_in_shard, width) on the scene's device — the variance of each pixel's mean (channels summed) and its
+        squared relative error.  The tensors are written asynchronously on `stream` and kept alive by the handle until the next
+        call.  With summary=True the call has waited for them.  With summary=False WAIT BEFORE READING THEM: `stats()` waits for
+        the handle's last evaluation (or synchronise your own stream).  Torch's stream is not ordered after the
+        write, so a `.cpu()` without that wait may read unwritten memory."""
+        import torch
+
+        dev = torch.device("cuda", self._scene.device)
+        tv = torch.empty(self.shape, dtype=torch.float32, device=dev) if var else None
+        tr = torch.empty(self.shape, dtype=torch.float32, device=dev) if rel2 else None
+        self._stream_prologue(stream)
+        prm = self._noise_params(rel_error, mean_floor)
+        sm = capi.NoiseSummary() if summary else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        rc = self._lib.rayz_hip_progressive_noise(self._h, C.byref(prm), ptr(tv), ptr(tr), C.byref(sm) if summary else None,
+                                                  C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_progressive_noise")
+        self._inflight = (tv, tr)
+        return sm, tv, tr
+
+    def noise_state(self, stream: int = 0):
+        """The moment state (`rayz_hip_progressive_noise_state`): a float64 tensor (rows_in_shard, width, 4), {Q_r, Q_g, Q_b, 0}."""
+        import torch
+
+        q = torch.empty(self.shape + (4,), dtype=torch.float64, device=torch.device("cuda", self._scene.device))
+        self._stream_prologue(stream)
+        rc = self._lib.rayz_hip_progressive_noise_state(self._h, C.c_void_p(q.data_ptr() if q.numel() else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_progressive_noise_state")
+        self._inflight = (q,)
+        return q
+
+    def render_until(self, rel_error: float | None = None, mean_floor: float | None = None, max_unconverged_fraction: float = 0.0,
+                     min_samples_per_pass: int = 0, out=None, stream: int = 0) -> capi.NoiseSummary:
+        """Render until converged (`rayz_hip_progressive_run_until`): passes of at least `min_samples_per_pass` samples until at most
+        `max_unconverged_fraction` of the pixels are unconverged or the schedule ends (`done` tells which).  `out`: an optional
+        torch tensor (rows_in_shard, width, 3) of the handle's precision on the scene's device that receives the frame it stopped
+        at.  Blocks; returns the last summary."""
+        import torch
+
+        if out is not None:
+            want = torch.float64 if self.f64 else torch.float32
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self._scene.device:
+                raise ValueError(f"out must be a torch tensor on cuda:{self._scene.device}")
+            if out.dtype != want or tuple(out.shape) != self.shape + (3,) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous {want} tensor shaped {self.shape + (3,)}")
+        self._stream_prologue(stream)
+        prm = self._noise_params(rel_error, mean_floor)
+        sm = capi.NoiseSummary()
+        fn = self._lib.rayz_hip_progressive_run_until_f64 if self.f64 else self._lib.rayz_hip_progressive_run_until
+        rc = fn(self._h, C.byref(prm), max_unconverged_fraction, min_samples_per_pass,
+                C.c_void_p(out.data_ptr() if out is not None and out.numel() else None), C.byref(sm), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_progressive_run_until")
+        self._inflight = (out,)
+        return sm
 
     def step(self, min_samples: int = 0, out_ptr: int = 0, stream: int = 0) -> None:
         """One pass of at least `min_samples` samples per pixel (0: one chunk; 0xFFFFFFFF: the rest), asynchronous on `stream`;
@@ -277,8 +356,9 @@ class Progressive:
 
     def close(self) -> None:
         if self._h:
-            self._lib.rayz_hip_progressive_destroy(self._h)
+            self._lib.rayz_hip_progressive_destroy(self._h)  # (waits for the last pass and the last evaluation)
             self._h = C.c_void_p()
+        self._inflight = None
 
     def __del__(self):
         try:
@@ -426,6 +506,27 @@ def kat(op: int, records, precision: int = capi.PRECISION_F32) -> np.ndarray:
     D = C.POINTER(C.c_double)
     capi.check(lib, lib.rayz_hip_kat(op, precision, rec.ctypes.data_as(D), len(rec), out.ctypes.data_as(D)), "rayz_hip_kat")
     return out
+
+
+def noise_kat(chunk_sums, chunk_sizes, precision: int = capi.PRECISION_F32, rel_error: float | None = None,
+              mean_floor: float | None = None):
+    """`rayz_hip_noise_kat`: the noise kernels on (n_chunks, n_pixels, 3) float64 chunk sums with `chunk_sizes` samples each.
+    Returns (Q (n_pixels, 3), var, rel2 (n_pixels,) float64, capi.NoiseSummary)."""
+    lib = capi.load()
+    sums = np.ascontiguousarray(chunk_sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[2] != 3:
+        raise ValueError(f"chunk_sums must be (n_chunks, n_pixels, 3), got {sums.shape}")
+    sizes = np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
+    if sizes.shape != (sums.shape[0],):
+        raise ValueError(f"chunk_sizes must be ({sums.shape[0]},), got {sizes.shape}")
+    k, n = sums.shape[:2]
+    q, var, rel2 = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+    prm, sm = Progressive._noise_params(rel_error, mean_floor), capi.NoiseSummary()
+    D = C.POINTER(C.c_double)
+    rc = lib.rayz_hip_noise_kat(precision, sums.ctypes.data_as(D), sizes.ctypes.data_as(C.POINTER(C.c_uint32)), n, k, C.byref(prm),
+                                q.ctypes.data_as(D), var.ctypes.data_as(D), rel2.ctypes.data_as(D), C.byref(sm))
+    capi.check(lib, rc, "rayz_hip_noise_kat")
+    return q, var, rel2, sm
 
 
 def tonemap_u8(rgb_ptr: int, out_ptr: int, n_pixels: int, stream: int = 0) -> None:

@@ -154,6 +154,90 @@ extern "c" fn rayz_hip_multi_render_f64(
 ) c_int;
 extern "c" fn rayz_hip_multi_destroy(multi: ?*RayzMulti) c_int;
 
+// ---- progressive rendering with a noise estimate: "render until converged" (include/rayz_hip.h, DESIGN.md §4.12) ----
+// A scene kept on the device, one frame in passes, and after every pass the fraction of pixels whose relative standard error
+// still exceeds `rel_error`.
+// NOT HELD TO THE HEADER BY THE TEXT CHECK — keep them in step with include/rayz_hip.h by hand:
+//   * the two structs below.  tests/test_zig_binding_text.py lists exactly the eight render structs, so a ninth `= extern struct`
+//     would fail it; `: type = extern struct` is the same declaration in a spelling its pattern does not match, which also means
+//     it does not compare their fields with the C structs;
+//   * the entry points further down that take `void* hip_stream`: Zig binds `void*` as `?*anyopaque`, which the check does
+//     not accept for a C `void*`, so they are declared `extern fn` (no "c"), a form it does not read.
+// Everything else here is `extern "c" fn` and checked as before.
+pub const RayzNoiseParams: type = extern struct {
+    rel_error: f64 = 0.05,
+    mean_floor: f64 = 0.02,
+};
+pub const RayzNoiseSummary: type = extern struct {
+    pixels: u64,
+    unconverged: u64,
+    max_rel2: f64,
+    mean_var: f64,
+    samples_done: u32,
+    chunks_done: u32,
+};
+pub const RayzScene = opaque {};
+pub const RayzProgressive = opaque {};
+pub extern "c" fn rayz_hip_scene_create(scene: *const RayzSceneDesc, out: *?*RayzScene) c_int;
+pub extern "c" fn rayz_hip_scene_destroy(scene: ?*RayzScene) c_int;
+pub extern "c" fn rayz_hip_progressive_create(
+    scene: *RayzScene,
+    camera: *const RayzCameraDesc,
+    params: *const RayzRenderParams,
+    out: *?*RayzProgressive,
+) c_int;
+pub extern "c" fn rayz_hip_progressive_track_noise(pr: *RayzProgressive) c_int;
+pub extern "c" fn rayz_hip_progressive_info(
+    pr: *const RayzProgressive,
+    samples_done: ?*u32,
+    chunks_done: ?*u32,
+    n_chunks: ?*u32,
+    total: ?*RayzRenderStats,
+) c_int;
+pub extern "c" fn rayz_hip_progressive_destroy(pr: ?*RayzProgressive) c_int;
+pub extern "c" fn rayz_hip_noise_kat(
+    precision: u32,
+    chunk_sums: [*]const f64,
+    chunk_sizes: [*]const u32,
+    n_pixels: u32,
+    n_chunks: u32,
+    p: ?*const RayzNoiseParams,
+    q_out: ?*f64, // (the three outputs: the first element of a host buffer, or null)
+    var_out: ?*f64,
+    rel2_out: ?*f64,
+    summary: ?*RayzNoiseSummary,
+) c_int;
+// The entry points that take a stream (NULL = the library's): UNCHECKED, see above.  The previews and d_q are DEVICE memory.
+pub extern fn rayz_hip_progressive_noise(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    d_var: ?[*]f32,
+    d_rel2: ?[*]f32,
+    summary: ?*RayzNoiseSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_noise_state(pr: *RayzProgressive, d_q: [*]f64, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_progressive_step(pr: *RayzProgressive, min_samples: u32, d_preview: ?[*]f32, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_progressive_step_f64(pr: *RayzProgressive, min_samples: u32, d_preview: ?[*]f64, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_progressive_run_until(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    max_unconverged_fraction: f64,
+    min_samples_per_pass: u32,
+    d_preview: ?[*]f32,
+    last_summary: ?*RayzNoiseSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_run_until_f64(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    max_unconverged_fraction: f64,
+    min_samples_per_pass: u32,
+    d_preview: ?[*]f64,
+    last_summary: ?*RayzNoiseSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+
 fn v3(v: vec.V3) [3]f64 {
     return .{ v.x, v.y, v.z };
 }
