@@ -5,6 +5,7 @@ the host mirror's C view (include/rayz_host.h), and the `rayz` command-line driv
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -40,15 +41,11 @@ def _stale(target: str, sources: list[str]) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     lib_src = [os.path.join(CSRC, "rayz_hip.hip"), os.path.join(HOST, "rayz_host.cpp")]
-    deps = lib_src + [
-        os.path.join(CSRC, "rayz_device.hpp"), os.path.join(CSRC, "plane_runs.hpp"), os.path.join(CSRC, "bvh_build.hpp"), os.path.join(CSRC, "denoise.hpp"),
-        os.path.join(CSRC, "noise.hpp"),
-        os.path.join(HOST, "rayz.hpp"),
-        # (compiled only with -DRAYZ_EXPERIMENTS, but files rayz_hip.hip can include: an edit must not leave a stale library)
-        *(os.path.join(CSRC, "experiments", f) for f in ("bvh2_kernel.hpp", "bvhx_kernel.hpp", "launch.hpp")),
-        os.path.join(ROOT, "include", "rayz_hip.h"), os.path.join(ROOT, "include", "rayz_host.h"),
-        os.path.abspath(__file__),
-    ]
+    # Everything the library can be compiled from, found in the tree: a header added later (rayz_hip.hip includes its feature
+    # headers, and experiments/ with -DRAYZ_EXPERIMENTS) cannot be forgotten here and leave a stale library behind.
+    deps = sorted({*lib_src, *glob.glob(os.path.join(CSRC, "**", "*.hpp"), recursive=True),
+                   *glob.glob(os.path.join(HOST, "*.[ch]pp")), *glob.glob(os.path.join(ROOT, "include", "*.h")),
+                   os.path.abspath(__file__)})
     extra = os.environ.get("RAYZ_EXTRA_HIPFLAGS", "").split()  # experiments only (e.g. -DRAYZ_GROUP=8)
     if force or extra or _stale(LIB, deps):
         cmd = [_hipcc(), *HIPFLAGS, *extra, "-shared", "-o", LIB, *lib_src]

@@ -178,7 +178,7 @@ template <int LOG2S, bool LAST> __global__ __launch_bounds__(256) void denoise_l
     dn_store<LAST>(a, (size_t)y * a.width + x, acc);
 }
 
-// ---- host side: the launches (rayz_hip.hip owns the handle, the validation and the stream) -------------------------------------
+// ---- host side: the launches (denoiser.hpp owns the handle, the validation and the stream) -------------------------------------
 inline dim3 denoise_grid(uint32_t width, uint32_t height) {
     return dim3((width + kDnTileW - 1) / kDnTileW, (height + kDnTileH - 1) / kDnTileH);
 }

@@ -18,7 +18,7 @@ int experiment_override(BvhLaunchPlan<R>& plan, TraceArgs<R>& A, const RayzScene
             plan.kernel = b.quantized ? trace_kernel_bvh2<float, true> : trace_kernel_bvh2<float, false>;
             plan.block = (int)kBvh2Wg;
             plan.items_per_lane = 2; // (a lane of the two-path kernel holds two items)
-            plan.stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kBvh2Wg * sizeof(uint32_t);
+            plan.stack_bytes = bvh_stack_bytes(s->bvh_dev.depth, kBvh2Wg);
             // three 256-thread workgroups per CU: less LDS to spare, a prefix of the top
             plan.top_records = std::min<uint32_t>(plan.top_records, b.quantized ? 512u : 256u);
             A.bvh_keep = (uint32_t)tuning(RAYZ_DEBUG_BVH2_KEEP, kBvh2Service | (kBvh2Blocked << 8) | (kBvh2Swap << 16) | (kBvhKeepStepping << 24));
@@ -31,7 +31,7 @@ int experiment_override(BvhLaunchPlan<R>& plan, TraceArgs<R>& A, const RayzScene
                            xprio = xk < 0 ? 0x6eu : (uint32_t)((xk >> 32) & 0xff); // shader | walker box steps << 2 | leaf / root phases << 4 | exchange << 6
             A.x_slots = ns;
             A.x_cfg = xmin | (xbatch << 8) | (xpat << 16) | (xprio << 24);
-            plan.stack_bytes = ((size_t)s->bvh_dev.depth + 3) * kXWalkerLanes * sizeof(uint32_t); // only its walker waves have stacks
+            plan.stack_bytes = bvh_stack_bytes(s->bvh_dev.depth, kXWalkerLanes); // only its walker waves have stacks
             plan.extra_lds_bytes = bvhx_exchange_bytes(ns); // the slot area, after the oversized hittables' records
             if (p->max_bounces >= (1u << 30)) return fail(RAYZ_ERR_BAD_ARG, "the exchange kernel packs flags into the segment count: max_bounces < 2^30");
             // the top: what the walkers' stacks and the slots leave of the budget

@@ -1876,9 +1876,12 @@ void trace_kernel_bvh(const TraceArgs<R> A) {
 }
 
 // The retired experiment kernels (two paths per lane; walker / shader waves — DESIGN.md §6) live in experiments/: they need the
-// walk above and nothing below needs them.  ONLY experiment code may live outside this file: bench.py ties a committed profile
-// to a build by hashing rayz_device.hpp, rayz_hip.hip, bvh_build.hpp and include/rayz_hip.h, so every line a product kernel is
-// compiled from has to stay in those four — do not split product device code into further headers.
+// walk above and nothing below needs them.  bench.py ties a committed profile to a build by hashing rayz_device.hpp, rayz_hip.hip,
+// bvh_build.hpp and include/rayz_hip.h, so every line a product trace kernel is compiled from, and everything that decides what it
+// is launched with (scene upload, chunk schedule, LDS layout, the trace launch itself: rayz_hip.hip), has to stay in those four — do
+// not split product DEVICE code or the trace launch into further headers.  Outside them may live experiment code, the host
+// library's base (host_base.hpp) and the host code of features that only use the trace launch (progressive.hpp, multi_device.hpp,
+// query.hpp, denoiser.hpp, known_answers.hpp).
 #ifdef RAYZ_EXPERIMENTS
 #include "experiments/bvh2_kernel.hpp"
 #include "experiments/bvhx_kernel.hpp"
