@@ -331,6 +331,12 @@ int rayz_hip_progressive_track_noise(RayzProgressive* pr);
  * rel_error or mean_floor that is not positive (NaN included) or whose square is not; RAYZ_ERR_STATE: an untracked handle. */
 int rayz_hip_progressive_noise(RayzProgressive* pr, const RayzNoiseParams* p_or_null, float* d_var_or_null, float* d_rel2_or_null,
                                RayzNoiseSummary* summary_or_null, void* hip_stream);
+/* The variance of the pixel mean PER CHANNEL, for a consumer that filters each channel on its own scale (the guided denoiser,
+ * rayz_hip_denoiser_run_guided): `d_var_rgb`, DEVICE memory, rows_in_shard*width*3 floats packed as frames are, receives
+ * var_ch = D_ch / ((K - 1) * N) with DESIGN.md §4.12's D_ch (its clamp at 0 included), computed in f64 and rounded once; before the
+ * second chunk all three are +inf.  Their sum is `var` up to the order of the roundings.  Asynchronous on `hip_stream` and ordered
+ * as rayz_hip_progressive_noise is; nothing blocks.  RAYZ_ERR_STATE: an untracked handle; RAYZ_ERR_BAD_ARG: a null buffer. */
+int rayz_hip_progressive_noise_rgb(RayzProgressive* pr, float* d_var_rgb, void* hip_stream);
 /* The moment state itself, for tests and tools: rows_in_shard*width*4 doubles {Q_r, Q_g, Q_b, 0} copied to DEVICE memory `d_q`
  * on `hip_stream`, ordered after the handle's last pass.  Blocks until the copy is done. */
 int rayz_hip_progressive_noise_state(RayzProgressive* pr, double* d_q, void* hip_stream);
@@ -567,6 +573,38 @@ int rayz_hip_denoiser_create(int device, uint32_t width, uint32_t height, RayzDe
  * not positive (NaN included), unknown flag bits, a missing required pointer.  RAYZ_ERR_STATE: a bad handle. */
 int rayz_hip_denoiser_run(RayzDenoiser* dn, const RayzDenoiseParams* params, const float* d_rgb_in,
                           const RayzQueryOutputs* gbuffer, float* d_rgb_out, void* hip_stream);
+/* ---- variance-guided denoising ----
+ * The spatial stage of SVGF (Schied et al. 2017) on the same handle and guides: the colour distance of a tap is measured in units
+ * of the centre pixel's own variance, so a pixel that has converged keeps its detail and one that has not is smoothed.
+ * `d_var_rgb`: DEVICE memory, height*width*3 floats, the variance of each channel of d_rgb_in's pixel means
+ * (rayz_hip_progressive_noise_rgb writes exactly this).  It is demodulated with the colour, summed over the channels, smoothed
+ * 3x3 per level and filtered along with the colour (weights squared), so every level sees the variance its input has.  A NaN,
+ * +inf (no estimate yet) or huge variance is taken as 2^32: that pixel trusts the guides only.  A tap's colour weight is
+ * 1 / (1 + |de|^2 / (sigma_color^2 x (variance + var_floor))): `sigma_color` is in STANDARD DEVIATIONS here, and `var_floor`
+ * keeps a pixel whose estimate is 0 (a black or a constant pixel) from refusing every neighbour.  The arithmetic is a contract
+ * (§4.13, the rules of §4.11), restated bit for bit by tests/denoise_guided_mirror.cpp.  Added in ABI 5 (additive). */
+#define RAYZ_DENOISE_GUIDED_DEFAULT_LEVELS 5u
+#define RAYZ_DENOISE_GUIDED_DEFAULT_SIGMA_COLOR 2.0 /* these three: DESIGN.md §6 says what they rest on; parameters, not contract */
+#define RAYZ_DENOISE_GUIDED_DEFAULT_VAR_FLOOR 1e-4
+
+typedef struct RayzDenoiseGuidedParams {
+    uint32_t levels;            /* as RayzDenoiseParams; 0 = RAYZ_DENOISE_GUIDED_DEFAULT_LEVELS */
+    uint32_t normal_power_log2; /* as RayzDenoiseParams */
+    uint32_t flags;             /* RAYZ_DENOISE_ALBEDO or 0 */
+    uint32_t _pad;
+    double sigma_color;         /* > 0, in standard deviations; +inf switches the colour term off exactly.  Used as f32; its f32 square must be > 0 */
+    double sigma_plane;         /* as RayzDenoiseParams */
+    double var_floor;           /* > 0, added to every pixel's variance.  Used as f32; f32(sigma_color)^2 x f32(var_floor) must be > 0 in f32 */
+} RayzDenoiseGuidedParams;
+
+/* As rayz_hip_denoiser_run (buffers, stream, the one run in flight per handle — of either mode —, timing, in place allowed), plus
+ * `d_var_rgb` (required) and `d_var_out_or_null`: DEVICE memory, height*width floats, the variance left in the DEMODULATED colour
+ * after the last level, channels summed (multiply by the squared modulation for a radiance variance).  params == NULL: all defaults.
+ * RAYZ_ERR_BAD_ARG as rayz_hip_denoiser_run, and: a var_floor that is not positive (NaN included) or whose f32 product with
+ * sigma_color^2 is not; d_var_rgb == NULL. */
+int rayz_hip_denoiser_run_guided(RayzDenoiser* dn, const RayzDenoiseGuidedParams* params, const float* d_rgb_in,
+                                 const float* d_var_rgb, const RayzQueryOutputs* gbuffer, float* d_rgb_out,
+                                 float* d_var_out_or_null, void* hip_stream);
 /* Waits for the handle's last run and returns its HIP-event times: *levels_or_null = L, the levels it ran; ms_or_null[0] = the
  * pack pass, ms_or_null[1 + l] = level l, for as many of the L + 1 entries as `capacity` holds.  RAYZ_ERR_STATE before any run. */
 int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);

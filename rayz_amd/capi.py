@@ -38,6 +38,8 @@ TRAVERSAL_LINEAR, TRAVERSAL_BVH, TRAVERSAL_AUTO = 0, 1, 2
 QUERY_NEAREST, QUERY_ANY = 0, 1
 DENOISE_ALBEDO = 1
 DENOISE_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 0.5, "sigma_plane": 0.25}
+DENOISE_GUIDED_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 2.0, "sigma_plane": 0.25,
+                           "var_floor": 1e-4}
 NOISE_DEFAULTS = {"rel_error": 0.05, "mean_floor": 0.02}
 
 D3 = C.c_double * 3
@@ -100,6 +102,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_double), ("sigma_plane", C.c_double)]
 
 
+class DenoiseGuidedParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
+                ("sigma_color", C.c_double), ("sigma_plane", C.c_double), ("var_floor", C.c_double)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [("rel_error", C.c_double), ("mean_floor", C.c_double)]
 
@@ -113,7 +120,7 @@ assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere)
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
-assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40
+assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -153,6 +160,7 @@ PROTOTYPES = [
     ("rayz_hip_progressive_track_noise", C.c_int, [C.c_void_p]),
     ("rayz_hip_progressive_noise", C.c_int,
      [C.c_void_p, C.POINTER(NoiseParams), C.c_void_p, C.c_void_p, C.POINTER(NoiseSummary), C.c_void_p]),
+    ("rayz_hip_progressive_noise_rgb", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_progressive_noise_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_progressive_run_until", C.c_int,
      [C.c_void_p, C.POINTER(NoiseParams), C.c_double, C.c_uint32, C.c_void_p, C.POINTER(NoiseSummary), C.c_void_p]),
@@ -187,6 +195,8 @@ PROTOTYPES = [
     ("rayz_hip_denoiser_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_denoiser_run", C.c_int,
      [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p]),
+    ("rayz_hip_denoiser_run_guided", C.c_int,
+     [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_denoiser_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]),
     ("rayz_hip_denoiser_destroy", C.c_int, [C.c_void_p]),
 ]

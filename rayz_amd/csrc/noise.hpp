@@ -145,6 +145,35 @@ __global__ __launch_bounds__(256) void noise_eval_kernel(const typename VecOf<R>
     }
 }
 
+// ---- the per-channel variance (rayz_hip_progressive_noise_rgb): one thread per pixel ------------------------------------------
+// var_ch = D_ch / ((K - 1) · N) with §4.12's D_ch, its clamp included: the terms nz_eval sums, kept apart, for a consumer that
+// filters each channel on its own scale (the guided denoiser, §4.13).  f64, rounded once to f32; K < 2: +inf.  Three floats per
+// pixel, packed as frames are.
+template <class R>
+__global__ __launch_bounds__(256) void noise_rgb_kernel(const typename VecOf<R>::type* __restrict__ acc, const d4* __restrict__ q,
+                                                        float* __restrict__ var_rgb, uint32_t shard_pixels, uint32_t chunks_done,
+                                                        uint32_t samples_done) {
+    typedef typename VecOf<R>::type r4;
+    const uint32_t lp = blockIdx.x * 256 + threadIdx.x;
+    if (lp >= shard_pixels) return;
+    const double K = (double)chunks_done, N = (double)samples_done;
+    double vr = __builtin_inf(), vg = vr, vb = vr;
+    if (!(K < 2.0)) {
+        const r4 a = acc[lp];
+        const d4 m = q[lp];
+        const double Mr = (double)a.x, Mg = (double)a.y, Mb = (double)a.z;
+        double Dr = m.x - (Mr * Mr) / N, Dg = m.y - (Mg * Mg) / N, Db = m.z - (Mb * Mb) / N;
+        Dr = Dr < 0.0 ? 0.0 : Dr; // (a NaN stays a NaN)
+        Dg = Dg < 0.0 ? 0.0 : Dg;
+        Db = Db < 0.0 ? 0.0 : Db;
+        const double d = (K - 1.0) * N;
+        vr = Dr / d, vg = Dg / d, vb = Db / d;
+    }
+    var_rgb[3 * (size_t)lp + 0] = (float)vr;
+    var_rgb[3 * (size_t)lp + 1] = (float)vg;
+    var_rgb[3 * (size_t)lp + 2] = (float)vb;
+}
+
 inline uint32_t noise_blocks(uint64_t pixels) { return (uint32_t)((pixels + 255) / 256); }
 
 } // namespace rayz_dev

@@ -257,6 +257,31 @@ int progressive_noise(RayzProgressive* pr, const RayzNoiseParams* params, float*
                              floor2, tau2, summary, stream);
 }
 
+// The per-channel variance of the mean (noise_rgb_kernel): ordered and owned as an evaluation is, without a summary.
+int progressive_noise_rgb(RayzProgressive* pr, float* d_var_rgb, void* stream_arg) {
+    if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
+    if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
+    if (!pr->shard_pixels) return RAYZ_OK;
+    if (!d_var_rgb) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
+    DeviceCtx* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    RAYZ_TRY(scene_stream(pr->scene->device, stream_arg, ctx, stream));
+    DeviceScope scope(pr->device);
+    if (pr->noise_stream && pr->noise_stream != stream) HIP_TRY(hipStreamSynchronize(pr->noise_stream));
+    if (pr->last_stream && pr->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, pr->pass_done, 0));
+    pr->noise_stream = stream; // (a reader of acc and q, as an evaluation is)
+    const uint32_t K = pr->chunks_done, N = pr->starts[K];
+    const dim3 grid(noise_blocks(pr->shard_pixels)), block(256);
+    if (pr->params.precision == RAYZ_PRECISION_F64)
+        hipLaunchKernelGGL(noise_rgb_kernel<double>, grid, block, 0, stream, (const VecOf<double>::type*)pr->acc.get(), (const d4*)pr->q, d_var_rgb,
+                           (uint32_t)pr->shard_pixels, K, N);
+    else
+        hipLaunchKernelGGL(noise_rgb_kernel<float>, grid, block, 0, stream, (const VecOf<float>::type*)pr->acc.get(), (const d4*)pr->q, d_var_rgb,
+                           (uint32_t)pr->shard_pixels, K, N);
+    HIP_TRY(hipGetLastError());
+    return RAYZ_OK;
+}
+
 int progressive_noise_state(RayzProgressive* pr, double* d_q, void* stream_arg) {
     if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
     if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
@@ -324,6 +349,10 @@ int rayz_hip_progressive_track_noise(RayzProgressive* pr) {
 int rayz_hip_progressive_noise(RayzProgressive* pr, const RayzNoiseParams* p, float* d_var, float* d_rel2, RayzNoiseSummary* summary,
                                void* stream) {
     return guarded([&] { return progressive_noise(pr, p, d_var, d_rel2, summary, stream); });
+}
+
+int rayz_hip_progressive_noise_rgb(RayzProgressive* pr, float* d_var_rgb, void* stream) {
+    return guarded([&] { return progressive_noise_rgb(pr, d_var_rgb, stream); });
 }
 
 int rayz_hip_progressive_noise_state(RayzProgressive* pr, double* d_q, void* stream) {

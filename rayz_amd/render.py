@@ -283,6 +283,20 @@ class Progressive:
         self._inflight = (tv, tr)
         return sm, tv, tr
 
+    def noise_rgb(self, stream: int = 0):
+        """The variance of the pixel mean per channel (`rayz_hip_progressive_noise_rgb`): a float32 tensor (rows_in_shard, width, 3)
+        on the scene's device, +inf before the second chunk — what `Denoiser.run_guided` takes as `var_rgb`.  Written asynchronously
+        on `stream` and kept alive by the handle until the next call; WAIT BEFORE READING IT on the host, as for `noise(summary=False)`
+        (`stats()` waits for it).  A `run_guided` on the same stream (0: the library's) is ordered behind it."""
+        import torch
+
+        v = torch.empty(self.shape + (3,), dtype=torch.float32, device=torch.device("cuda", self._scene.device))
+        self._stream_prologue(stream)
+        rc = self._lib.rayz_hip_progressive_noise_rgb(self._h, C.c_void_p(v.data_ptr() if v.numel() else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_progressive_noise_rgb")
+        self._inflight = (v,)
+        return v
+
     def noise_state(self, stream: int = 0):
         """The moment state (`rayz_hip_progressive_noise_state`): a float64 tensor (rows_in_shard, width, 4), {Q_r, Q_g, Q_b, 0}."""
         import torch
@@ -369,7 +383,8 @@ class Progressive:
 
 class Denoiser:
     """A G-buffer-guided à-trous filter for whole float32 frames of one size (`rayz_hip_denoiser_*`):
-    `run(frame, scene.gbuffer(camera, params))` returns the filtered frame.  `device` None: the default device of init()."""
+    `run(frame, scene.gbuffer(camera, params))` returns the filtered frame; `run_guided(frame, progressive.noise_rgb(), gbuffer)`
+    also weighs every pixel by its own noise estimate (§4.13).  `device` None: the default device of init()."""
 
     def __init__(self, width: int, height: int, device: int | None = None):
         self._lib = capi.load()
@@ -422,6 +437,58 @@ class Denoiser:
         capi.check(self._lib, rc, "rayz_hip_denoiser_run")
         self._inflight = (rgb, gbuffer, out)
         return out
+
+    def run_guided(self, rgb, var_rgb, gbuffer: "QueryResult", out=None, var_out=None, stream: int = 0, **params):
+        """The variance-guided filter (`rayz_hip_denoiser_run_guided`): as `run`, with `var_rgb` — (height, width, 3)
+        float32, the variance of each channel of `rgb`'s pixel means (`Progressive.noise_rgb()`) — steering the colour weight pixel
+        by pixel.  `var_out`: True for a new (height, width) float32 tensor, or such a tensor, to receive the variance left in the
+        demodulated colour; then the call returns (out, var_out).  `params`: the fields of RayzDenoiseGuidedParams (levels,
+        normal_power_log2, flags, sigma_color — in standard deviations —, sigma_plane, var_floor); unnamed ones take
+        capi.DENOISE_GUIDED_DEFAULTS."""
+        import torch
+
+        unknown = set(params) - set(capi.DENOISE_GUIDED_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown denoise parameter(s) {sorted(unknown)}; choose from {sorted(capi.DENOISE_GUIDED_DEFAULTS)}")
+        prm = capi.DenoiseGuidedParams(**{**capi.DENOISE_GUIDED_DEFAULTS, **params})
+        frame = (self.height, self.width, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
+        tensors = [("rgb", rgb, torch.float32, frame), ("var_rgb", var_rgb, torch.float32, frame)]
+        for k in need:
+            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
+                            frame[:2] if k == "index" else frame))
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=dev)
+        tensors.append(("out", out, torch.float32, frame))
+        if var_out is True:
+            var_out = torch.empty(frame[:2], dtype=torch.float32, device=dev)
+        elif var_out is False:
+            var_out = None
+        if var_out is not None:
+            tensors.append(("var_out", var_out, torch.float32, frame[:2]))
+        for name, t, dtype, shape in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"{name} must be a torch tensor in GPU memory")
+            if t.device.index != self._device:
+                raise ValueError(f"{name} is on cuda:{t.device.index}, the denoiser on cuda:{self._device}")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if not stream:
+            torch.cuda.synchronize(self._device)
+        o = capi.QueryOutputs()
+        for k in need:
+            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        rc = self._lib.rayz_hip_denoiser_run_guided(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()),
+                                                    C.byref(o), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(var_out.data_ptr() if var_out is not None else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_denoiser_run_guided")
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out)
+        return out if var_out is None else (out, var_out)
 
     def timing(self):
         """Waits for the last run; its HIP-event times in ms: (pack pass, [level 0, level 1, ..]) (`rayz_hip_denoiser_timing`)."""

@@ -238,6 +238,33 @@ pub extern fn rayz_hip_progressive_run_until_f64(
     hip_stream: ?*anyopaque,
 ) c_int;
 
+// ---- variance-guided denoising (include/rayz_hip.h, DESIGN.md §4.13): the per-channel variance of a tracked handle steers an
+// à-trous filter pixel by pixel.  UNCHECKED BY THE TEXT CHECK as the noise entries above are, for the same two reasons (a struct
+// beyond the eight render structs; `void* hip_stream`); tests/test_denoise_guided_cpu.py holds this struct and these two
+// prototypes to the header instead.  The G-buffer is what rayz_hip_scene_query_camera filled; buffers are DEVICE memory.
+pub const RayzDenoiser = opaque {};
+pub const RayzQueryOutputs = opaque {}; // (eight device pointers, include/rayz_hip.h; passed through by address only)
+pub const RayzDenoiseGuidedParams: type = extern struct {
+    levels: u32 = 0,
+    normal_power_log2: u32 = 6,
+    flags: u32 = 1,
+    _pad: u32 = 0,
+    sigma_color: f64 = 2.0,
+    sigma_plane: f64 = 0.25,
+    var_floor: f64 = 1e-4,
+};
+pub extern fn rayz_hip_progressive_noise_rgb(pr: *RayzProgressive, d_var_rgb: [*]f32, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_denoiser_run_guided(
+    dn: *RayzDenoiser,
+    params: ?*const RayzDenoiseGuidedParams,
+    d_rgb_in: [*]const f32,
+    d_var_rgb: [*]const f32,
+    gbuffer: *const RayzQueryOutputs,
+    d_rgb_out: [*]f32,
+    d_var_out: ?[*]f32,
+    hip_stream: ?*anyopaque,
+) c_int;
+
 fn v3(v: vec.V3) [3]f64 {
     return .{ v.x, v.y, v.z };
 }

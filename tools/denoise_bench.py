@@ -12,8 +12,13 @@
 2. Against what.  The 16-spp config-3 BVH frame the pass is meant to save re-rendering at more samples, timed in the same run
    (the library's trace-kernel events, rayz_hip_scene_sync, median of 9), next to the whole pass.
 3. What it buys.  MSE of the noisy and the denoised 16-spp frame against a 1024-spp frame (--ref-spp), at 1920x1080.
+4. --guided: the variance-guided mode (rayz_hip_denoiser_run_guided) INSTEAD of 1-3.  Config 3 at 1920x1080, a
+   16-spp frame from a tracked progressive handle stepped in 8 passes of one 2-sample chunk, its per-channel variance
+   (rayz_hip_progressive_noise_rgb) and G-buffer; MSE against the --ref-spp frame of: the noisy frame, the unguided filter at its
+   defaults, and the guided filter over sigma_color {1, 2, 4, 8} x var_floor {1e-6, 1e-4, 1e-2} x levels {3, 4, 5} — the sweep the
+   guided defaults are taken from; then the per-level HIP-event times of both modes on that frame, same process, 5 levels.
 
-    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE]"""
+    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE] [--guided]"""
 import argparse
 import json
 import os
@@ -64,6 +69,100 @@ def frame_and_gbuffer(width, spp, seed=1):
     return t, ds, cam, p, out, g, statistics.median(ms)
 
 
+def level_times(dn, fn, levels, reps, warmup):
+    """Median [min, max] of the handle's own event times over `reps` runs of fn(): [pack, level 0, ..]."""
+    for _ in range(warmup):
+        fn()
+    rows = [[] for _ in range(levels + 1)]
+    for _ in range(reps):
+        fn()
+        pk, ms = dn.timing()
+        for k, x in enumerate([pk] + list(ms)):
+            rows[k].append(x)
+    return [(statistics.median(r), min(r), max(r)) for r in rows]
+
+
+def guided(args):
+    """Section 4 of the module docstring."""
+    t = tracer.randomBouncing(1920, -50, 50, seed=42)  # config 3
+    t.samples_per_px, t.max_bounces = 16, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=2)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    ds = render.DeviceScene(sd)
+    pr = ds.progressive(cam, p, track_noise=True)
+    noisy = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    passes = 0
+    while not pr.done:
+        pr.step(0, noisy.data_ptr())
+        passes += 1
+    var = pr.noise_rgb()
+    st16 = pr.stats()
+    sm, _, _ = pr.noise()
+    g = ds.gbuffer(cam, p)
+    ds.query_sync()
+    print(f"{w}x{h} config 3: 16 spp in {passes} passes on a tracked handle ({st16.kernel_ms:.2f} ms of trace kernels); mean var {sm.mean_var:.4e}, "
+          f"{sm.unconverged} of {sm.pixels} pixels unconverged at the default rel_error", flush=True)
+    p.samples_per_px, p.chunk_spp = args.ref_spp, 0
+    ref = torch.empty_like(noisy)
+    torch.cuda.synchronize()
+    ds.render_into(cam, p, ref.data_ptr())
+    ref_ms = ds.sync().kernel_ms
+    mse = lambda a: float(((a.double() - ref.double()) ** 2).mean())  # noqa: E731
+    dn = render.Denoiser(w, h)
+    out = torch.empty_like(noisy)
+    res = {"size": f"{w}x{h}", "ref_spp": args.ref_spp, "ref_ms": ref_ms, "passes": passes, "mse_noisy": mse(noisy), "sweep": []}
+    dn.run(noisy, g, out=out)
+    torch.cuda.synchronize()
+    res["mse_unguided_defaults"] = mse(out)
+    print(f"MSE against {args.ref_spp} spp ({ref_ms:.1f} ms): noisy {res['mse_noisy']:.6e}; unguided at its defaults {res['mse_unguided_defaults']:.6e} "
+          f"(ratio {res['mse_unguided_defaults'] / res['mse_noisy']:.4f})", flush=True)
+    best = None
+    for levels in (3, 4, 5):
+        for sc in (1.0, 2.0, 4.0, 8.0):
+            for vf in (1e-6, 1e-4, 1e-2):
+                dn.run_guided(noisy, var, g, out=out, levels=levels, sigma_color=sc, var_floor=vf)
+                torch.cuda.synchronize()
+                m = mse(out)
+                row = {"levels": levels, "sigma_color": sc, "var_floor": vf, "mse": m, "ratio_to_noisy": m / res["mse_noisy"],
+                       "ratio_to_unguided": m / res["mse_unguided_defaults"]}
+                res["sweep"].append(row)
+                if best is None or m < best["mse"]:
+                    best = row
+                print(f"  guided levels {levels} sigma_color {sc:g} var_floor {vf:g}: MSE {m:.6e} = {row['ratio_to_noisy']:.4f} x noisy, "
+                      f"{row['ratio_to_unguided']:.4f} x unguided", flush=True)
+    res["best"] = best
+    print(f"best: {best}", flush=True)
+    d = capi.DENOISE_GUIDED_DEFAULTS
+    dn.run_guided(noisy, var, g, out=out)
+    torch.cuda.synchronize()
+    res["mse_guided_defaults"] = mse(out)
+    print(f"guided at the shipped defaults (levels {d['levels']}, sigma_color {d['sigma_color']:g}, var_floor {d['var_floor']:g}): "
+          f"MSE {res['mse_guided_defaults']:.6e}", flush=True)
+    L = 5
+    a = level_times(dn, lambda: dn.run(noisy, g, out=out, levels=L), L, args.reps, args.warmup)
+    b = level_times(dn, lambda: dn.run_guided(noisy, var, g, out=out, levels=L), L, args.reps, args.warmup)
+    res["times"] = []
+    for k in range(L + 1):
+        what = "pack" if k == 0 else f"level {k - 1} (stride {1 << (k - 1)}{', last' if k == L else ''})"
+        print(f"  {what:24s}: unguided {a[k][0]:.4f} ms [{a[k][1]:.4f}, {a[k][2]:.4f}]   guided {b[k][0]:.4f} ms [{b[k][1]:.4f}, {b[k][2]:.4f}]   "
+              f"= {b[k][0] / a[k][0]:.2f} x", flush=True)
+        res["times"].append({"what": what, "unguided_ms": a[k][0], "unguided_min": a[k][1], "unguided_max": a[k][2], "guided_ms": b[k][0],
+                             "guided_min": b[k][1], "guided_max": b[k][2]})
+    ta, tb = sum(x[0] for x in a), sum(x[0] for x in b)
+    res["kernels_unguided_ms"], res["kernels_guided_ms"] = ta, tb
+    print(f"  whole {L}-level pass, kernels: unguided {ta:.4f} ms, guided {tb:.4f} ms = {tb / ta:.2f} x", flush=True)
+    pr.close()
+    dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -73,8 +172,11 @@ def main():
     ap.add_argument("--paths", action="store_true")
     ap.add_argument("--sizes", default="1920,3840")
     ap.add_argument("--json", default=None, help="also write the figures to this file")
+    ap.add_argument("--guided", action="store_true", help="the variance-guided mode's sweep and level times instead")
     args = ap.parse_args()
     render.init(0)
+    if args.guided:
+        return guided(args)
     stream = torch.cuda.Stream()
     result = {"levels": args.levels, "reps": args.reps, "sizes": {}}
     keep = None
