@@ -360,6 +360,70 @@ int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint3
                        uint32_t n_chunks, const RayzNoiseParams* p_or_null, double* q_out, double* var_out, double* rel2_out,
                        RayzNoiseSummary* summary_or_null);
 
+/* ---- adaptive passes: stop tracing the pixels the estimate calls done ----------------------------------------------------
+ * BUILD-DEFINED, DESIGN.md §4.14 (restated by tests/adaptive_ref.py).  A handle in ADAPTIVE mode is tracked and keeps one uint32
+ * per shard pixel, frozen_at: 0 = active, else the chunk count K_i at which the pixel froze.  A pass takes the window
+ * rayz_hip_progressive_step would take, traces it for the ACTIVE pixels only (every sample keeps its stream, so a chunk sum is
+ * the one-shot render's), folds the sums into those pixels' accumulator and moments in chunk order, and freezes every active
+ * pixel with chunks_done >= min_chunks and rel2 <= rel_error^2 (the estimate above at K = chunks_done, N = samples_done; a NaN
+ * never freezes).  A pixel's value is acc_i * (1 / N_i), N_i = the samples it received: a pixel that never freezes ends as the
+ * one-shot pixel bit for bit, a frozen one is the plain handle's preview at chunk K_i bit for bit.  Stopping on a sample
+ * variance biases frozen pixels slightly (those whose early chunks happen to agree stop early); min_chunks limits it.
+ * rayz_hip_progressive_noise / _noise_rgb evaluate every pixel of an adaptive handle with its own (K_i, N_i) (the summary's
+ * samples_done / chunks_done stay the schedule's cursor); rayz_hip_progressive_info's primary_rays counts the samples traced.
+ * One device per handle: a shard handle works like any other, several devices are the caller's to combine.  Added in ABI 5
+ * (additive). */
+#define RAYZ_ADAPTIVE_DEFAULT_MIN_CHUNKS 4u /* a parameter, not contract (provisional) */
+typedef struct RayzAdaptiveSummary {
+    uint64_t pixels;         /* pixels of the handle's shard */
+    uint64_t active;         /* of those, pixels still traced by the next pass */
+    uint64_t samples_traced; /* the sum of N_i over the shard's pixels = primary rays so far */
+    uint32_t passes;         /* passes that traced something so far */
+    uint32_t chunks_done;    /* the schedule cursor: what an active pixel has received */
+    uint32_t samples_done;
+    uint32_t _pad;
+} RayzAdaptiveSummary;
+/* Puts `pr` in adaptive mode (and makes it a tracked handle): frozen_at and two active lists, rows_in_shard*width*12 bytes
+ * besides the moment state.  RAYZ_ERR_BAD_ARG (checked first): min_chunks < 2 — there is no estimate before the second chunk.
+ * RAYZ_ERR_STATE: after the first step.  In adaptive mode rayz_hip_progressive_step and _run_until are RAYZ_ERR_STATE. */
+int rayz_hip_progressive_set_adaptive(RayzProgressive* pr, uint32_t min_chunks);
+/* One adaptive pass with `min_samples` as rayz_hip_progressive_step takes it.  Blocks: the next pass is sized by the number of
+ * pixels this one left active, which `summary_or_null` reports.  THE PREVIEW RULE: a pass writes to `d_preview_or_null` the
+ * pixels it traced; a pixel's last write, in the pass it froze in, is its final value, so a buffer passed to every pass holds
+ * the whole frame after each.  A pass given another buffer than the previous pass wrote (the first pass, and the pass after
+ * one that got NULL: any) writes ALL pixels.  "The same buffer" is the same ADDRESS: the handle does not know whether the memory
+ * behind it was freed and allocated again in between, so a caller that replaces its buffer asks for all pixels once, by a pass
+ * with NULL before it or a step on the finished run.
+ * On a finished run (no pixel active, or the schedule exhausted) the call is RAYZ_OK, traces nothing, moves no cursor, and
+ * writes all pixels to the buffer if there is one.  p_or_null as rayz_hip_progressive_noise's (checked first).
+ * RAYZ_ERR_STATE: a handle not in adaptive mode. */
+int rayz_hip_progressive_adaptive_step(RayzProgressive* pr, const RayzNoiseParams* p_or_null, uint32_t min_samples,
+                                       float* d_preview_or_null, RayzAdaptiveSummary* summary_or_null, void* hip_stream);
+int rayz_hip_progressive_adaptive_step_f64(RayzProgressive* pr, const RayzNoiseParams* p_or_null, uint32_t min_samples,
+                                           double* d_preview_or_null, RayzAdaptiveSummary* summary_or_null, void* hip_stream);
+/* Adaptive passes until no pixel is active or the schedule ends; the frame is in `d_preview_or_null`.  Blocks. */
+int rayz_hip_progressive_run_adaptive(RayzProgressive* pr, const RayzNoiseParams* p_or_null, uint32_t min_samples_per_pass,
+                                      float* d_preview_or_null, RayzAdaptiveSummary* last_summary_or_null, void* hip_stream);
+int rayz_hip_progressive_run_adaptive_f64(RayzProgressive* pr, const RayzNoiseParams* p_or_null, uint32_t min_samples_per_pass,
+                                          double* d_preview_or_null, RayzAdaptiveSummary* last_summary_or_null, void* hip_stream);
+/* N_i, the samples behind every pixel's value (`d_counts`), and frozen_at itself (`d_frozen_at`): rows_in_shard*width uint32
+ * each, DEVICE memory, written on `hip_stream` after the handle's last pass.  Block until written.  RAYZ_ERR_STATE: a handle not
+ * in adaptive mode; RAYZ_ERR_BAD_ARG: a null buffer. */
+int rayz_hip_progressive_sample_counts(RayzProgressive* pr, uint32_t* d_counts, void* hip_stream);
+int rayz_hip_progressive_frozen_at(RayzProgressive* pr, uint32_t* d_frozen_at, void* hip_stream);
+/* Known answers, as rayz_hip_noise_kat: the fold, the freeze and the compaction of adaptive passes on caller chunk sums (HOST,
+ * chunk_sums[(k*n_pixels + i)*3 + ch], chunk_sizes[k] > 0), on the default device; no scene.  Pass p covers the chunks
+ * [pass_ends[p-1], pass_ends[p]) (pass_ends strictly increasing, the last <= n_chunks) and is given the compact sums of its
+ * active list, as a trace pass would leave them.  `width`: 0 deals the pixels 0, 1, 2, ..; otherwise n_pixels is rows x width
+ * and the pixels are dealt as a shard of that shape is (8x8 tiles of whole tile rows where width % 8 == 0, then rows).
+ * Outputs (HOST, each optional): frozen_at_out n_pixels; acc_out, q_out, frame_out n_pixels*3 doubles; lists_out
+ * (n_passes + 1)*n_pixels — list p, the list pass p traced (list n_passes: what is left), in its first list_sizes_out[p]
+ * entries; list_sizes_out n_passes + 1. */
+int rayz_hip_adaptive_kat(uint32_t precision, const double* chunk_sums, const uint32_t* chunk_sizes, uint32_t n_pixels,
+                          uint32_t n_chunks, const uint32_t* pass_ends, uint32_t n_passes, uint32_t width, uint32_t min_chunks,
+                          const RayzNoiseParams* p_or_null, uint32_t* frozen_at_out, double* acc_out, double* q_out,
+                          double* frame_out, uint32_t* lists_out, uint32_t* list_sizes_out);
+
 /* ---- several GPUs behind ONE call -------------------------------------------------------------------------
  * The reference's caller makes one call, `tracer.render()` (src/rayz.zig:26, src/renderer.zig:72-101).  These
  * entry points give that one call every GPU of the node: the pool is replicated (one scene per device), image

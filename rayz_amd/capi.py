@@ -41,6 +41,7 @@ DENOISE_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO
 DENOISE_GUIDED_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 2.0, "sigma_plane": 0.25,
                            "var_floor": 1e-4}
 NOISE_DEFAULTS = {"rel_error": 0.05, "mean_floor": 0.02}
+ADAPTIVE_DEFAULT_MIN_CHUNKS = 4
 
 D3 = C.c_double * 3
 
@@ -116,11 +117,17 @@ class NoiseSummary(C.Structure):
                 ("samples_done", C.c_uint32), ("chunks_done", C.c_uint32)]
 
 
+class AdaptiveSummary(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("active", C.c_uint64), ("samples_traced", C.c_uint64), ("passes", C.c_uint32),
+                ("chunks_done", C.c_uint32), ("samples_done", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
 assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
+assert C.sizeof(AdaptiveSummary) == 40
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -169,6 +176,21 @@ PROTOTYPES = [
     ("rayz_hip_noise_kat", C.c_int,
      [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(NoiseParams),
       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(NoiseSummary)]),
+    ("rayz_hip_progressive_set_adaptive", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("rayz_hip_progressive_adaptive_step", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_uint32, C.c_void_p, C.POINTER(AdaptiveSummary), C.c_void_p]),
+    ("rayz_hip_progressive_adaptive_step_f64", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_uint32, C.c_void_p, C.POINTER(AdaptiveSummary), C.c_void_p]),
+    ("rayz_hip_progressive_run_adaptive", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_uint32, C.c_void_p, C.POINTER(AdaptiveSummary), C.c_void_p]),
+    ("rayz_hip_progressive_run_adaptive_f64", C.c_int,
+     [C.c_void_p, C.POINTER(NoiseParams), C.c_uint32, C.c_void_p, C.POINTER(AdaptiveSummary), C.c_void_p]),
+    ("rayz_hip_progressive_sample_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_progressive_frozen_at", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_adaptive_kat", C.c_int,
+     [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+      C.c_uint32, C.POINTER(NoiseParams), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("rayz_hip_multi_create", C.c_int,
      [C.POINTER(C.c_int), C.c_int, C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_multi_destroy", C.c_int, [C.c_void_p]),

@@ -145,6 +145,59 @@ __global__ __launch_bounds__(256) void noise_eval_kernel(const typename VecOf<R>
     }
 }
 
+// The same evaluation for an adaptive handle: every pixel with its own (K_i, N_i) — K_i = frozen_at[i], or
+// chunks_done where that is 0, and N_i = starts[K_i].  A kernel of its own, its text repeated, so that noise_eval_kernel stays
+// the kernel it was, instruction for instruction (as a shared body function it came out with two conversions reordered).
+template <class R>
+__global__ __launch_bounds__(256) void noise_eval_adaptive_kernel(const typename VecOf<R>::type* __restrict__ acc, const d4* __restrict__ q,
+                                                                  float* __restrict__ var_out, float* __restrict__ rel2_out,
+                                                                  double* __restrict__ var64_out, double* __restrict__ rel264_out,
+                                                                  unsigned long long* __restrict__ summary, double* __restrict__ block_sum,
+                                                                  uint32_t shard_pixels, uint32_t chunks_done, uint32_t samples_done,
+                                                                  double floor2, double tau2, const uint32_t* __restrict__ frozen_at,
+                                                                  const uint32_t* __restrict__ starts) {
+    typedef typename VecOf<R>::type r4;
+    __shared__ double s_sum[4];
+    __shared__ unsigned long long s_max[4];
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t lp = blockIdx.x * 256 + threadIdx.x;
+    const bool live = lp < shard_pixels;
+    double sum = 0.0;
+    unsigned long long mx = 0;
+    bool unconverged = false;
+    if (live) { // (no early return: every lane takes part in the reductions below)
+        const r4 a = acc[lp];
+        const d4 m = q[lp];
+        const uint32_t f = frozen_at[lp], K = f ? f : chunks_done, N = f ? starts[f] : samples_done;
+        const NzEval e = nz_eval((double)a.x, (double)a.y, (double)a.z, m.x, m.y, m.z, (double)K, (double)N, floor2);
+        if (var_out) var_out[lp] = (float)e.var;
+        if (rel2_out) rel2_out[lp] = (float)e.rel2;
+        if (var64_out) var64_out[lp] = e.var;
+        if (rel264_out) rel264_out[lp] = e.rel2;
+        unconverged = !(e.rel2 <= tau2);
+        mx = (unsigned long long)__double_as_longlong(e.rel2) & 0x7fffffffffffffffull;
+        if (__builtin_isfinite(e.var)) sum = e.var;
+    }
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(unconverged));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        sum = sum + __shfl_xor(sum, off);
+        const unsigned long long o = __shfl_xor(mx, off);
+        mx = o > mx ? o : mx;
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) s_sum[wave] = sum, s_max[wave] = mx, s_cnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        block_sum[blockIdx.x] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+        const uint32_t c = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        unsigned long long m = s_max[0];
+        for (int w = 1; w < 4; ++w) m = s_max[w] > m ? s_max[w] : m;
+        if (c) atomicAdd(&summary[0], (unsigned long long)c);
+        if (m) atomicMax(&summary[1], m);
+    }
+}
+
 // ---- the per-channel variance (rayz_hip_progressive_noise_rgb): one thread per pixel ------------------------------------------
 // var_ch = D_ch / ((K - 1) · N) with §4.12's D_ch, its clamp included: the terms nz_eval sums, kept apart, for a consumer that
 // filters each channel on its own scale (the guided denoiser, §4.13).  f64, rounded once to f32; K < 2: +inf.  Three floats per
@@ -157,6 +210,34 @@ __global__ __launch_bounds__(256) void noise_rgb_kernel(const typename VecOf<R>:
     const uint32_t lp = blockIdx.x * 256 + threadIdx.x;
     if (lp >= shard_pixels) return;
     const double K = (double)chunks_done, N = (double)samples_done;
+    double vr = __builtin_inf(), vg = vr, vb = vr;
+    if (!(K < 2.0)) {
+        const r4 a = acc[lp];
+        const d4 m = q[lp];
+        const double Mr = (double)a.x, Mg = (double)a.y, Mb = (double)a.z;
+        double Dr = m.x - (Mr * Mr) / N, Dg = m.y - (Mg * Mg) / N, Db = m.z - (Mb * Mb) / N;
+        Dr = Dr < 0.0 ? 0.0 : Dr; // (a NaN stays a NaN)
+        Dg = Dg < 0.0 ? 0.0 : Dg;
+        Db = Db < 0.0 ? 0.0 : Db;
+        const double d = (K - 1.0) * N;
+        vr = Dr / d, vg = Dg / d, vb = Db / d;
+    }
+    var_rgb[3 * (size_t)lp + 0] = (float)vr;
+    var_rgb[3 * (size_t)lp + 1] = (float)vg;
+    var_rgb[3 * (size_t)lp + 2] = (float)vb;
+}
+
+// .. and for an adaptive handle, (K_i, N_i) per pixel as noise_eval_adaptive_kernel takes them.
+template <class R>
+__global__ __launch_bounds__(256) void noise_rgb_adaptive_kernel(const typename VecOf<R>::type* __restrict__ acc, const d4* __restrict__ q,
+                                                                 float* __restrict__ var_rgb, uint32_t shard_pixels, uint32_t chunks_done,
+                                                                 uint32_t samples_done, const uint32_t* __restrict__ frozen_at,
+                                                                 const uint32_t* __restrict__ starts) {
+    typedef typename VecOf<R>::type r4;
+    const uint32_t lp = blockIdx.x * 256 + threadIdx.x;
+    if (lp >= shard_pixels) return;
+    const uint32_t f = frozen_at[lp];
+    const double K = (double)(f ? f : chunks_done), N = (double)(f ? starts[f] : samples_done);
     double vr = __builtin_inf(), vg = vr, vb = vr;
     if (!(K < 2.0)) {
         const r4 a = acc[lp];

@@ -29,6 +29,16 @@ struct RayzProgressive {
     DevBuf<double> nz_block_sum;            // Σ finite var per block of noise_eval_kernel
     DevEvent pass_done;                     // recorded behind every pass: what an evaluation on another stream waits for
     hipStream_t noise_stream = nullptr;     // the stream of the last evaluation (it reads acc and q: the next pass waits for it)
+    // adaptive mode (rayz_hip_progressive_set_adaptive; adaptive_passes.hpp): absent from any other handle
+    bool adaptive = false;
+    uint32_t min_chunks = 0;
+    DevBuf<uint32_t> frozen_at;             // shard_pixels: 0 = active, else the chunk count the pixel froze at
+    DevBuf<uint32_t> active[2];             // the active list of the next pass (active[cur]) and the one being built
+    DevBuf<uint32_t> survivors;             // per block of adaptive_fold_kernel: survivors, then their exclusive prefix sums
+    DevBuf<uint32_t> d_n_active;            // [0] what the compaction counted
+    int cur = 0;
+    uint32_t n_active = 0, passes = 0;
+    const void* last_preview = nullptr;     // the buffer the last pass wrote (the preview rule, adaptive.hpp)
     ~RayzProgressive() { // the accumulator's last pass, and the last evaluation, have finished before the members go
         if (device < 0) return;
         DeviceScope scope(device);
@@ -80,6 +90,7 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
     if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
     if (pr->params.precision != precision)
         return fail(RAYZ_ERR_BAD_ARG, "params.precision %u does not match this entry point", pr->params.precision);
+    if (pr->adaptive) return fail(RAYZ_ERR_STATE, "the handle is in adaptive mode: step it with rayz_hip_progressive_adaptive_step");
     const uint32_t n = (uint32_t)pr->starts.size() - 1, c0 = pr->chunks_done;
     if (c0 >= n) return fail(RAYZ_ERR_STATE, "the progressive render is finished (%u of %u chunks done)", c0, n);
     // the fewest whole chunks from the cursor that add at least min_samples samples (at least one, at most the rest)
@@ -208,13 +219,17 @@ int progressive_track_noise(RayzProgressive* pr) {
 template <class R>
 int noise_eval(const void* acc, const d4* q, float* d_var, float* d_rel2, double* d_var64, double* d_rel264, unsigned long long* d_summary,
                double* d_block_sum, uint64_t pixels, uint32_t chunks_done, uint32_t samples_done, double floor2, double tau2,
-               RayzNoiseSummary* summary, hipStream_t stream) {
+               RayzNoiseSummary* summary, hipStream_t stream, const uint32_t* frozen_at = nullptr, const uint32_t* d_starts = nullptr) {
     typedef typename VecOf<R>::type r4;
     const uint32_t blocks = noise_blocks(pixels);
     if (pixels) {
         HIP_TRY(hipMemsetAsync(d_summary, 0, 2 * sizeof(unsigned long long), stream));
-        hipLaunchKernelGGL(noise_eval_kernel<R>, dim3(blocks), dim3(256), 0, stream, (const r4*)acc, q, d_var, d_rel2, d_var64, d_rel264,
-                           d_summary, d_block_sum, (uint32_t)pixels, chunks_done, samples_done, floor2, tau2);
+        if (frozen_at) // an adaptive handle: every pixel with its own (K_i, N_i)
+            hipLaunchKernelGGL(noise_eval_adaptive_kernel<R>, dim3(blocks), dim3(256), 0, stream, (const r4*)acc, q, d_var, d_rel2, d_var64,
+                               d_rel264, d_summary, d_block_sum, (uint32_t)pixels, chunks_done, samples_done, floor2, tau2, frozen_at, d_starts);
+        else
+            hipLaunchKernelGGL(noise_eval_kernel<R>, dim3(blocks), dim3(256), 0, stream, (const r4*)acc, q, d_var, d_rel2, d_var64, d_rel264,
+                               d_summary, d_block_sum, (uint32_t)pixels, chunks_done, samples_done, floor2, tau2);
         HIP_TRY(hipGetLastError());
     }
     if (!summary) return RAYZ_OK;
@@ -250,11 +265,12 @@ int progressive_noise(RayzProgressive* pr, const RayzNoiseParams* params, float*
     if (pr->last_stream && pr->last_stream != stream && pr->shard_pixels) HIP_TRY(hipStreamWaitEvent(stream, pr->pass_done, 0));
     pr->noise_stream = stream;
     const uint32_t K = pr->chunks_done, N = pr->starts[K];
+    const uint32_t* frozen_at = pr->adaptive ? pr->frozen_at.get() : nullptr; // (the summary's cursor stays the schedule's)
     if (pr->params.precision == RAYZ_PRECISION_F64)
         return noise_eval<double>(pr->acc.get(), pr->q, d_var, d_rel2, nullptr, nullptr, pr->nz_summary, pr->nz_block_sum, pr->shard_pixels, K,
-                                  N, floor2, tau2, summary, stream);
+                                  N, floor2, tau2, summary, stream, frozen_at, pr->d_starts);
     return noise_eval<float>(pr->acc.get(), pr->q, d_var, d_rel2, nullptr, nullptr, pr->nz_summary, pr->nz_block_sum, pr->shard_pixels, K, N,
-                             floor2, tau2, summary, stream);
+                             floor2, tau2, summary, stream, frozen_at, pr->d_starts);
 }
 
 // The per-channel variance of the mean (noise_rgb_kernel): ordered and owned as an evaluation is, without a summary.
@@ -272,7 +288,13 @@ int progressive_noise_rgb(RayzProgressive* pr, float* d_var_rgb, void* stream_ar
     pr->noise_stream = stream; // (a reader of acc and q, as an evaluation is)
     const uint32_t K = pr->chunks_done, N = pr->starts[K];
     const dim3 grid(noise_blocks(pr->shard_pixels)), block(256);
-    if (pr->params.precision == RAYZ_PRECISION_F64)
+    if (pr->adaptive && pr->params.precision == RAYZ_PRECISION_F64)
+        hipLaunchKernelGGL(noise_rgb_adaptive_kernel<double>, grid, block, 0, stream, (const VecOf<double>::type*)pr->acc.get(), (const d4*)pr->q,
+                           d_var_rgb, (uint32_t)pr->shard_pixels, K, N, pr->frozen_at.get(), pr->d_starts.get());
+    else if (pr->adaptive)
+        hipLaunchKernelGGL(noise_rgb_adaptive_kernel<float>, grid, block, 0, stream, (const VecOf<float>::type*)pr->acc.get(), (const d4*)pr->q,
+                           d_var_rgb, (uint32_t)pr->shard_pixels, K, N, pr->frozen_at.get(), pr->d_starts.get());
+    else if (pr->params.precision == RAYZ_PRECISION_F64)
         hipLaunchKernelGGL(noise_rgb_kernel<double>, grid, block, 0, stream, (const VecOf<double>::type*)pr->acc.get(), (const d4*)pr->q, d_var_rgb,
                            (uint32_t)pr->shard_pixels, K, N);
     else
@@ -308,6 +330,7 @@ int progressive_run_until(RayzProgressive* pr, const RayzNoiseParams* params, do
         return fail(RAYZ_ERR_BAD_ARG, "max_unconverged_fraction %g: must lie in [0, 1]", max_fraction);
     if (!pr) return fail(RAYZ_ERR_STATE, "progressive handle is null");
     if (!pr->tracked) return fail(RAYZ_ERR_STATE, "the handle does not track noise (rayz_hip_progressive_track_noise before the first step)");
+    if (pr->adaptive) return fail(RAYZ_ERR_STATE, "the handle is in adaptive mode: run it with rayz_hip_progressive_run_adaptive");
     const uint32_t n = (uint32_t)pr->starts.size() - 1;
     RayzNoiseSummary sm{};
     for (;;) {

@@ -14,6 +14,7 @@
 #include "bvh_build.hpp"
 #include "denoise.hpp"
 #include "noise.hpp"
+#include "adaptive.hpp"
 #include "host_base.hpp"
 
 using namespace rayz_dev;
@@ -823,17 +824,21 @@ ShardGeometry shard_geometry(const RayzRenderParams* p) {
 // p->samples_per_px stays the total, so every sample keeps its stream (pixel · spp + s): a chunk's sum does not depend on the
 // window it is traced in.  The first `reset_bytes` of `counters` are cleared first (the queue head, counters[0], at least);
 // ev0 / ev1 bracket the kernel; `experiment` returns BvhLaunchPlan::experiment.
+// With `active_list` (an adaptive pass): the window's chunks of the list's `n_active` pixels only, through the
+// adaptive_pass_kernel[_bvh] — queue entry k · n_active + j sums chunk c0 + k of pixel active_list[j] into partial[k · n_active + j].
 template <class R>
 int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
                  bool use_bvh, const std::vector<uint32_t>& starts, const uint32_t* d_starts, uint32_t c0, uint32_t c1,
                  unsigned long long* counters, size_t reset_bytes, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream,
-                 int& experiment) {
+                 int& experiment, const uint32_t* active_list = nullptr, uint32_t n_active = 0) {
     typedef typename VecOf<R>::type r4;
     const ShardGeometry shard = shard_geometry(p);
     const uint64_t shard_pixels64 = (uint64_t)shard.rows * p->width;
     const uint32_t chunks_per_px = c1 - c0;
-    const uint64_t items64 = shard_pixels64 * chunks_per_px;
-    RAYZ_TRY(check_items(shard_pixels64, chunks_per_px));
+    const uint64_t traced_pixels64 = active_list ? n_active : shard_pixels64;
+    const uint64_t items64 = traced_pixels64 * chunks_per_px;
+    RAYZ_TRY(check_items(shard_pixels64, 1));
+    RAYZ_TRY(check_items(traced_pixels64, chunks_per_px));
     const size_t need = (size_t)items64 * sizeof(r4);
     if (need > s->partial.capacity()) {
         HIP_TRY(hipStreamSynchronize(stream));
@@ -865,20 +870,23 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     A.tiled_pixels = shard.tiled_pixels;
     A.total_items = (uint32_t)items64;
     A.queue_grab = (uint32_t)std::max(1ll, tuning(RAYZ_DEBUG_QUEUE_GRAB, kQueueGrab));
+    A.n_active = active_list ? n_active : 0u;
+    A.active_list = active_list;
     // scheduling thresholds of the BVH kernel (no effect on results; rayz_hip_debug_set refuses values outside 1 .. 64 lanes)
     A.bvh_keep = (uint32_t)tuning(RAYZ_DEBUG_BVH_KEEP, kBvhKeepActive | (kBvhKeepStepping << 8));
 
     BvhLaunchPlan<R> plan{};
-    plan.kernel = trace_kernel<R, 1>;
+    plan.kernel = active_list ? adaptive_pass_kernel<R, 1> : trace_kernel<R, 1>;
     plan.block = 256;
     plan.items_per_lane = 1;
     if (use_bvh) {
-        plan.kernel = b.quantized ? trace_kernel_bvh<R, true> : trace_kernel_bvh<R, false>;
+        if (active_list) plan.kernel = b.quantized ? adaptive_pass_kernel_bvh<R, true> : adaptive_pass_kernel_bvh<R, false>;
+        else plan.kernel = b.quantized ? trace_kernel_bvh<R, true> : trace_kernel_bvh<R, false>;
         plan.block = (int)kBvhWg;
         plan.stack_bytes = bvh_stack_bytes(s->bvh_dev.depth, kBvhWg);
         // the tree's top: first in LDS.  The scene numbered b.bvh_top records breadth-first for this kernel's workgroup
         plan.top_records = b.bvh_top;
-        RAYZ_TRY(experiment_override<R>(plan, A, s, b, p)); // (the product build: nothing)
+        if (!active_list) RAYZ_TRY(experiment_override<R>(plan, A, s, b, p)); // (the product build: nothing; no retired kernel reads a list)
     }
     experiment = plan.experiment;
     // The LDS request (+ RAYZ_DEBUG_LDS_PAD unused bytes behind the kernel's own: an occupancy experiment — fewer workgroups per CU,
@@ -1259,6 +1267,7 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 
 // ---- the features on top of the trace launch (order: see the head of this file) ---------------------------------------------
 #include "progressive.hpp"
+#include "adaptive_passes.hpp"
 #include "known_answers.hpp"
 #include "multi_device.hpp"
 #include "query.hpp"

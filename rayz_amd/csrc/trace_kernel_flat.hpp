@@ -1,0 +1,78 @@
+// trace_kernel_flat.hpp — the text of the persistent flat-list trace kernel (described in rayz_device.hpp, which includes this file
+// TWICE: as trace_kernel, the product kernel, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
+// adaptive pass).  One text, two kernels of two NAMES, and not a second template flag on trace_kernel:
+// tests/test_isa_invariants.py counts the kernels named trace_kernel.. (six) and holds each to the product's limits, so a kernel
+// of that name is a product kernel; the adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared
+// body FUNCTION: handing the kernel's argument block to it changes the product kernel's register allocation; compiled twice,
+// trace_kernel's ISA is what it was.  No include guard.
+template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
+    constexpr bool kAdaptive = RAYZ_TRACE_KERNEL_ADAPTIVE; // work items over the active list (place_item)
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    PathState<R> p[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) path_init<R>(p[r]);
+    uint32_t nseg = 0;
+    WaveQueue wq; // wave-uniform
+#ifdef RAYZ_FLAT_PROFILE // measurement build only: wave time per phase (refill, ray setup, scan, narrow flush, shade)
+    unsigned long long ft[5] = {0, 0, 0, 0, 0}, ft0 = __builtin_amdgcn_s_memtime(), fiters = 0;
+#define RAYZ_FPROF(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ft[k] += now_ - ft0; ft0 = now_; }
+#else
+#define RAYZ_FPROF(k)
+#endif
+
+    for (;;) {
+        // ---- retire finished chunks, refill idle slots ----
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            path_refill<R, kAdaptive>(p[r], A, lane, wq);
+            any = any || p[r].alive;
+        }
+        if (__ballot(any) == 0ull) break; // queue drained and every slot idle: the wave is done
+
+        RAYZ_FPROF(0)
+        // ---- nearest hit (full EXEC; idle tail slots recompute their last ray, results unused) ----
+        ScanRay<R> ray[NR];
+        V<R> ud[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            ud[r] = unit(p[r].d);
+            scan_begin<R, NR>(ray[r], p[r].o, p[r].d, ud[r], p[r].time);
+        }
+        RAYZ_FPROF(1)
+#ifdef RAYZ_FLAT_PROFILE
+        fiters++;
+        scan_sphere_classes<R, NR>(A.sc, ray, A.tmin);
+        RAYZ_FPROF(2)
+        narrow_flush<R, NR>(A.sc, ray, A.tmin);
+        scan_triangles<R, NR>(A.sc, ray, A.tmin);
+        RAYZ_FPROF(3)
+#else
+        scan_spheres<R, NR>(A.sc, ray, A.tmin);
+#endif
+
+        // ---- shade ----
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (p[r].alive) {
+                nseg++;
+                p[r].seg++;
+                bool cont = shade<R>(A.sc, p[r].g, p[r].o, p[r].d, ud[r], p[r].time, ray[r].tbest, ray[r].ibest, p[r].thr,
+                                     p[r].acc);
+                if (p[r].seg >= A.max_bounces) cont = false; // depth exhausted → black, src/renderer.zig:104-105
+                p[r].alive = cont;
+            }
+        RAYZ_FPROF(4)
+    }
+#ifdef RAYZ_FLAT_PROFILE
+    if (lane == 0) {
+        for (int k = 0; k < 5; ++k) atomicAdd(&A.counters[4 + k], ft[k]);
+        atomicAdd(&A.counters[9], fiters);
+    }
+#endif
+    // ---- counters: one atomic per wave ----
+    unsigned long long tot = nseg;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
+    if (lane == 0) atomicAdd(&A.counters[1], tot);
+}

@@ -333,6 +333,11 @@ struct GpuOptions {
     // at most `until_fraction` of the pixels exceed the relative standard error `until_rel_error`, or samples_per_px is reached; 0: off.
     // render() refuses the combination with more than one device, and leaves where it stopped in Tracer::until_summary.
     double until_rel_error = 0.0, until_fraction = 0.01;
+    // one device only, as `until_rel_error` (and not together with it): adaptive passes (rayz_hip_progressive_run_adaptive, DESIGN.md
+    // §4.14) of about 1/16 of the samples — every pixel is traced until ITS relative standard error is at most `adaptive_rel_error`, or
+    // samples_per_px is reached; 0: off.  render() leaves the outcome in Tracer::adaptive_summary and returns the samples traced.
+    double adaptive_rel_error = 0.0;
+    uint32_t adaptive_min_chunks = RAYZ_ADAPTIVE_DEFAULT_MIN_CHUNKS;
 };
 
 static const double ASPECT_RATIO = 16.0 / 9.0; // src/renderer.zig:16
@@ -347,6 +352,7 @@ struct Tracer {
     MemPool pool;
     GpuOptions gpu;
     RayzRenderStats stats{};
+    RayzAdaptiveSummary adaptive_summary{}; // the outcome of the last render() with gpu.adaptive_rel_error (rayz_hip_progressive_run_adaptive)
     RayzNoiseSummary until_summary{}; // where the last render() with gpu.until_rel_error stopped (rayz_hip_progressive_run_until)
     // Several GPUs (gpu.devices): the per-device scenes and the RCCL communicators (`ncclCommInitAll`: tens of
     // milliseconds per device) are kept across render() calls and rebuilt only when the pool or the device list changes,
@@ -459,7 +465,9 @@ struct Tracer {
         const size_t n = img.h * img.w;
         if (gpu.until_rel_error > 0.0 && gpu.devices.size() > 1)
             throw GpuRenderFailed(RAYZ_ERR_BAD_ARG, "render until converged runs on one device: not with a list of several");
-        if ((gpu.progress || gpu.until_rel_error > 0.0) && gpu.devices.size() <= 1) {
+        if (gpu.adaptive_rel_error > 0.0 && (gpu.devices.size() > 1 || gpu.until_rel_error > 0.0))
+            throw GpuRenderFailed(RAYZ_ERR_BAD_ARG, "adaptive passes run on one device, and not together with render until converged");
+        if ((gpu.progress || gpu.until_rel_error > 0.0 || gpu.adaptive_rel_error > 0.0) && gpu.devices.size() <= 1) {
             if (gpu.precision == RAYZ_PRECISION_F32) {
                 std::vector<float> rgb(n * 3);
                 renderProgressive(sd, cd, p, rgb.data(), sizeof(float));
@@ -530,6 +538,19 @@ struct Tracer {
         if (hipMalloc(&d_rgb, bytes ? bytes : 16) != hipSuccess) return done(RAYZ_ERR_OOM, "hipMalloc(frame) failed");
         const uint32_t spp = p.samples_per_px, pass = (spp + 99) / 100;
         uint32_t samples = 0, chunks = 0, n_chunks = 1;
+        if (gpu.adaptive_rel_error > 0.0) { // adaptive passes: the library's own loop
+            const RayzNoiseParams np{gpu.adaptive_rel_error, RAYZ_NOISE_DEFAULT_MEAN_FLOOR};
+            RayzAdaptiveSummary sm{};
+            rc = rayz_hip_progressive_set_adaptive(pr, gpu.adaptive_min_chunks);
+            if (rc == RAYZ_OK)
+                rc = p.precision == RAYZ_PRECISION_F64 ? rayz_hip_progressive_run_adaptive_f64(pr, &np, (spp + 15) / 16, (double*)d_rgb, &sm, nullptr)
+                                                       : rayz_hip_progressive_run_adaptive(pr, &np, (spp + 15) / 16, (float*)d_rgb, &sm, nullptr);
+            if (rc == RAYZ_OK) rc = rayz_hip_progressive_info(pr, &samples, &chunks, &n_chunks, &stats);
+            if (rc != RAYZ_OK) return done(rc, rayz_hip_last_error());
+            adaptive_summary = sm;
+            if (hipMemcpy(rgb, d_rgb, bytes, hipMemcpyDeviceToHost) != hipSuccess) return done(RAYZ_ERR_HIP, "hipMemcpy(frame) failed");
+            return done(RAYZ_OK, "");
+        }
         if (gpu.until_rel_error > 0.0) { // render until converged: the library's own loop, one evaluation per pass
             const RayzNoiseParams np{gpu.until_rel_error, RAYZ_NOISE_DEFAULT_MEAN_FLOOR};
             RayzNoiseSummary sm{};

@@ -11,25 +11,40 @@
 // of more than one ordinal renders in one call, without progress).  And one optional argument anywhere on the line:
 // `--until <rel_error>` renders until converged (rayz_hip_progressive_run_until: passes of about 1/16 of RAYZ_SPP until at
 // most 1 % of the pixels exceed that relative standard error, or RAYZ_SPP is reached) and prints, after the rate line, the
-// samples per pixel it stopped at and the unconverged fraction.  Without it the output is what it always was.
+// samples per pixel it stopped at and the unconverged fraction; or `--adaptive <rel_error>` (not both) renders in adaptive passes
+// (rayz_hip_progressive_run_adaptive: every pixel is traced until its own relative standard error is at most that, or RAYZ_SPP is
+// reached; no pixel stops before its 4th chunk) and prints the samples traced against pixels x RAYZ_SPP.
+// Without either the output is what it always was.
 #include "rayz.hpp"
 
 #include <chrono>
 #include <cstdlib>
 
 int main(int argc, char** argv) {
-    double until = 0.0;
-    for (int i = 1; i < argc; ++i) { // take `--until <rel_error>` out of the line: the rest is the reference's interface
-        if (std::string(argv[i]) != "--until") continue;
+    double until = 0.0, adaptive = 0.0;
+    for (int i = 1; i < argc;) { // take `--until <rel_error>` / `--adaptive <rel_error>` out of the line: the rest is the reference's interface
+        const std::string opt = argv[i];
+        if (opt != "--until" && opt != "--adaptive") {
+            ++i;
+            continue;
+        }
+        double& value = opt == "--until" ? until : adaptive;
+        if (value > 0.0) { // only the first of each is taken, as `--until` always was
+            ++i;
+            continue;
+        }
         char* uend = nullptr;
-        if (i + 1 < argc) until = std::strtod(argv[i + 1], &uend);
-        if (i + 1 >= argc || !(until > 0.0) || (uend && *uend)) {
-            std::fprintf(stderr, "error: --until needs a positive relative error\n");
+        if (i + 1 < argc) value = std::strtod(argv[i + 1], &uend);
+        if (i + 1 >= argc || !(value > 0.0) || (uend && *uend)) {
+            std::fprintf(stderr, "error: %s needs a positive relative error\n", opt.c_str());
             return 2;
         }
         for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
         argc -= 2;
-        break;
+    }
+    if (until > 0.0 && adaptive > 0.0) {
+        std::fprintf(stderr, "error: --until and --adaptive exclude each other\n");
+        return 2;
     }
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <img_w> [out.ppm]\n", argv[0]); // the reference panics on `.?`, src/rayz.zig:16
@@ -76,6 +91,11 @@ int main(int argc, char** argv) {
         return 2;
     }
     tracer.gpu.until_rel_error = until;
+    if (adaptive > 0.0 && tracer.gpu.devices.size() > 1) {
+        std::fprintf(stderr, "error: --adaptive renders on one device: not with a RAYZ_DEVICES list of several\n");
+        return 2;
+    }
+    tracer.gpu.adaptive_rel_error = adaptive;
 
     if (rayz_hip_init(tracer.gpu.devices.empty() ? 0 : tracer.gpu.devices[0]) != RAYZ_OK) {
         std::fprintf(stderr, "error: GpuRenderFailed: %s\n", rayz_hip_last_error());
@@ -96,6 +116,13 @@ int main(int argc, char** argv) {
         const RayzNoiseSummary& sm = tracer.until_summary;
         std::fprintf(stderr, "Stopped at %u of %zu samples per pixel: %.2f%% of the pixels above %g relative error\n", sm.samples_done,
                      (size_t)tracer.samples_per_px, sm.pixels ? 100.0 * (double)sm.unconverged / (double)sm.pixels : 0.0, until);
+    }
+    if (adaptive > 0.0) {
+        const RayzAdaptiveSummary& sm = tracer.adaptive_summary;
+        const double full = (double)sm.pixels * (double)tracer.samples_per_px;
+        std::fprintf(stderr, "Traced %llu of %.0f samples (%.2f%%) in %u passes: %.2f%% of the pixels still above %g relative error\n",
+                     (unsigned long long)sm.samples_traced, full, full > 0 ? 100.0 * (double)sm.samples_traced / full : 0.0, sm.passes,
+                     sm.pixels ? 100.0 * (double)sm.active / (double)sm.pixels : 0.0, adaptive);
     }
 
     if (argc > 2) {

@@ -135,10 +135,13 @@ class DeviceScene:
         rc = fn(self._h, C.byref(camera), C.byref(params), C.c_void_p(out_ptr), C.c_void_p(stream))
         capi.check(self._lib, rc, "rayz_hip_render_device")
 
-    def progressive(self, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False) -> "Progressive":
+    def progressive(self, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False, adaptive: bool = False,
+                    min_chunks: int | None = None) -> "Progressive":
         """The frame of `render_into(camera, params, ...)` in passes of whole chunks (`rayz_hip_progressive_create`);
-        `track_noise` makes it a tracked handle (`Progressive.noise`, `Progressive.render_until`)."""
-        return Progressive(self, camera, params, track_noise=track_noise)
+        `track_noise` makes it a tracked handle (`Progressive.noise`, `Progressive.render_until`), `adaptive` an adaptive one
+        (`Progressive.adaptive_step`, `Progressive.render_adaptive`: DESIGN.md §4.14) that freezes no pixel before `min_chunks`
+        chunks (default capi.ADAPTIVE_DEFAULT_MIN_CHUNKS)."""
+        return Progressive(self, camera, params, track_noise=track_noise, adaptive=adaptive, min_chunks=min_chunks)
 
     def sync(self) -> capi.RenderStats:
         st = capi.RenderStats()
@@ -232,7 +235,8 @@ class Progressive:
     """One frame rendered in passes (`rayz_hip_progressive_*`): every `step` adds whole chunks of the chunk schedule and may
     write the frame so far; the last one writes the one-shot frame bit for bit.  Close it before its scene."""
 
-    def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False):
+    def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False,
+                 adaptive: bool = False, min_chunks: int | None = None):
         self._lib = scene._lib
         self._scene = scene  # (kept alive: the handle renders on it)
         self._h = C.c_void_p()
@@ -243,6 +247,10 @@ class Progressive:
                                                                     C.byref(self._h)), "rayz_hip_progressive_create")
         if track_noise:
             self.track_noise()
+        if adaptive:
+            self.set_adaptive(min_chunks)
+        elif min_chunks is not None:
+            raise ValueError("min_chunks belongs to adaptive=True")
 
     def track_noise(self) -> None:
         """`rayz_hip_progressive_track_noise`: keep the chunk sums' second moments (before the first step only)."""
@@ -331,6 +339,68 @@ class Progressive:
         capi.check(self._lib, rc, "rayz_hip_progressive_run_until")
         self._inflight = (out,)
         return sm
+
+    # ---- adaptive passes (`rayz_hip_progressive_set_adaptive` ..) ----
+    def set_adaptive(self, min_chunks: int | None = None) -> None:
+        """`rayz_hip_progressive_set_adaptive`: trace only unconverged pixels from now on (before the first step only)."""
+        mc = capi.ADAPTIVE_DEFAULT_MIN_CHUNKS if min_chunks is None else int(min_chunks)
+        capi.check(self._lib, self._lib.rayz_hip_progressive_set_adaptive(self._h, mc), "rayz_hip_progressive_set_adaptive")
+
+    def _check_out(self, out):
+        import torch
+
+        if out is None:
+            return
+        want = torch.float64 if self.f64 else torch.float32
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self._scene.device:
+            raise ValueError(f"out must be a torch tensor on cuda:{self._scene.device}")
+        if out.dtype != want or tuple(out.shape) != self.shape + (3,) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {want} tensor shaped {self.shape + (3,)}")
+
+    def _adaptive_call(self, name, rel_error, mean_floor, min_samples, out, stream) -> capi.AdaptiveSummary:
+        self._check_out(out)
+        self._stream_prologue(stream)
+        prm = self._noise_params(rel_error, mean_floor)
+        sm = capi.AdaptiveSummary()
+        fn = getattr(self._lib, name + ("_f64" if self.f64 else ""))
+        rc = fn(self._h, C.byref(prm), min_samples, C.c_void_p(out.data_ptr() if out is not None and out.numel() else None), C.byref(sm),
+                C.c_void_p(stream or None))
+        capi.check(self._lib, rc, name)
+        self._inflight = (out,)
+        return sm
+
+    def adaptive_step(self, rel_error: float | None = None, mean_floor: float | None = None, min_samples: int = 0, out=None,
+                      stream: int = 0) -> capi.AdaptiveSummary:
+        """One adaptive pass (`rayz_hip_progressive_adaptive_step`): the window `step(min_samples)` would take, for the pixels
+        still active; then every active pixel with rel2 <= rel_error^2 freezes.  `out`: an optional torch tensor (rows_in_shard,
+        width, 3) of the handle's precision; pass the SAME tensor to every pass and it holds the whole frame after each (another
+        tensor than the last pass's — and any tensor after a pass that got none — is written whole).  On a finished run nothing is traced and `out` receives the frame.
+        Blocks; returns the summary (`active`: pixels the next pass traces)."""
+        return self._adaptive_call("rayz_hip_progressive_adaptive_step", rel_error, mean_floor, min_samples, out, stream)
+
+    def render_adaptive(self, rel_error: float | None = None, mean_floor: float | None = None, min_samples_per_pass: int = 0, out=None,
+                        stream: int = 0) -> capi.AdaptiveSummary:
+        """Adaptive passes until no pixel is active or the schedule ends (`rayz_hip_progressive_run_adaptive`); `out` receives the
+        frame.  Blocks; returns the last summary (`samples_traced` against pixels x spp is the saving)."""
+        return self._adaptive_call("rayz_hip_progressive_run_adaptive", rel_error, mean_floor, min_samples_per_pass, out, stream)
+
+    def _adaptive_read(self, name, stream):
+        import torch
+
+        t = torch.empty(self.shape, dtype=torch.int32, device=torch.device("cuda", self._scene.device))  # (uint32 values < 2^31)
+        self._stream_prologue(stream)
+        rc = getattr(self._lib, name)(self._h, C.c_void_p(t.data_ptr() if t.numel() else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, name)
+        return t
+
+    def sample_counts(self, stream: int = 0):
+        """N_i, the samples behind every pixel's value (`rayz_hip_progressive_sample_counts`): an int32 tensor (rows_in_shard,
+        width) on the scene's device.  Blocks."""
+        return self._adaptive_read("rayz_hip_progressive_sample_counts", stream)
+
+    def frozen_at(self, stream: int = 0):
+        """The chunk count at which every pixel froze, 0 for an active one (`rayz_hip_progressive_frozen_at`).  Blocks."""
+        return self._adaptive_read("rayz_hip_progressive_frozen_at", stream)
 
     def step(self, min_samples: int = 0, out_ptr: int = 0, stream: int = 0) -> None:
         """One pass of at least `min_samples` samples per pixel (0: one chunk; 0xFFFFFFFF: the rest), asynchronous on `stream`;
@@ -594,6 +664,32 @@ def noise_kat(chunk_sums, chunk_sizes, precision: int = capi.PRECISION_F32, rel_
                                 q.ctypes.data_as(D), var.ctypes.data_as(D), rel2.ctypes.data_as(D), C.byref(sm))
     capi.check(lib, rc, "rayz_hip_noise_kat")
     return q, var, rel2, sm
+
+
+def adaptive_kat(chunk_sums, chunk_sizes, pass_ends, precision: int = capi.PRECISION_F32, rel_error: float | None = None,
+                 mean_floor: float | None = None, min_chunks: int = capi.ADAPTIVE_DEFAULT_MIN_CHUNKS, width: int = 0):
+    """`rayz_hip_adaptive_kat`: fold, freeze and compaction of adaptive passes on (n_chunks, n_pixels, 3) float64 chunk sums; pass p
+    ends at chunk count pass_ends[p].  Returns a dict: frozen_at (n_pixels,) uint32; acc, Q, frame (n_pixels, 3) float64; lists — the
+    active list every pass traced, then what is left (len(pass_ends) + 1 uint32 arrays)."""
+    lib = capi.load()
+    sums = np.ascontiguousarray(chunk_sums, dtype=np.float64)
+    if sums.ndim != 3 or sums.shape[2] != 3:
+        raise ValueError(f"chunk_sums must be (n_chunks, n_pixels, 3), got {sums.shape}")
+    sizes = np.ascontiguousarray(chunk_sizes, dtype=np.uint32)
+    if sizes.shape != (sums.shape[0],):
+        raise ValueError(f"chunk_sizes must be ({sums.shape[0]},), got {sizes.shape}")
+    ends = np.ascontiguousarray(pass_ends, dtype=np.uint32)
+    k, n = sums.shape[:2]
+    frozen = np.zeros(n, dtype=np.uint32)
+    acc, q, frame = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    lists, lens = np.zeros((len(ends) + 1, max(n, 1)), dtype=np.uint32), np.zeros(len(ends) + 1, dtype=np.uint32)
+    prm = Progressive._noise_params(rel_error, mean_floor)
+    D, U = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+    rc = lib.rayz_hip_adaptive_kat(precision, sums.ctypes.data_as(D), sizes.ctypes.data_as(U), n, k, ends.ctypes.data_as(U), len(ends), width,
+                                   min_chunks, C.byref(prm), frozen.ctypes.data_as(U), acc.ctypes.data_as(D), q.ctypes.data_as(D),
+                                   frame.ctypes.data_as(D), lists.ctypes.data_as(U) if n else None, lens.ctypes.data_as(U))
+    capi.check(lib, rc, "rayz_hip_adaptive_kat")
+    return {"frozen_at": frozen, "acc": acc, "Q": q, "frame": frame, "lists": [lists[p, :lens[p]].copy() for p in range(len(ends) + 1)]}
 
 
 def tonemap_u8(rgb_ptr: int, out_ptr: int, n_pixels: int, stream: int = 0) -> None:

@@ -238,6 +238,72 @@ pub extern fn rayz_hip_progressive_run_until_f64(
     hip_stream: ?*anyopaque,
 ) c_int;
 
+// ---- adaptive passes (include/rayz_hip.h, DESIGN.md §4.14): a handle in adaptive mode stops tracing the pixels whose relative
+// standard error has dropped to `rel_error`; `samples_traced` against pixels x spp is the saving.  UNCHECKED BY THE TEXT CHECK as
+// the noise entries above are, for the same two reasons; tests/test_adaptive_cpu.py holds the struct and the names to the header.
+pub const RayzAdaptiveSummary: type = extern struct {
+    pixels: u64,
+    active: u64,
+    samples_traced: u64,
+    passes: u32,
+    chunks_done: u32,
+    samples_done: u32,
+    _pad: u32,
+};
+pub extern fn rayz_hip_progressive_set_adaptive(pr: *RayzProgressive, min_chunks: u32) c_int;
+pub extern fn rayz_hip_progressive_adaptive_step(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    min_samples: u32,
+    d_preview: ?[*]f32,
+    summary: ?*RayzAdaptiveSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_adaptive_step_f64(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    min_samples: u32,
+    d_preview: ?[*]f64,
+    summary: ?*RayzAdaptiveSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_run_adaptive(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    min_samples_per_pass: u32,
+    d_preview: ?[*]f32,
+    last_summary: ?*RayzAdaptiveSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_run_adaptive_f64(
+    pr: *RayzProgressive,
+    p: ?*const RayzNoiseParams,
+    min_samples_per_pass: u32,
+    d_preview: ?[*]f64,
+    last_summary: ?*RayzAdaptiveSummary,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_progressive_sample_counts(pr: *RayzProgressive, d_counts: [*]u32, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_progressive_frozen_at(pr: *RayzProgressive, d_frozen_at: [*]u32, hip_stream: ?*anyopaque) c_int;
+pub extern fn rayz_hip_adaptive_kat(
+    precision: u32,
+    chunk_sums: [*]const f64,
+    chunk_sizes: [*]const u32,
+    n_pixels: u32,
+    n_chunks: u32,
+    pass_ends: [*]const u32,
+    n_passes: u32,
+    width: u32,
+    min_chunks: u32,
+    p: ?*const RayzNoiseParams,
+    frozen_at_out: ?[*]u32, // (the outputs: host buffers, or null)
+    acc_out: ?[*]f64,
+    q_out: ?[*]f64,
+    frame_out: ?[*]f64,
+    lists_out: ?[*]u32,
+    list_sizes_out: ?[*]u32,
+) c_int;
+
 // ---- variance-guided denoising (include/rayz_hip.h, DESIGN.md §4.13): the per-channel variance of a tracked handle steers an
 // à-trous filter pixel by pixel.  UNCHECKED BY THE TEXT CHECK as the noise entries above are, for the same two reasons (a struct
 // beyond the eight render structs; `void* hip_stream`); tests/test_denoise_guided_cpu.py holds this struct and these two
