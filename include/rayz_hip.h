@@ -674,6 +674,64 @@ int rayz_hip_denoiser_run_guided(RayzDenoiser* dn, const RayzDenoiseGuidedParams
 int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);
 int rayz_hip_denoiser_destroy(RayzDenoiser* dn);
 
+/* ---- temporal accumulation: reproject the history across camera moves -----------------------------
+ * BUILD-DEFINED: the temporal stage of SVGF (Schied et al. 2017) for a caller that keeps a scene in device memory and moves the
+ * camera.  A step takes the current frame (WHOLE f32 frame in DEVICE memory), its per-channel variance
+ * (rayz_hip_progressive_noise_rgb) and the G-buffer a rayz_hip_scene_query_camera call of F32 precision filled for the same
+ * camera; every pixel's first-hit point is projected into the PREVIOUS step's camera, the four history pixels around that position
+ * are accepted where they are the same surface (same hittable, normals within `normal_cos_min`, points within `max_rel_dist` of
+ * the distance to the previous camera), and the current frame is blended into their interpolated mean by sample count:
+ * alpha = max(spp / (history samples + spp), alpha_min).  The variance of the blended mean is carried along, so the outputs go
+ * straight into rayz_hip_denoiser_run_guided.  A camera equal to the previous step's byte for byte is a STATIC step: every pixel
+ * takes its own history, no projection.  The arithmetic is a contract (§4.15, the rules of §4.11), restated bit for bit by
+ * tests/temporal_mirror.cpp.  Added in ABI 5 (additive: no existing symbol changed); it changes no image any other entry point
+ * produces.
+ * Limits of this version: the UNFILTERED accumulated colour is the history (SVGF's feedback of the filtered colour is not built);
+ * no motion vectors — the guides are first-hit, time-0 guides, so a moving sphere is matched where it is at time 0 and its blur is
+ * carried as if painted on it; reflections and refractions are not reprojected (a mirror's image is carried on the mirror's
+ * surface); whole frames only (rows of a shard are not image neighbours: gather first, as for the denoiser); f32 only; no switch
+ * of the `rayz` command line. */
+typedef struct RayzTemporal RayzTemporal; /* opaque: two history buffers (ping-pong) for one frame size on one device + the last camera */
+
+#define RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN 0.05       /* these four: PROVISIONAL until DESIGN.md §6's measurement; parameters, not contract */
+#define RAYZ_TEMPORAL_DEFAULT_N_MAX 65536.0
+#define RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN 0.9
+#define RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST 0.05
+
+typedef struct RayzTemporalParams {
+    double alpha_min;      /* in [0, 1]: the least weight of the current frame; 0 = the running sample-weighted mean, 1 = no history */
+    double n_max;          /* >= 1 (+inf allowed): the history length, in samples, is capped here */
+    double normal_cos_min; /* in [-1, 1]: a history pixel is accepted if dot(its normal, the current normal) >= this */
+    double max_rel_dist;   /* > 0: .. and if its point lies within this fraction of the current point's distance to the previous camera */
+} RayzTemporalParams;      /* all four are used as f32 */
+
+/* device < 0: the default device (RAYZ_ERR_NO_DEVICE before rayz_hip_init); otherwise creates that device's context if needed.
+ * RAYZ_ERR_BAD_ARG: a zero size, or width*height > RAYZ_DENOISE_MAX_PIXELS.  The handle owns 128 bytes per pixel. */
+int rayz_hip_temporal_create(int device, uint32_t width, uint32_t height, RayzTemporal** out);
+/* One frame.  d_rgb_in, d_var_rgb, d_rgb_out, d_var_out: DEVICE memory, height*width*3 floats each; d_length_out_or_null:
+ * height*width floats, the history length in samples after the step (spp where no history was found).  d_rgb_out == d_rgb_in and
+ * d_var_out == d_var_rgb are allowed (a pixel reads only its own current values).  `gbuffer`: index, normal and point are
+ * required, the other fields are ignored.  `camera`: the camera the frame and the G-buffer were made with; `spp`: the frame's
+ * samples per pixel — render every frame in at least 2 chunks, or its variance is +inf, which is carried as 2^32.
+ * params_or_null == NULL: all defaults.  The first step of a handle, and the first after rayz_hip_temporal_reset, has no
+ * history: its outputs are its inputs (the variance clamped to [0, 2^32], a NaN taken as 2^32).
+ * Asynchronous on `hip_stream` (NULL: the library's stream of the handle's device); the inputs must stay allocated until the step
+ * has finished.  One step in flight per handle: a step first makes its stream wait, on the device, for the handle's previous
+ * step (through an event of the handle's own, so the previous step's stream may have been destroyed by then; _destroy waits the
+ * same way).
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): a missing pointer (only d_length_out and params may
+ * be NULL); spp == 0 or spp > 2^24; alpha_min outside [0, 1]; n_max not >= 1; normal_cos_min outside [-1, 1]; max_rel_dist not
+ * > 0 (a NaN fails each of these); a camera whose px_du, px_dv and px_origin - look_from have a determinant that is 0 or not
+ * finite.  RAYZ_ERR_STATE: a bad handle. */
+int rayz_hip_temporal_step(RayzTemporal* tm, const RayzTemporalParams* params_or_null, const RayzCameraDesc* camera, uint32_t spp,
+                           const float* d_rgb_in, const float* d_var_rgb, const RayzQueryOutputs* gbuffer, float* d_rgb_out,
+                           float* d_var_out, float* d_length_out_or_null, void* hip_stream);
+/* Forgets the history: the next step is a first frame.  Touches no device. */
+int rayz_hip_temporal_reset(RayzTemporal* tm);
+/* Waits for the handle's last step and returns its HIP-event time in *ms (may be NULL: just wait).  RAYZ_ERR_STATE before any step. */
+int rayz_hip_temporal_timing(RayzTemporal* tm, float* ms);
+int rayz_hip_temporal_destroy(RayzTemporal* tm);
+
 #ifdef __cplusplus
 }
 #endif

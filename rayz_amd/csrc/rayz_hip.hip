@@ -13,6 +13,7 @@
 #include "rayz_device.hpp"
 #include "bvh_build.hpp"
 #include "denoise.hpp"
+#include "temporal_kernel.hpp"
 #include "noise.hpp"
 #include "adaptive.hpp"
 #include "host_base.hpp"
@@ -1272,3 +1273,4 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "multi_device.hpp"
 #include "query.hpp"
 #include "denoiser.hpp"
+#include "temporal.hpp"

@@ -1,0 +1,165 @@
+// temporal_kernel.hpp — temporal accumulation's device code (include/rayz_hip.h: rayz_hip_temporal_*; the handle,
+// the host part of a step and the validation: temporal.hpp).
+//
+// ONE launch per step: every pixel of the current frame finds where its first-hit point lay in the previous frame, gathers the four
+// history pixels around that position, keeps the ones that are the same surface, blends the current sample into their
+// interpolated mean by sample count and writes the new history, the blended colour and its variance.  A gather-and-stream kernel:
+// per pixel it reads 52 bytes of the caller's frame (colour, variance, index, normal, point) and one history record of 4 x 16 B,
+// and writes one history record and 24 (28 with the length) bytes; the other three taps of a pixel are its neighbours' compulsory
+// reads, which is why pixels are dealt as the denoiser's 32x8 tiles — a wave covers two rows of 32 pixels, and for a pan of a few
+// pixels its taps fall in the 33x3 records around them, 16-byte records in four arrays read and written as dwordx4.  No LDS: a tap's
+// position is data-dependent, and a tile's taps need not lie in a tile.
+//
+// The arithmetic is a contract (§4.15): + - x, the FMAs written below, correctly rounded divides, floor, comparisons — so that
+// tests/temporal_mirror.cpp restates it bit for bit.  What a tap decides is in ta_accepts(), what it adds in ta_add(); the static
+// form (the camera did not move: the one tap is the pixel's own record) is a template flag of the same kernel.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "denoise.hpp" // dn4, dn_dot, the tile and its grid
+
+namespace rayz_dev {
+
+constexpr float kTaMinWeight = 0.015625f; // 2^-6: below this accepted bilinear weight there is no history
+
+struct TemporalHistory { // four arrays of one 16-byte record per pixel
+    dn4* c; // {c.r, c.g, c.b, N}: accumulated radiance, history length in samples
+    dn4* v; // {v.r, v.g, v.b, 0}: variance of that mean
+    dn4* g; // {n.x, n.y, n.z, bits(index)}
+    dn4* p; // {P.x, P.y, P.z, 0}
+};
+
+struct TemporalArgs {
+    const float* rgb;                  // the current frame, packed RGB (may be rgb_out: a pixel reads only its own)
+    const float* var;                  // its per-channel variance (may be var_out)
+    const int32_t* __restrict__ index; // the current frame's guides
+    const float* __restrict__ normal;
+    const float* __restrict__ point;
+    TemporalHistory prev, next;        // ping-pong: never the same buffer
+    float* rgb_out;
+    float* var_out;
+    float* len_out;                    // or NULL
+    uint32_t width, height;
+    uint32_t has_history;
+    float M[9];                        // the PREVIOUS camera's: rows (v×a)/det, (a×u)/det, (u×v)/det
+    float from[3];                     // the previous camera's look_from
+    float spp, am, nm, cm, r2;         // f32 of samples per pixel, alpha_min, n_max, normal_cos_min; r2 = f32(max_rel_dist)²
+};
+
+struct TaAcc {
+    float B, Hr, Hg, Hb, Vr, Vg, Vb, N;
+};
+
+// A tap's guide records against the current pixel's id, n, P and lim = r2·|P − from|²: is this history pixel the same surface?
+__device__ __forceinline__ bool ta_accepts(const TemporalArgs& a, const dn4 g, const dn4 pp, int32_t id, float nx, float ny, float nz,
+                                           float Px, float Py, float Pz, float lim) {
+    if (__float_as_int(g.w) != id) return false;
+    if (!(dn_dot(g.x, g.y, g.z, nx, ny, nz) >= a.cm)) return false;
+    const float dx = pp.x - Px, dy = pp.y - Py, dz = pp.z - Pz;
+    return dn_dot(dx, dy, dz, dx, dy, dz) <= lim;
+}
+
+// An accepted tap of bilinear weight b: its colour + length and variance records join the sums, in tap order.
+__device__ __forceinline__ void ta_add(const dn4 c, const dn4 v, float b, TaAcc& acc) {
+    acc.B = acc.B + b;
+    acc.Hr = __builtin_fmaf(b, c.x, acc.Hr);
+    acc.Vr = __builtin_fmaf(b, v.x, acc.Vr);
+    acc.Hg = __builtin_fmaf(b, c.y, acc.Hg);
+    acc.Vg = __builtin_fmaf(b, v.y, acc.Vg);
+    acc.Hb = __builtin_fmaf(b, c.z, acc.Hb);
+    acc.Vb = __builtin_fmaf(b, v.z, acc.Vb);
+    acc.N = __builtin_fmaf(b, c.w, acc.N);
+}
+
+__device__ __forceinline__ float ta_clamp_var(float t) { return !(t < kDnVarCap) ? kDnVarCap : (t > 0.0f ? t : 0.0f); } // §4.13's pack clamp
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_step_kernel(const TemporalArgs a) {
+    const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
+    const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
+    if (x >= (int)a.width || y >= (int)a.height) return;
+    const size_t p = (size_t)y * a.width + (size_t)x;
+    const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
+    const float sr = ta_clamp_var(a.var[3 * p]), sg = ta_clamp_var(a.var[3 * p + 1]), sb = ta_clamp_var(a.var[3 * p + 2]);
+    const int32_t id = a.index[p];
+    const float nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
+    const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
+    float or_ = cr, og = cg, ob = cb, vr = sr, vg = sg, vb = sb, No = a.spp; // no history: the input, by selection
+    if (id >= 0 && a.has_history) {
+        const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
+        const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
+        TaAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (STATIC) {
+            if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim)) ta_add(a.prev.c[p], a.prev.v[p], 1.0f, acc);
+        } else {
+            const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
+            const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
+            const float ga = __builtin_fmaf(a.M[8], wz, __builtin_fmaf(a.M[7], wy, a.M[6] * wx));
+            if (ga > 0.0f) {
+                const float hx = al / ga, hy = be / ga;
+                if (hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height) { // (so the casts below are in range)
+                    const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
+                    const float fx = hx - x0, fy = hy - y0;
+                    const int ix = (int)x0, iy = (int)y0;
+                    // The four taps in two rounds of loads, so that a pixel waits for memory twice and not once per record: first
+                    // every tap's guide records, then the colour and variance records.  A tap outside the frame loads the nearest
+                    // pixel inside it (a valid address) and is refused; a refused tap's records are loaded and not used.
+                    size_t q[4];
+                    bool ok[4];
+                    dn4 g[4], pp[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int qx = ix + (t & 1), qy = iy + (t >> 1);
+                        ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
+                        const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
+                        const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
+                        q[t] = (size_t)cy * a.width + (size_t)cx;
+                        g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
+                    }
+                    dn4 c[4], v[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
+                        c[t] = a.prev.c[q[t]], v[t] = a.prev.v[q[t]];
+                    }
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
+                        if (ok[t]) ta_add(c[t], v[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
+                }
+            }
+        }
+        if (acc.B >= kTaMinWeight) {
+            const float hN = acc.N / acc.B;
+            const float Ns = hN + a.spp;
+            const float a0 = a.spp / Ns;
+            const float alpha = a0 < a.am ? a.am : a0;
+            const float k = 1.0f - alpha;
+            const float a2 = alpha * alpha, k2 = k * k;
+            const float hr = acc.Hr / acc.B, hg = acc.Hg / acc.B, hb = acc.Hb / acc.B;
+            or_ = __builtin_fmaf(alpha, cr - hr, hr);
+            og = __builtin_fmaf(alpha, cg - hg, hg);
+            ob = __builtin_fmaf(alpha, cb - hb, hb);
+            vr = __builtin_fmaf(a2, sr, k2 * (acc.Vr / acc.B));
+            vg = __builtin_fmaf(a2, sg, k2 * (acc.Vg / acc.B));
+            vb = __builtin_fmaf(a2, sb, k2 * (acc.Vb / acc.B));
+            No = Ns > a.nm ? a.nm : Ns;
+        }
+    }
+    a.next.c[p] = dn4{or_, og, ob, No};
+    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
+    a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
+    a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
+    a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
+    a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
+    if (a.len_out) a.len_out[p] = No;
+}
+
+// ---- host side: the launch (temporal.hpp owns the handle, the validation and the stream) ----------------------------------------
+inline void temporal_launch_step(hipStream_t st, const TemporalArgs& a, bool is_static) {
+    const dim3 grid = denoise_grid(a.width, a.height), block(256);
+    if (is_static) hipLaunchKernelGGL((temporal_step_kernel<true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((temporal_step_kernel<false>), grid, block, 0, st, a);
+}
+
+} // namespace rayz_dev

@@ -579,6 +579,100 @@ class Denoiser:
             pass
 
 
+class Temporal:
+    """Temporal accumulation for whole float32 frames of one size (`rayz_hip_temporal_*`): every `step` blends
+    the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
+    per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init()."""
+
+    def __init__(self, width: int, height: int, device: int | None = None):
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        self.width, self.height = int(width), int(height)
+        capi.check(self._lib, self._lib.rayz_hip_temporal_create(-1 if device is None else device, self.width, self.height,
+                                                                 C.byref(self._h)), "rayz_hip_temporal_create")
+        self._device = device if device is not None else _default_device
+        self._inflight = None  # the tensors of the last step: kept alive until the next step or close() (the kernel may still use them)
+
+    def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
+             stream: int = 0, **params):
+        """One frame: `rgb` and `var_rgb` ((height, width, 3) float32 on the handle's device: the frame and the variance of each
+        channel of its pixel means, `Progressive.noise_rgb()`), `gbuffer` (index, normal, point of a float32 camera query of the same
+        frame), the `camera` both were made with and the frame's samples per pixel.  Returns (out, var_out) — new tensors by
+        default; `out=rgb` / `var_out=var_rgb` step in place — and, with `length` True or a (height, width) float32 tensor, the
+        history length in samples as a third value.  `params`: the fields of RayzTemporalParams (alpha_min, n_max, normal_cos_min,
+        max_rel_dist); unnamed ones take capi.TEMPORAL_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
+        work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
+        import torch
+
+        unknown = set(params) - set(capi.TEMPORAL_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal parameter(s) {sorted(unknown)}; choose from {sorted(capi.TEMPORAL_DEFAULTS)}")
+        prm = capi.TemporalParams(**{**capi.TEMPORAL_DEFAULTS, **params})
+        frame = (self.height, self.width, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"]
+        tensors = [("rgb", rgb, torch.float32, frame), ("var_rgb", var_rgb, torch.float32, frame)]
+        for k in need:
+            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
+                            frame[:2] if k == "index" else frame))
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=dev)
+        if var_out is None:
+            var_out = torch.empty(frame, dtype=torch.float32, device=dev)
+        tensors += [("out", out, torch.float32, frame), ("var_out", var_out, torch.float32, frame)]
+        if length is True:
+            length = torch.empty(frame[:2], dtype=torch.float32, device=dev)
+        elif length is False:
+            length = None
+        if length is not None:
+            tensors.append(("length", length, torch.float32, frame[:2]))
+        for name, t, dtype, shape in tensors:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f"{name} must be a torch tensor in GPU memory")
+            if t.device.index != self._device:
+                raise ValueError(f"{name} is on cuda:{t.device.index}, the temporal handle on cuda:{self._device}")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        if not stream:
+            torch.cuda.synchronize(self._device)
+        o = capi.QueryOutputs()
+        for k in need:
+            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        rc = self._lib.rayz_hip_temporal_step(self._h, C.byref(prm), C.byref(camera), int(spp), C.c_void_p(rgb.data_ptr()),
+                                              C.c_void_p(var_rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
+                                              C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_temporal_step")
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length)
+        return (out, var_out) if length is None else (out, var_out, length)
+
+    def reset(self) -> None:
+        """Forgets the history: the next step is a first frame (`rayz_hip_temporal_reset`)."""
+        capi.check(self._lib, self._lib.rayz_hip_temporal_reset(self._h), "rayz_hip_temporal_reset")
+
+    def timing(self) -> float:
+        """Waits for the last step; its HIP-event time in ms (`rayz_hip_temporal_timing`)."""
+        ms = C.c_float()
+        capi.check(self._lib, self._lib.rayz_hip_temporal_timing(self._h, C.byref(ms)), "rayz_hip_temporal_timing")
+        return ms.value
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.rayz_hip_temporal_destroy(self._h)  # (waits for the handle's last step)
+            self._h = C.c_void_p()
+        self._inflight = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MultiScene:
     """The pool replicated on several GPUs of the node (`rayz_hip_multi_create`): one call renders the whole frame —
     rows dealt to the devices in interleaved tiles, one RCCL gather (or peer copies) to devices[0], host output."""

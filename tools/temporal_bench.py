@@ -1,0 +1,190 @@
+#!/usr/bin/env python3
+"""Temporal accumulation (rayz_hip_temporal_*) on an MI355X: what a step costs, against what, and what it buys.
+
+Config 3 at 1920x1080 under a camera that pans --pan pixels per frame (px_origin moved along px_du) over --frames frames of 16 spp,
+each from a tracked progressive handle with its own seed, in chunks of 2 samples (8 chunks: a variance estimate every frame), with
+its camera G-buffer and its per-channel variance; and a --ref-spp frame of every camera.  Everything is made from seeds; nothing
+is read from outside the tree.
+
+(a) Cost.  The step kernel by the handle's own HIP events (rayz_hip_temporal_timing), median [min, max] of --reps steps after
+    --warmup: a first frame (no history), a static step, a panned step; next to a device-to-device copy, timed with events in the
+    same process, that moves the step's COMPULSORY BYTES — the current colour, variance and guides in (52 B per pixel), one history
+    record in (64 B), the history, colour and variance out (88 B): 204 B per pixel, i.e. a copy of 102 B per pixel (read + write) —
+    and the ratio step / copy.
+(b) Quality.  Per frame, MSE against the --ref-spp frame of the same camera of: the raw frame, `run_guided` alone, the temporal
+    step alone, and the temporal step followed by `run_guided` — at the shipped defaults.
+(c) Coverage.  Per frame, the share of hit pixels that found history (length > spp).
+(d) The sweep the defaults are to be chosen from: alpha_min x max_rel_dist, the mean over the panned frames of (b)'s temporal and
+    temporal + guided MSE ratios to the raw frame, and of (c).
+
+    python tools/temporal_bench.py [--frames 16] [--pan 3] [--spp 16] [--ref-spp 1024] [--reps 100] [--warmup 10] [--width 1920] [--json FILE]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from rayz_amd import capi, render, tracer  # noqa: E402
+
+STEP_BYTES = 52 + 64 + 88  # per pixel: what a step must read and write (module docstring)
+
+
+def panned(cam, pixels):
+    c = capi.CameraDesc.from_buffer_copy(cam)
+    for j in range(3):
+        c.px_origin[j] = cam.px_origin[j] + pixels * cam.px_du[j]
+    return c
+
+
+def copy_ms(n_bytes, reps, warmup):
+    """Median [min, max] of an event-bracketed device copy of n_bytes (read) to n_bytes (written)."""
+    src = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+    dst = torch.empty(n_bytes, dtype=torch.uint8, device="cuda")
+    for _ in range(warmup):
+        dst.copy_(src)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        dst.copy_(src)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--pan", type=float, default=3.0, help="pixels per frame")
+    ap.add_argument("--spp", type=int, default=16)
+    ap.add_argument("--chunk-spp", type=int, default=2)
+    ap.add_argument("--ref-spp", type=int, default=1024)
+    ap.add_argument("--reps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--json", default=None, help="also write the figures to this file")
+    args = ap.parse_args()
+    render.init(0)
+    t = tracer.randomBouncing(args.width, -50, 50, seed=42)  # config 3
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=args.chunk_spp)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    ds = render.DeviceScene(sd)
+    res = {"size": f"{w}x{h}", "frames": args.frames, "pan_px": args.pan, "spp": args.spp, "chunk_spp": args.chunk_spp, "ref_spp": args.ref_spp,
+           "reps": args.reps, "step_bytes_per_pixel": STEP_BYTES}
+
+    # ---- the sequence: frame, variance, G-buffer and reference per camera ----------------------------------------------------
+    seq = []
+    for k in range(args.frames):
+        c = panned(cam, args.pan * k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed = 1000 + k
+        pr = ds.progressive(c, q, track_noise=True)
+        frame = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        while not pr.done:
+            pr.step(0, frame.data_ptr())
+        assert pr.chunks_done >= 2, "a frame needs at least 2 chunks for a variance estimate"
+        var = pr.noise_rgb()
+        trace_ms = pr.stats().kernel_ms
+        pr.close()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        q.samples_per_px, q.chunk_spp, q.seed = args.ref_spp, 0, 7
+        ref = torch.empty_like(frame)
+        torch.cuda.synchronize()
+        ds.render_into(c, q, ref.data_ptr())
+        ds.sync()
+        seq.append((c, frame, var, g, ref, trace_ms))
+        print(f"frame {k}: {args.spp} spp in chunks of {args.chunk_spp} ({trace_ms:.2f} ms of trace kernels), reference {args.ref_spp} spp", flush=True)
+    res["frame_trace_ms"] = statistics.median(s[5] for s in seq)
+    mse = lambda a, ref: float(((a.double() - ref.double()) ** 2).mean())  # noqa: E731
+
+    # ---- (a) cost -------------------------------------------------------------------------------------------------------------
+    cp = copy_ms(n * STEP_BYTES // 2, args.reps, args.warmup)
+    print(f"copy moving a step's compulsory bytes ({n * STEP_BYTES / 1e6:.1f} MB read + written): {cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}] "
+          f"({n * STEP_BYTES / cp[0] / 1e9:.2f} TB/s)", flush=True)
+    res["copy_ms"], res["copy_min"], res["copy_max"] = cp
+    tm = render.Temporal(w, h)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    length = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    res["cost"] = {}
+    for what in ("first", "static", "panned"):
+        ms = []
+        for r in range(args.warmup + args.reps):
+            tm.reset()
+            if what == "first":
+                tm.step(seq[0][1], seq[0][2], seq[0][3], seq[0][0], args.spp, out=out, var_out=vout, length=length)
+            else:
+                tm.step(seq[0][1], seq[0][2], seq[0][3], seq[0][0], args.spp, out=out, var_out=vout, length=length)
+                s = seq[0] if what == "static" else seq[1]
+                tm.step(s[1], s[2], s[3], s[0], args.spp, out=out, var_out=vout, length=length)
+            x = tm.timing()
+            if r >= args.warmup:
+                ms.append(x)
+        med = statistics.median(ms)
+        print(f"step kernel, {what:6s}: {med:.4f} ms [{min(ms):.4f}, {max(ms):.4f}] = {med / cp[0]:.2f} x the copy of its compulsory bytes "
+              f"({n * STEP_BYTES / med / 1e9:.2f} TB/s of them); {med / res['frame_trace_ms']:.4f} x the {args.spp}-spp frame's trace kernels", flush=True)
+        res["cost"][what] = {"ms": med, "min": min(ms), "max": max(ms), "ratio_to_copy": med / cp[0]}
+
+    # ---- (b), (c) at the defaults; (d) the sweep ---------------------------------------------------------------------------------
+    dn = render.Denoiser(w, h)
+    den = torch.empty_like(out)
+
+    def run(guided_too, **prm):
+        tm.reset()
+        rows = []
+        for k, (c, frame, var, g, ref, _) in enumerate(seq):
+            tm.step(frame, var, g, c, args.spp, out=out, var_out=vout, length=length, **prm)
+            torch.cuda.synchronize()
+            hit = g.index >= 0
+            row = {"frame": k, "mse_raw": mse(frame, ref), "mse_temporal": mse(out, ref),
+                   "found": float((length[hit] > args.spp).float().mean()) if bool(hit.any()) else 0.0}
+            if guided_too:
+                dn.run_guided(out, vout, g, out=den)
+                torch.cuda.synchronize()
+                row["mse_temporal_guided"] = mse(den, ref)
+            rows.append(row)
+        return rows
+
+    rows = run(True)
+    for row, (c, frame, var, g, ref, _) in zip(rows, seq):
+        dn.run_guided(frame, var, g, out=den)
+        torch.cuda.synchronize()
+        row["mse_guided"] = mse(den, ref)
+        r = row["mse_raw"]
+        print(f"frame {row['frame']:2d}: MSE raw {r:.4e}; guided alone x{row['mse_guided'] / r:.4f}; temporal alone x{row['mse_temporal'] / r:.4f}; "
+              f"temporal + guided x{row['mse_temporal_guided'] / r:.4f}; {row['found']:.4f} of the hit pixels found history", flush=True)
+    res["defaults"] = {"params": capi.TEMPORAL_DEFAULTS, "rows": rows}
+    res["sweep"] = []
+    for am in (0.0, 0.05, 0.1, 0.2):
+        for md in (0.01, 0.05, 0.2):
+            rr = run(True, alpha_min=am, max_rel_dist=md)[1:]
+            mean = lambda key: statistics.mean(x[key] / x["mse_raw"] for x in rr)  # noqa: E731
+            row = {"alpha_min": am, "max_rel_dist": md, "temporal": mean("mse_temporal"), "temporal_guided": mean("mse_temporal_guided"),
+                   "found": statistics.mean(x["found"] for x in rr), "last_temporal": rr[-1]["mse_temporal"] / rr[-1]["mse_raw"],
+                   "last_temporal_guided": rr[-1]["mse_temporal_guided"] / rr[-1]["mse_raw"]}
+            res["sweep"].append(row)
+            print(f"  alpha_min {am:g} max_rel_dist {md:g}: mean over frames 1.. of MSE / raw: temporal {row['temporal']:.4f}, temporal + guided "
+                  f"{row['temporal_guided']:.4f} (last frame {row['last_temporal']:.4f}, {row['last_temporal_guided']:.4f}); found {row['found']:.4f}",
+                  flush=True)
+    tm.close()
+    dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
