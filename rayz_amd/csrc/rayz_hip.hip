@@ -1272,5 +1272,6 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "known_answers.hpp"
 #include "multi_device.hpp"
 #include "query.hpp"
+#include "frame_handle.hpp"
 #include "denoiser.hpp"
 #include "temporal.hpp"

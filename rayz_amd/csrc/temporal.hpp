@@ -1,63 +1,20 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
-// temporal_kernel.hpp).
+// temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp).
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
-struct RayzTemporal {
-    uint32_t magic = 0;
-    int device = -1;
-    uint32_t width = 0, height = 0;
-    DevBuf<dn4> hist[2][4]; // ping-pong x {colour + length, variance, normal + index, point}: n_pixels records each
-    int cur = 0;            // the buffer the last step wrote: what the next step reads
+// buf: ping-pong x {colour + length, variance, normal + index, point}.  ev[0]: the step starts; ev[1]: it is done.
+struct RayzTemporal : FrameHandle<2 * 4, 2> {
+    static constexpr uint32_t kMagic = 0x544d5a52u;
+    static constexpr const char* kNoun = "temporal";
+    int cur = 0;            // the side of buf the last step wrote: what the next step reads
     bool has_history = false;
     RayzCameraDesc cam{};   // the last step's camera, with its M and from: what the next step projects with
     float M[9] = {}, from[3] = {};
-    DevEvent ev[2];         // ev[0]: the step starts; ev[1]: it is done
-    int last_ev = -1;       // the last event recorded, of a failed step too: what the next step and destroy wait for (-1: none yet)
     bool timed = false;     // the last step ran to its end: ev[0] .. ev[1] is its time
-    ~RayzTemporal() {
-        if (last_ev >= 0) { // (waits on the handle's own event, never on the caller's stream, which may be gone by now)
-            DeviceScope scope(device);
-            (void)hipEventSynchronize(ev[last_ev]);
-        }
-        magic = 0;
-    }
 };
 
 namespace {
-
-constexpr uint32_t kTemporalMagic = 0x544d5a52u;
-
-int temporal_free(RayzTemporal* tm) {
-    if (!tm) return RAYZ_OK;
-    if (tm->magic != kTemporalMagic) return fail(RAYZ_ERR_STATE, "not a temporal handle");
-    delete tm;
-    return RAYZ_OK;
-}
-
-int temporal_create(int device, uint32_t width, uint32_t height, RayzTemporal** out) {
-    if (!out) return fail(RAYZ_ERR_BAD_ARG, "out handle pointer is null");
-    *out = nullptr;
-    if (!width || !height) return fail(RAYZ_ERR_BAD_ARG, "temporal frame %ux%u: zero size", width, height);
-    if ((uint64_t)width * height > RAYZ_DENOISE_MAX_PIXELS)
-        return fail(RAYZ_ERR_BAD_ARG, "temporal frame %ux%u: more than RAYZ_DENOISE_MAX_PIXELS pixels", width, height);
-    if (device < 0) {
-        hipStream_t unused;
-        RAYZ_TRY(default_device(device, unused));
-    } else RAYZ_TRY(ensure_ctx_locked(device));
-    DeviceScope scope(device);
-    auto tm = std::make_unique<RayzTemporal>();
-    tm->magic = kTemporalMagic, tm->device = device, tm->width = width, tm->height = height;
-    hipError_t e = hipSuccess;
-    for (auto& side : tm->hist)
-        for (DevBuf<dn4>& b : side)
-            if (e == hipSuccess) e = b.alloc((size_t)width * height);
-    for (DevEvent& ev : tm->ev)
-        if (e == hipSuccess) e = ev.create();
-    if (e != hipSuccess) return hip_fail(e, "temporal buffers");
-    *out = tm.release();
-    return RAYZ_OK;
-}
 
 // The host part of a step (§4.15), f64, every operation written out: M = the inverse of the matrix with columns px_du, px_dv and
 // px_origin − look_from, each entry rounded once to f32, and look_from in f32.  False: det is zero or not finite.
@@ -95,28 +52,21 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     if (!spp || spp > (1u << 24)) return fail(RAYZ_ERR_BAD_ARG, "temporal spp %u: must lie in 1 .. 2^24 (it is used as f32)", spp);
     if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
     if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
-    if (!g) return fail(RAYZ_ERR_BAD_ARG, "temporal: null G-buffer");
-    if (!g->index || !g->normal || !g->point) return fail(RAYZ_ERR_BAD_ARG, "temporal: the G-buffer needs index, normal and point");
+    RAYZ_TRY(frame_gbuffer_check("temporal", g));
     if (!cam) return fail(RAYZ_ERR_BAD_ARG, "temporal: null camera");
     float M[9], from[3];
     if (!temporal_camera_matrix(cam, M, from))
         return fail(RAYZ_ERR_BAD_ARG, "temporal: the camera's px_du, px_dv and px_origin - look_from span no volume (det is 0 or not finite)");
-    if (!tm || tm->magic != kTemporalMagic) return fail(RAYZ_ERR_STATE, "not a temporal handle");
-    hipStream_t st = stream_or(stream_arg, nullptr);
-    if (!st) { // (the device's own stream, which has to exist then; a caller's stream is taken as it is)
-        std::lock_guard<std::mutex> lock(g_mu);
-        if (!g_ctx[tm->device].ok) return fail(RAYZ_ERR_NO_DEVICE, "device %d is not initialised (rayz_hip_init / shutdown order)", tm->device);
-        st = g_ctx[tm->device].stream;
-    }
+    RAYZ_TRY(frame_handle_check(tm));
+    hipStream_t st;
+    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
     DeviceScope scope(tm->device);
-    // one step in flight per handle: this step reads what the previous one wrote, so its stream first waits (on the device) for the
-    // previous step's last event — whichever stream that was on, and whether or not that stream still exists
-    if (tm->last_ev >= 0) HIP_TRY(hipStreamWaitEvent(st, tm->ev[tm->last_ev], 0));
+    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (this step reads what the previous one wrote)
     const bool is_static = tm->has_history && std::memcmp(cam, &tm->cam, sizeof(RayzCameraDesc)) == 0;
     const float r = (float)p.max_rel_dist;
     TemporalArgs a{};
     a.rgb = d_in, a.var = d_var, a.index = g->index, a.normal = (const float*)g->normal, a.point = (const float*)g->point;
-    DevBuf<dn4>*prev = tm->hist[tm->cur], *next = tm->hist[tm->cur ^ 1];
+    const DevBuf<dn4>*prev = tm->buf + 4 * tm->cur, *next = tm->buf + 4 * (tm->cur ^ 1);
     a.prev = TemporalHistory{prev[0], prev[1], prev[2], prev[3]};
     a.next = TemporalHistory{next[0], next[1], next[2], next[3]};
     a.rgb_out = d_out, a.var_out = d_var_out, a.len_out = d_len_out;
@@ -125,12 +75,9 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     std::memcpy(a.from, tm->from, sizeof(a.from));
     a.spp = (float)spp, a.am = (float)p.alpha_min, a.nm = (float)p.n_max, a.cm = (float)p.normal_cos_min, a.r2 = r * r;
     tm->timed = false; // (a step that fails half-way leaves no timing)
-    HIP_TRY(hipEventRecord(tm->ev[0], st));
-    tm->last_ev = 0;
+    RAYZ_TRY(frame_handle_record(tm, 0, st));
     temporal_launch_step(st, a, is_static);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(tm->ev[1], st));
-    tm->last_ev = 1;
+    RAYZ_TRY(frame_handle_launched(tm, 1, st));
     // the step is enqueued: the handle now describes the history it leaves
     tm->cur ^= 1, tm->has_history = true, tm->cam = *cam, tm->timed = true;
     std::memcpy(tm->M, M, sizeof(M));
@@ -139,13 +86,13 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
 }
 
 int temporal_reset(RayzTemporal* tm) {
-    if (!tm || tm->magic != kTemporalMagic) return fail(RAYZ_ERR_STATE, "not a temporal handle");
+    RAYZ_TRY(frame_handle_check(tm));
     tm->has_history = false; // (the buffers keep their bytes; no step reads them before it has written them)
     return RAYZ_OK;
 }
 
 int temporal_timing(RayzTemporal* tm, float* ms) {
-    if (!tm || tm->magic != kTemporalMagic) return fail(RAYZ_ERR_STATE, "not a temporal handle");
+    RAYZ_TRY(frame_handle_check(tm));
     if (!tm->timed) return fail(RAYZ_ERR_STATE, "no temporal step to time");
     DeviceScope scope(tm->device);
     HIP_TRY(hipEventSynchronize(tm->ev[1]));
@@ -158,7 +105,7 @@ int temporal_timing(RayzTemporal* tm, float* ms) {
 extern "C" {
 
 int rayz_hip_temporal_create(int device, uint32_t width, uint32_t height, RayzTemporal** out) {
-    return guarded([&] { return temporal_create(device, width, height, out); });
+    return guarded([&] { return frame_handle_create(device, width, height, out); });
 }
 
 int rayz_hip_temporal_step(RayzTemporal* tm, const RayzTemporalParams* params_or_null, const RayzCameraDesc* camera, uint32_t spp,
@@ -179,7 +126,7 @@ int rayz_hip_temporal_timing(RayzTemporal* tm, float* ms) {
 }
 
 int rayz_hip_temporal_destroy(RayzTemporal* tm) {
-    return guarded([&] { return temporal_free(tm); });
+    return guarded([&] { return frame_handle_free(tm); });
 }
 
 } // extern "C"

@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "denoise.hpp" // dn4, dn_dot, the tile and its grid
+#include "denoise.hpp" // dn4, dn_dot, dn_clamp_var, the tile and its grid
 
 namespace rayz_dev {
 
@@ -73,15 +73,13 @@ __device__ __forceinline__ void ta_add(const dn4 c, const dn4 v, float b, TaAcc&
     acc.N = __builtin_fmaf(b, c.w, acc.N);
 }
 
-__device__ __forceinline__ float ta_clamp_var(float t) { return !(t < kDnVarCap) ? kDnVarCap : (t > 0.0f ? t : 0.0f); } // §4.13's pack clamp
-
 template <bool STATIC> __global__ __launch_bounds__(256) void temporal_step_kernel(const TemporalArgs a) {
     const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
     const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
     if (x >= (int)a.width || y >= (int)a.height) return;
     const size_t p = (size_t)y * a.width + (size_t)x;
     const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
-    const float sr = ta_clamp_var(a.var[3 * p]), sg = ta_clamp_var(a.var[3 * p + 1]), sb = ta_clamp_var(a.var[3 * p + 2]);
+    const float sr = dn_clamp_var(a.var[3 * p]), sg = dn_clamp_var(a.var[3 * p + 1]), sb = dn_clamp_var(a.var[3 * p + 2]);
     const int32_t id = a.index[p];
     const float nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
     const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];

@@ -54,6 +54,87 @@ def render_host(scene: capi.SceneDesc, camera: capi.CameraDesc, params: capi.Ren
     return out, st
 
 
+class _Handle:
+    """Owns a library handle: `_h`, `close()` and `__del__`.  A class names the library function that destroys its handle (and waits
+    for the handle's last work) in `_destroy`."""
+
+    _destroy = None
+    _h = None
+
+    def close(self) -> None:
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+        self._inflight = None  # (tensors a handle kept alive for its last call)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _check_tensor(name, t, dtype, shape, device, owner) -> None:
+    """`t` is a contiguous torch tensor of `dtype` and `shape` in the memory of GPU `device`, where `owner` ("the denoiser") lives."""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a torch tensor in GPU memory")
+    if t.device.index != device:
+        raise ValueError(f"{name} is on cuda:{t.device.index}, {owner} on cuda:{device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _params(struct, defaults, given, what):
+    """`struct(**defaults)` with the fields `given` names replaced; `what` ("denoise") names the parameters in the refusal."""
+    unknown = set(given) - set(defaults)
+    if unknown:
+        raise ValueError(f"unknown {what} parameter(s) {sorted(unknown)}; choose from {sorted(defaults)}")
+    return struct(**{**defaults, **given})
+
+
+def _check_frame_tensors(owner, device, frame, inputs, gbuffer, need, outputs) -> None:
+    """A frame filter's tensors in argument order: the float32 `inputs` [(name, tensor)] shaped `frame`, the guides `need` names (index
+    is int32 (height, width), the others float32 frames) and the float32 `outputs` [(name, tensor, shape)], a None among them not
+    being asked for."""
+    import torch
+
+    tensors = [(name, t, torch.float32, frame) for name, t in inputs]
+    tensors += [(f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32, frame[:2] if k == "index" else frame)
+                for k in need]
+    tensors += [(name, t, torch.float32, shape) for name, t, shape in outputs if t is not None]
+    for t in tensors:
+        _check_tensor(*t, device, owner)
+
+
+def _gbuffer_pointers(gbuffer, need) -> capi.QueryOutputs:
+    o = capi.QueryOutputs()
+    for k in need:
+        setattr(o, k, getattr(gbuffer, k).data_ptr())
+    return o
+
+
+def _stream_prologue(stream: int, device: int) -> None:
+    import torch
+
+    if not stream:  # the library's stream does not order itself after torch's
+        torch.cuda.synchronize(device)
+
+
+def _optional_out(out, shape, device):
+    """The optional-output convention: True for a new float32 tensor of `shape`, False for none, or the caller's tensor."""
+    import torch
+
+    if out is True:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    return None if out is False else out
+
+
 QUERY_OUTPUTS = ("index", "t", "point", "normal", "front_face", "material", "albedo")
 
 
@@ -96,8 +177,10 @@ class QueryResult:
         return o
 
 
-class DeviceScene:
+class DeviceScene(_Handle):
     """A pool resident in HBM (`rayz_hip_scene_create`; `device` binds it to that HIP ordinal now)."""
+
+    _destroy = "rayz_hip_scene_destroy"  # (waits for the scene's last launch)
 
     def __init__(self, scene: capi.SceneDesc, device: int | None = None):
         self._lib = capi.load()
@@ -218,22 +301,12 @@ class DeviceScene:
         self._inflight = None
         return st
 
-    def close(self) -> None:
-        if self._h:
-            self._lib.rayz_hip_scene_destroy(self._h)  # (waits for the scene's last launch)
-            self._h = C.c_void_p()
-        self._inflight = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Progressive:
+class Progressive(_Handle):
     """One frame rendered in passes (`rayz_hip_progressive_*`): every `step` adds whole chunks of the chunk schedule and may
     write the frame so far; the last one writes the one-shot frame bit for bit.  Close it before its scene."""
+
+    _destroy = "rayz_hip_progressive_destroy"  # (waits for the last pass and the last evaluation)
 
     def __init__(self, scene: DeviceScene, camera: capi.CameraDesc, params: capi.RenderParams, track_noise: bool = False,
                  adaptive: bool = False, min_chunks: int | None = None):
@@ -262,10 +335,7 @@ class Progressive:
         return capi.NoiseParams(d["rel_error"] if rel_error is None else rel_error, d["mean_floor"] if mean_floor is None else mean_floor)
 
     def _stream_prologue(self, stream: int) -> None:
-        import torch
-
-        if not stream:  # the library's stream does not order itself after torch's
-            torch.cuda.synchronize(self._scene.device)
+        _stream_prologue(stream, self._scene.device)
 
     def noise(self, rel_error: float | None = None, mean_floor: float | None = None, var: bool = False, rel2: bool = False,
               summary: bool = True, stream: int = 0):
@@ -322,14 +392,7 @@ class Progressive:
         `max_unconverged_fraction` of the pixels are unconverged or the schedule ends (`done` tells which).  `out`: an optional
         torch tensor (rows_in_shard, width, 3) of the handle's precision on the scene's device that receives the frame it stopped
         at.  Blocks; returns the last summary."""
-        import torch
-
-        if out is not None:
-            want = torch.float64 if self.f64 else torch.float32
-            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self._scene.device:
-                raise ValueError(f"out must be a torch tensor on cuda:{self._scene.device}")
-            if out.dtype != want or tuple(out.shape) != self.shape + (3,) or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous {want} tensor shaped {self.shape + (3,)}")
+        self._check_out(out)
         self._stream_prologue(stream)
         prm = self._noise_params(rel_error, mean_floor)
         sm = capi.NoiseSummary()
@@ -438,23 +501,13 @@ class Progressive:
         """Counters summed over the passes so far (waits for them)."""
         return self._info(total=True)[3]
 
-    def close(self) -> None:
-        if self._h:
-            self._lib.rayz_hip_progressive_destroy(self._h)  # (waits for the last pass and the last evaluation)
-            self._h = C.c_void_p()
-        self._inflight = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Denoiser:
+class Denoiser(_Handle):
     """A G-buffer-guided à-trous filter for whole float32 frames of one size (`rayz_hip_denoiser_*`):
     `run(frame, scene.gbuffer(camera, params))` returns the filtered frame; `run_guided(frame, progressive.noise_rgb(), gbuffer)`
     also weighs every pixel by its own noise estimate (§4.13).  `device` None: the default device of init()."""
+
+    _destroy = "rayz_hip_denoiser_destroy"  # (waits for the handle's last run)
 
     def __init__(self, width: int, height: int, device: int | None = None):
         self._lib = capi.load()
@@ -465,43 +518,30 @@ class Denoiser:
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
 
+    def _checked(self, prm, inputs, gbuffer, out, var_out):
+        """The tensor checks of a run, in argument order: the (name, tensor) `inputs`, the guides `prm.flags` asks for, `out` (None: a
+        new tensor) and the optional `var_out`.  Returns (out, var_out or None, the guides' names)."""
+        import torch
+
+        frame = (self.height, self.width, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=dev)
+        var_out = _optional_out(var_out, frame[:2], dev)
+        _check_frame_tensors("the denoiser", self._device, frame, inputs, gbuffer, need, [("out", out, frame), ("var_out", var_out, frame[:2])])
+        return out, var_out, need
+
     def run(self, rgb, gbuffer: "QueryResult", out=None, stream: int = 0, **params):
         """Filters `rgb` ((height, width, 3) float32 on the handle's device) guided by `gbuffer` (index, normal, point and — unless
         flags drops DENOISE_ALBEDO — albedo of a float32 camera query of the same frame) into `out` (default: a new tensor;
         `out=rgb` filters in place).  `params`: the fields of RayzDenoiseParams (levels, normal_power_log2, flags, sigma_color,
         sigma_plane); unnamed ones take capi.DENOISE_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
         work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
-        import torch
-
-        unknown = set(params) - set(capi.DENOISE_DEFAULTS)
-        if unknown:
-            raise ValueError(f"unknown denoise parameter(s) {sorted(unknown)}; choose from {sorted(capi.DENOISE_DEFAULTS)}")
-        prm = capi.DenoiseParams(**{**capi.DENOISE_DEFAULTS, **params})
-        frame = (self.height, self.width, 3)
-        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
-        tensors = [("rgb", rgb, torch.float32, frame)]
-        for k in need:
-            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
-                            frame[:2] if k == "index" else frame))
-        if out is None:
-            out = torch.empty(frame, dtype=torch.float32, device=torch.device("cuda", self._device))
-        tensors.append(("out", out, torch.float32, frame))
-        for name, t, dtype, shape in tensors:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{name} must be a torch tensor in GPU memory")
-            if t.device.index != self._device:
-                raise ValueError(f"{name} is on cuda:{t.device.index}, the denoiser on cuda:{self._device}")
-            if t.dtype != dtype:
-                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        if not stream:
-            torch.cuda.synchronize(self._device)
-        o = capi.QueryOutputs()
-        for k in need:
-            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        prm = _params(capi.DenoiseParams, capi.DENOISE_DEFAULTS, params, "denoise")
+        out, _, need = self._checked(prm, [("rgb", rgb)], gbuffer, out, False)
+        _stream_prologue(stream, self._device)
+        o = _gbuffer_pointers(gbuffer, need)
         rc = self._lib.rayz_hip_denoiser_run(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(stream or None))
         capi.check(self._lib, rc, "rayz_hip_denoiser_run")
@@ -515,44 +555,10 @@ class Denoiser:
         demodulated colour; then the call returns (out, var_out).  `params`: the fields of RayzDenoiseGuidedParams (levels,
         normal_power_log2, flags, sigma_color — in standard deviations —, sigma_plane, var_floor); unnamed ones take
         capi.DENOISE_GUIDED_DEFAULTS."""
-        import torch
-
-        unknown = set(params) - set(capi.DENOISE_GUIDED_DEFAULTS)
-        if unknown:
-            raise ValueError(f"unknown denoise parameter(s) {sorted(unknown)}; choose from {sorted(capi.DENOISE_GUIDED_DEFAULTS)}")
-        prm = capi.DenoiseGuidedParams(**{**capi.DENOISE_GUIDED_DEFAULTS, **params})
-        frame = (self.height, self.width, 3)
-        dev = torch.device("cuda", self._device)
-        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
-        tensors = [("rgb", rgb, torch.float32, frame), ("var_rgb", var_rgb, torch.float32, frame)]
-        for k in need:
-            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
-                            frame[:2] if k == "index" else frame))
-        if out is None:
-            out = torch.empty(frame, dtype=torch.float32, device=dev)
-        tensors.append(("out", out, torch.float32, frame))
-        if var_out is True:
-            var_out = torch.empty(frame[:2], dtype=torch.float32, device=dev)
-        elif var_out is False:
-            var_out = None
-        if var_out is not None:
-            tensors.append(("var_out", var_out, torch.float32, frame[:2]))
-        for name, t, dtype, shape in tensors:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{name} must be a torch tensor in GPU memory")
-            if t.device.index != self._device:
-                raise ValueError(f"{name} is on cuda:{t.device.index}, the denoiser on cuda:{self._device}")
-            if t.dtype != dtype:
-                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        if not stream:
-            torch.cuda.synchronize(self._device)
-        o = capi.QueryOutputs()
-        for k in need:
-            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        prm = _params(capi.DenoiseGuidedParams, capi.DENOISE_GUIDED_DEFAULTS, params, "denoise")
+        out, var_out, need = self._checked(prm, [("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, out, var_out)
+        _stream_prologue(stream, self._device)
+        o = _gbuffer_pointers(gbuffer, need)
         rc = self._lib.rayz_hip_denoiser_run_guided(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()),
                                                     C.byref(o), C.c_void_p(out.data_ptr()),
                                                     C.c_void_p(var_out.data_ptr() if var_out is not None else None), C.c_void_p(stream or None))
@@ -566,23 +572,13 @@ class Denoiser:
         capi.check(self._lib, self._lib.rayz_hip_denoiser_timing(self._h, C.byref(n), ms, 9), "rayz_hip_denoiser_timing")
         return ms[0], [ms[1 + l] for l in range(n.value)]
 
-    def close(self) -> None:
-        if self._h:
-            self._lib.rayz_hip_denoiser_destroy(self._h)  # (waits for the handle's last run)
-            self._h = C.c_void_p()
-        self._inflight = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Temporal:
+class Temporal(_Handle):
     """Temporal accumulation for whole float32 frames of one size (`rayz_hip_temporal_*`): every `step` blends
     the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
     per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init()."""
+
+    _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
     def __init__(self, width: int, height: int, device: int | None = None):
         self._lib = capi.load()
@@ -604,44 +600,19 @@ class Temporal:
         work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
         import torch
 
-        unknown = set(params) - set(capi.TEMPORAL_DEFAULTS)
-        if unknown:
-            raise ValueError(f"unknown temporal parameter(s) {sorted(unknown)}; choose from {sorted(capi.TEMPORAL_DEFAULTS)}")
-        prm = capi.TemporalParams(**{**capi.TEMPORAL_DEFAULTS, **params})
+        prm = _params(capi.TemporalParams, capi.TEMPORAL_DEFAULTS, params, "temporal")
         frame = (self.height, self.width, 3)
         dev = torch.device("cuda", self._device)
         need = ["index", "normal", "point"]
-        tensors = [("rgb", rgb, torch.float32, frame), ("var_rgb", var_rgb, torch.float32, frame)]
-        for k in need:
-            tensors.append((f"gbuffer.{k}", getattr(gbuffer, k), torch.int32 if k == "index" else torch.float32,
-                            frame[:2] if k == "index" else frame))
         if out is None:
             out = torch.empty(frame, dtype=torch.float32, device=dev)
         if var_out is None:
             var_out = torch.empty(frame, dtype=torch.float32, device=dev)
-        tensors += [("out", out, torch.float32, frame), ("var_out", var_out, torch.float32, frame)]
-        if length is True:
-            length = torch.empty(frame[:2], dtype=torch.float32, device=dev)
-        elif length is False:
-            length = None
-        if length is not None:
-            tensors.append(("length", length, torch.float32, frame[:2]))
-        for name, t, dtype, shape in tensors:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ValueError(f"{name} must be a torch tensor in GPU memory")
-            if t.device.index != self._device:
-                raise ValueError(f"{name} is on cuda:{t.device.index}, the temporal handle on cuda:{self._device}")
-            if t.dtype != dtype:
-                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{name} must be contiguous")
-        if not stream:
-            torch.cuda.synchronize(self._device)
-        o = capi.QueryOutputs()
-        for k in need:
-            setattr(o, k, getattr(gbuffer, k).data_ptr())
+        length = _optional_out(length, frame[:2], dev)
+        _check_frame_tensors("the temporal handle", self._device, frame, [("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, need,
+                             [("out", out, frame), ("var_out", var_out, frame), ("length", length, frame[:2])])
+        _stream_prologue(stream, self._device)
+        o = _gbuffer_pointers(gbuffer, need)
         rc = self._lib.rayz_hip_temporal_step(self._h, C.byref(prm), C.byref(camera), int(spp), C.c_void_p(rgb.data_ptr()),
                                               C.c_void_p(var_rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
                                               C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
@@ -660,22 +631,12 @@ class Temporal:
         capi.check(self._lib, self._lib.rayz_hip_temporal_timing(self._h, C.byref(ms)), "rayz_hip_temporal_timing")
         return ms.value
 
-    def close(self) -> None:
-        if self._h:
-            self._lib.rayz_hip_temporal_destroy(self._h)  # (waits for the handle's last step)
-            self._h = C.c_void_p()
-        self._inflight = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MultiScene:
+class MultiScene(_Handle):
     """The pool replicated on several GPUs of the node (`rayz_hip_multi_create`): one call renders the whole frame —
     rows dealt to the devices in interleaved tiles, one RCCL gather (or peer copies) to devices[0], host output."""
+
+    _destroy = "rayz_hip_multi_destroy"
 
     def __init__(self, scene: capi.SceneDesc, devices, transport: int = capi.GATHER_RCCL):
         self._lib = capi.load()
@@ -716,17 +677,6 @@ class MultiScene:
         g, f = C.c_double(), C.c_double()
         capi.check(self._lib, self._lib.rayz_hip_multi_timing(self._h, C.byref(g), C.byref(f)), "rayz_hip_multi_timing")
         return g.value, f.value
-
-    def close(self) -> None:
-        if self._h:
-            self._lib.rayz_hip_multi_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def kat(op: int, records, precision: int = capi.PRECISION_F32) -> np.ndarray:

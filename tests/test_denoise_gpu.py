@@ -63,17 +63,18 @@ def test_device_equals_the_mirror_on_small_frames(gpu, w, h):
 
 def test_every_staging_form_gives_the_same_bits(gpu):
     """Every staging setting on one input: one image (the forms differ in where a tap is fetched from, nothing else),
-    at a size with partial tiles on both edges, for the other parameter values too (normal_power_log2 0 and 16, levels = 0 -> 5)."""
-    w, h = 131, 77
-    rgb, index, normal, point, albedo = synthetic(w, h, 5)
-    g = to_gbuffer(index, normal, point, albedo)
-    dn = render.Denoiser(w, h)
-    for npl, levels in ((0, 0), (16, 3), (6, 5)):
-        want = denoise_ref.denoise(rgb, index, normal, point, albedo, levels=levels, normal_power_log2=npl)
-        for st in STAGING:
-            got = gpu_run(dn, rgb, g, False, staging=st, levels=levels, normal_power_log2=npl)
-            assert_images_equal(got, want, f"npl={npl} levels={levels} staging={st}")
-    dn.close()
+    at a size with partial tiles on both edges, for the other parameter values too (normal_power_log2 0 and 16, levels = 0 -> 5);
+    and, with 5 levels, at 5x3 (smaller than every halo) and 45x23 (no tile multiple; a stride-4 halo crosses the frame on all sides)."""
+    for w, h, states in ((131, 77, ((0, 0), (16, 3), (6, 5))), (5, 3, ((6, 5),)), (45, 23, ((6, 5),))):
+        rgb, index, normal, point, albedo = synthetic(w, h, 5)
+        g = to_gbuffer(index, normal, point, albedo)
+        dn = render.Denoiser(w, h)
+        for npl, levels in states:
+            want = denoise_ref.denoise(rgb, index, normal, point, albedo, levels=levels, normal_power_log2=npl)
+            for st in STAGING:
+                got = gpu_run(dn, rgb, g, False, staging=st, levels=levels, normal_power_log2=npl)
+                assert_images_equal(got, want, f"{w}x{h} npl={npl} levels={levels} staging={st}")
+        dn.close()
 
 
 def test_device_equals_the_mirror_at_1920x1080(gpu):

@@ -77,20 +77,23 @@ def test_device_equals_the_mirror(gpu, w, h):
 
 
 def test_every_staging_form_gives_the_same_bits(gpu):
-    w, h = 97, 41
-    rgb, index, normal, point, albedo = synthetic(w, h, 9741)
-    var = guided_variance(rgb, 11)
-    g = to_gbuffer(index, normal, point, albedo)
-    dn = render.Denoiser(w, h)
-    want = denoise_guided_ref.denoise(rgb, var, index, normal, point, albedo, **capi.DENOISE_GUIDED_DEFAULTS)
-    try:
-        for st in STAGING:
-            got, gv = gpu_run(dn, rgb, var, g, staging=st)
-            same_bits(got, want[0], f"staging={st}")
-            same_bits(gv, want[1], f"staging={st} (variance)")
-    finally:
-        render.debug_set(capi.DEBUG_DENOISE_LDS_STRIDE, -1)
-    dn.close()
+    """Every staging setting and the built-in choice on one input, 5 levels: at 97x41, at 5x3 (smaller than every halo) and at 45x23
+    (no tile multiple; a stride-4 halo crosses the frame on all sides)."""
+    assert capi.DENOISE_GUIDED_DEFAULTS["levels"] == 5
+    for w, h in ((97, 41), (5, 3), (45, 23)):
+        rgb, index, normal, point, albedo = synthetic(w, h, 9741)
+        var = guided_variance(rgb, 11)
+        g = to_gbuffer(index, normal, point, albedo)
+        dn = render.Denoiser(w, h)
+        want = denoise_guided_ref.denoise(rgb, var, index, normal, point, albedo, **capi.DENOISE_GUIDED_DEFAULTS)
+        try:
+            for st in (-1,) + STAGING:
+                got, gv = gpu_run(dn, rgb, var, g, staging=st)
+                same_bits(got, want[0], f"{w}x{h} staging={st}")
+                same_bits(gv, want[1], f"{w}x{h} staging={st} (variance)")
+        finally:
+            render.debug_set(capi.DEBUG_DENOISE_LDS_STRIDE, -1)
+        dn.close()
 
 
 def test_device_gives_the_hand_derived_answers(gpu):

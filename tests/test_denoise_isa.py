@@ -1,5 +1,6 @@
-"""The denoiser's kernels as compiled for gfx950 (cross-compiled, as tests/test_isa_invariants.py does): no vector register spilled,
-no scratch, static LDS within 64 KiB, the records fetched with 16-byte loads — and names that stay out of the trace kernels' count."""
+"""The denoiser's kernels of both modes as compiled for gfx950 (cross-compiled, as tests/test_isa_invariants.py does): no vector
+register spilled, no scratch, static LDS within 64 KiB, the records fetched with 16-byte loads — and names that stay out of the trace
+kernels' count."""
 import os
 import re
 import shutil
@@ -29,8 +30,9 @@ def test_denoise_kernels_codegen(tmp_path):
         if "name" in fields:
             meta[fields["name"]] = fields
     dn = {k: v for k, v in meta.items() if "denoise_" in k}
-    # pack + direct x {level, last} + LDS x {stride 1, 2, 4} x {level, last}
-    assert len(dn) == 1 + 2 + 6, sorted(dn)
+    # {plain, guided} x (pack + direct x {level, last} + LDS x {stride 1, 2, 4} x {level, last})
+    assert len(dn) == 2 * (1 + 2 + 6), sorted(dn)
+    assert sum("_pack_" in k for k in dn) == 2 and sum("_direct_" in k for k in dn) == 4 and sum("_lds_" in k for k in dn) == 12, sorted(dn)
     lds_sizes = set()
     for name, f in dn.items():
         assert "trace_kernel" not in name
