@@ -512,7 +512,7 @@ typedef enum RayzKatOp {
     RAYZ_KAT_BACKGROUND = 7,  /* in: dir[0..2]                                     out: colour[0..2]    src/renderer.zig:124-125 */
     RAYZ_KAT_TRIANGLE_HIT = 8,/* in: v0[0..2] v1[3..5] v2[6..8] origin[9..11] dir[12..14] tmin[15] tmax[16]
                                  out: hit[0] t[1] passed_filter[2]                 build-defined */
-    RAYZ_KAT_SCAN_DISCS = 9   /* one 4-sphere block of the flat list's scan streams, as the SCAN LOOP evaluates it (packed FMAs,
+    RAYZ_KAT_SCAN_DISCS = 9,  /* one 4-sphere block of the flat list's scan streams, as the SCAN LOOP evaluates it (packed FMAs,
                                  two spheres per instruction; the values are f32 for both precisions):
                                  in: cx[0..3] cy[4..7] cz[8..11] radius[12..15] (padded and squared by the library as the scene
                                      upload does) vy[16..19] origin[20..22] dir[23..25] time[26] class[27]: 0 static, 1 y-moving
@@ -524,6 +524,12 @@ typedef enum RayzKatOp {
                                  out: r2 - p1^2 - p2^2 per sphere [0..3] (>= 0: candidate; the plane form for classes 2 / 3), the
                                       same value from the general-velocity form the BVH leaves use [4..7], the padded r2 (f32) the
                                       library used [8..11] if want_r2, else 0              src/geom.zig:40-50, DESIGN.md 4.3 */
+    RAYZ_KAT_BUCKET_DISCS = 10 /* one 4-sphere block of a SPEED BUCKET of a y-moving plane run, as the scan loop evaluates it
+                                 (ScanGroup<float, 5>: the static plane form, the bucket's speed folded into K2):
+                                 in: cx[0..3] cy[4] (the run's height) cz[8..11] radius[12..15] vy[16..19] origin[20..22]
+                                     dir[23..25] time[26] v0[27] (the bucket's speed; finite, RAYZ_ERR_BAD_ARG otherwise)
+                                 out: r2b - p1^2 - p2^2 per sphere [0..3], K2 = fm(v0, time * e2y, fm(cy, e2y, k2)) [4], the
+                                      padded r2b (f32) of radius + |vy - v0| the library used [8..11]      DESIGN.md 4.3 */
 } RayzKatOp;
 #define RAYZ_KAT_IN_STRIDE 48
 #define RAYZ_KAT_OUT_STRIDE 12

@@ -20,7 +20,7 @@ GATHER_ALLOW_DUPLICATE_DEVICES = 0x100  # flag bit, peer-copy only (tests on a o
  DEBUG_LDS_PAD, DEBUG_BVH_TOP_ORDER, DEBUG_BVH_NODES, DEBUG_BVH_SPLIT, DEBUG_BVHX, DEBUG_CHUNK_CAP,
  DEBUG_DENOISE_LDS_STRIDE) = range(13)
 (KAT_REFRACT, KAT_REFLECTANCE, KAT_GET_RAY, KAT_BOX_HIT, KAT_SPHERE_HIT, KAT_SCATTER, KAT_CHECKER, KAT_BACKGROUND,
- KAT_TRIANGLE_HIT, KAT_SCAN_DISCS) = range(10)
+ KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS) = range(11)
 KAT_IN_STRIDE, KAT_OUT_STRIDE = 48, 12
 
 OK = 0

@@ -90,7 +90,7 @@ int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint3
 // ---- known answers: the kernel's device functions on caller inputs ---------------------------------------------
 int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, double* out) {
     return guarded([&] {
-        if (op > RAYZ_KAT_SCAN_DISCS) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
+        if (op > RAYZ_KAT_BUCKET_DISCS) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
         if (precision > RAYZ_PRECISION_F64) return fail(RAYZ_ERR_BAD_ARG, "bad precision %u", precision);
         if (!n) return (int)RAYZ_OK;
         if (!in || !out) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
@@ -150,6 +150,20 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
                 }
                 for (int k = 0; k < 4; ++k)
                     a[28 + k] = precision == RAYZ_PRECISION_F32 ? (double)pad_radius2_scan<float>(q[k], S) : (double)pad_radius2_scan<double>(q[k], S);
+            }
+            if (op == RAYZ_KAT_BUCKET_DISCS) { // the padded squares a speed bucket of speed v0 would hold for these four spheres
+                if (!std::isfinite(a[27])) return fail(RAYZ_ERR_BAD_ARG, "record %u: v0 = %g is not finite", i, a[27]);
+                double S = norm3(a + 20);
+                RayzSphere q[4] = {};
+                for (int k = 0; k < 4; ++k) {
+                    q[k].center[0] = a[k], q[k].center[1] = a[4], q[k].center[2] = a[8 + k];
+                    q[k].radius = a[12 + k];
+                    q[k].velocity[1] = a[16 + k];
+                    S = std::max(S, norm3(q[k].center) + norm3(q[k].velocity) + std::fabs(q[k].radius));
+                }
+                for (int k = 0; k < 4; ++k)
+                    a[28 + k] = precision == RAYZ_PRECISION_F32 ? (double)pad_radius2_bucket<float>(q[k], S, (float)a[27])
+                                                                : (double)pad_radius2_bucket<double>(q[k], S, (float)a[27]);
             }
             if (op == RAYZ_KAT_SPHERE_HIT) {
                 RayzSphere q{};

@@ -64,4 +64,74 @@ uint32_t plan_runs(const std::vector<uint32_t>& cls, CyOf cy_of, uint32_t group,
     return at;
 }
 
+// ---- speed buckets of a y-moving plane run -------------------------------------------------------
+// A y-moving run's reject test differs from the static plane form by one stage, p2 += vy·(time·e2y), which exists only because
+// vy differs from sphere to sphere.  Members of nearly one speed are tested with ONE speed v0 instead, hoisted into the ray's
+// K2 like the run's height; what that leaves out, (vy − v0)·time·e2y, is at most h = |vy − v0| (|time·e2y| ≤ 1), and the host
+// adds h to the radius the filter holds.  A bucket then runs the static plane form: 6 packed FMAs per sphere pair, not 7.
+constexpr size_t kBucketMin = 64; // members a bucket needs (what a run needs, for the same costs)
+constexpr int kBucketCap = 16;    // h ≤ r_min / 16 in a bucket: the filter's disc grows by at most (1 + 1/16)² in area
+
+struct SpeedBucket { // one record of the stream's bucket table (32 bytes)
+    float v0;            // the bucket's speed: the midpoint of its members' f32 vy
+    float cy;            // its run's height
+    uint32_t first, end; // its slots, relative to the class's first slot: whole group pairs, no pads
+    uint32_t base;       // word of the stream at which the 3-field block of class slot 0 WOULD start (slot i: base + 3·i)
+    uint32_t run;        // its run
+    uint32_t _pad[2];
+};
+
+struct RunBuckets {
+    std::vector<uint32_t> order;     // the run's members in slot order: the buckets' (by run, then speed), then the remainder's
+    std::vector<uint32_t> count;     // members of each bucket, a multiple of 2·group
+    std::vector<float> v0;           // speed of each bucket
+    uint32_t bucketed = 0;           // members in buckets = the remainder's first slot, relative to the run's
+};
+
+inline float bucket_mid(float lo, float hi) { return (float)(((double)lo + (double)hi) * 0.5); }
+// max |vy − v0| over [lo, hi] in f32, not rounded down
+inline float bucket_half_width(float lo, float hi) {
+    const double v0 = bucket_mid(lo, hi), h = std::max(v0 - (double)lo, (double)hi - v0);
+    float f = (float)h;
+    if ((double)f < h) f = std::nextafter(f, INFINITY);
+    return f;
+}
+
+// The members `m` of one y-moving run (pool indices, pool order; vy_of(pool) = the f32 speed the scan streams hold, r_of(pool)
+// = |radius|) ordered by (vy, pool index) and cut greedily into buckets: a bucket is closed before the sphere that would push
+// its half width over min |radius| / kBucketCap, and cut down to whole group pairs; fewer than kBucketMin members form no
+// bucket, and the first of them joins the remainder (as every sphere of a non-finite speed does).  The remainder keeps pool
+// order and the run's own 4-field blocks.
+template <class VyOf, class ROf> RunBuckets plan_buckets(const std::vector<uint32_t>& m, VyOf vy_of, ROf r_of, uint32_t group) {
+    RunBuckets out;
+    std::vector<uint32_t> sorted, rest;
+    for (uint32_t pool : m) (std::isfinite(vy_of(pool)) ? sorted : rest).push_back(pool);
+    std::sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return vy_of(a) != vy_of(b) ? vy_of(a) < vy_of(b) : a < b; });
+    const size_t pair = 2 * (size_t)group;
+    size_t s = 0;
+    while (s < sorted.size()) {
+        const float lo = vy_of(sorted[s]);
+        double rmin = r_of(sorted[s]);
+        size_t e = s + 1;
+        for (; e < sorted.size(); ++e) {
+            const double r = std::min(rmin, (double)r_of(sorted[e]));
+            if (!((double)bucket_half_width(lo, vy_of(sorted[e])) <= r / kBucketCap)) break;
+            rmin = r;
+        }
+        const size_t n = (e - s) / pair * pair;
+        if (n < kBucketMin) {
+            rest.push_back(sorted[s++]);
+            continue;
+        }
+        out.count.push_back((uint32_t)n);
+        out.v0.push_back(bucket_mid(lo, vy_of(sorted[s + n - 1])));
+        out.order.insert(out.order.end(), sorted.begin() + s, sorted.begin() + s + n);
+        s += n;
+    }
+    out.bucketed = (uint32_t)out.order.size();
+    std::sort(rest.begin(), rest.end());
+    out.order.insert(out.order.end(), rest.begin(), rest.end());
+    return out;
+}
+
 } // namespace rayz_plane

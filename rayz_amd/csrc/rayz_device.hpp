@@ -62,7 +62,7 @@ template <> struct VecOf<double> { typedef d4 type; typedef d2 pair; };
 // cy field, cx[G] cz[G] r²[G] (+ vy[G]); the run's cy is held once, in the stream's head.  Per stream:
 //   [head][plane blocks of run 0, run 1, ...][two spare plane groups][loose blocks, the layout above][two spare groups]
 // The stream's head (kPlaneHeader words) holds its layout: {number of runs, plane_slots = the slots the runs cover, 0, 0},
-// then kMaxPlaneRuns PlaneRun records.  It is read with scalar loads at every scan: a run table in the kernel arguments
+// then kMaxPlaneRuns PlaneRun records (mov-Y: words 2, 3 = the bucket section, below).  It is read with scalar loads at every scan: a run table in the kernel arguments
 // indexed by the run counter is copied to scratch, and any new argument is loaded once per kernel and held (spilled)
 // across the whole persistent loop.
 // The block layout puts the same field of two neighbouring spheres in one aligned SGPR pair, which is what a
@@ -73,6 +73,17 @@ using rayz_plane::kMaxPlaneRuns;
 using rayz_plane::PlaneRun;
 constexpr int kPlaneHeader = 16; // words of layout at the head of the static and mov-Y streams (64 B: blocks stay aligned)
 static_assert(4 * sizeof(uint32_t) + kMaxPlaneRuns * sizeof(PlaneRun) <= kPlaneHeader * sizeof(float), "run table fits the head");
+// SPEED BUCKETS (mov-Y stream only; rayz_plane::plan_buckets): the members of a y-moving run whose f32 vy lie
+// within r_min / 8 of each other are tested with ONE speed v0, folded into the ray's K2 as the run's height is, against a radius
+// grown by |vy − v0|: the static plane form, 6 packed FMAs per sphere pair.  A run's slots are its buckets' (by speed), then
+// the members no bucket took, in the run's own 4-field blocks, then its pads.  Behind the loose section the stream carries
+//   [kBucketHeader words: per run, the first slot of its 4-field remainder][SpeedBucket records][the buckets' blocks
+//    cx[G] cz[G] r2b[G], back to back][two spare groups]
+// and the head's words 2 and 3 hold that section's word offset and the number of buckets.  Read with scalar loads at every
+// scan, as the run table is and for its reasons.
+using rayz_plane::SpeedBucket;
+constexpr int kBucketHeader = 8;
+static_assert(sizeof(SpeedBucket) == 32 && kMaxPlaneRuns <= kBucketHeader, "bucket table layout");
 
 template <class R> struct DevScene {
     typedef typename VecOf<R>::type r4;
@@ -570,6 +581,12 @@ template <class R> struct ScanGroup<R, 4> { // mov-Y, plane run
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
 
+// A speed bucket of a y-moving plane run: the static plane form (b.k2 = the bucket's K2) on the mov-Y class's slots.
+template <class R> struct ScanGroup<R, 5> : ScanGroup<R, 3> {
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
+};
+
 // What the scan needs of one ray (one of the NR rays a lane carries).
 template <class R> struct ScanRay {
     V<R> o, d;
@@ -689,6 +706,11 @@ __device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay
 }
 // A plane run's K2 for one ray: cy·e2y + k2 in ONE rounding (the run loop below and RAYZ_KAT_SCAN_DISCS classes 2 / 3).
 __device__ __forceinline__ float plane_run_k2(float cy, float e2y, float k2) { return fm(cy, e2y, k2); }
+// A speed bucket's K2 for one ray: the run's K2, then v0·(time·e2y) in one more rounding (the bucket loop below and
+// RAYZ_KAT_SCAN_DISCS class 4).
+__device__ __forceinline__ float bucket_k2(float v0, float cy, float ftime, float e2y, float k2) {
+    return fm(v0, ftime * e2y, plane_run_k2(cy, e2y, k2));
+}
 // The static (CLS 0) or mov-Y (CLS 1) class: its plane runs, then its loose spheres.  Per run, K2 = fm(cy, e2y, k2) replaces
 // each ray's k2 (one FMA per ray and run), which is put back before the loose spheres.  The head is read here, every scan
 // (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
@@ -706,14 +728,37 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
         for (int r = 0; r < NR; ++r) k2[r] = ray[r].basis.k2;
         for (int j = 0; j < nr; ++j) {
             const float cy = runs[j].cy;
+            int first = (int)runs[j].first;
+            const int end = (int)runs[j].end;
+            if constexpr (CLS == 1) { // the run's first slots belong to its speed buckets (below)
+                first = (int)((const RAYZ_CONSTANT uint32_t*)(head + h[2]))[j];
+                if (first == end) continue;
+            }
 #pragma unroll
             for (int r = 0; r < NR; ++r) ray[r].basis.k2 = plane_run_k2(cy, ray[r].basis.e2y, k2[r]);
-            scan_blocks<R, CLS + 3, NR>(sc, head + kPlaneHeader, (int)runs[j].first, (int)runs[j].end, ray, tmin);
+            scan_blocks<R, CLS + 3, NR>(sc, head + kPlaneHeader, first, end, ray, tmin);
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) ray[r].basis.k2 = k2[r];
     }
     if (n_class > plane) scan_blocks<R, CLS, NR>(sc, head + kPlaneHeader + P * (plane + 2 * G), 0, n_class - plane, ray, tmin);
+    if constexpr (CLS == 1) { // the speed buckets, after the loose spheres (scan order is free: scan_sphere_classes)
+        const int nb = (int)h[3];
+        if (nb != 0) {
+            const RAYZ_CONSTANT SpeedBucket* bk = (const RAYZ_CONSTANT SpeedBucket*)(head + h[2] + kBucketHeader);
+            float k2[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) k2[r] = ray[r].basis.k2;
+            for (int j = 0; j < nb; ++j) {
+                const float v0 = bk[j].v0, cy = bk[j].cy;
+#pragma unroll
+                for (int r = 0; r < NR; ++r) ray[r].basis.k2 = bucket_k2(v0, cy, ray[r].ftime, ray[r].basis.e2y, k2[r]);
+                scan_blocks<R, 5, NR>(sc, head + bk[j].base, (int)bk[j].first, (int)bk[j].end, ray, tmin);
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = k2[r];
+        }
+    }
 }
 // Every sphere class in slot order (the slot order only matters to the candidates' parking order; the acceptance rule
 // decides ties by pool index, so the hit is the same in any order).
@@ -1859,6 +1904,23 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
             r[4 + k] = (double)basis_disc<float>(p1, p2, (float)a[28 + k]);
             r[8 + k] = a[32] != 0.0 ? (double)(float)a[28 + k] : 0.0;
         }
+        break;
+    }
+    case 10: { // BUCKET_DISCS: one block of a speed bucket (scan_plane_class's bucket loop): cx[4] cy[0] cz[4] radius[4] vy[4]
+               // o(3) d(3) time v0 (+ the bucket's padded r2b[4] at 28, from the host) -> disc[4] K2b 0 0 0 r2b[4]
+        const V<R> o = v3(20), d = v3(23);
+        const V<R> ud = unit(d);
+        RayBasis<float> b = make_basis<float>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
+        b.k2 = bucket_k2((float)a[27], (float)a[4], (float)(R)a[26], b.e2y, b.k2);
+        ScanGroup<float, 5> g;
+        for (int q = 0; q < 2; ++q) {
+            g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
+            g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
+        }
+        float out4[4];
+        g.discs(out4, b, 0.0f);
+        for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = (double)(float)a[28 + k];
+        r[4] = (double)b.k2;
         break;
     }
     default: break;

@@ -51,6 +51,9 @@ struct NarrowBuffers {
     std::vector<std::vector<uint32_t>> run_members[2]; // pool indices of each run
     std::vector<uint32_t> loose[2];
     uint32_t plane_slots[2] = {0, 0};
+    // speed buckets of each mov-Y run (rayz_plane::plan_buckets): the run's slot order is its buckets' members, its other
+    // members, its pads
+    std::vector<rayz_plane::RunBuckets> buckets;
     bool ready = false, bvh_ready = false;
 };
 
@@ -141,6 +144,18 @@ template <class R> float pad_radius2_scan(const RayzSphere& q, double S) {
     const double rp = std::fabs(q.radius) + E;
     return rayz_bvh::roundUp<float>(rp * rp);
 }
+// A speed bucket's sphere (rayz_plane::plan_buckets) is tested as the sphere of velocity (0, v0, 0) and radius
+// r + h, h ≥ |vy − v0|: at every time in [0, 1] that sphere contains the pool's own, so a line that meets the pool's sphere
+// meets it, and the pad rule above holds for it as for any sphere (its |v| is at most |v| + h).  h is taken against the
+// pool's f64 speed and the f32 one the buckets were cut by, rounded up.
+template <class R> float pad_radius2_bucket(const RayzSphere& q, double S, float v0) {
+    const double vy = q.velocity[1], h0 = std::max(std::fabs(vy - (double)v0), std::fabs((double)(float)vy - (double)v0));
+    const double h = h0 * (1.0 + 0x1p-50) + 1e-300;
+    const double E = (sizeof(R) == 4 ? 32.0 : 40.0) * unit_roundoff<float>() *
+                     (norm3(q.center) + norm3(q.velocity) + h + std::fabs(q.radius) + h + S);
+    const double rp = std::fabs(q.radius) + h + E;
+    return rayz_bvh::roundUp<float>(rp * rp);
+}
 double scene_origin_bound(const RayzScene* s);
 double camera_origin_bound(const RayzCameraDesc* c) { return norm3(c->look_from) + norm3(c->defocus_u) + norm3(c->defocus_v); }
 
@@ -225,6 +240,13 @@ int upload_narrow_body(RayzScene* s) {
     for (int c = 0; c < 2; ++c)
         nb.plane_slots[c] = rayz_plane::plan_runs(s->cls[c], [&](uint32_t pool) { return (float)s->spheres[pool].center[1]; },
                                                   kStaticGroup, nb.runs[c], nb.run_members[c], nb.loose[c]);
+    nb.buckets.clear();
+    for (std::vector<uint32_t>& m : nb.run_members[1]) {
+        nb.buckets.push_back(rayz_plane::plan_buckets(
+            m, [&](uint32_t pool) { return (float)s->spheres[pool].velocity[1]; },
+            [&](uint32_t pool) { return std::fabs(s->spheres[pool].radius); }, kMovYGroup));
+        m = nb.buckets.back().order; // slot order from here on
+    }
     nb.ns_pad = nb.plane_slots[0] + scan_len(nb.loose[0].size(), kStaticGroup);
     nb.ny_pad = nb.plane_slots[1] + scan_len(nb.loose[1].size(), kMovYGroup);
     nb.ng_pad = scan_len(s->cls[2].size(), kMovGGroup);
@@ -301,6 +323,39 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
             blk[0] = r.x, blk[G] = r.y, blk[2 * G] = r.z, blk[3 * G] = r.w;
             if (F == 5) blk[4 * G] = (float)s->spheres[pool].velocity[1];
         }
+        if (c != 1) return v;
+        // mov-Y only: the bucket section (rayz_device.hpp) — per run the first slot of its 4-field remainder, the bucket table,
+        // the buckets' 3-field blocks cx[G] cz[G] r2b[G] back to back, two spare groups.  Head words 2 and 3: where, how many.
+        // (The buckets' slots keep their places in the plane section above, unused.)
+        std::vector<rayz_plane::SpeedBucket> table;
+        uint32_t rem_first[kMaxPlaneRuns] = {0, 0, 0, 0}, bucket_slots = 0;
+        for (size_t j = 0; j < nb.runs[1].size(); ++j) {
+            uint32_t at = nb.runs[1][j].first;
+            for (size_t q = 0; q < nb.buckets[j].count.size(); ++q) {
+                table.push_back(rayz_plane::SpeedBucket{nb.buckets[j].v0[q], nb.runs[1][j].cy, at, at + nb.buckets[j].count[q], bucket_slots, (uint32_t)j, {0u, 0u}});
+                at += nb.buckets[j].count[q], bucket_slots += nb.buckets[j].count[q];
+            }
+            rem_first[j] = at;
+        }
+        const size_t section = (v.size() + 15) / 16 * 16; // 64-byte aligned, as the blocks are
+        const size_t blocks0 = section + kBucketHeader + table.size() * (sizeof(rayz_plane::SpeedBucket) / sizeof(float));
+        v.resize(blocks0 + 3 * (size_t)(bucket_slots + 2 * G), 0.0f);
+        float* const bk = v.data() + blocks0;
+        for (uint32_t k = 0; k < bucket_slots + 2 * G; ++k) bk[(size_t)(k / G) * 3 * G + 2 * G + k % G] = ninf32;
+        for (rayz_plane::SpeedBucket& t : table) {
+            const uint32_t at = t.base; // the bucket's first slot of the section
+            for (uint32_t k = t.first; k < t.end; ++k) {
+                const uint32_t pool = nb.run_members[1][t.run][k - nb.runs[1][t.run].first], sk = at + (k - t.first);
+                const RayzSphere& q = s->spheres[pool];
+                float* blk = bk + (size_t)(sk / G) * 3 * G + sk % G;
+                blk[0] = (float)q.center[0], blk[G] = (float)q.center[2], blk[2 * G] = pad_radius2_bucket<R>(q, b.pad_S, t.v0);
+            }
+            t.base = (uint32_t)blocks0 + 3 * at - 3 * t.first; // (>= 0: the section lies behind 4 words per plane slot)
+        }
+        const uint32_t where[2] = {(uint32_t)section, (uint32_t)table.size()};
+        std::memcpy(v.data() + 2, where, sizeof(where));
+        std::memcpy(v.data() + section, rem_first, sizeof(rem_first));
+        if (!table.empty()) std::memcpy(v.data() + section + kBucketHeader, table.data(), table.size() * sizeof(rayz_plane::SpeedBucket));
         return v;
     };
     const std::vector<float> stat = blocks(0, 4, s->narrow.ns_pad), movy = blocks(1, 5, s->narrow.ny_pad);
