@@ -299,9 +299,9 @@ def plane_sequence(w, h, seed, origins, margin=3):
     return frames
 
 
-def general_sequence(w, h, seed):
+def general_sequence(w, h, seed, shifts=((0.0, 0.0), (0.0, 0.0), (1.37, 0.61))):
     """Three frames through a general camera whose arithmetic is NOT exact — first, the same camera again (static), then a pan of
-    (1.37, 0.61) pixels: the world is the plane z = 5 + x/10, every point the f32 of the f64 intersection of its pixel's ray; the
+    (1.37, 0.61) pixels (`shifts`: each frame's pan from the first camera, in pixels): the world is the plane z = 5 + x/10, every point the f32 of the f64 intersection of its pixel's ray; the
     hittable index is constant over blocks of 6x4 pixels, `synthetic`'s normals and background."""
     from denoise_cases import synthetic
     from denoise_guided_cases import guided_variance
@@ -311,7 +311,7 @@ def general_sequence(w, h, seed):
     po0 = lf + np.array([0.0, 0.0, 1.0]) - u * (w / 2) - v * (h / 2)
     gx, gy = np.meshgrid(np.arange(w), np.arange(h))
     frames = []
-    for k, shift in enumerate(((0.0, 0.0), (0.0, 0.0), (1.37, 0.61))):
+    for k, shift in enumerate(shifts):
         po = po0 + shift[0] * u + shift[1] * v
         d = (po - lf)[None, None, :] + gx[..., None] * u + gy[..., None] * v
         t = (5.0 + 0.1 * lf[0] - lf[2]) / (d[..., 2] - 0.1 * d[..., 0])  # z = 5 + x/10 along lf + t·d
@@ -323,3 +323,105 @@ def general_sequence(w, h, seed):
         camera = dict(look_from=tuple(lf), px_du=tuple(u), px_dv=tuple(v), px_origin=tuple(po))
         frames.append(dict(rgb=rgb, var=guided_variance(rgb, seed + k), index=idx, normal=nrm, point=pt, camera=camera))
     return frames
+
+
+def edge_sequence(w, h, seed):
+    """`general_sequence`'s world under pans that put the frame's first column, then its first row, 1/128 of a pixel inside the
+    history's border: x = px − 127/128, so at px = 0 the tap at −1 is outside and the tap at 0 has b = 1/128 < 2^-6 — no history, by
+    the weight threshold.  A reading that lets the outside tap take the clamped pixel has B = 1 there and blends: at a frame's edge
+    the clamped tap and its in-frame neighbour are the same pixel, so B is the ONLY thing such a reading changes."""
+    return general_sequence(w, h, seed, shifts=((0.0, 0.0), (-127 / 128, 0.0), (-127 / 128 + 0.25, -127 / 128)))
+
+
+MOVING_SPP = (4, 8, 16, 8, 4)
+
+
+def _turned(vecs, yaw, pitch, roll):
+    """The vectors turned about the world's y, x and z axes by the three (small) angles."""
+    cy, sy, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+    R = (np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]) @ np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]])
+         @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]]))
+    return [R @ x for x in vecs]
+
+
+def moving_cameras(w, h):
+    """Five general cameras over the world of `moving_sequence`: a first one; the same again (a static step); look_from moved
+    sideways and forward by a fraction of the scene's depth (about 15); the view turned by a few pixels' worth of angle, a roll
+    included, so that px_du, px_dv and px_origin all change; and one more move with a further small turn."""
+    u, v, f = np.array([0.0123, 0.0004, -0.0007]), np.array([0.0003, -0.0119, 0.0011]), np.array([0.0, 0.0, 1.0])
+    lf = np.array([0.3, 1.7, -6.1])
+    poses = [(lf, (u, v, f))] * 2
+    lf3 = lf + np.array([0.62, -0.17, 0.55])
+    poses.append((lf3, (u, v, f)))
+    t4 = _turned((u, v, f), 0.031, -0.017, 0.012)  # a pixel is 0.0123 rad wide
+    poses.append((lf3, t4))
+    poses.append((lf3 + np.array([-0.33, 0.21, 0.4]), _turned(t4, -0.011, 0.008, -0.004)))
+    cams = []
+    for o, (uu, vv, ff) in poses:
+        po = o + ff - uu * (w / 2) - vv * (h / 2)
+        cams.append(dict(look_from=tuple(o), px_du=tuple(uu), px_dv=tuple(vv), px_origin=tuple(po)))
+    return cams
+
+
+def moving_sequence(w, h, seed):
+    """Five frames of ONE synthetic world through `moving_cameras`, spp 4, 8, 16, 8, 4 (frame["spp"]).  Two depth layers, about 15
+    and 10 from the first camera: the far plane z = 9 + x/10 − y/20 where |x − 0.3| < 0.3·w·0.0123·15 (beyond it is background, so
+    the frame has background columns that move with the camera), and in front of it the slab z = 4 + 3y/100 over the world
+    rectangle −0.9 < x < 0.5, 0.8 < y < 2.3 — silhouettes, parallax between the layers and disocclusion behind the slab's edges when
+    look_from moves.  Every point is the f32 of the f64 intersection of its pixel's ray; index and normal belong to the surface hit
+    and are functions of the WORLD position: the index is constant over world cells a few pixels wide (taps inside agree, across do
+    not), the normal is the plane's with a ripple that turns it by up to ~0.2 rad between neighbouring pixels (so normal_cos_min =
+    0.99 refuses taps that 0.9 accepts) and is NEGATED on stripes of the far plane (a back-facing patch of one hittable: what tells
+    `dot >= cm` from `|dot| >= cm`).  Colour and variance are drawn per frame as `general_sequence` draws them."""
+    from denoise_cases import synthetic
+    from denoise_guided_cases import guided_variance
+
+    gx, gy = np.meshgrid(np.arange(w), np.arange(h))
+    planes = [(np.array([-0.1, 0.05, 1.0]), 9.0), (np.array([0.0, -0.03, 1.0]), 4.0)]  # n·X = c
+    half_width = 0.3 * w * 0.0123 * 15
+    frames = []
+    for k, camera in enumerate(moving_cameras(w, h)):
+        lf, u, v, po = (np.array(camera[f]) for f in ("look_from", "px_du", "px_dv", "px_origin"))
+        d = (po - lf)[None, None, :] + gx[..., None] * u + gy[..., None] * v
+        X, hitl = [], []
+        for pn, pc in planes:
+            t = (pc - pn @ lf) / (d @ pn)
+            X.append(lf[None, None, :] + t[..., None] * d)
+            hitl.append(t > 0)
+        far, slab = X
+        on_far = hitl[0] & (np.abs(far[..., 0] - 0.3) < half_width)
+        on_slab = hitl[1] & (slab[..., 0] > -0.9) & (slab[..., 0] < 0.5) & (slab[..., 1] > 0.8) & (slab[..., 1] < 2.3)
+        pt = np.where(on_slab[..., None], slab, far)
+        cell = np.where(on_slab, 300 + np.floor(pt[..., 0] / 0.37) + 10 * np.floor(pt[..., 1] / 0.29),
+                        100 + np.floor(pt[..., 0] / 0.83) + 20 * np.floor(pt[..., 1] / 0.61))
+        idx = np.where(on_slab | on_far, cell, -1).astype(np.int32)
+        base = np.where(on_slab[..., None], -planes[1][0], -planes[0][0])  # facing the camera
+        freq = np.where(on_slab, 19.0, 12.0)
+        ripple = np.stack([np.sin(freq * pt[..., 0]), np.cos(freq * 0.8 * pt[..., 1] + 0.4), np.zeros((h, w))], axis=2)
+        nrm = base + 0.12 * ripple
+        nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
+        nrm = np.where((~on_slab & (np.sin(2.3 * pt[..., 0] + 0.7 * pt[..., 1]) > 0.75))[..., None], -nrm, nrm)
+        rgb = synthetic(w, h, seed + 13 * (k + 1))[0]
+        pt, nrm = pt.astype(np.float32), nrm.astype(np.float32)
+        pt[idx < 0] = 0
+        nrm[idx < 0] = 0
+        frames.append(dict(rgb=rgb, var=guided_variance(rgb, seed + k), index=idx, normal=np.ascontiguousarray(nrm),
+                           point=np.ascontiguousarray(pt), camera=camera, spp=MOVING_SPP[k]))
+    return frames
+
+
+def orbit_views():
+    """Five (look_from, look_at) pairs around threeSpheres' own view ((-2, 2, 1) towards (0, 0, -1), about 3.5 away, a pixel about
+    0.01 rad at 64x36): the first; the same again; an orbit sideways and up with look_at following; a dolly towards the scene; and
+    an orbit back with look_at raised — moves of a pixel or two each, with look_from AND look_at changing."""
+    return [((-2.0, 2.0, 1.0), (0.0, 0.0, -1.0)), ((-2.0, 2.0, 1.0), (0.0, 0.0, -1.0)), ((-1.94, 2.03, 1.05), (0.02, 0.0, -1.0)),
+            ((-1.86, 1.95, 0.97), (0.02, 0.0, -1.0)), ((-1.9, 1.92, 1.04), (0.0, 0.03, -0.98))]
+
+
+def orbit_camera(oracle, view, w, h):
+    """threeSpheres' camera (vfov 20, focus 3.4, no defocus) at a view of `orbit_views`, from the oracle's camera_init."""
+    from rayz_amd import capi
+
+    c = capi.CameraDesc()
+    oracle.load().rayz_oracle_camera_init(20.0, 3.4, 0.0, capi.D3(*view[0]), capi.D3(*view[1]), capi.D3(0, 1, 0), h, w, c)
+    return c

@@ -30,6 +30,21 @@ struct Acc {
     float B, H[3], Hv[3], HN;
 };
 
+// Step 2's position: w = P − from, then (x, y, γ) through M.  x and y mean something only where γ > 0.  The step and
+// temporal_mirror_project both go through these two, so what the latter reports is what the former uses.
+struct Proj {
+    float x, y, ga;
+};
+inline void offset(const float* P, const float* from, float* w) {
+    for (int j = 0; j < 3; ++j) w[j] = P[j] - from[j];
+}
+inline Proj project(const float* M, const float* w) {
+    const float al = std::fmaf(M[2], w[2], std::fmaf(M[1], w[1], M[0] * w[0]));
+    const float be = std::fmaf(M[5], w[2], std::fmaf(M[4], w[1], M[3] * w[0]));
+    const float ga = std::fmaf(M[8], w[2], std::fmaf(M[7], w[1], M[6] * w[0]));
+    return Proj{al / ga, be / ga, ga};
+}
+
 } // namespace
 
 extern "C" {
@@ -48,6 +63,19 @@ int temporal_mirror_camera(const double* cam, float* M, float* from) {
         for (int j = 0; j < 3; ++j) M[3 * k + j] = (float)(r[k][j] / det);
     for (int j = 0; j < 3; ++j) from[j] = (float)lf[j];
     return 1;
+}
+
+// The f32 (x, y, γ) that a step projecting with M / from computes for each of `count` points: out[3·i] = x, [3·i + 1] = y, [3·i + 2] = γ
+// (x and y as divided, whatever γ is).  For the test of §4.15's accuracy statement.
+void temporal_mirror_project(const float* point, size_t count, const float* M, const float* from, float* out) {
+    for (size_t i = 0; i < count; ++i) {
+        float w[3];
+        offset(point + 3 * i, from, w);
+        const Proj pr = project(M, w);
+        out[3 * i] = pr.x;
+        out[3 * i + 1] = pr.y;
+        out[3 * i + 2] = pr.ga;
+    }
 }
 
 // One step.  prev_* : the history the previous step wrote (ignored when !has_history); next_* : the history this step writes.
@@ -72,7 +100,8 @@ void temporal_mirror_step(const float* rgb, const float* var, const int32_t* ind
             const float* P = point + 3 * p;
             float co[3] = {c[0], c[1], c[2]}, vo[3] = {s[0], s[1], s[2]}, No = spp;
             if (id >= 0 && has_history) {
-                const float w[3] = {P[0] - from[0], P[1] - from[1], P[2] - from[2]};
+                float w[3];
+                offset(P, from, w);
                 const float lim = r2 * dot3(w, w);
                 Acc acc{0.0f, {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0.0f};
                 auto tap = [&](long qx, long qy, float b) {
@@ -94,11 +123,9 @@ void temporal_mirror_step(const float* rgb, const float* var, const int32_t* ind
                 if (is_static) {
                     tap(px, py, 1.0f);
                 } else {
-                    const float al = std::fmaf(M[2], w[2], std::fmaf(M[1], w[1], M[0] * w[0]));
-                    const float be = std::fmaf(M[5], w[2], std::fmaf(M[4], w[1], M[3] * w[0]));
-                    const float ga = std::fmaf(M[8], w[2], std::fmaf(M[7], w[1], M[6] * w[0]));
-                    if (ga > 0.0f) {
-                        const float x = al / ga, y = be / ga;
+                    const Proj pr = project(M, w);
+                    if (pr.ga > 0.0f) {
+                        const float x = pr.x, y = pr.y;
                         if (x > -1.0f && x < Wf && y > -1.0f && y < Hf) {
                             const float x0 = std::floor(x), y0 = std::floor(y);
                             const float fx = x - x0, fy = y - y0;

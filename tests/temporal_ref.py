@@ -35,6 +35,8 @@ def load():
     lib.temporal_mirror_step.argtypes = [_F, _F, _I, _F, _F] + [_F] * 8 + [_F, _F, _F, C.c_uint32, C.c_uint32, C.c_int, C.c_int, _F, _F] + \
         [C.c_float] * 5
     lib.temporal_mirror_step.restype = None
+    lib.temporal_mirror_project.argtypes = [_F, C.c_size_t, _F, _F, _F]
+    lib.temporal_mirror_project.restype = None
     _lib = lib
     return lib
 
@@ -63,6 +65,15 @@ def camera_matrix(cam):
     M, fr = np.empty(9, np.float32), np.empty(3, np.float32)
     ok = load().temporal_mirror_camera(c.ctypes.data_as(_D), _f(M), _f(fr))
     return (M, fr) if ok else None
+
+
+def project(points, M, fr):
+    """The f32 (x, y, γ) of §4.15's step 2 for points (n, 3) float32 through `M`, `fr` of camera_matrix: (n, 3) float32."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    out = np.empty_like(points)
+    with np.errstate(all="ignore"):
+        load().temporal_mirror_project(_f(points), len(points), _f(M), _f(fr), _f(out))
+    return out
 
 
 class Temporal:
