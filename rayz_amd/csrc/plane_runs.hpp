@@ -64,6 +64,18 @@ uint32_t plan_runs(const std::vector<uint32_t>& cls, CyOf cy_of, uint32_t group,
     return at;
 }
 
+// ---- how far a scan reads ----------------------------------------------------------------------------------------------
+// The scan (rayz_device.hpp: scan_blocks) tests the slots [first, end) of a section of a stream in pairs of groups, and while
+// it tests a group it loads the next one: the furthest group it loads is the ONE behind its last pair (the loop before round 7
+// loaded two).  Every section (plane blocks, loose blocks, bucket blocks, the mov-G stream) ends in kScanSpareGroups groups of
+// never-hit pads, so a scan that ends with its section stays inside it.  scan_reach = one past the last slot a scan loads; the
+// host holds every scan it lays out to scan_reach <= the section's slots (rayz_hip.hip: upload_body).
+constexpr uint32_t kScanSpareGroups = 2;
+inline uint32_t scan_reach(uint32_t first, uint32_t end, uint32_t group) {
+    const uint32_t pair = 2 * group, n = end > first ? end - first : 0;
+    return first + (n + pair - 1) / pair * pair + group;
+}
+
 // ---- speed buckets of a y-moving plane run -------------------------------------------------------
 // A y-moving run's reject test differs from the static plane form by one stage, p2 += vy·(time·e2y), which exists only because
 // vy differs from sphere to sphere.  Members of nearly one speed are tested with ONE speed v0 instead, hoisted into the ray's

@@ -407,8 +407,9 @@ __device__ __forceinline__ void tri_accept(R filt, V<R> v0, V<R> e1, V<R> e2, V<
 // Slots the plane runs of a static / mov-Y stream cover (its head: see DevScene).
 __device__ __forceinline__ uint32_t plane_slots(const float* stream) { return ((const RAYZ_CONSTANT uint32_t*)stream)[1]; }
 
-// One scan group of a velocity class, held in SGPRs: load() issues the scalar loads, test() runs the
-// reject test of its spheres against 64 rays and sends candidates to the narrow phase.
+// One scan group of a velocity class, held in SGPRs: load() issues the scalar loads, discs() runs the reject test of its
+// spheres against 64 rays.  ready(at) waits for the loads; the stream pointer `at` passes through the same empty asm, so the
+// load the scan issues next, at an offset from `at`, depends on the wait and cannot be issued in front of it.
 template <class R, int CLS> struct ScanGroup;
 
 // The reject tests of a block run two spheres per instruction: each stage is ONE packed FMA (v_pk_fma_f32 for
@@ -416,18 +417,21 @@ template <class R, int CLS> struct ScanGroup;
 // gfx950 (tools/ubench): a VALU instruction that reads a different SGPR each time issues at ≈2.75 cycles, not 2,
 // so the 7 scalar reads of a test bound the scalar-FMA form at ≈21 ticks per wave-test; the packed form needs
 // 3.5 pair reads per test and runs at 14.7.  Every half of a packed FMA is an ordinary IEEE FMA: results are
-// bit-identical to the scalar form (and to the oracle).
+// bit-identical to the scalar form (and to the oracle).  discs() is written stage by stage across the group's pairs, not
+// pair by pair: a packed FMA that reads the result of the one just issued costs gfx950 an s_nop, and in this order hipcc
+// finds the other pair's FMA to put between them (the same FMAs on the same values either way).
 template <class R> struct ScanGroup<R, 0> { // static
     typedef typename VecOf<R>::pair pr;
     static constexpr int G = group_size<R>(), H = G / 2;
     pr cx[H], cy[H], cz[H], r2[H];
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 4 * i);
+    static constexpr int kWords = 4; // words of the stream per sphere
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) { // g: the group's first word
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
 #pragma unroll
         for (int q = 0; q < H; ++q) cx[q] = p[q], cy[q] = p[H + q], cz[q] = p[2 * H + q], r2[q] = p[3 * H + q];
     }
-    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0])); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0])); }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cy[q]), "+s"(cz[q]), "+s"(r2[q]));
@@ -435,17 +439,23 @@ template <class R> struct ScanGroup<R, 0> { // static
     __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R) const {
         const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
             K1{b.k1, b.k1}, K2{b.k2, b.k2};
+        pr p1[H], p2[H], d[H];
 #pragma unroll
-        for (int q = 0; q < H; ++q) {
-            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
-            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
-            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
-            p2 = __builtin_elementwise_fma(cy[q], E2y, p2);
-            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
-            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
-            out[2 * q] = d.x;
-            out[2 * q + 1] = d.y;
-        }
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)plane_slots(sc.stat); }
 };
@@ -454,13 +464,14 @@ template <class R> struct ScanGroup<R, 1> { // mov-Y
     static constexpr int G = group_size<R>(), H = G / 2;
     pr cx[H], cy[H], cz[H], r2[H], vy[H];
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 5 * i);
+    static constexpr int kWords = 5;
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
 #pragma unroll
         for (int q = 0; q < H; ++q)
             cx[q] = p[q], cy[q] = p[H + q], cz[q] = p[2 * H + q], r2[q] = p[3 * H + q], vy[q] = p[4 * H + q];
     }
-    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0]), "s"(vy[0])); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0]), "s"(vy[0])); }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cy[q]), "+s"(cz[q]), "+s"(r2[q]), "+s"(vy[q]));
@@ -469,18 +480,25 @@ template <class R> struct ScanGroup<R, 1> { // mov-Y
         const R t2y = time * b.e2y;
         const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
             K1{b.k1, b.k1}, K2{b.k2, b.k2}, T2y{t2y, t2y};
+        pr p1[H], p2[H], d[H];
 #pragma unroll
-        for (int q = 0; q < H; ++q) {
-            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
-            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
-            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
-            p2 = __builtin_elementwise_fma(cy[q], E2y, p2);
-            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
-            p2 = __builtin_elementwise_fma(vy[q], T2y, p2);
-            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
-            out[2 * q] = d.x;
-            out[2 * q + 1] = d.y;
-        }
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)(sc.ns_pad + plane_slots(sc.movy)); }
 };
@@ -489,12 +507,13 @@ template <class R> struct ScanGroup<R, 2> { // mov-G
     static constexpr int G = kMovGGroup;
     r4 c[G], v[G];
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movg; }
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
-        const RAYZ_CONSTANT r4* p = (const RAYZ_CONSTANT r4*)base + 2 * i;
+    static constexpr int kWords = 8;
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
+        const RAYZ_CONSTANT r4* p = (const RAYZ_CONSTANT r4*)g;
 #pragma unroll
         for (int k = 0; k < G; ++k) c[k] = p[2 * k], v[k] = p[2 * k + 1];
     }
-    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(c[0].x)); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(c[0].x)); }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int k = 0; k < G; ++k)
@@ -522,28 +541,34 @@ template <class R> struct ScanGroup<R, 3> { // static, plane run
     static constexpr int G = group_size<R>(), H = G / 2;
     pr cx[H], cz[H], r2[H];
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 3 * i);
+    static constexpr int kWords = 3;
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
 #pragma unroll
         for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q];
     }
-    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0])); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0])); }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
     }
     __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R) const { // b.k2 = the run's K2
         const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2};
+        pr p1[H], p2[H], d[H];
 #pragma unroll
-        for (int q = 0; q < H; ++q) {
-            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
-            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
-            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
-            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
-            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
-            out[2 * q] = d.x;
-            out[2 * q + 1] = d.y;
-        }
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC&) { return 0; }
 };
@@ -552,12 +577,13 @@ template <class R> struct ScanGroup<R, 4> { // mov-Y, plane run
     static constexpr int G = group_size<R>(), H = G / 2;
     pr cx[H], cz[H], r2[H], vy[H];
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* base, int i) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)(base + 4 * i);
+    static constexpr int kWords = 4;
+    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
+        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
 #pragma unroll
         for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q], vy[q] = p[3 * H + q];
     }
-    __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(cx[0]), "s"(vy[0])); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0]), "s"(vy[0])); }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]), "+s"(vy[q]));
@@ -566,17 +592,23 @@ template <class R> struct ScanGroup<R, 4> { // mov-Y, plane run
         const R t2y = time * b.e2y;
         const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2},
             T2y{t2y, t2y};
+        pr p1[H], p2[H], d[H];
 #pragma unroll
-        for (int q = 0; q < H; ++q) {
-            pr p1 = __builtin_elementwise_fma(cx[q], E1x, K1);
-            pr p2 = __builtin_elementwise_fma(cx[q], E2x, K2);
-            p1 = __builtin_elementwise_fma(cz[q], E1z, p1);
-            p2 = __builtin_elementwise_fma(cz[q], E2z, p2);
-            p2 = __builtin_elementwise_fma(vy[q], T2y, p2);
-            const pr d = __builtin_elementwise_fma(-p1, p1, __builtin_elementwise_fma(-p2, p2, r2[q]));
-            out[2 * q] = d.x;
-            out[2 * q + 1] = d.y;
-        }
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
@@ -654,20 +686,28 @@ __device__ __forceinline__ void group_collect(const DevScene<R>& sc, int first, 
         }
 }
 
-// One velocity class.  n is a multiple of 2·G and the stream carries two spare groups.  Per iteration: wait for
-// the two groups loaded during the previous iteration, test group a and immediately reload its SGPR set with the
-// group after next, the same for b, then ONE reject branch for the 2·G tests.  (Scalar loads return out of
-// order, so a wave can only wait for all of them — lgkmcnt(0) — hence the explicit order; the sched_barriers
-// keep hipcc from sinking the loads.  The branch costs ≈10 cycles of a wave's time: once per 8 tests, not 4.)
+// One velocity class.  n is a multiple of 2·G and the stream carries two spare groups.  Scalar loads return out of order,
+// so a wave can only wait for all of them (lgkmcnt(0)): every load is therefore issued right AFTER a wait, into the set
+// that is free, and has the 12 – 16 packed FMAs of the other set's test in front of the wait that covers it.  Per iteration:
+// wait for a, load b with the next group, test a; wait for b, load a with the group after it, test b; then ONE reject
+// branch for the 2·G tests (≈10 cycles of a wave's time: once per 8 tests, not 4), wave-uniform by a ballot.  (The
+// sched_barriers keep hipcc from moving the tests across the waits.)  The loop carries the stream pointer `at` of the
+// group pair (the loads' offsets from it are immediates) and a down-counter of the slots left, from which the candidate
+// branch, the only user of the slot number, recovers it.  The furthest group a scan loads is the one behind its last pair:
+// rayz_plane::scan_reach, held inside every section's spare groups where the host builds the streams.
 // scan_blocks tests the stream's slots i0 .. i1 (relative to the class's first slot, ScanGroup::slot0).
 template <class R, int CLS, int NR>
 __device__ __forceinline__ void scan_blocks(const DevScene<R>& sc, const RAYZ_CONSTANT float* base, int i0, int i1,
                                             ScanRay<R> (&ray)[NR], R tmin) {
-    constexpr int G = ScanGroup<float, CLS>::G;
-    ScanGroup<float, CLS> a, b;
-    a.load(base, i0);
-    b.load(base, i0 + G);
-    for (int i = i0; i < i1; i += 2 * G) {
+    typedef ScanGroup<float, CLS> Grp;
+    constexpr int G = Grp::G, W = Grp::kWords * G; // words of a group
+    const RAYZ_CONSTANT float* at = base + Grp::kWords * i0;
+    Grp a, b;
+    a.load(at);
+#ifdef RAYZ_DEBUG_NOFEED
+    b.load(at + W);
+#endif
+    for (int left = i1 - i0; left > 0; left -= 2 * G, at += 2 * W) {
         float da[NR][G], db[NR][G];
         float m = -1.0f;
 #ifdef RAYZ_DEBUG_NOFEED // timing experiment only: never reload (wrong results); values kept opaque to the compiler
@@ -676,22 +716,24 @@ __device__ __forceinline__ void scan_blocks(const DevScene<R>& sc, const RAYZ_CO
         b.opaque();
         group_discs<R, CLS, NR>(b, ray, db, m, false);
 #else
-        a.touch();
+        a.ready(at);
+        b.load(at + W);
+        __builtin_amdgcn_sched_barrier(0);
         group_discs<R, CLS, NR>(a, ray, da, m, true);
-        a.load(base, i + 2 * G);
+        __builtin_amdgcn_sched_barrier(0);
+        b.ready(at);
+        a.load(at + 2 * W);
         __builtin_amdgcn_sched_barrier(0);
         group_discs<R, CLS, NR>(b, ray, db, m, false);
-        b.load(base, i + 3 * G);
-        __builtin_amdgcn_sched_barrier(0);
 #endif
 #ifdef RAYZ_DEBUG_NONARROW // timing experiment only (wrong results)
-        if (m >= 1e30f) {
+        if (__ballot(m >= 1e30f) != 0ull) {
 #else
-        if (m >= 0.0f) { // any lane, any ray, any of the 2·G spheres: rare
+        if (__ballot(m >= 0.0f) != 0ull) { // any lane, any ray, any of the 2·G spheres: rare.  Lanes that have none park nothing
 #endif
-            const int slot0 = ScanGroup<float, CLS>::slot0(sc);
-            group_collect<R, CLS, NR>(sc, slot0 + i, ray, da, tmin);
-            group_collect<R, CLS, NR>(sc, slot0 + i + G, ray, db, tmin);
+            const int first = Grp::slot0(sc) + i1 - left;
+            group_collect<R, CLS, NR>(sc, first, ray, da, tmin);
+            group_collect<R, CLS, NR>(sc, first + G, ray, db, tmin);
         }
     }
 }
@@ -824,7 +866,8 @@ __device__ __forceinline__ void scan_triangles(const DevScene<R>& sc, ScanRay<R>
 // ---- the flat-list scan: nearest hit of each of the lane's NR rays over every hittable -------------------
 // Wave-uniform in the sphere index: records arrive by scalar loads and feed the VALU as SGPR operands.  What
 // bounds the loop was established by elimination (tools/ubench/): not the sphere feed (a build
-// that never reloads runs in the same time), not occupancy, not instruction-level parallelism — but the rate at
+// that never reloads ran in the same time in round 2; 4 % per segment in round 7, half of which scan_blocks' order of loads
+// and discs' order of FMAs recovered), not occupancy, not instruction-level parallelism — but the rate at
 // which VALU instructions can read DIFFERENT scalar registers (≈2.75 cycles each), plus ≈10 cycles per reject
 // branch.  Hence two spheres per packed FMA (ScanGroup::discs) and one branch per 8 tests (scan_class).
 // NR = rays per lane; the product instantiates NR = 1 (two rays per lane halve the scalar loads per test and

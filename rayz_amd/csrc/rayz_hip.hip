@@ -296,10 +296,18 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         const RayzSphere& q = s->spheres[pool];
         return f4{(float)q.center[0], (float)q.center[1], (float)q.center[2], pad_radius2_scan<R>(q, b.pad_S)};
     };
+    // every scan the device runs over these streams stays inside its section's spare groups (rayz_plane::scan_reach)
+    static_assert(rayz_plane::kScanSpareGroups == 2, "the sections below end in two spare groups");
+    bool reach_ok = true;
+    auto reach = [&](uint32_t first, uint32_t end, uint32_t group, uint32_t section_slots) {
+        reach_ok = reach_ok && rayz_plane::scan_reach(first, end, group) <= section_slots;
+    };
     auto blocks = [&](int c, uint32_t F, uint32_t class_slots) {
         const NarrowBuffers& nb = s->narrow;
         const uint32_t G = group_size<float>(), P = F - 1;
         const uint32_t n_plane = nb.plane_slots[c] + 2 * G, n_loose = class_slots - nb.plane_slots[c] + 2 * G;
+        for (const PlaneRun& r : nb.runs[c]) reach(r.first, r.end, G, n_plane); // (a mov-Y run's remainder starts later, ends there)
+        reach(0, class_slots - nb.plane_slots[c], G, n_loose);
         std::vector<float> v(kPlaneHeader + (size_t)n_plane * P + (size_t)n_loose * F, 0.0f);
         const uint32_t head[4] = {(uint32_t)nb.runs[c].size(), nb.plane_slots[c], 0u, 0u}; // the stream's head (rayz_device.hpp)
         std::memcpy(v.data(), head, sizeof(head));
@@ -350,6 +358,7 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
                 float* blk = bk + (size_t)(sk / G) * 3 * G + sk % G;
                 blk[0] = (float)q.center[0], blk[G] = (float)q.center[2], blk[2 * G] = pad_radius2_bucket<R>(q, b.pad_S, t.v0);
             }
+            reach(at, at + (t.end - t.first), G, bucket_slots + 2 * G);
             t.base = (uint32_t)blocks0 + 3 * at - 3 * t.first; // (>= 0: the section lies behind 4 words per plane slot)
         }
         const uint32_t where[2] = {(uint32_t)section, (uint32_t)table.size()};
@@ -360,6 +369,8 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
     };
     const std::vector<float> stat = blocks(0, 4, s->narrow.ns_pad), movy = blocks(1, 5, s->narrow.ny_pad);
     std::vector<f4> movg(2 * (size_t)stream_len(s->cls[2].size(), kMovGGroup), f4{0.0f, 0.0f, 0.0f, 0.0f});
+    reach(0, s->narrow.ng_pad, kMovGGroup, (uint32_t)(movg.size() / 2));
+    if (!reach_ok) return fail(RAYZ_ERR_STATE, "scan stream layout: a scan would load past its section's spare groups");
     for (size_t k = 0; k < movg.size(); k += 2) movg[k] = f4{0.0f, 0.0f, 0.0f, ninf32};
     for (size_t k = 0; k < s->cls[2].size(); ++k) {
         const RayzSphere& q = s->spheres[s->cls[2][k]];
