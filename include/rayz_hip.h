@@ -718,7 +718,8 @@ int rayz_hip_temporal_create(int device, uint32_t width, uint32_t height, RayzTe
  * height*width floats, the history length in samples after the step (spp where no history was found).  d_rgb_out == d_rgb_in and
  * d_var_out == d_var_rgb are allowed (a pixel reads only its own current values).  `gbuffer`: index, normal and point are
  * required, the other fields are ignored.  `camera`: the camera the frame and the G-buffer were made with; `spp`: the frame's
- * samples per pixel — render every frame in at least 2 chunks, or its variance is +inf, which is carried as 2^32.
+ * samples per pixel — render every frame in at least 2 chunks, or its variance is +inf, which is carried as 2^32 (or use
+ * the moments mode below, which takes the variance from the history: rayz_hip_temporal_step_moments).
  * params_or_null == NULL: all defaults.  The first step of a handle, and the first after rayz_hip_temporal_reset, has no
  * history: its outputs are its inputs (the variance clamped to [0, 2^32], a NaN taken as 2^32).
  * Asynchronous on `hip_stream` (NULL: the library's stream of the handle's device); the inputs must stay allocated until the step
@@ -737,6 +738,41 @@ int rayz_hip_temporal_reset(RayzTemporal* tm);
 /* Waits for the handle's last step and returns its HIP-event time in *ms (may be NULL: just wait).  RAYZ_ERR_STATE before any step. */
 int rayz_hip_temporal_timing(RayzTemporal* tm, float* ms);
 int rayz_hip_temporal_destroy(RayzTemporal* tm);
+
+/* ---- temporal accumulation, moments mode: the variance from the history, for one-chunk frames -------
+ * BUILD-DEFINED, additive within ABI 5.  A frame of one chunk (1 .. 16 spp under the automatic schedule), a one-shot
+ * rayz_hip_render_device frame or a gathered multi-GPU frame has no per-pixel variance to feed rayz_hip_temporal_step.  A handle in
+ * MOMENTS MODE needs none: as SVGF does, it accumulates the second moment of the colour with the same blend as the colour and
+ * reports, per channel, max(m2 - c^2, 0) * W2 / (1 - W2) — W2 being the sum of the squared weights of the frames in the
+ * accumulated colour, 1/W2 the effective frame count.  Where the history is too short (W2 > w2_max: a first frame, a
+ * disocclusion) the variance is estimated over the CURRENT frame's 7x7 neighbourhood on the same surface (same hittable, normals
+ * within normal_cos_min; fewer than min_taps accepted taps: 2^32, "trust the guides only").  The colour and the history length of a
+ * moments step equal the plain step's bit for bit.  The arithmetic is a contract (§4.16), restated by
+ * tests/temporal_moments_mirror.cpp. */
+#define RAYZ_TEMPORAL_MOMENTS_DEFAULT_W2_MAX 0.25   /* these two: PROVISIONAL until DESIGN.md §6's measurement; parameters, not contract */
+#define RAYZ_TEMPORAL_MOMENTS_DEFAULT_MIN_TAPS 4.0
+
+typedef struct RayzTemporalMomentsParams {
+    double w2_max;   /* in [0, 1]: the spatial estimate is taken where W2 > this (0: always; 1: never) */
+    double min_taps; /* in [2, 49]: .. and needs at least this many accepted taps of the 49 */
+} RayzTemporalMomentsParams; /* both are used as f32 */
+
+/* Puts the handle into moments mode: one more 16-byte record per pixel on each ping-pong side (160 bytes per pixel instead of
+ * 128).  Allowed only while the handle has no history — after _create or after rayz_hip_temporal_reset — else RAYZ_ERR_STATE; a
+ * second call is RAYZ_OK and does nothing.  If the allocation fails the handle stays a plain one.  From then on the handle takes
+ * _step_moments and refuses _step with RAYZ_ERR_STATE (a plain handle refuses _step_moments the same way); _reset, _timing and
+ * _destroy serve both kinds. */
+int rayz_hip_temporal_track_moments(RayzTemporal* tm);
+/* One frame, as rayz_hip_temporal_step without the variance input.  d_var_out: height*width*3 floats, the variance of each
+ * channel of d_rgb_out's accumulated mean (0 on background pixels), in [0, 2^32]; d_w2_out_or_null: height*width floats, W2 after
+ * the step (1 where no history was found).  d_rgb_out == d_rgb_in is NOT allowed: neighbours read the current frame.
+ * mparams_or_null == NULL: the defaults above.  RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): what
+ * rayz_hip_temporal_step refuses, minus the variance input; w2_max outside [0, 1]; min_taps outside [2, 49] (a NaN fails both);
+ * d_rgb_out == d_rgb_in.  RAYZ_ERR_STATE: a bad handle, or one that is not in moments mode. */
+int rayz_hip_temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params_or_null,
+                                   const RayzTemporalMomentsParams* mparams_or_null, const RayzCameraDesc* camera, uint32_t spp,
+                                   const float* d_rgb_in, const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out,
+                                   float* d_length_out_or_null, float* d_w2_out_or_null, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,7 @@ DENOISE_GUIDED_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE
 NOISE_DEFAULTS = {"rel_error": 0.05, "mean_floor": 0.02}
 ADAPTIVE_DEFAULT_MIN_CHUNKS = 4
 TEMPORAL_DEFAULTS = {"alpha_min": 0.05, "n_max": 65536.0, "normal_cos_min": 0.9, "max_rel_dist": 0.05}  # provisional
+TEMPORAL_MOMENTS_DEFAULTS = {"w2_max": 0.25, "min_taps": 4.0}  # provisional
 
 D3 = C.c_double * 3
 
@@ -127,12 +128,16 @@ class TemporalParams(C.Structure):
     _fields_ = [("alpha_min", C.c_double), ("n_max", C.c_double), ("normal_cos_min", C.c_double), ("max_rel_dist", C.c_double)]
 
 
+class TemporalMomentsParams(C.Structure):
+    _fields_ = [("w2_max", C.c_double), ("min_taps", C.c_double)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
 assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
-assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32
+assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32 and C.sizeof(TemporalMomentsParams) == 16
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -233,6 +238,10 @@ PROTOTYPES = [
     ("rayz_hip_temporal_reset", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rayz_hip_temporal_destroy", C.c_int, [C.c_void_p]),
+    ("rayz_hip_temporal_track_moments", C.c_int, [C.c_void_p]),
+    ("rayz_hip_temporal_step_moments", C.c_int,
+     [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(TemporalMomentsParams), C.POINTER(CameraDesc), C.c_uint32, C.c_void_p,
+      C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 

@@ -14,6 +14,7 @@
 #include "bvh_build.hpp"
 #include "denoise.hpp"
 #include "temporal_kernel.hpp"
+#include "temporal_moments_kernel.hpp"
 #include "noise.hpp"
 #include "adaptive.hpp"
 #include "host_base.hpp"
@@ -1341,3 +1342,4 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "frame_handle.hpp"
 #include "denoiser.hpp"
 #include "temporal.hpp"
+#include "temporal_moments.hpp"

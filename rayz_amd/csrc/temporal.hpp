@@ -1,5 +1,5 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
-// temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp).
+// temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp).
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
@@ -12,6 +12,8 @@ struct RayzTemporal : FrameHandle<2 * 4, 2> {
     RayzCameraDesc cam{};   // the last step's camera, with its M and from: what the next step projects with
     float M[9] = {}, from[3] = {};
     bool timed = false;     // the last step ran to its end: ev[0] .. ev[1] is its time
+    bool moments = false;   // rayz_hip_temporal_track_moments: the handle takes _step_moments and not _step (§4.16)
+    DevBuf<dn4> mom[2];     // .. and owns, per ping-pong side, one more record per pixel {m2.r, m2.g, m2.b, W2}; empty otherwise
 };
 
 namespace {
@@ -38,31 +40,29 @@ bool temporal_camera_matrix(const RayzCameraDesc* c, float* M, float* from) {
     return true;
 }
 
-// Every argument is checked before the handle, and nothing here touches a device until all of them passed.
-int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, const float* d_in,
-                  const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, void* stream_arg) {
-    RayzTemporalParams p{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
-                         RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
-    if (params) p = *params;
+// The checks both kinds of step make of the parameters and the sample count ..
+int temporal_params_check(const RayzTemporalParams& p, uint32_t spp) {
     if (!(p.alpha_min >= 0 && p.alpha_min <= 1)) return fail(RAYZ_ERR_BAD_ARG, "temporal alpha_min %g: must lie in [0, 1]", p.alpha_min);
     if (!(p.n_max >= 1)) return fail(RAYZ_ERR_BAD_ARG, "temporal n_max %g: must be at least 1", p.n_max);
     if (!(p.normal_cos_min >= -1 && p.normal_cos_min <= 1))
         return fail(RAYZ_ERR_BAD_ARG, "temporal normal_cos_min %g: must lie in [-1, 1]", p.normal_cos_min);
     if (!(p.max_rel_dist > 0)) return fail(RAYZ_ERR_BAD_ARG, "temporal max_rel_dist %g: must be positive", p.max_rel_dist);
     if (!spp || spp > (1u << 24)) return fail(RAYZ_ERR_BAD_ARG, "temporal spp %u: must lie in 1 .. 2^24 (it is used as f32)", spp);
-    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
-    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
+    return RAYZ_OK;
+}
+
+// .. and of the guides and the camera, whose M and from they return.
+int temporal_frame_check(const RayzQueryOutputs* g, const RayzCameraDesc* cam, float* M, float* from) {
     RAYZ_TRY(frame_gbuffer_check("temporal", g));
     if (!cam) return fail(RAYZ_ERR_BAD_ARG, "temporal: null camera");
-    float M[9], from[3];
     if (!temporal_camera_matrix(cam, M, from))
         return fail(RAYZ_ERR_BAD_ARG, "temporal: the camera's px_du, px_dv and px_origin - look_from span no volume (det is 0 or not finite)");
-    RAYZ_TRY(frame_handle_check(tm));
-    hipStream_t st;
-    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
-    DeviceScope scope(tm->device);
-    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (this step reads what the previous one wrote)
-    const bool is_static = tm->has_history && std::memcmp(cam, &tm->cam, sizeof(RayzCameraDesc)) == 0;
+    return RAYZ_OK;
+}
+
+// The kernel's arguments of a step of either kind (d_var: the plain step's variance input, or NULL).
+TemporalArgs temporal_args(const RayzTemporal* tm, const RayzTemporalParams& p, uint32_t spp, const float* d_in, const float* d_var,
+                           const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out) {
     const float r = (float)p.max_rel_dist;
     TemporalArgs a{};
     a.rgb = d_in, a.var = d_var, a.index = g->index, a.normal = (const float*)g->normal, a.point = (const float*)g->point;
@@ -74,14 +74,40 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     std::memcpy(a.M, tm->M, sizeof(a.M));
     std::memcpy(a.from, tm->from, sizeof(a.from));
     a.spp = (float)spp, a.am = (float)p.alpha_min, a.nm = (float)p.n_max, a.cm = (float)p.normal_cos_min, a.r2 = r * r;
+    return a;
+}
+
+// The step is enqueued: the handle now describes the history it leaves.
+void temporal_stepped(RayzTemporal* tm, const RayzCameraDesc* cam, const float* M, const float* from) {
+    tm->cur ^= 1, tm->has_history = true, tm->cam = *cam, tm->timed = true;
+    std::memcpy(tm->M, M, sizeof(tm->M));
+    std::memcpy(tm->from, from, sizeof(tm->from));
+}
+
+// Every argument is checked before the handle, and nothing here touches a device until all of them passed.
+int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, const float* d_in,
+                  const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, void* stream_arg) {
+    RayzTemporalParams p{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
+                         RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
+    if (params) p = *params;
+    RAYZ_TRY(temporal_params_check(p, spp));
+    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
+    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
+    float M[9], from[3];
+    RAYZ_TRY(temporal_frame_check(g, cam, M, from));
+    RAYZ_TRY(frame_handle_check(tm));
+    if (tm->moments) return fail(RAYZ_ERR_STATE, "a temporal handle in moments mode takes rayz_hip_temporal_step_moments");
+    hipStream_t st;
+    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
+    DeviceScope scope(tm->device);
+    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (this step reads what the previous one wrote)
+    const bool is_static = tm->has_history && std::memcmp(cam, &tm->cam, sizeof(RayzCameraDesc)) == 0;
+    const TemporalArgs a = temporal_args(tm, p, spp, d_in, d_var, g, d_out, d_var_out, d_len_out);
     tm->timed = false; // (a step that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(tm, 0, st));
     temporal_launch_step(st, a, is_static);
     RAYZ_TRY(frame_handle_launched(tm, 1, st));
-    // the step is enqueued: the handle now describes the history it leaves
-    tm->cur ^= 1, tm->has_history = true, tm->cam = *cam, tm->timed = true;
-    std::memcpy(tm->M, M, sizeof(M));
-    std::memcpy(tm->from, from, sizeof(from));
+    temporal_stepped(tm, cam, M, from);
     return RAYZ_OK;
 }
 

@@ -1,0 +1,80 @@
+// temporal_moments.hpp — the moments mode of temporal accumulation's handle (rayz_hip_temporal_track_moments, _step_moments;
+// DESIGN.md §4.16; the kernel and its launch: temporal_moments_kernel.hpp; the handle and what both kinds of step share:
+// temporal.hpp).  Included by rayz_hip.hip after temporal.hpp.
+#pragma once
+
+namespace {
+
+// Only a handle without history may change its kind: a plain step's history has no moment records to go on from.
+int temporal_track_moments(RayzTemporal* tm) {
+    RAYZ_TRY(frame_handle_check(tm));
+    if (tm->moments) return RAYZ_OK;
+    if (tm->has_history)
+        return fail(RAYZ_ERR_STATE, "temporal track_moments: the handle has history (call it after create or after rayz_hip_temporal_reset)");
+    DeviceScope scope(tm->device);
+    DevBuf<dn4> m[2];
+    for (DevBuf<dn4>& b : m) {
+        const hipError_t e = b.alloc((size_t)tm->width * tm->height);
+        if (e != hipSuccess) return hip_fail(e, "temporal moment buffers"); // (m frees itself: the handle stays a plain one)
+    }
+    tm->mom[0] = std::move(m[0]), tm->mom[1] = std::move(m[1]);
+    tm->moments = true;
+    return RAYZ_OK;
+}
+
+// Every argument is checked before the handle, and nothing here touches a device until all of them passed.
+int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, const RayzTemporalMomentsParams* mparams,
+                          const RayzCameraDesc* cam, uint32_t spp, const float* d_in, const RayzQueryOutputs* g, float* d_out,
+                          float* d_var_out, float* d_len_out, float* d_w2_out, void* stream_arg) {
+    RayzTemporalParams p{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
+                         RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
+    RayzTemporalMomentsParams mp{RAYZ_TEMPORAL_MOMENTS_DEFAULT_W2_MAX, RAYZ_TEMPORAL_MOMENTS_DEFAULT_MIN_TAPS};
+    if (params) p = *params;
+    if (mparams) mp = *mparams;
+    RAYZ_TRY(temporal_params_check(p, spp));
+    if (!(mp.w2_max >= 0 && mp.w2_max <= 1)) return fail(RAYZ_ERR_BAD_ARG, "temporal w2_max %g: must lie in [0, 1]", mp.w2_max);
+    if (!(mp.min_taps >= 2 && mp.min_taps <= 49)) return fail(RAYZ_ERR_BAD_ARG, "temporal min_taps %g: must lie in [2, 49]", mp.min_taps);
+    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
+    if (!d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer");
+    if (d_out == d_in)
+        return fail(RAYZ_ERR_BAD_ARG, "temporal: a moments step cannot run in place (d_rgb_out == d_rgb_in: neighbours read the current frame)");
+    float M[9], from[3];
+    RAYZ_TRY(temporal_frame_check(g, cam, M, from));
+    RAYZ_TRY(frame_handle_check(tm));
+    if (!tm->moments) return fail(RAYZ_ERR_STATE, "a plain temporal handle takes rayz_hip_temporal_step (rayz_hip_temporal_track_moments first)");
+    hipStream_t st;
+    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
+    DeviceScope scope(tm->device);
+    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (this step reads what the previous one wrote)
+    const bool is_static = tm->has_history && std::memcmp(cam, &tm->cam, sizeof(RayzCameraDesc)) == 0;
+    TemporalMomentsArgs a{};
+    a.t = temporal_args(tm, p, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out);
+    a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
+    a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
+    tm->timed = false; // (a step that fails half-way leaves no timing)
+    RAYZ_TRY(frame_handle_record(tm, 0, st));
+    temporal_moments_launch_step(st, a, is_static);
+    RAYZ_TRY(frame_handle_launched(tm, 1, st));
+    temporal_stepped(tm, cam, M, from);
+    return RAYZ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int rayz_hip_temporal_track_moments(RayzTemporal* tm) {
+    return guarded([&] { return temporal_track_moments(tm); });
+}
+
+int rayz_hip_temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params_or_null,
+                                   const RayzTemporalMomentsParams* mparams_or_null, const RayzCameraDesc* camera, uint32_t spp,
+                                   const float* d_rgb_in, const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out,
+                                   float* d_length_out_or_null, float* d_w2_out_or_null, void* hip_stream) {
+    return guarded([&] {
+        return temporal_step_moments(tm, params_or_null, mparams_or_null, camera, spp, d_rgb_in, gbuffer, d_rgb_out, d_var_out,
+                                     d_length_out_or_null, d_w2_out_or_null, hip_stream);
+    });
+}
+
+} // extern "C"

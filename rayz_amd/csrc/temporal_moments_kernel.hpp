@@ -1,0 +1,203 @@
+// temporal_moments_kernel.hpp — the device code of temporal accumulation's moments mode (include/rayz_hip.h:
+// rayz_hip_temporal_step_moments; the handle and the validation: temporal_moments.hpp; the plain step: temporal_kernel.hpp).
+//
+// ONE launch per step, as the plain step: 32x8 tiles, 256 threads, the taps in two rounds of loads.  The colour and the length are
+// the plain step's, operation for operation (§4.15 steps 1-4); the variance comes from the history instead of from the caller: a
+// fifth record per pixel, {m2.r, m2.g, m2.b, W2}, carries the second moment of the colour under the same blend and the sum of the
+// squared frame weights, and v = max(m2 − c², 0)·W2 / (1 − W2).  Where the history is too short to say anything (W2 > w2_max: a
+// first frame, a disocclusion) the variance is estimated over the CURRENT frame's 7x7 neighbourhood on the same surface.
+//
+// That neighbourhood is the only part that reads other pixels of the current frame, and the only part that uses LDS: every thread
+// first finishes its pixel's temporal part and learns whether it needs the spatial estimate, the workgroup votes, and only a
+// workgroup with at least one such pixel stages its tile plus a 3-pixel halo (38x14 positions of {r, g, b, bits(index)} and
+// {n.x, n.y, n.z, 0}: 17,024 bytes) and runs the 49 taps from there.  A workgroup whose history is settled costs the plain step plus
+// one record each way.
+//
+// THE BARRIERS: the vote and the barrier behind the staging are reached by all 256 threads of a workgroup, always.  A thread whose
+// pixel lies outside the frame does not return early as the plain kernel's does: it votes "no", helps to stage, and skips only the
+// per-pixel work and the stores.  The staging branch is taken by a whole workgroup or by none (the vote's result is the same in
+// every thread), so the barrier inside it is not under divergent control flow.
+#pragma once
+
+#include "temporal_kernel.hpp"
+
+namespace rayz_dev {
+
+constexpr int kTmHalo = 3;                                                    // the spatial estimate's taps: −3 .. 3 on both axes
+constexpr int kTmLdsW = kDnTileW + 2 * kTmHalo, kTmLdsH = kDnTileH + 2 * kTmHalo; // 38 x 14 staged positions
+constexpr int kTmOutside = (int)0x80000000;                                   // the index of a staged position outside the frame: equals no id >= 0
+
+struct TemporalMomentsArgs {
+    TemporalArgs t;    // the plain step's arguments; t.var is not read, t.var_out receives v_out, t.prev.v is not read
+    const dn4* prev_m; // per pixel {m2.r, m2.g, m2.b, W2}: the history's second moment and its sum of squared frame weights
+    dn4* next_m;
+    float* w2_out;     // or NULL
+    float wm, mt;      // f32 of w2_max and min_taps
+};
+
+struct TmAcc {
+    float B, Hr, Hg, Hb, N, Qr, Qg, Qb, W;
+};
+
+// An accepted tap of bilinear weight b: its colour + length and moment records join the sums, in tap order.
+__device__ __forceinline__ void tm_add(const dn4 c, const dn4 m, float b, TmAcc& acc) {
+    acc.B = acc.B + b;
+    acc.Hr = __builtin_fmaf(b, c.x, acc.Hr);
+    acc.Qr = __builtin_fmaf(b, m.x, acc.Qr);
+    acc.Hg = __builtin_fmaf(b, c.y, acc.Hg);
+    acc.Qg = __builtin_fmaf(b, m.y, acc.Qg);
+    acc.Hb = __builtin_fmaf(b, c.z, acc.Hb);
+    acc.Qb = __builtin_fmaf(b, m.z, acc.Qb);
+    acc.N = __builtin_fmaf(b, c.w, acc.N);
+    acc.W = __builtin_fmaf(b, m.w, acc.W);
+}
+
+// §4.16 step 3 for one channel: the variance of the accumulated mean from its second moment.
+__device__ __forceinline__ float tm_temporal_var(float m2, float c, float W2) {
+    const float e = m2 - (c * c);
+    const float ep = e > 0.0f ? e : 0.0f;
+    return dn_clamp_var((ep * W2) / (1.0f - W2));
+}
+
+// §4.16 step 4 for one channel, behind the sums: the unbiased sample variance of the neighbourhood, scaled to the mean's weight.
+__device__ __forceinline__ float tm_spatial_var(float S0, float S1, float S2, float W2) {
+    const float mu = S1 / S0;
+    const float d = S2 / S0 - mu * mu;
+    const float dp = d > 0.0f ? d : 0.0f;
+    return dn_clamp_var(((dp * S0) / (S0 - 1.0f)) * W2);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_step_kernel(const TemporalMomentsArgs m) {
+    const TemporalArgs& a = m.t;
+    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
+    const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
+    const int x = (int)(blockIdx.x * kDnTileW) + tx, y = (int)(blockIdx.y * kDnTileH) + ty;
+    const bool inside = x < (int)a.width && y < (int)a.height; // NO early return: every thread reaches the vote and the barrier
+    const size_t p = inside ? (size_t)y * a.width + (size_t)x : 0;
+    float cr = 0.0f, cg = 0.0f, cb = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, Px = 0.0f, Py = 0.0f, Pz = 0.0f;
+    float or_ = 0.0f, og = 0.0f, ob = 0.0f, No = 0.0f, qr = 0.0f, qg = 0.0f, qb = 0.0f, W2 = 1.0f, vr = 0.0f, vg = 0.0f, vb = 0.0f;
+    int32_t id = -1;
+    bool spatial = false;
+    if (inside) {
+        cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
+        id = a.index[p];
+        nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
+        Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
+        or_ = cr, og = cg, ob = cb, No = a.spp;              // no history: the input, by selection ..
+        qr = cr * cr, qg = cg * cg, qb = cb * cb, W2 = 1.0f; // .. its square, and the weight of one frame
+        if (id >= 0 && a.has_history) {
+            const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
+            const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
+            TmAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            if (STATIC) {
+                if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim)) tm_add(a.prev.c[p], m.prev_m[p], 1.0f, acc);
+            } else {
+                const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
+                const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
+                const float ga = __builtin_fmaf(a.M[8], wz, __builtin_fmaf(a.M[7], wy, a.M[6] * wx));
+                if (ga > 0.0f) {
+                    const float hx = al / ga, hy = be / ga;
+                    if (hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height) { // (so the casts below are in range)
+                        const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
+                        const float fx = hx - x0, fy = hy - y0;
+                        const int ix = (int)x0, iy = (int)y0;
+                        // Two rounds of loads, as in the plain step: every tap's guide records, then its colour and moment records.
+                        // A tap outside the frame loads the nearest pixel inside it (a valid address) and is refused.
+                        size_t q[4];
+                        bool ok[4];
+                        dn4 g[4], pp[4];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const int qx = ix + (t & 1), qy = iy + (t >> 1);
+                            ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
+                            const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
+                            const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
+                            q[t] = (size_t)cy * a.width + (size_t)cx;
+                            g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
+                        }
+                        dn4 c[4], mm[4];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
+                            c[t] = a.prev.c[q[t]], mm[t] = m.prev_m[q[t]];
+                        }
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
+                            if (ok[t]) tm_add(c[t], mm[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
+                    }
+                }
+            }
+            if (acc.B >= kTaMinWeight) {
+                const float hN = acc.N / acc.B;
+                const float Ns = hN + a.spp;
+                const float a0 = a.spp / Ns;
+                const float alpha = a0 < a.am ? a.am : a0;
+                const float k = 1.0f - alpha;
+                const float a2 = alpha * alpha, k2 = k * k;
+                const float hr = acc.Hr / acc.B, hg = acc.Hg / acc.B, hb = acc.Hb / acc.B;
+                or_ = __builtin_fmaf(alpha, cr - hr, hr);
+                og = __builtin_fmaf(alpha, cg - hg, hg);
+                ob = __builtin_fmaf(alpha, cb - hb, hb);
+                const float hqr = acc.Qr / acc.B, hqg = acc.Qg / acc.B, hqb = acc.Qb / acc.B;
+                qr = __builtin_fmaf(alpha, cr * cr - hqr, hqr);
+                qg = __builtin_fmaf(alpha, cg * cg - hqg, hqg);
+                qb = __builtin_fmaf(alpha, cb * cb - hqb, hqb);
+                W2 = __builtin_fmaf(k2, acc.W / acc.B, a2);
+                No = Ns > a.nm ? a.nm : Ns;
+            }
+        }
+        spatial = id >= 0 && W2 > m.wm;
+        if (id >= 0 && !spatial) vr = tm_temporal_var(qr, or_, W2), vg = tm_temporal_var(qg, og, W2), vb = tm_temporal_var(qb, ob, W2);
+    }
+    // The vote: reached by every thread of the workgroup; its result is the same in all of them.
+    if (__syncthreads_or(spatial ? 1 : 0)) {
+        const int bx = (int)(blockIdx.x * kDnTileW) - kTmHalo, by = (int)(blockIdx.y * kDnTileH) - kTmHalo;
+        for (int t = (int)threadIdx.x; t < kTmLdsW * kTmLdsH; t += 256) { // (t < 532: inside both arrays)
+            const int gx = bx + t % kTmLdsW, gy = by + t / kTmLdsW;
+            dn4 vc{0.0f, 0.0f, 0.0f, __int_as_float(kTmOutside)}, vn{0.0f, 0.0f, 0.0f, 0.0f};
+            if (gx >= 0 && gx < (int)a.width && gy >= 0 && gy < (int)a.height) {
+                const size_t q = (size_t)gy * a.width + (size_t)gx;
+                vc = dn4{a.rgb[3 * q], a.rgb[3 * q + 1], a.rgb[3 * q + 2], __int_as_float(a.index[q])};
+                vn = dn4{a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2], 0.0f};
+            }
+            s_col[t] = vc, s_nrm[t] = vn;
+        }
+        __syncthreads(); // all 256 threads are here: the branch is the workgroup's, not a thread's
+        if (spatial) {
+            float S0 = 0.0f, S1r = 0.0f, S1g = 0.0f, S1b = 0.0f, S2r = 0.0f, S2g = 0.0f, S2b = 0.0f;
+            const int centre = (ty + kTmHalo) * kTmLdsW + tx + kTmHalo; // taps: centre + j·38 + i stays within [0, 532)
+            for (int j = -kTmHalo; j <= kTmHalo; ++j)
+#pragma unroll
+                for (int i = -kTmHalo; i <= kTmHalo; ++i) {
+                    const int s = centre + j * kTmLdsW + i;
+                    const dn4 qc = s_col[s], qn = s_nrm[s];
+                    if (__float_as_int(qc.w) == id && ((i == 0 && j == 0) || dn_dot(qn.x, qn.y, qn.z, nx, ny, nz) >= a.cm)) {
+                        S0 = S0 + 1.0f;
+                        S1r = S1r + qc.x, S1g = S1g + qc.y, S1b = S1b + qc.z;
+                        S2r = __builtin_fmaf(qc.x, qc.x, S2r), S2g = __builtin_fmaf(qc.y, qc.y, S2g), S2b = __builtin_fmaf(qc.z, qc.z, S2b);
+                    }
+                }
+            vr = vg = vb = kDnVarCap;
+            if (S0 >= m.mt) vr = tm_spatial_var(S0, S1r, S2r, W2), vg = tm_spatial_var(S0, S1g, S2g, W2), vb = tm_spatial_var(S0, S1b, S2b, W2);
+        }
+    }
+    if (!inside) return; // (behind the last barrier)
+    a.next.c[p] = dn4{or_, og, ob, No};
+    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
+    a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
+    a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
+    m.next_m[p] = dn4{qr, qg, qb, W2};
+    a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
+    a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
+    if (a.len_out) a.len_out[p] = No;
+    if (m.w2_out) m.w2_out[p] = W2;
+}
+
+// ---- host side: the launch (temporal_moments.hpp owns the validation) ------------------------------------------------------------
+inline void temporal_moments_launch_step(hipStream_t st, const TemporalMomentsArgs& m, bool is_static) {
+    const dim3 grid = denoise_grid(m.t.width, m.t.height), block(256);
+    if (is_static) hipLaunchKernelGGL((temporal_moments_step_kernel<true>), grid, block, 0, st, m);
+    else hipLaunchKernelGGL((temporal_moments_step_kernel<false>), grid, block, 0, st, m);
+}
+
+} // namespace rayz_dev

@@ -576,11 +576,12 @@ class Denoiser(_Handle):
 class Temporal(_Handle):
     """Temporal accumulation for whole float32 frames of one size (`rayz_hip_temporal_*`): every `step` blends
     the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
-    per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init()."""
+    per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init().  `moments` True: the
+    handle is put into moments mode (`track_moments`, §4.16) and takes `step_moments`, which needs no variance input."""
 
     _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
-    def __init__(self, width: int, height: int, device: int | None = None):
+    def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False):
         self._lib = capi.load()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
@@ -588,6 +589,17 @@ class Temporal(_Handle):
                                                                  C.byref(self._h)), "rayz_hip_temporal_create")
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last step: kept alive until the next step or close() (the kernel may still use them)
+        if moments:
+            try:
+                self.track_moments()
+            except Exception:
+                self.close()
+                raise
+
+    def track_moments(self) -> None:
+        """Puts the handle into moments mode (`rayz_hip_temporal_track_moments`): only while it has no history — after creation
+        or after `reset` —; a second call does nothing.  From then on the handle takes `step_moments` and refuses `step`."""
+        capi.check(self._lib, self._lib.rayz_hip_temporal_track_moments(self._h), "rayz_hip_temporal_track_moments")
 
     def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
              stream: int = 0, **params):
@@ -620,6 +632,49 @@ class Temporal(_Handle):
         capi.check(self._lib, rc, "rayz_hip_temporal_step")
         self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length)
         return (out, var_out) if length is None else (out, var_out, length)
+
+    def step_moments(self, rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
+                     w2=False, stream: int = 0, **params):
+        """One frame of a handle in moments mode (`rayz_hip_temporal_step_moments`): as `step` without `var_rgb` —
+        the variance of the accumulated mean comes from the history's second moment, or where the history is too short from the
+        frame's 7x7 neighbourhood on the same surface, so `rgb` may be a one-chunk frame from any source.  Returns (out, var_out)
+        — new tensors by default; `out` must not be `rgb`: neighbours read the current frame — then, with `length` True or a
+        (height, width) float32 tensor, the history length in samples, then, with `w2` likewise, W2 (the sum of the squared weights
+        of the frames in `out`; 1 / W2 is the effective frame count).  `params`: the fields of RayzTemporalParams and of
+        RayzTemporalMomentsParams (w2_max, min_taps); unnamed ones take capi.TEMPORAL_DEFAULTS and
+        capi.TEMPORAL_MOMENTS_DEFAULTS.  Asynchronous on `stream`, as `step`."""
+        import torch
+
+        unknown = set(params) - set(capi.TEMPORAL_DEFAULTS) - set(capi.TEMPORAL_MOMENTS_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown temporal parameter(s) {sorted(unknown)}; choose from "
+                             f"{sorted({**capi.TEMPORAL_DEFAULTS, **capi.TEMPORAL_MOMENTS_DEFAULTS})}")
+        prm = _params(capi.TemporalParams, capi.TEMPORAL_DEFAULTS, {k: v for k, v in params.items() if k in capi.TEMPORAL_DEFAULTS},
+                      "temporal")
+        mprm = _params(capi.TemporalMomentsParams, capi.TEMPORAL_MOMENTS_DEFAULTS,
+                       {k: v for k, v in params.items() if k in capi.TEMPORAL_MOMENTS_DEFAULTS}, "temporal")
+        frame = (self.height, self.width, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"]
+        if out is rgb or (isinstance(out, torch.Tensor) and isinstance(rgb, torch.Tensor) and out.data_ptr() == rgb.data_ptr()):
+            raise ValueError("out must not be rgb: a moments step cannot run in place (neighbours read the current frame)")
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=dev)
+        if var_out is None:
+            var_out = torch.empty(frame, dtype=torch.float32, device=dev)
+        length, w2 = _optional_out(length, frame[:2], dev), _optional_out(w2, frame[:2], dev)
+        _check_frame_tensors("the temporal handle", self._device, frame, [("rgb", rgb)], gbuffer, need,
+                             [("out", out, frame), ("var_out", var_out, frame), ("length", length, frame[:2]), ("w2", w2, frame[:2])])
+        _stream_prologue(stream, self._device)
+        o = _gbuffer_pointers(gbuffer, need)
+        rc = self._lib.rayz_hip_temporal_step_moments(self._h, C.byref(prm), C.byref(mprm), C.byref(camera), int(spp),
+                                                      C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
+                                                      C.c_void_p(var_out.data_ptr()),
+                                                      C.c_void_p(length.data_ptr() if length is not None else None),
+                                                      C.c_void_p(w2.data_ptr() if w2 is not None else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_temporal_step_moments")
+        self._inflight = (rgb, gbuffer, out, var_out, length, w2)
+        return (out, var_out) + tuple(t for t in (length, w2) if t is not None)
 
     def reset(self) -> None:
         """Forgets the history: the next step is a first frame (`rayz_hip_temporal_reset`)."""

@@ -17,7 +17,23 @@ is read from outside the tree.
 (d) The sweep the defaults are to be chosen from: alpha_min x max_rel_dist, the mean over the panned frames of (b)'s temporal and
     temporal + guided MSE ratios to the raw frame, and of (c).
 
-    python tools/temporal_bench.py [--frames 16] [--pan 3] [--spp 16] [--ref-spp 1024] [--reps 100] [--warmup 10] [--width 1920] [--json FILE]"""
+    python tools/temporal_bench.py [--frames 16] [--pan 3] [--spp 16] [--ref-spp 1024] [--reps 100] [--warmup 10] [--width 1920] [--json FILE]
+
+--moments measures the moments mode instead (rayz_hip_temporal_step_moments), on the same sequence with every
+frame rendered TWICE from one seed: in ONE chunk by `render_into` (no variance: what the moments step takes) and in two chunks by
+a tracked progressive handle (frame + variance: what the plain step takes).
+(a) Cost, plain and moments step by the handles' own HIP events in the same process, each beside a device copy of its compulsory
+    bytes.  The moments step's: the current colour and guides in (40 B per pixel), one history record in — colour + length, normal
+    + index, point, moments; the variance record is not read — (64 B), five history records, colour and variance out (104 B):
+    208 B per pixel, a copy of 104 B per pixel.  Four states: a first frame (every workgroup stages its tile for the spatial
+    estimate), a second static frame (W2 = 1/2 > w2_max: still every workgroup), a static and a panned step on a SETTLED history
+    of --settle frames (W2 < w2_max: no workgroup, or only those at disocclusions).
+(b) Quality.  Per frame, MSE against the --ref-spp frame of: the raw one-chunk frame; plain step on the two-chunk tracked frame,
+    then `run_guided`; moments step on the one-chunk frame, then `run_guided`; and the share of hit pixels with W2 > w2_max.
+(c) The sweep the defaults are to be chosen from: w2_max x min_taps, the first frame's and the mean over the later frames of (b)'s
+    moments + guided MSE ratio to the raw frame.
+
+    python tools/temporal_bench.py --moments [--settle 6] [the switches above]"""
 import argparse
 import json
 import os
@@ -31,6 +47,7 @@ import torch  # noqa: E402
 from rayz_amd import capi, render, tracer  # noqa: E402
 
 STEP_BYTES = 52 + 64 + 88  # per pixel: what a step must read and write (module docstring)
+MOMENTS_STEP_BYTES = 40 + 64 + 104  # .. and a moments step
 
 
 def panned(cam, pixels):
@@ -58,6 +75,147 @@ def copy_ms(n_bytes, reps, warmup):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def main_moments(args):
+    """--moments: see the module docstring."""
+    render.init(0)
+    t = tracer.randomBouncing(args.width, -50, 50, seed=42)  # config 3
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    assert args.spp % 2 == 0 and args.spp <= 16, "--moments wants an even spp of at most 16: one automatic chunk, two tracked ones"
+    ds = render.DeviceScene(sd)
+    res = {"mode": "moments", "size": f"{w}x{h}", "frames": args.frames, "pan_px": args.pan, "spp": args.spp, "ref_spp": args.ref_spp,
+           "reps": args.reps, "settle": args.settle, "step_bytes_per_pixel": STEP_BYTES, "moments_step_bytes_per_pixel": MOMENTS_STEP_BYTES}
+    seq = []
+    for k in range(args.frames):
+        c = panned(cam, args.pan * k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed, q.chunk_spp = 1000 + k, 0
+        one = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")  # the frame in ONE chunk: no variance to be had
+        torch.cuda.synchronize()
+        ds.render_into(c, q, one.data_ptr())
+        ds.sync()
+        q.chunk_spp = args.spp // 2
+        pr = ds.progressive(c, q, track_noise=True)  # the same seed in two chunks, tracked: another summation tree, and a variance
+        two = torch.empty_like(one)
+        torch.cuda.synchronize()
+        while not pr.done:
+            pr.step(0, two.data_ptr())
+        assert pr.chunks_done == 2
+        var = pr.noise_rgb()
+        pr.stats()
+        pr.close()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        q.samples_per_px, q.chunk_spp, q.seed = args.ref_spp, 0, 7
+        ref = torch.empty_like(one)
+        torch.cuda.synchronize()
+        ds.render_into(c, q, ref.data_ptr())
+        ds.sync()
+        seq.append((c, one, two, var, g, ref))
+        print(f"frame {k}: {args.spp} spp in one chunk and in two, reference {args.ref_spp} spp", flush=True)
+    mse = lambda a, ref: float(((a.double() - ref.double()) ** 2).mean())  # noqa: E731
+
+    # ---- (a) cost -------------------------------------------------------------------------------------------------------------
+    res["copy"] = {}
+    for name, nbytes in (("plain", STEP_BYTES), ("moments", MOMENTS_STEP_BYTES)):
+        cp = copy_ms(n * nbytes // 2, args.reps, args.warmup)
+        res["copy"][name] = {"ms": cp[0], "min": cp[1], "max": cp[2]}
+        print(f"copy moving a {name} step's compulsory bytes ({n * nbytes / 1e6:.1f} MB read + written): {cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}] "
+              f"({n * nbytes / cp[0] / 1e9:.2f} TB/s)", flush=True)
+    plain, mom = render.Temporal(w, h), render.Temporal(w, h, moments=True)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    length, w2 = torch.empty((h, w), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda")
+
+    def plain_step(s):
+        plain.step(s[2], s[3], s[4], s[0], args.spp, out=out, var_out=vout, length=length)
+
+    def moments_step(s, **prm):
+        mom.step_moments(s[1], s[4], s[0], args.spp, out=out, var_out=vout, length=length, w2=w2, **prm)
+
+    # (state, steps before the timed one, the timed frame)
+    states = [("first", 0, 0), ("static-second", 1, 0), ("static-settled", args.settle, 0), ("panned-settled", args.settle, 1)]
+    res["cost"] = {}
+    for what, before, last in states:
+        row = {}
+        for name, tm, step, nbytes in (("plain", plain, plain_step, STEP_BYTES), ("moments", mom, moments_step, MOMENTS_STEP_BYTES)):
+            ms = []
+            for r in range(args.warmup + args.reps):
+                tm.reset()
+                for _ in range(before):
+                    step(seq[0])
+                step(seq[last])
+                x = tm.timing()
+                if r >= args.warmup:
+                    ms.append(x)
+            med = statistics.median(ms)
+            cpm = res["copy"][name]["ms"]
+            row[name] = {"ms": med, "min": min(ms), "max": max(ms), "ratio_to_copy": med / cpm}
+            print(f"{name:7s} step, {what:14s}: {med:.4f} ms [{min(ms):.4f}, {max(ms):.4f}] = {med / cpm:.2f} x the copy of its compulsory bytes "
+                  f"({n * nbytes / med / 1e9:.2f} TB/s of them)", flush=True)
+        if what != "first":
+            torch.cuda.synchronize()
+            hit = seq[last][4].index >= 0
+            row["share_spatial"] = float((w2[hit] > capi.TEMPORAL_MOMENTS_DEFAULTS["w2_max"]).float().mean())
+            print(f"        {what}: {row['share_spatial']:.4f} of the hit pixels took the spatial estimate", flush=True)
+        row["moments_over_plain"] = row["moments"]["ms"] / row["plain"]["ms"]
+        res["cost"][what] = row
+
+    # ---- (b) quality at the defaults; (c) the sweep ------------------------------------------------------------------------------
+    dn = render.Denoiser(w, h)
+    den = torch.empty_like(out)
+    plain.reset()
+    rows = []
+    for k, s in enumerate(seq):
+        plain_step(s)
+        dn.run_guided(out, vout, s[4], out=den)
+        torch.cuda.synchronize()
+        rows.append({"frame": k, "mse_raw": mse(s[1], s[5]), "mse_raw_two_chunks": mse(s[2], s[5]), "mse_plain": mse(out, s[5]),
+                     "mse_plain_guided": mse(den, s[5])})
+
+    def run(**prm):
+        mom.reset()
+        got = []
+        for k, s in enumerate(seq):
+            moments_step(s, **prm)
+            dn.run_guided(out, vout, s[4], out=den)
+            torch.cuda.synchronize()
+            hit = s[4].index >= 0
+            wm = prm.get("w2_max", capi.TEMPORAL_MOMENTS_DEFAULTS["w2_max"])
+            got.append({"mse_moments": mse(out, s[5]), "mse_moments_guided": mse(den, s[5]),
+                        "share_spatial": float((w2[hit] > wm).float().mean()) if bool(hit.any()) else 0.0})
+        return got
+
+    for row, m in zip(rows, run()):
+        row.update(m)
+        r = row["mse_raw"]
+        print(f"frame {row['frame']:2d}: MSE raw (one chunk) {r:.4e}; plain step on the two-chunk frame x{row['mse_plain'] / r:.4f}, + guided "
+              f"x{row['mse_plain_guided'] / r:.4f}; moments step x{row['mse_moments'] / r:.4f}, + guided x{row['mse_moments_guided'] / r:.4f}; "
+              f"{row['share_spatial']:.4f} of the hit pixels took the spatial estimate", flush=True)
+    res["defaults"] = {"params": {**capi.TEMPORAL_DEFAULTS, **capi.TEMPORAL_MOMENTS_DEFAULTS}, "rows": rows}
+    res["sweep"] = []
+    for wm in (0.0, 0.125, 0.25, 0.5, 1.0):
+        for mt in (2.0, 4.0, 9.0, 16.0, 25.0):
+            got = run(w2_max=wm, min_taps=mt)
+            ratio = [g["mse_moments_guided"] / r["mse_raw"] for g, r in zip(got, rows)]
+            row = {"w2_max": wm, "min_taps": mt, "first": ratio[0], "second": ratio[1], "mean_later": statistics.mean(ratio[1:]), "last": ratio[-1],
+                   "share_spatial_later": statistics.mean(g["share_spatial"] for g in got[1:])}
+            res["sweep"].append(row)
+            print(f"  w2_max {wm:g} min_taps {mt:g}: moments + guided MSE / raw: first frame {row['first']:.4f}, second {row['second']:.4f}, mean over "
+                  f"frames 1.. {row['mean_later']:.4f}, last {row['last']:.4f}; spatial share on frames 1.. {row['share_spatial_later']:.4f}", flush=True)
+    plain.close()
+    mom.close()
+    dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -69,7 +227,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--json", default=None, help="also write the figures to this file")
+    ap.add_argument("--moments", action="store_true", help="measure the moments mode (DESIGN.md §4.16) beside the plain step")
+    ap.add_argument("--settle", type=int, default=6, help="--moments: static frames behind a 'settled' history (W2 = 1 / settle)")
     args = ap.parse_args()
+    if args.moments:
+        return main_moments(args)
     render.init(0)
     t = tracer.randomBouncing(args.width, -50, 50, seed=42)  # config 3
     t.samples_per_px, t.max_bounces = args.spp, 50
