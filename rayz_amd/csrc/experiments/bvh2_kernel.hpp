@@ -4,6 +4,20 @@
 #pragma once
 
 constexpr uint32_t kBvh2Wg = 256; // (the retired two-path kernel needs 168 VGPRs: 256-thread workgroups, 3 per CU)
+// Phases L and C as this kernel runs them: one leaf entry at a time, fetched here; the candidate's pool index fetched again
+// from its leaf record (the product fetches both entries together and carries the pool indices along: bvh_leaf_pair).
+template <class R>
+__device__ __forceinline__ uint32_t bvh_leaf_entry(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t leaf, uint32_t k, V<R> o,
+                                                   V<R> d, V<R> ud, R time, R tmin) {
+    typedef typename VecOf<R>::type r4;
+    const r4* rec = sc.bvh_leaf + (size_t)sc.bvh_leaf_stride * ((leaf >> 4) + k);
+    return bvh_leaf_eval<R>(sc, q, leaf, k, rec[0], rec[1], o, d, ud, time, tmin);
+}
+template <class R>
+__device__ __forceinline__ void bvh_candidate(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t slot, V<R> o, V<R> d, R time,
+                                              R tmin) {
+    bvh_candidate<R>(sc, q, slot, (int)bits(sc.bvh_leaf[(size_t)sc.bvh_leaf_stride * slot + 1].w), o, d, time, tmin);
+}
 // ---- persistent trace kernel, BVH traversal, TWO paths per lane -------------------------------------------------
 // RETIRED EXPERIMENT (round 3: bit-identical, 19 % slower — DESIGN.md §6): compiled only with -DRAYZ_EXPERIMENTS (tools/bvh2_bench.py
 // builds its own library with it); the product library does not contain it.

@@ -412,6 +412,15 @@ __device__ __forceinline__ uint32_t plane_slots(const float* stream) { return ((
 // load the scan issues next, at an offset from `at`, depends on the wait and cannot be issued in front of it.
 template <class R, int CLS> struct ScanGroup;
 
+// One sphere of a packed block as the host hands it over; the default is the pad sphere (r² = -inf: never a candidate).
+template <class R> struct BlockSphere { R cx = R(0), cy = R(0), cz = R(0), r2 = -(R)__builtin_inff(), vy = R(0); };
+
+// The packed block: G spheres, SoA, cx[G] (cy[G]) cz[G] r²[G] (vy[G]).  The static and mov-Y classes, loose and in plane runs,
+// are ONE form that differs in two facts: whether a block carries cy (kCy: loose spheres; a plane run holds its height once,
+// in the stream's head) and whether it carries vy (kVy: the mov-Y class).  A field a form lacks has no place in the stream,
+// is never loaded or read, and costs no register.  The offsets below are the layout's one statement: load() reads by them,
+// and the host writes the streams through put().
+//
 // The reject tests of a block run two spheres per instruction: each stage is ONE packed FMA (v_pk_fma_f32 for
 // R = float) whose scalar operand is an SGPR PAIR — the same field of two neighbouring spheres.  Measured on
 // gfx950 (tools/ubench): a VALU instruction that reads a different SGPR each time issues at ≈2.75 cycles, not 2,
@@ -420,25 +429,51 @@ template <class R, int CLS> struct ScanGroup;
 // bit-identical to the scalar form (and to the oracle).  discs() is written stage by stage across the group's pairs, not
 // pair by pair: a packed FMA that reads the result of the one just issued costs gfx950 an s_nop, and in this order hipcc
 // finds the other pair's FMA to put between them (the same FMAs on the same values either way).
-template <class R> struct ScanGroup<R, 0> { // static
+//
+// Plane-run blocks (kCy = false): every sphere of the run has the same cy, so cy·e2y + k2 is ONE value per ray and run, K2,
+// which the run loop (scan_plane_class) puts in the basis's k2 before the run: discs() finds it in b.k2.
+// p2 = fm(cz, e2z, fm(cx, e2x, K2)): 6 packed FMAs per sphere pair instead of 7 (static), 7 instead of 8 (mov-Y).  The same
+// three roundings as basis_p2, in another order, with the same bounds on the partial sums: the pad E stays.
+template <class R, bool kCy, bool kVy> struct PackedGroup {
     typedef typename VecOf<R>::pair pr;
     static constexpr int G = group_size<R>(), H = G / 2;
-    pr cx[H], cy[H], cz[H], r2[H];
-    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
-    static constexpr int kWords = 4; // words of the stream per sphere
+    static constexpr int kWords = 3 + kCy + kVy; // words of the stream per sphere
+    // word offset of each field inside a block (a field the form lacks: -1)
+    static constexpr int kOffCx = 0, kOffCy = kCy ? G : -1, kOffCz = (1 + kCy) * G, kOffR2 = (2 + kCy) * G, kOffVy = kVy ? (3 + kCy) * G : -1;
+    pr cx[H], cy[H], cz[H], r2[H], vy[H];
+    // Host: sphere s at slot k of a section of blocks in this form.
+    static void put(R* section, size_t k, const BlockSphere<R>& s = BlockSphere<R>()) {
+        R* blk = section + k / G * (kWords * G) + k % G;
+        blk[kOffCx] = s.cx, blk[kOffCz] = s.cz, blk[kOffR2] = s.r2;
+        if constexpr (kCy) blk[kOffCy] = s.cy;
+        if constexpr (kVy) blk[kOffVy] = s.vy;
+    }
     __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) { // g: the group's first word
         const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
 #pragma unroll
-        for (int q = 0; q < H; ++q) cx[q] = p[q], cy[q] = p[H + q], cz[q] = p[2 * H + q], r2[q] = p[3 * H + q];
+        for (int q = 0; q < H; ++q) {
+            cx[q] = p[kOffCx / 2 + q];
+            if constexpr (kCy) cy[q] = p[kOffCy / 2 + q];
+            cz[q] = p[kOffCz / 2 + q], r2[q] = p[kOffR2 / 2 + q];
+            if constexpr (kVy) vy[q] = p[kOffVy / 2 + q];
+        }
     }
-    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0])); }
+    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const {
+        if constexpr (kVy) asm volatile("" : "+s"(at) : "s"(cx[0]), "s"(vy[0]));
+        else asm volatile("" : "+s"(at) : "s"(cx[0]));
+    }
     __device__ __forceinline__ void opaque() {
 #pragma unroll
-        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cy[q]), "+s"(cz[q]), "+s"(r2[q]));
+        for (int q = 0; q < H; ++q) {
+            asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
+            if constexpr (kCy) asm volatile("" : "+s"(cy[q]));
+            if constexpr (kVy) asm volatile("" : "+s"(vy[q]));
+        }
     }
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R) const {
-        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
-            K1{b.k1, b.k1}, K2{b.k2, b.k2};
+    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, [[maybe_unused]] R time) const {
+        const R t2y = kVy ? time * b.e2y : R(0);
+        [[maybe_unused]] const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
+            K1{b.k1, b.k1}, K2{b.k2, b.k2}, T2y{t2y, t2y}; // (a form uses E2y, T2y only with the field they multiply)
         pr p1[H], p2[H], d[H];
 #pragma unroll
         for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
@@ -446,10 +481,16 @@ template <class R> struct ScanGroup<R, 0> { // static
         for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
 #pragma unroll
         for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
+        if constexpr (kCy) {
 #pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
+            for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
+        }
 #pragma unroll
         for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+        if constexpr (kVy) {
+#pragma unroll
+            for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
+        }
 #pragma unroll
         for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
 #pragma unroll
@@ -457,50 +498,28 @@ template <class R> struct ScanGroup<R, 0> { // static
 #pragma unroll
         for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
+};
+// The forms: their stream, and the slot their first block's first sphere has (DevScene's slot order).
+template <class R> struct ScanGroup<R, 0> : PackedGroup<R, true, false> { // static
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)plane_slots(sc.stat); }
 };
-template <class R> struct ScanGroup<R, 1> { // mov-Y
-    typedef typename VecOf<R>::pair pr;
-    static constexpr int G = group_size<R>(), H = G / 2;
-    pr cx[H], cy[H], cz[H], r2[H], vy[H];
+template <class R> struct ScanGroup<R, 1> : PackedGroup<R, true, true> { // mov-Y
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
-    static constexpr int kWords = 5;
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
-#pragma unroll
-        for (int q = 0; q < H; ++q)
-            cx[q] = p[q], cy[q] = p[H + q], cz[q] = p[2 * H + q], r2[q] = p[3 * H + q], vy[q] = p[4 * H + q];
-    }
-    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0]), "s"(vy[0])); }
-    __device__ __forceinline__ void opaque() {
-#pragma unroll
-        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cy[q]), "+s"(cz[q]), "+s"(r2[q]), "+s"(vy[q]));
-    }
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R time) const {
-        const R t2y = time * b.e2y;
-        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
-            K1{b.k1, b.k1}, K2{b.k2, b.k2}, T2y{t2y, t2y};
-        pr p1[H], p2[H], d[H];
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
-    }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)(sc.ns_pad + plane_slots(sc.movy)); }
+};
+template <class R> struct ScanGroup<R, 3> : PackedGroup<R, false, false> { // static, plane run
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC&) { return 0; }
+};
+template <class R> struct ScanGroup<R, 4> : PackedGroup<R, false, true> { // mov-Y, plane run
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
+};
+// A speed bucket of a y-moving plane run: the static plane form (b.k2 = the bucket's K2) on the mov-Y class's slots.
+template <class R> struct ScanGroup<R, 5> : ScanGroup<R, 3> {
+    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
+    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
 template <class R> struct ScanGroup<R, 2> { // mov-G
     typedef typename VecOf<R>::type r4;
@@ -530,93 +549,6 @@ template <class R> struct ScanGroup<R, 2> { // mov-G
         for (int k = 0; k < G; ++k) out[k] = disc(k, b, time);
     }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)(sc.ns_pad + sc.ny_pad); }
-};
-
-// Plane-run blocks (static: CLS 3, mov-Y: CLS 4): every sphere of the run has the same cy, so cy·e2y + k2 is ONE value per
-// ray and run, K2, which the run loop (scan_plane_class) puts in the basis's k2 before the run.  p2 = fm(cz, e2z, fm(cx, e2x, K2)):
-// 6 packed FMAs per sphere pair instead of 7 (static), 7 instead of 8 (mov-Y).  The same three roundings as basis_p2, in
-// another order, with the same bounds on the partial sums: the pad E stays.
-template <class R> struct ScanGroup<R, 3> { // static, plane run
-    typedef typename VecOf<R>::pair pr;
-    static constexpr int G = group_size<R>(), H = G / 2;
-    pr cx[H], cz[H], r2[H];
-    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.stat; }
-    static constexpr int kWords = 3;
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
-#pragma unroll
-        for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q];
-    }
-    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0])); }
-    __device__ __forceinline__ void opaque() {
-#pragma unroll
-        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
-    }
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R) const { // b.k2 = the run's K2
-        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2};
-        pr p1[H], p2[H], d[H];
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
-    }
-    template <class SC> static __device__ __forceinline__ int slot0(const SC&) { return 0; }
-};
-template <class R> struct ScanGroup<R, 4> { // mov-Y, plane run
-    typedef typename VecOf<R>::pair pr;
-    static constexpr int G = group_size<R>(), H = G / 2;
-    pr cx[H], cz[H], r2[H], vy[H];
-    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
-    static constexpr int kWords = 4;
-    __device__ __forceinline__ void load(const RAYZ_CONSTANT R* g) {
-        const RAYZ_CONSTANT pr* p = (const RAYZ_CONSTANT pr*)g;
-#pragma unroll
-        for (int q = 0; q < H; ++q) cx[q] = p[q], cz[q] = p[H + q], r2[q] = p[2 * H + q], vy[q] = p[3 * H + q];
-    }
-    __device__ __forceinline__ void ready(const RAYZ_CONSTANT R*& at) const { asm volatile("" : "+s"(at) : "s"(cx[0]), "s"(vy[0])); }
-    __device__ __forceinline__ void opaque() {
-#pragma unroll
-        for (int q = 0; q < H; ++q) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]), "+s"(vy[q]));
-    }
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R time) const { // b.k2 = the run's K2
-        const R t2y = time * b.e2y;
-        const pr E1x{b.e1x, b.e1x}, E1z{b.e1z, b.e1z}, E2x{b.e2x, b.e2x}, E2z{b.e2z, b.e2z}, K1{b.k1, b.k1}, K2{b.k2, b.k2},
-            T2y{t2y, t2y};
-        pr p1[H], p2[H], d[H];
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cz[q], E1z, p1[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
-#pragma unroll
-        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
-    }
-    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
-};
-
-// A speed bucket of a y-moving plane run: the static plane form (b.k2 = the bucket's K2) on the mov-Y class's slots.
-template <class R> struct ScanGroup<R, 5> : ScanGroup<R, 3> {
-    template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
-    template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
 
 // What the scan needs of one ray (one of the NR rays a lane carries).
@@ -758,7 +690,7 @@ __device__ __forceinline__ float bucket_k2(float v0, float cy, float ftime, floa
 // (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
 template <class R, int CLS, int NR>
 __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_class, ScanRay<R> (&ray)[NR], R tmin) {
-    constexpr int P = CLS == 0 ? 3 : 4, G = ScanGroup<float, CLS>::G; // words per plane sphere
+    constexpr int P = ScanGroup<float, CLS + 3>::kWords, G = ScanGroup<float, CLS>::G; // words per plane sphere: the run form's
     const RAYZ_CONSTANT float* head = ScanGroup<float, CLS>::stream(sc);
     asm volatile("" : "+s"(head));
     const RAYZ_CONSTANT uint32_t* h = (const RAYZ_CONSTANT uint32_t*)head;
@@ -1566,13 +1498,6 @@ __device__ __forceinline__ uint32_t bvh_leaf_eval(const DevScene<R>& sc, BvhQuer
     return leaf_reject_test(b, (float)time, V<float>{(float)c.x, (float)c.y, (float)c.z}, V<float>{(float)v.x, (float)v.y, (float)v.z}, (float)c.w)
                ? slot + 1u : 0u;
 }
-template <class R>
-__device__ __forceinline__ uint32_t bvh_leaf_entry(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t leaf, uint32_t k, V<R> o,
-                                                   V<R> d, V<R> ud, R time, R tmin) {
-    typedef typename VecOf<R>::type r4;
-    const r4* rec = sc.bvh_leaf + (size_t)sc.bvh_leaf_stride * ((leaf >> 4) + k);
-    return bvh_leaf_eval<R>(sc, q, leaf, k, rec[0], rec[1], o, d, ud, time, tmin);
-}
 // Both entries of a parked leaf (phase L): their records are FETCHED together — entry 1's loads do not wait for entry 0's
 // test (two dependent memory round trips per leaf phase otherwise); a leaf of one repeats entry 0's address, its second
 // result is dropped.  R = float only: the f64 kernel has no eight registers to spare and tests one entry after the other.
@@ -1605,37 +1530,16 @@ __device__ __forceinline__ void bvh_leaf_pair(const DevScene<R>& sc, BvhQuery<R>
     }
 }
 
-// Phase C — the f64 quadratic of a parked sphere candidate (same arithmetic as narrow_phase()).
+// Phase C — a parked sphere candidate: the flat list's narrow phase (narrow_eval) on the candidate's f64 record, into the
+// query's nearest hit.  bvh_candidate takes the record from the leaf-ordered f64 copy by the candidate's slot.
 template <class R>
-__device__ __forceinline__ void bvh_candidate(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t slot, int pool, V<R> o, V<R> d, R time,
-                                              R tmin);
-template <class R>
-__device__ __forceinline__ void bvh_candidate(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t slot, V<R> o, V<R> d, R time,
-                                              R tmin) {
-    bvh_candidate<R>(sc, q, slot, (int)bits(sc.bvh_leaf[(size_t)sc.bvh_leaf_stride * slot + 1].w), o, d, time, tmin);
+__device__ __forceinline__ void bvh_candidate_eval(BvhQuery<R>& q, const d4 c2, const d4 v2, int pool, V<R> o, V<R> d, R time, R tmin) {
+    narrow_eval<R>(c2, v2, pool, o, d, time, q.inv_a2, tmin, q.tbest, q.ibest);
 }
-template <class R>
-__device__ __forceinline__ void bvh_candidate_eval(BvhQuery<R>& q, const d4 c2, const d4 v2, int pool, V<R> o, V<R> d, R time, R tmin);
 template <class R>
 __device__ __forceinline__ void bvh_candidate(const DevScene<R>& sc, BvhQuery<R>& q, uint32_t slot, int pool, V<R> o, V<R> d, R time,
                                               R tmin) {
     bvh_candidate_eval<R>(q, sc.bvh_sph64[2 * slot], sc.bvh_sph64[2 * slot + 1], pool, o, d, time, tmin);
-}
-template <class R>
-__device__ __forceinline__ void bvh_candidate_eval(BvhQuery<R>& q, const d4 c2, const d4 v2, int pool, V<R> o, V<R> d, R time, R tmin) {
-    const double dx = d.x, dy = d.y, dz = d.z, tm = time;
-    const double qx = fm(v2.x, tm, c2.x - (double)o.x), qy = fm(v2.y, tm, c2.y - (double)o.y),
-                 qz = fm(v2.z, tm, c2.z - (double)o.z);
-    const double a2 = fm(dz, dz, fm(dy, dy, dx * dx));
-    const double hb2 = fm(dz, qz, fm(dy, qy, dx * qx));
-    const double cc2 = fm(qz, qz, fm(qy, qy, fm(qx, qx, -c2.w)));
-    const double disc2 = fm(-a2, cc2, hb2 * hb2);
-    if (disc2 >= 0.0) {
-        const double rt = __builtin_sqrt(disc2);
-        const R t1r = (R)((hb2 - rt) * q.inv_a2), t2r = (R)((hb2 + rt) * q.inv_a2);
-        const R t = t1r >= tmin ? t1r : t2r;
-        accept_root<R>(t, pool, tmin, q.tbest, q.ibest);
-    }
 }
 
 // Phase C of a round, as query_kernel_bvh and experiments/ run it (trace_kernel_bvh restates it: calling this there changes the f64
@@ -1771,6 +1675,14 @@ __global__ __launch_bounds__(256) void tonemap_kernel(const float* __restrict__ 
 // One thread per record; records are RAYZ_KAT_IN_STRIDE doubles in, RAYZ_KAT_OUT_STRIDE doubles out (layouts in
 // include/rayz_hip.h).  Inputs are narrowed to R exactly as the scene and camera are when they cross the ABI.
 constexpr int kKatIn = 48, kKatOut = 12;
+// One block of the scan in form CLS from a known-answer record (cx[4] at 0, cy[4] at 4, cz[4] at 8, vy[4] at 16, padded r²[4]
+// at 28: the form takes the fields it has), through ScanGroup::discs as the scan loop runs it.
+template <int CLS> __device__ __forceinline__ void kat_block_discs(const double* a, const RayBasis<float>& b, float ft, float (&out)[4]) {
+    ScanGroup<float, CLS> g;
+    auto pair = [&](int at, int q) { return f2{(float)a[at + 2 * q], (float)a[at + 2 * q + 1]}; };
+    for (int q = 0; q < 2; ++q) g.cx[q] = pair(0, q), g.cy[q] = pair(4, q), g.cz[q] = pair(8, q), g.vy[q] = pair(16, q), g.r2[q] = pair(28, q);
+    g.discs(out, b, ft);
+}
 template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op, const double* in, uint32_t n, double* out) {
     typedef typename VecOf<R>::type r4;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1904,41 +1816,13 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
         const float ft = (float)(R)a[26];
         const int cls = (int)a[27];
         const bool movy = cls == 1 || cls == 3;
+        RayBasis<float> bk = b;
+        if (cls >= 2) bk.k2 = plane_run_k2((float)a[4], b.e2y, b.k2);
         float out4[4];
-        if (cls == 0) {
-            ScanGroup<float, 0> g;
-            for (int q = 0; q < 2; ++q) {
-                g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cy[q] = f2{(float)a[4 + 2 * q], (float)a[5 + 2 * q]};
-                g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]}, g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
-            }
-            g.discs(out4, b, ft);
-        } else if (cls == 1) {
-            ScanGroup<float, 1> g;
-            for (int q = 0; q < 2; ++q) {
-                g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cy[q] = f2{(float)a[4 + 2 * q], (float)a[5 + 2 * q]};
-                g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]}, g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
-                g.vy[q] = f2{(float)a[16 + 2 * q], (float)a[17 + 2 * q]};
-            }
-            g.discs(out4, b, ft);
-        } else {
-            RayBasis<float> bk = b;
-            bk.k2 = plane_run_k2((float)a[4], b.e2y, b.k2);
-            if (cls == 2) {
-                ScanGroup<float, 3> g;
-                for (int q = 0; q < 2; ++q) {
-                    g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
-                    g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
-                }
-                g.discs(out4, bk, ft);
-            } else {
-                ScanGroup<float, 4> g;
-                for (int q = 0; q < 2; ++q) {
-                    g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
-                    g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]}, g.vy[q] = f2{(float)a[16 + 2 * q], (float)a[17 + 2 * q]};
-                }
-                g.discs(out4, bk, ft);
-            }
-        }
+        if (cls == 0) kat_block_discs<0>(a, bk, ft, out4);
+        else if (cls == 1) kat_block_discs<1>(a, bk, ft, out4);
+        else if (cls == 2) kat_block_discs<3>(a, bk, ft, out4);
+        else kat_block_discs<4>(a, bk, ft, out4);
         for (int k = 0; k < 4; ++k) {
             r[k] = (double)out4[k];
             const float vy = movy ? (float)a[16 + k] : 0.0f;
@@ -1955,13 +1839,8 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
         const V<R> ud = unit(d);
         RayBasis<float> b = make_basis<float>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
         b.k2 = bucket_k2((float)a[27], (float)a[4], (float)(R)a[26], b.e2y, b.k2);
-        ScanGroup<float, 5> g;
-        for (int q = 0; q < 2; ++q) {
-            g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
-            g.r2[q] = f2{(float)a[28 + 2 * q], (float)a[29 + 2 * q]};
-        }
         float out4[4];
-        g.discs(out4, b, 0.0f);
+        kat_block_discs<5>(a, b, 0.0f, out4);
         for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = (double)(float)a[28 + k];
         r[4] = (double)b.k2;
         break;

@@ -291,11 +291,12 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
     // static / mov-Y streams (f32 for both precisions): blocks of G spheres, SoA inside a block (field f of sphere k of
     // block g at g·W·G + f·G + k).  After the head (kPlaneHeader words: layout and run table, rayz_device.hpp), the plane
     // section — its runs at their slots, W = F − 1 fields (no cy: the run table holds it), two spare groups — then the
-    // loose section, W = F, two spare groups.  Pad spheres {0, (0,) 0, r² = -inf, vy = 0}.
+    // loose section, W = F, two spare groups.  Pad spheres {0, (0,) 0, r² = -inf, vy = 0}.  The field offsets are the device
+    // forms' own (PackedGroup in rayz_device.hpp): every sphere and pad below is placed by the form's put().
     const float ninf32 = -std::numeric_limits<float>::infinity();
-    auto rec32 = [&](uint32_t pool) { // w = the PADDED r² of the conservative filter
+    auto rec32 = [&](uint32_t pool) { // r2 = the PADDED r² of the conservative filter
         const RayzSphere& q = s->spheres[pool];
-        return f4{(float)q.center[0], (float)q.center[1], (float)q.center[2], pad_radius2_scan<R>(q, b.pad_S)};
+        return BlockSphere<float>{(float)q.center[0], (float)q.center[1], (float)q.center[2], pad_radius2_scan<R>(q, b.pad_S), (float)q.velocity[1]};
     };
     // every scan the device runs over these streams stays inside its section's spare groups (rayz_plane::scan_reach)
     static_assert(rayz_plane::kScanSpareGroups == 2, "the sections below end in two spare groups");
@@ -303,9 +304,13 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
     auto reach = [&](uint32_t first, uint32_t end, uint32_t group, uint32_t section_slots) {
         reach_ok = reach_ok && rayz_plane::scan_reach(first, end, group) <= section_slots;
     };
-    auto blocks = [&](int c, uint32_t F, uint32_t class_slots) {
+    auto blocks = [&](auto cls, uint32_t class_slots) { // cls: the class as a constant; its forms place the fields (PackedGroup::put)
+        constexpr int c = decltype(cls)::value;
+        typedef ScanGroup<float, c> Loose;
+        typedef ScanGroup<float, c + 3> Run;
+        typedef ScanGroup<float, 5> Bucket;
         const NarrowBuffers& nb = s->narrow;
-        const uint32_t G = group_size<float>(), P = F - 1;
+        const uint32_t G = group_size<float>(), F = Loose::kWords, P = Run::kWords;
         const uint32_t n_plane = nb.plane_slots[c] + 2 * G, n_loose = class_slots - nb.plane_slots[c] + 2 * G;
         for (const PlaneRun& r : nb.runs[c]) reach(r.first, r.end, G, n_plane); // (a mov-Y run's remainder starts later, ends there)
         reach(0, class_slots - nb.plane_slots[c], G, n_loose);
@@ -315,23 +320,14 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         std::memcpy(v.data() + 4, nb.runs[c].data(), nb.runs[c].size() * sizeof(PlaneRun));
         float* const plane = v.data() + kPlaneHeader;
         float* const loose = plane + (size_t)n_plane * P;
-        for (uint32_t k = 0; k < n_plane; ++k) plane[(size_t)(k / G) * P * G + 2 * G + k % G] = ninf32;
-        for (uint32_t k = 0; k < n_loose; ++k) loose[(size_t)(k / G) * F * G + 3 * G + k % G] = ninf32;
+        for (uint32_t k = 0; k < n_plane; ++k) Run::put(plane, k);
+        for (uint32_t k = 0; k < n_loose; ++k) Loose::put(loose, k);
         for (size_t j = 0; j < nb.runs[c].size(); ++j)
             for (size_t m = 0; m < nb.run_members[c][j].size(); ++m) {
                 const uint32_t pool = nb.run_members[c][j][m], k = nb.runs[c][j].first + (uint32_t)m;
-                const f4 r = rec32(pool);
-                float* blk = plane + (size_t)(k / G) * P * G + k % G;
-                blk[0] = r.x, blk[G] = r.z, blk[2 * G] = r.w;
-                if (F == 5) blk[3 * G] = (float)s->spheres[pool].velocity[1];
+                Run::put(plane, k, rec32(pool));
             }
-        for (size_t k = 0; k < nb.loose[c].size(); ++k) {
-            const uint32_t pool = nb.loose[c][k];
-            const f4 r = rec32(pool);
-            float* blk = loose + (k / G) * F * G + k % G;
-            blk[0] = r.x, blk[G] = r.y, blk[2 * G] = r.z, blk[3 * G] = r.w;
-            if (F == 5) blk[4 * G] = (float)s->spheres[pool].velocity[1];
-        }
+        for (size_t k = 0; k < nb.loose[c].size(); ++k) Loose::put(loose, k, rec32(nb.loose[c][k]));
         if (c != 1) return v;
         // mov-Y only: the bucket section (rayz_device.hpp) — per run the first slot of its 4-field remainder, the bucket table,
         // the buckets' 3-field blocks cx[G] cz[G] r2b[G] back to back, two spare groups.  Head words 2 and 3: where, how many.
@@ -348,19 +344,18 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         }
         const size_t section = (v.size() + 15) / 16 * 16; // 64-byte aligned, as the blocks are
         const size_t blocks0 = section + kBucketHeader + table.size() * (sizeof(rayz_plane::SpeedBucket) / sizeof(float));
-        v.resize(blocks0 + 3 * (size_t)(bucket_slots + 2 * G), 0.0f);
+        v.resize(blocks0 + Bucket::kWords * (size_t)(bucket_slots + 2 * G), 0.0f);
         float* const bk = v.data() + blocks0;
-        for (uint32_t k = 0; k < bucket_slots + 2 * G; ++k) bk[(size_t)(k / G) * 3 * G + 2 * G + k % G] = ninf32;
+        for (uint32_t k = 0; k < bucket_slots + 2 * G; ++k) Bucket::put(bk, k);
         for (rayz_plane::SpeedBucket& t : table) {
             const uint32_t at = t.base; // the bucket's first slot of the section
             for (uint32_t k = t.first; k < t.end; ++k) {
                 const uint32_t pool = nb.run_members[1][t.run][k - nb.runs[1][t.run].first], sk = at + (k - t.first);
                 const RayzSphere& q = s->spheres[pool];
-                float* blk = bk + (size_t)(sk / G) * 3 * G + sk % G;
-                blk[0] = (float)q.center[0], blk[G] = (float)q.center[2], blk[2 * G] = pad_radius2_bucket<R>(q, b.pad_S, t.v0);
+                Bucket::put(bk, sk, {(float)q.center[0], 0.0f, (float)q.center[2], pad_radius2_bucket<R>(q, b.pad_S, t.v0), 0.0f});
             }
             reach(at, at + (t.end - t.first), G, bucket_slots + 2 * G);
-            t.base = (uint32_t)blocks0 + 3 * at - 3 * t.first; // (>= 0: the section lies behind 4 words per plane slot)
+            t.base = (uint32_t)blocks0 + Bucket::kWords * (at - t.first); // (>= 0: the section lies behind 4 words per plane slot)
         }
         const uint32_t where[2] = {(uint32_t)section, (uint32_t)table.size()};
         std::memcpy(v.data() + 2, where, sizeof(where));
@@ -368,14 +363,15 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         if (!table.empty()) std::memcpy(v.data() + section + kBucketHeader, table.data(), table.size() * sizeof(rayz_plane::SpeedBucket));
         return v;
     };
-    const std::vector<float> stat = blocks(0, 4, s->narrow.ns_pad), movy = blocks(1, 5, s->narrow.ny_pad);
+    const std::vector<float> stat = blocks(std::integral_constant<int, 0>(), s->narrow.ns_pad),
+                             movy = blocks(std::integral_constant<int, 1>(), s->narrow.ny_pad);
     std::vector<f4> movg(2 * (size_t)stream_len(s->cls[2].size(), kMovGGroup), f4{0.0f, 0.0f, 0.0f, 0.0f});
     reach(0, s->narrow.ng_pad, kMovGGroup, (uint32_t)(movg.size() / 2));
     if (!reach_ok) return fail(RAYZ_ERR_STATE, "scan stream layout: a scan would load past its section's spare groups");
     for (size_t k = 0; k < movg.size(); k += 2) movg[k] = f4{0.0f, 0.0f, 0.0f, ninf32};
     for (size_t k = 0; k < s->cls[2].size(); ++k) {
         const RayzSphere& q = s->spheres[s->cls[2][k]];
-        movg[2 * k] = rec32(s->cls[2][k]);
+        movg[2 * k] = f4{(float)q.center[0], (float)q.center[1], (float)q.center[2], pad_radius2_scan<R>(q, b.pad_S)};
         movg[2 * k + 1] = f4{(float)q.velocity[0], (float)q.velocity[1], (float)q.velocity[2], 0.0f};
     }
     // triangles: {v0, bits(material)}, {e1, 0}, {e2, 0}; edges subtracted in f64, then narrowed
