@@ -675,6 +675,15 @@ typedef struct RayzDenoiseGuidedParams {
 int rayz_hip_denoiser_run_guided(RayzDenoiser* dn, const RayzDenoiseGuidedParams* params, const float* d_rgb_in,
                                  const float* d_var_rgb, const RayzQueryOutputs* gbuffer, float* d_rgb_out,
                                  float* d_var_out_or_null, void* hip_stream);
+/* rayz_hip_denoiser_run_guided with a TAP: while it runs it also writes to `d_tap_rgb` (DEVICE memory, height*width*3 floats) the
+ * re-modulated colour after `tap_level` levels — bit for bit what rayz_hip_denoiser_run_guided with levels = tap_level writes to its
+ * d_rgb_out.  d_rgb_out and d_var_out are what the untapped run writes.  1 <= tap_level <= levels; tap_level = 1 is the image SVGF
+ * feeds back into its colour history (rayz_hip_temporal_feedback).  The tap costs one more 12-byte store per pixel in the tapped
+ * level (and that level's read of the modulation record, unless it is the last).  RAYZ_ERR_BAD_ARG (before the handle) as
+ * rayz_hip_denoiser_run_guided, and: tap_level 0 or above the resolved `levels`; d_tap_rgb NULL, or equal to d_rgb_in or d_rgb_out. */
+int rayz_hip_denoiser_run_guided_tap(RayzDenoiser* dn, const RayzDenoiseGuidedParams* params, const float* d_rgb_in,
+                                     const float* d_var_rgb, const RayzQueryOutputs* gbuffer, float* d_rgb_out,
+                                     float* d_var_out_or_null, uint32_t tap_level, float* d_tap_rgb, void* hip_stream);
 /* Waits for the handle's last run and returns its HIP-event times: *levels_or_null = L, the levels it ran; ms_or_null[0] = the
  * pack pass, ms_or_null[1 + l] = level l, for as many of the L + 1 entries as `capacity` holds.  RAYZ_ERR_STATE before any run. */
 int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);
@@ -692,7 +701,8 @@ int rayz_hip_denoiser_destroy(RayzDenoiser* dn);
  * takes its own history, no projection.  The arithmetic is a contract (§4.15, the rules of §4.11), restated bit for bit by
  * tests/temporal_mirror.cpp.  Added in ABI 5 (additive: no existing symbol changed); it changes no image any other entry point
  * produces.
- * Limits of this version: the UNFILTERED accumulated colour is the history (SVGF's feedback of the filtered colour is not built);
+ * Limits of this version: the unfiltered accumulated colour is the history unless the caller feeds a filtered one back, which only a
+ * moments handle takes (rayz_hip_temporal_track_feedback, rayz_hip_temporal_feedback below; the plain step has no such mode);
  * no motion vectors — the guides are first-hit, time-0 guides, so a moving sphere is matched where it is at time 0 and its blur is
  * carried as if painted on it; reflections and refractions are not reprojected (a mirror's image is carried on the mirror's
  * surface); whole frames only (rows of a shard are not image neighbours: gather first, as for the denoiser); f32 only; no switch
@@ -773,6 +783,30 @@ int rayz_hip_temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* p
                                    const RayzTemporalMomentsParams* mparams_or_null, const RayzCameraDesc* camera, uint32_t spp,
                                    const float* d_rgb_in, const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out,
                                    float* d_length_out_or_null, float* d_w2_out_or_null, void* hip_stream);
+
+/* ---- temporal accumulation, feedback of the filtered colour -------------------------------------------
+ * BUILD-DEFINED, additive within ABI 5.  SVGF writes the output of its first à-trous level back as the colour history: the next
+ * frame then blends into a colour that has been smoothed once, while the variance still comes from RAW moments.  A moments handle
+ * that TRACKS FEEDBACK keeps, in the record a moments step writes its variance to and never reads, the raw first moment m1 — what
+ * the accumulated colour would be had no feedback ever been given — reprojects and blends it exactly as the colour, and reports
+ * max(m2 - m1^2, 0) * W2 / (1 - W2).  Everything else of a step is §4.16's, operation for operation; a handle that tracks
+ * feedback and is never given any returns what a moments handle returns, bit for bit.  The arithmetic is a contract (§4.17),
+ * restated by tests/temporal_feedback_mirror.cpp.  Per frame: _step_moments, rayz_hip_denoiser_run_guided_tap with tap_level 1 on its
+ * outputs, _feedback with the tap.
+ * Limits of this version: moments handles only; opt-in, no default changed; the caller chooses what to feed back. */
+/* Allowed only on a handle in moments mode that has no history — after _track_moments or after rayz_hip_temporal_reset — else
+ * RAYZ_ERR_STATE; a second call is RAYZ_OK and does nothing.  Allocates nothing.  From then on rayz_hip_temporal_step_moments keeps m1
+ * and the handle takes rayz_hip_temporal_feedback. */
+int rayz_hip_temporal_track_feedback(RayzTemporal* tm);
+/* Replaces the accumulated colour of every pixel of the history the last step left with d_rgb's pixel (DEVICE memory,
+ * height*width*3 floats); the history length, m1, the second moment, W2 and the guides stay.  A pixel with a channel of d_rgb that
+ * is not finite keeps its colour.  The next step returns, and keeps as its colour history, the blend of its frame with this
+ * colour.  A second call before the next step replaces the first.  Asynchronous on `hip_stream` (NULL: the library's stream of the
+ * handle's device): it first makes its stream wait for the handle's previous work, and the next step and _destroy wait for it as
+ * they wait for a step; d_rgb must stay allocated until it has finished.  rayz_hip_temporal_timing keeps reporting the last step.
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): d_rgb NULL.  RAYZ_ERR_STATE: a bad handle, one that
+ * does not track feedback, or one without history (before the first step, after _reset). */
+int rayz_hip_temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -229,6 +229,9 @@ PROTOTYPES = [
      [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p]),
     ("rayz_hip_denoiser_run_guided", C.c_int,
      [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_denoiser_run_guided_tap", C.c_int,
+     [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_uint32,
+      C.c_void_p, C.c_void_p]),
     ("rayz_hip_denoiser_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]),
     ("rayz_hip_denoiser_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
@@ -242,6 +245,8 @@ PROTOTYPES = [
     ("rayz_hip_temporal_step_moments", C.c_int,
      [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(TemporalMomentsParams), C.POINTER(CameraDesc), C.c_uint32, C.c_void_p,
       C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_temporal_track_feedback", C.c_int, [C.c_void_p]),
+    ("rayz_hip_temporal_feedback", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 

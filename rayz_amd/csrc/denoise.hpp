@@ -43,6 +43,8 @@ struct DenoiseArgs {
     dn4* __restrict__ dst;        // next level's colours (not the last level)
     float* __restrict__ rgb;      // packed RGB out (the last level)
     float* __restrict__ var;      // guided: the last level's variance out, one float per pixel, or NULL
+    float* tap;                   // packed RGB out of THIS level, re-modulated as the last level's is, or NULL (all levels but the
+                                  // tapped one: rayz_hip_denoiser_run_guided_tap); never rgb
     uint32_t width, height;
     int stride;                   // 2^l
     uint32_t normal_power_log2;
@@ -123,8 +125,13 @@ template <bool GUIDED, bool LAST> __device__ __forceinline__ void dn_store(const
         a.rgb[3 * p + 1] = g * m.y;
         a.rgb[3 * p + 2] = b * m.z;
         if (GUIDED && a.var) a.var[p] = v;
+        if (a.tap) a.tap[3 * p + 0] = r * m.x, a.tap[3 * p + 1] = g * m.y, a.tap[3 * p + 2] = b * m.z;
     } else {
         a.dst[p] = dn4{r, g, b, v};
+        if (a.tap) { // the tapped level: what a run of this many levels writes as its output
+            const dn4 m = a.mod[p];
+            a.tap[3 * p + 0] = r * m.x, a.tap[3 * p + 1] = g * m.y, a.tap[3 * p + 2] = b * m.z;
+        }
     }
 }
 

@@ -26,10 +26,12 @@ RayzDenoiseGuidedParams denoise_params(const RayzDenoiseGuidedParams* p) {
     return *p;
 }
 
-// A run of either mode; d_var_rgb and d_var_out belong to the guided one.
+// A run of either mode; d_var_rgb and d_var_out belong to the guided one, and so does the tap: tap_level 0 is a run without one,
+// otherwise d_tap receives the re-modulated colour after that many levels (rayz_hip_denoiser_run_guided_tap).
 // Every argument is checked before the handle, and nothing here touches a device until all of them passed.
 int denoiser_run(RayzDenoiser* dn, bool guided, const RayzDenoiseGuidedParams& p, const float* d_in, const float* d_var_rgb,
-                 const RayzQueryOutputs* g, float* d_out, float* d_var_out, void* stream_arg) {
+                 const RayzQueryOutputs* g, float* d_out, float* d_var_out, void* stream_arg, uint32_t tap_level = 0,
+                 float* d_tap = nullptr) {
     if (p.levels > 8) return fail(RAYZ_ERR_BAD_ARG, "denoise levels %u > 8", p.levels);
     if (p.normal_power_log2 > 16) return fail(RAYZ_ERR_BAD_ARG, "denoise normal_power_log2 %u > 16", p.normal_power_log2);
     if (p.flags & ~kDenoiseFlags) return fail(RAYZ_ERR_BAD_ARG, "unknown denoise flag bits 0x%x", p.flags & ~kDenoiseFlags);
@@ -45,12 +47,12 @@ int denoiser_run(RayzDenoiser* dn, bool guided, const RayzDenoiseGuidedParams& p
     RAYZ_TRY(frame_gbuffer_check("denoise", g));
     const bool demod = p.flags & RAYZ_DENOISE_ALBEDO;
     if (demod && !g->albedo) return fail(RAYZ_ERR_BAD_ARG, "denoise: RAYZ_DENOISE_ALBEDO needs the G-buffer's albedo");
+    const uint32_t levels = p.levels ? p.levels : guided ? RAYZ_DENOISE_GUIDED_DEFAULT_LEVELS : RAYZ_DENOISE_DEFAULT_LEVELS;
     RAYZ_TRY(frame_handle_check(dn));
     hipStream_t st;
     RAYZ_TRY(frame_handle_stream(dn, stream_arg, st));
     DeviceScope scope(dn->device);
     RAYZ_TRY(frame_handle_wait_previous(dn, st)); // (a run of either mode)
-    const uint32_t levels = p.levels ? p.levels : guided ? RAYZ_DENOISE_GUIDED_DEFAULT_LEVELS : RAYZ_DENOISE_DEFAULT_LEVELS;
     dn4 *const ga = dn->buf[0], *const gb = dn->buf[1], *const mod = dn->buf[2], *const col[2] = {dn->buf[3], dn->buf[4]};
     dn->levels_run = 0; // (a run that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(dn, 0, st));
@@ -66,6 +68,7 @@ int denoiser_run(RayzDenoiser* dn, bool guided, const RayzDenoiseGuidedParams& p
         a.src = col[l & 1], a.dst = col[(l & 1) ^ 1];
         a.stride = 1 << l, a.cl = (float)(1u << (2 * l));
         const bool lds = l <= (uint32_t)kDnMaxLdsLog2 && (1u << l) <= lds_max;
+        a.tap = l + 1 == tap_level ? d_tap : nullptr;
         denoise_launch_level(st, guided, l + 1 == levels, a, l, lds);
         RAYZ_TRY(frame_handle_launched(dn, 2 + (int)l, st));
     }
@@ -100,6 +103,20 @@ int rayz_hip_denoiser_run_guided(RayzDenoiser* dn, const RayzDenoiseGuidedParams
                                  const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out_or_null, void* hip_stream) {
     return guarded([&] {
         return denoiser_run(dn, true, denoise_params(params), d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out_or_null, hip_stream);
+    });
+}
+
+int rayz_hip_denoiser_run_guided_tap(RayzDenoiser* dn, const RayzDenoiseGuidedParams* params, const float* d_rgb_in, const float* d_var_rgb,
+                                     const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out_or_null, uint32_t tap_level,
+                                     float* d_tap_rgb, void* hip_stream) {
+    return guarded([&] {
+        const RayzDenoiseGuidedParams p = denoise_params(params);
+        const uint32_t levels = p.levels ? p.levels : RAYZ_DENOISE_GUIDED_DEFAULT_LEVELS;
+        if (!tap_level || tap_level > levels) return fail(RAYZ_ERR_BAD_ARG, "denoise tap_level %u: must lie in 1 .. levels = %u", tap_level, levels);
+        if (!d_tap_rgb) return fail(RAYZ_ERR_BAD_ARG, "denoise: null tap buffer");
+        if (d_tap_rgb == d_rgb_in || d_tap_rgb == d_rgb_out)
+            return fail(RAYZ_ERR_BAD_ARG, "denoise: the tap buffer must be neither d_rgb_in nor d_rgb_out");
+        return denoiser_run(dn, true, p, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out_or_null, hip_stream, tap_level, d_tap_rgb);
     });
 }
 

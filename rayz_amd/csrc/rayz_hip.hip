@@ -15,6 +15,7 @@
 #include "denoise.hpp"
 #include "temporal_kernel.hpp"
 #include "temporal_moments_kernel.hpp"
+#include "temporal_feedback_kernel.hpp"
 #include "noise.hpp"
 #include "adaptive.hpp"
 #include "host_base.hpp"

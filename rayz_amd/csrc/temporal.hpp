@@ -3,8 +3,9 @@
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
-// buf: ping-pong x {colour + length, variance, normal + index, point}.  ev[0]: the step starts; ev[1]: it is done.
-struct RayzTemporal : FrameHandle<2 * 4, 2> {
+// buf: ping-pong x {colour + length, variance, normal + index, point}.  ev[0]: the step starts; ev[1]: it is done; ev[2]: the
+// feedback written behind it is done (rayz_hip_temporal_feedback; an event of its own, so that ev[0] .. ev[1] stays the step's time).
+struct RayzTemporal : FrameHandle<2 * 4, 3> {
     static constexpr uint32_t kMagic = 0x544d5a52u;
     static constexpr const char* kNoun = "temporal";
     int cur = 0;            // the side of buf the last step wrote: what the next step reads
@@ -14,6 +15,8 @@ struct RayzTemporal : FrameHandle<2 * 4, 2> {
     bool timed = false;     // the last step ran to its end: ev[0] .. ev[1] is its time
     bool moments = false;   // rayz_hip_temporal_track_moments: the handle takes _step_moments and not _step (§4.16)
     DevBuf<dn4> mom[2];     // .. and owns, per ping-pong side, one more record per pixel {m2.r, m2.g, m2.b, W2}; empty otherwise
+    bool feedback = false;  // rayz_hip_temporal_track_feedback: a moments handle whose variance records hold the raw first moment
+                            // m1 instead, and which takes rayz_hip_temporal_feedback (§4.17)
 };
 
 namespace {

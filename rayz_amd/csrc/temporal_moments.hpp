@@ -1,6 +1,7 @@
 // temporal_moments.hpp — the moments mode of temporal accumulation's handle (rayz_hip_temporal_track_moments, _step_moments;
 // DESIGN.md §4.16; the kernel and its launch: temporal_moments_kernel.hpp; the handle and what both kinds of step share:
-// temporal.hpp).  Included by rayz_hip.hip after temporal.hpp.
+// temporal.hpp) and its feedback mode (rayz_hip_temporal_track_feedback, _feedback; §4.17; temporal_feedback_kernel.hpp).
+// Included by rayz_hip.hip after temporal.hpp.
 #pragma once
 
 namespace {
@@ -19,6 +20,33 @@ int temporal_track_moments(RayzTemporal* tm) {
     }
     tm->mom[0] = std::move(m[0]), tm->mom[1] = std::move(m[1]);
     tm->moments = true;
+    return RAYZ_OK;
+}
+
+// Only a moments handle without history may start to keep m1: a moments step's history has variances where m1 belongs.
+// Allocates nothing: the v records change their meaning.
+int temporal_track_feedback(RayzTemporal* tm) {
+    RAYZ_TRY(frame_handle_check(tm));
+    if (tm->feedback) return RAYZ_OK;
+    if (!tm->moments) return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is not in moments mode (rayz_hip_temporal_track_moments first)");
+    if (tm->has_history)
+        return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle has history (call it after track_moments or after rayz_hip_temporal_reset)");
+    tm->feedback = true;
+    return RAYZ_OK;
+}
+
+// The colour of the side the last step wrote is replaced; the next step, a second feedback and _destroy wait for ev[2].
+int temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* stream_arg) {
+    if (!d_rgb) return fail(RAYZ_ERR_BAD_ARG, "temporal feedback: null colour buffer");
+    RAYZ_TRY(frame_handle_check(tm));
+    if (!tm->feedback) return fail(RAYZ_ERR_STATE, "temporal feedback: the handle does not track feedback (rayz_hip_temporal_track_feedback first)");
+    if (!tm->has_history) return fail(RAYZ_ERR_STATE, "temporal feedback: the handle has no history to write to (step it first)");
+    hipStream_t st;
+    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
+    DeviceScope scope(tm->device);
+    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (the step that wrote this side, or an earlier feedback)
+    temporal_feedback_launch_write(st, tm->buf[4 * tm->cur], d_rgb, tm->width, tm->height);
+    RAYZ_TRY(frame_handle_launched(tm, 2, st));
     return RAYZ_OK;
 }
 
@@ -53,7 +81,8 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
     a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
     tm->timed = false; // (a step that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(tm, 0, st));
-    temporal_moments_launch_step(st, a, is_static);
+    if (tm->feedback) temporal_feedback_launch_step(st, a, is_static);
+    else temporal_moments_launch_step(st, a, is_static);
     RAYZ_TRY(frame_handle_launched(tm, 1, st));
     temporal_stepped(tm, cam, M, from);
     return RAYZ_OK;
@@ -65,6 +94,14 @@ extern "C" {
 
 int rayz_hip_temporal_track_moments(RayzTemporal* tm) {
     return guarded([&] { return temporal_track_moments(tm); });
+}
+
+int rayz_hip_temporal_track_feedback(RayzTemporal* tm) {
+    return guarded([&] { return temporal_track_feedback(tm); });
+}
+
+int rayz_hip_temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* hip_stream) {
+    return guarded([&] { return temporal_feedback(tm, d_rgb, hip_stream); });
 }
 
 int rayz_hip_temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params_or_null,

@@ -17,6 +17,10 @@
 // pixel lies outside the frame does not return early as the plain kernel's does: it votes "no", helps to stage, and skips only the
 // per-pixel work and the stores.  The staging branch is taken by a whole workgroup or by none (the vote's result is the same in
 // every thread), so the barrier inside it is not under divergent control flow.
+//
+// The step's body is ONE function, tm_step<STATIC, FEEDBACK>: the two kernels here instantiate it with FEEDBACK = false, the
+// feedback handle's two (temporal_feedback_kernel.hpp, §4.17) with true — there every accepted tap also reads the history's raw first
+// moment m1 from the v record, and step 3 takes the variance from it instead of from the colour, which may be a fed-back one.
 #pragma once
 
 #include "temporal_kernel.hpp"
@@ -28,7 +32,8 @@ constexpr int kTmLdsW = kDnTileW + 2 * kTmHalo, kTmLdsH = kDnTileH + 2 * kTmHalo
 constexpr int kTmOutside = (int)0x80000000;                                   // the index of a staged position outside the frame: equals no id >= 0
 
 struct TemporalMomentsArgs {
-    TemporalArgs t;    // the plain step's arguments; t.var is not read, t.var_out receives v_out, t.prev.v is not read
+    TemporalArgs t;    // the plain step's arguments; t.var is not read, t.var_out receives v_out, t.prev.v is not read (the feedback
+                       // step, §4.17: t.prev.v and t.next.v hold {m1.r, m1.g, m1.b, 0}, the raw first moment)
     const dn4* prev_m; // per pixel {m2.r, m2.g, m2.b, W2}: the history's second moment and its sum of squared frame weights
     dn4* next_m;
     float* w2_out;     // or NULL
@@ -37,10 +42,12 @@ struct TemporalMomentsArgs {
 
 struct TmAcc {
     float B, Hr, Hg, Hb, N, Qr, Qg, Qb, W;
+    float M1r, M1g, M1b; // the feedback step's sums of m1; unused otherwise
 };
 
-// An accepted tap of bilinear weight b: its colour + length and moment records join the sums, in tap order.
-__device__ __forceinline__ void tm_add(const dn4 c, const dn4 m, float b, TmAcc& acc) {
+// An accepted tap of bilinear weight b: its colour + length and moment records join the sums, in tap order; in the feedback step
+// its raw first moment f too, exactly as the colour does.
+template <bool FEEDBACK> __device__ __forceinline__ void tm_add(const dn4 c, const dn4 m, const dn4 f, float b, TmAcc& acc) {
     acc.B = acc.B + b;
     acc.Hr = __builtin_fmaf(b, c.x, acc.Hr);
     acc.Qr = __builtin_fmaf(b, m.x, acc.Qr);
@@ -50,6 +57,11 @@ __device__ __forceinline__ void tm_add(const dn4 c, const dn4 m, float b, TmAcc&
     acc.Qb = __builtin_fmaf(b, m.z, acc.Qb);
     acc.N = __builtin_fmaf(b, c.w, acc.N);
     acc.W = __builtin_fmaf(b, m.w, acc.W);
+    if (FEEDBACK) {
+        acc.M1r = __builtin_fmaf(b, f.x, acc.M1r);
+        acc.M1g = __builtin_fmaf(b, f.y, acc.M1g);
+        acc.M1b = __builtin_fmaf(b, f.z, acc.M1b);
+    }
 }
 
 // §4.16 step 3 for one channel: the variance of the accumulated mean from its second moment.
@@ -67,15 +79,17 @@ __device__ __forceinline__ float tm_spatial_var(float S0, float S1, float S2, fl
     return dn_clamp_var(((dp * S0) / (S0 - 1.0f)) * W2);
 }
 
-template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_step_kernel(const TemporalMomentsArgs m) {
+// The step of one workgroup; s_col and s_nrm: the kernel's two LDS arrays of kTmLdsH·kTmLdsW records.
+template <bool STATIC, bool FEEDBACK>
+__device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const s_col, dn4* const s_nrm) {
     const TemporalArgs& a = m.t;
-    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
     const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
     const int x = (int)(blockIdx.x * kDnTileW) + tx, y = (int)(blockIdx.y * kDnTileH) + ty;
     const bool inside = x < (int)a.width && y < (int)a.height; // NO early return: every thread reaches the vote and the barrier
     const size_t p = inside ? (size_t)y * a.width + (size_t)x : 0;
     float cr = 0.0f, cg = 0.0f, cb = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f, Px = 0.0f, Py = 0.0f, Pz = 0.0f;
     float or_ = 0.0f, og = 0.0f, ob = 0.0f, No = 0.0f, qr = 0.0f, qg = 0.0f, qb = 0.0f, W2 = 1.0f, vr = 0.0f, vg = 0.0f, vb = 0.0f;
+    float fr = 0.0f, fg = 0.0f, fb = 0.0f; // FEEDBACK: m1', the raw first moment
     int32_t id = -1;
     bool spatial = false;
     if (inside) {
@@ -85,12 +99,15 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
         Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
         or_ = cr, og = cg, ob = cb, No = a.spp;              // no history: the input, by selection ..
         qr = cr * cr, qg = cg * cg, qb = cb * cb, W2 = 1.0f; // .. its square, and the weight of one frame
+        fr = cr, fg = cg, fb = cb;
         if (id >= 0 && a.has_history) {
             const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
             const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
-            TmAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            TmAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            const dn4 none{0.0f, 0.0f, 0.0f, 0.0f};
             if (STATIC) {
-                if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim)) tm_add(a.prev.c[p], m.prev_m[p], 1.0f, acc);
+                if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim))
+                    tm_add<FEEDBACK>(a.prev.c[p], m.prev_m[p], FEEDBACK ? a.prev.v[p] : none, 1.0f, acc);
             } else {
                 const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
                 const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
@@ -101,7 +118,8 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
                         const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
                         const float fx = hx - x0, fy = hy - y0;
                         const int ix = (int)x0, iy = (int)y0;
-                        // Two rounds of loads, as in the plain step: every tap's guide records, then its colour and moment records.
+                        // Two rounds of loads, as in the plain step: every tap's guide records, then its colour and moment records
+                        // (and, in the feedback step, its m1 record).
                         // A tap outside the frame loads the nearest pixel inside it (a valid address) and is refused.
                         size_t q[4];
                         bool ok[4];
@@ -115,15 +133,16 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
                             q[t] = (size_t)cy * a.width + (size_t)cx;
                             g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
                         }
-                        dn4 c[4], mm[4];
+                        dn4 c[4], mm[4], f[4];
 #pragma unroll
                         for (int t = 0; t < 4; ++t) {
                             ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
                             c[t] = a.prev.c[q[t]], mm[t] = m.prev_m[q[t]];
+                            f[t] = FEEDBACK ? a.prev.v[q[t]] : none;
                         }
 #pragma unroll
                         for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
-                            if (ok[t]) tm_add(c[t], mm[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
+                            if (ok[t]) tm_add<FEEDBACK>(c[t], mm[t], f[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
                     }
                 }
             }
@@ -143,11 +162,21 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
                 qg = __builtin_fmaf(alpha, cg * cg - hqg, hqg);
                 qb = __builtin_fmaf(alpha, cb * cb - hqb, hqb);
                 W2 = __builtin_fmaf(k2, acc.W / acc.B, a2);
+                if (FEEDBACK) {
+                    const float h1r = acc.M1r / acc.B, h1g = acc.M1g / acc.B, h1b = acc.M1b / acc.B;
+                    fr = __builtin_fmaf(alpha, cr - h1r, h1r);
+                    fg = __builtin_fmaf(alpha, cg - h1g, h1g);
+                    fb = __builtin_fmaf(alpha, cb - h1b, h1b);
+                }
                 No = Ns > a.nm ? a.nm : Ns;
             }
         }
         spatial = id >= 0 && W2 > m.wm;
-        if (id >= 0 && !spatial) vr = tm_temporal_var(qr, or_, W2), vg = tm_temporal_var(qg, og, W2), vb = tm_temporal_var(qb, ob, W2);
+        if (id >= 0 && !spatial) { // (the feedback step: from the raw first moment, whatever colour was fed back)
+            vr = tm_temporal_var(qr, FEEDBACK ? fr : or_, W2);
+            vg = tm_temporal_var(qg, FEEDBACK ? fg : og, W2);
+            vb = tm_temporal_var(qb, FEEDBACK ? fb : ob, W2);
+        }
     }
     // The vote: reached by every thread of the workgroup; its result is the same in all of them.
     if (__syncthreads_or(spatial ? 1 : 0)) {
@@ -183,7 +212,7 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
     }
     if (!inside) return; // (behind the last barrier)
     a.next.c[p] = dn4{or_, og, ob, No};
-    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
+    a.next.v[p] = FEEDBACK ? dn4{fr, fg, fb, 0.0f} : dn4{vr, vg, vb, 0.0f};
     a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
     a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
     m.next_m[p] = dn4{qr, qg, qb, W2};
@@ -191,6 +220,11 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_s
     a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
     if (a.len_out) a.len_out[p] = No;
     if (m.w2_out) m.w2_out[p] = W2;
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_step_kernel(const TemporalMomentsArgs m) {
+    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
+    tm_step<STATIC, false>(m, s_col, s_nrm);
 }
 
 // ---- host side: the launch (temporal_moments.hpp owns the validation) ------------------------------------------------------------

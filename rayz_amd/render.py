@@ -548,17 +548,37 @@ class Denoiser(_Handle):
         self._inflight = (rgb, gbuffer, out)
         return out
 
-    def run_guided(self, rgb, var_rgb, gbuffer: "QueryResult", out=None, var_out=None, stream: int = 0, **params):
+    def run_guided(self, rgb, var_rgb, gbuffer: "QueryResult", out=None, var_out=None, stream: int = 0, tap_level: int = 0, tap_out=None,
+                   **params):
         """The variance-guided filter (`rayz_hip_denoiser_run_guided`): as `run`, with `var_rgb` — (height, width, 3)
         float32, the variance of each channel of `rgb`'s pixel means (`Progressive.noise_rgb()`) — steering the colour weight pixel
         by pixel.  `var_out`: True for a new (height, width) float32 tensor, or such a tensor, to receive the variance left in the
         demodulated colour; then the call returns (out, var_out).  `params`: the fields of RayzDenoiseGuidedParams (levels,
         normal_power_log2, flags, sigma_color — in standard deviations —, sigma_plane, var_floor); unnamed ones take
-        capi.DENOISE_GUIDED_DEFAULTS."""
+        capi.DENOISE_GUIDED_DEFAULTS.  `tap_level` t > 0 (`rayz_hip_denoiser_run_guided_tap`): the run also writes the re-modulated
+        colour after t levels — what a run with levels=t returns — to `tap_out` (default: a new tensor; neither `rgb` nor `out`),
+        which the call returns as a further value; t = 1 is what `Temporal.feedback` takes."""
+        import torch
+
         prm = _params(capi.DenoiseGuidedParams, capi.DENOISE_GUIDED_DEFAULTS, params, "denoise")
         out, var_out, need = self._checked(prm, [("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, out, var_out)
+        if tap_level:
+            frame = (self.height, self.width, 3)
+            if tap_out is None:
+                tap_out = torch.empty(frame, dtype=torch.float32, device=torch.device("cuda", self._device))
+            _check_tensor("tap_out", tap_out, torch.float32, frame, self._device, "the denoiser")
+        elif tap_out is not None:
+            raise ValueError("tap_out needs tap_level > 0")
         _stream_prologue(stream, self._device)
         o = _gbuffer_pointers(gbuffer, need)
+        if tap_level:
+            rc = self._lib.rayz_hip_denoiser_run_guided_tap(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()),
+                                                            C.byref(o), C.c_void_p(out.data_ptr()),
+                                                            C.c_void_p(var_out.data_ptr() if var_out is not None else None), int(tap_level),
+                                                            C.c_void_p(tap_out.data_ptr()), C.c_void_p(stream or None))
+            capi.check(self._lib, rc, "rayz_hip_denoiser_run_guided_tap")
+            self._inflight = (rgb, var_rgb, gbuffer, out, var_out, tap_out)
+            return (out, tap_out) if var_out is None else (out, var_out, tap_out)
         rc = self._lib.rayz_hip_denoiser_run_guided(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()),
                                                     C.byref(o), C.c_void_p(out.data_ptr()),
                                                     C.c_void_p(var_out.data_ptr() if var_out is not None else None), C.c_void_p(stream or None))
@@ -577,11 +597,12 @@ class Temporal(_Handle):
     """Temporal accumulation for whole float32 frames of one size (`rayz_hip_temporal_*`): every `step` blends
     the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
     per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init().  `moments` True: the
-    handle is put into moments mode (`track_moments`, §4.16) and takes `step_moments`, which needs no variance input."""
+    handle is put into moments mode (`track_moments`, §4.16) and takes `step_moments`, which needs no variance input; with
+    `feedback` True as well it also tracks feedback (`track_feedback`, §4.17) and takes `feedback`."""
 
     _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
-    def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False):
+    def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False, feedback: bool = False):
         self._lib = capi.load()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
@@ -589,9 +610,14 @@ class Temporal(_Handle):
                                                                  C.byref(self._h)), "rayz_hip_temporal_create")
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last step: kept alive until the next step or close() (the kernel may still use them)
+        if feedback and not moments:
+            self.close()
+            raise ValueError("feedback=True needs moments=True: only a moments handle tracks feedback")
         if moments:
             try:
                 self.track_moments()
+                if feedback:
+                    self.track_feedback()
             except Exception:
                 self.close()
                 raise
@@ -600,6 +626,25 @@ class Temporal(_Handle):
         """Puts the handle into moments mode (`rayz_hip_temporal_track_moments`): only while it has no history — after creation
         or after `reset` —; a second call does nothing.  From then on the handle takes `step_moments` and refuses `step`."""
         capi.check(self._lib, self._lib.rayz_hip_temporal_track_moments(self._h), "rayz_hip_temporal_track_moments")
+
+    def track_feedback(self) -> None:
+        """Makes a moments handle keep the raw first moment beside its colour (`rayz_hip_temporal_track_feedback`): only while it
+        has no history; a second call does nothing.  From then on `step_moments` takes its variance from that moment, and the
+        handle takes `feedback`."""
+        capi.check(self._lib, self._lib.rayz_hip_temporal_track_feedback(self._h), "rayz_hip_temporal_track_feedback")
+
+    def feedback(self, rgb, stream: int = 0) -> None:
+        """Replaces the colour history the last step left with `rgb` ((height, width, 3) float32 on the handle's device) — SVGF's
+        feedback, `rgb` being `Denoiser.run_guided(..., tap_level=1)`'s tap (`rayz_hip_temporal_feedback`).  The
+        history length and the moments stay; a pixel of `rgb` that is not finite keeps its colour.  Asynchronous on `stream`, as
+        `step`."""
+        import torch
+
+        _check_tensor("rgb", rgb, torch.float32, (self.height, self.width, 3), self._device, "the temporal handle")
+        _stream_prologue(stream, self._device)
+        capi.check(self._lib, self._lib.rayz_hip_temporal_feedback(self._h, C.c_void_p(rgb.data_ptr()), C.c_void_p(stream or None)),
+                   "rayz_hip_temporal_feedback")
+        self._inflight = (self._inflight, rgb)  # (beside the last step's tensors, which the step's kernel may still use)
 
     def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
              stream: int = 0, **params):

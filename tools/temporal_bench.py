@@ -33,7 +33,19 @@ a tracked progressive handle (frame + variance: what the plain step takes).
 (c) The sweep the defaults are to be chosen from: w2_max x min_taps, the first frame's and the mean over the later frames of (b)'s
     moments + guided MSE ratio to the raw frame.
 
-    python tools/temporal_bench.py --moments [--settle 6] [the switches above]"""
+    python tools/temporal_bench.py --moments [--settle 6] [the switches above]
+
+--feedback measures the feedback of the filtered colour (rayz_hip_temporal_track_feedback / _feedback and
+rayz_hip_denoiser_run_guided_tap) on --moments' one-chunk frames.
+(a) Cost.  The feedback step beside the moments step, by the handles' own HIP events in the same process, in --moments' four
+    states, each beside a device copy of its compulsory bytes: the feedback step reads one more history record, m1 (224 B per pixel
+    against 208; what it writes to the v record changes its meaning, not its size).  The write kernel, by events around
+    `Temporal.feedback`, beside a copy of its 44 B per pixel (12 B of the image and one 16-byte record in, the record out).  The
+    guided run with a tap at level 1 beside the untapped run, both by the denoiser's own events (pack pass + levels).
+(b) Quality.  Per frame, MSE against the --ref-spp frame of: the raw one-chunk frame; moments step + `run_guided`; and moments
+    step on a feedback handle + `run_guided(tap_level=1)` with the tap fed back — both at the shipped defaults.
+
+    python tools/temporal_bench.py --feedback [--settle 6] [the switches above]"""
 import argparse
 import json
 import os
@@ -48,6 +60,8 @@ from rayz_amd import capi, render, tracer  # noqa: E402
 
 STEP_BYTES = 52 + 64 + 88  # per pixel: what a step must read and write (module docstring)
 MOMENTS_STEP_BYTES = 40 + 64 + 104  # .. and a moments step
+FEEDBACK_STEP_BYTES = MOMENTS_STEP_BYTES + 16  # .. and a feedback step: the m1 record in
+FEEDBACK_WRITE_BYTES = 12 + 16 + 16  # the write kernel: the image and the colour record in, the record out
 
 
 def panned(cam, pixels):
@@ -216,6 +230,143 @@ def main_moments(args):
             json.dump(res, f, indent=1)
 
 
+def event_ms(fn, reps, warmup):
+    """Median [min, max] of fn() between two events on torch's current stream (fn enqueues there)."""
+    ms = []
+    for r in range(warmup + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if r >= warmup:
+            ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main_feedback(args):
+    """--feedback: see the module docstring."""
+    render.init(0)
+    t = tracer.randomBouncing(args.width, -50, 50, seed=42)  # config 3
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    assert args.spp <= 16, "--feedback wants an spp of at most 16: one automatic chunk"
+    ds = render.DeviceScene(sd)
+    res = {"mode": "feedback", "size": f"{w}x{h}", "frames": args.frames, "pan_px": args.pan, "spp": args.spp, "ref_spp": args.ref_spp,
+           "reps": args.reps, "settle": args.settle, "moments_step_bytes_per_pixel": MOMENTS_STEP_BYTES,
+           "feedback_step_bytes_per_pixel": FEEDBACK_STEP_BYTES, "feedback_write_bytes_per_pixel": FEEDBACK_WRITE_BYTES}
+    seq = []
+    for k in range(args.frames):
+        c = panned(cam, args.pan * k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed, q.chunk_spp = 1000 + k, 0
+        one = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ds.render_into(c, q, one.data_ptr())
+        ds.sync()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        q.samples_per_px, q.seed = args.ref_spp, 7
+        ref = torch.empty_like(one)
+        torch.cuda.synchronize()
+        ds.render_into(c, q, ref.data_ptr())
+        ds.sync()
+        seq.append((c, one, g, ref))
+        print(f"frame {k}: {args.spp} spp in one chunk, reference {args.ref_spp} spp", flush=True)
+    mse = lambda a, ref: float(((a.double() - ref.double()) ** 2).mean())  # noqa: E731
+
+    # ---- (a) cost -------------------------------------------------------------------------------------------------------------
+    res["copy"] = {}
+    for name, nbytes in (("moments", MOMENTS_STEP_BYTES), ("feedback", FEEDBACK_STEP_BYTES), ("write", FEEDBACK_WRITE_BYTES)):
+        cp = copy_ms(n * nbytes // 2, args.reps, args.warmup)
+        res["copy"][name] = {"ms": cp[0], "min": cp[1], "max": cp[2]}
+        print(f"copy moving the compulsory bytes of a {name} ({n * nbytes / 1e6:.1f} MB read + written): {cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}] "
+              f"({n * nbytes / cp[0] / 1e9:.2f} TB/s)", flush=True)
+    mom, fbk = render.Temporal(w, h, moments=True), render.Temporal(w, h, moments=True, feedback=True)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    length, w2 = torch.empty((h, w), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda")
+
+    def step(tm, s):
+        tm.step_moments(s[1], s[2], s[0], args.spp, out=out, var_out=vout, length=length, w2=w2)
+
+    states = [("first", 0, 0), ("static-second", 1, 0), ("static-settled", args.settle, 0), ("panned-settled", args.settle, 1)]
+    res["cost"] = {}
+    for what, before, last in states:
+        row = {}
+        for name, tm, nbytes in (("moments", mom, MOMENTS_STEP_BYTES), ("feedback", fbk, FEEDBACK_STEP_BYTES)):
+            ms = []
+            for r in range(args.warmup + args.reps):
+                tm.reset()
+                for _ in range(before):
+                    step(tm, seq[0])
+                step(tm, seq[last])
+                x = tm.timing()
+                if r >= args.warmup:
+                    ms.append(x)
+            med = statistics.median(ms)
+            cpm = res["copy"][name]["ms"]
+            row[name] = {"ms": med, "min": min(ms), "max": max(ms), "ratio_to_copy": med / cpm}
+            print(f"{name:8s} step, {what:14s}: {med:.4f} ms [{min(ms):.4f}, {max(ms):.4f}] = {med / cpm:.2f} x the copy of its compulsory bytes "
+                  f"({n * nbytes / med / 1e9:.2f} TB/s of them)", flush=True)
+        row["feedback_over_moments"] = row["feedback"]["ms"] / row["moments"]["ms"]
+        res["cost"][what] = row
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()  # (a stream of torch's own: its events bracket what the library enqueues there)
+    with torch.cuda.stream(side):
+        wr = event_ms(lambda: fbk.feedback(out, stream=side.cuda_stream), args.reps, args.warmup)
+    torch.cuda.synchronize()
+    cpm = res["copy"]["write"]["ms"]
+    res["cost"]["write"] = {"ms": wr[0], "min": wr[1], "max": wr[2], "ratio_to_copy": wr[0] / cpm}
+    print(f"feedback write: {wr[0]:.4f} ms [{wr[1]:.4f}, {wr[2]:.4f}] = {wr[0] / cpm:.2f} x the copy of its compulsory bytes "
+          f"({n * FEEDBACK_WRITE_BYTES / wr[0] / 1e9:.2f} TB/s of them)", flush=True)
+    dn = render.Denoiser(w, h)
+    den, tap = torch.empty_like(out), torch.empty_like(out)
+    s0 = seq[0]
+    step(mom, s0)
+    runs = {}
+    for name, kw in (("untapped", {}), ("tapped", dict(tap_level=1, tap_out=tap))):
+        ms = []
+        for r in range(args.warmup + args.reps):
+            dn.run_guided(out, vout, s0[2], out=den, **kw)
+            pack, levels = dn.timing()
+            if r >= args.warmup:
+                ms.append((pack + sum(levels), levels[0]))
+        tot, l0 = [m[0] for m in ms], [m[1] for m in ms]
+        runs[name] = {"ms": statistics.median(tot), "min": min(tot), "max": max(tot), "level0_ms": statistics.median(l0)}
+        print(f"run_guided, {name:8s}: {runs[name]['ms']:.4f} ms [{min(tot):.4f}, {max(tot):.4f}] (pack pass + levels), level 0 alone "
+              f"{runs[name]['level0_ms']:.4f} ms", flush=True)
+    runs["tapped_over_untapped"] = runs["tapped"]["ms"] / runs["untapped"]["ms"]
+    res["cost"]["run_guided"] = runs
+
+    # ---- (b) quality at the defaults -----------------------------------------------------------------------------------------------
+    mom.reset(), fbk.reset()
+    rows = []
+    for k, s in enumerate(seq):
+        step(mom, s)
+        dn.run_guided(out, vout, s[2], out=den)
+        torch.cuda.synchronize()
+        row = {"frame": k, "mse_raw": mse(s[1], s[3]), "mse_moments": mse(out, s[3]), "mse_moments_guided": mse(den, s[3])}
+        step(fbk, s)
+        dn.run_guided(out, vout, s[2], out=den, tap_level=1, tap_out=tap)
+        fbk.feedback(tap)
+        torch.cuda.synchronize()
+        row.update({"mse_feedback": mse(out, s[3]), "mse_feedback_guided": mse(den, s[3])})
+        rows.append(row)
+        r = row["mse_raw"]
+        print(f"frame {k:2d}: MSE raw (one chunk) {r:.4e}; moments step x{row['mse_moments'] / r:.4f}, + guided x{row['mse_moments_guided'] / r:.4f}; "
+              f"with the level-1 tap fed back: step x{row['mse_feedback'] / r:.4f}, + guided x{row['mse_feedback_guided'] / r:.4f}", flush=True)
+    res["defaults"] = {"params": {**capi.TEMPORAL_DEFAULTS, **capi.TEMPORAL_MOMENTS_DEFAULTS}, "rows": rows}
+    mom.close(), fbk.close(), dn.close(), ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -229,7 +380,10 @@ def main():
     ap.add_argument("--json", default=None, help="also write the figures to this file")
     ap.add_argument("--moments", action="store_true", help="measure the moments mode (DESIGN.md §4.16) beside the plain step")
     ap.add_argument("--settle", type=int, default=6, help="--moments: static frames behind a 'settled' history (W2 = 1 / settle)")
+    ap.add_argument("--feedback", action="store_true", help="measure the feedback of the filtered colour (DESIGN.md §4.17) beside the moments step")
     args = ap.parse_args()
+    if args.feedback:
+        return main_feedback(args)
     if args.moments:
         return main_moments(args)
     render.init(0)
