@@ -107,6 +107,7 @@ class TemporalF64:
         self.has_history = False
         self.key = self.cam = None
         self.last_static = None
+        self.taps = None  # the per-tap quantities of the last step that read history (see _blend)
         self.hist = None  # dict: c, v (h, w, 3); N, K (h, w); n, P (h, w, 3); id (h, w); Ec, Ev (h, w, 3); EN (h, w); excluded (h, w)
 
     def reset(self):
@@ -271,6 +272,9 @@ class TemporalF64:
         Ev = s * da2[..., None] + hv * dk2[..., None] + k3 * k3 * Ehv + U * k3 * k3 * hv + U * v_b
         N_b = np.where(Ns > nm, nm, Ns)
         excluded = hit & (near | (has & taint))
+        # what a step that rides the same taps needs (tests/temporal_moments_f64.py); nothing above depends on it
+        self.taps = dict(b=b, db=db, ba=ba, dba=dba, qy=qy, qx=qx, inside=inside, ok=ok, div=div, has=has, al=al, da0=da0, hc=hc,
+                         near=near, taint=taint, gather=gather)
         return has, excluded, (c_b, v_b, N_b, hK + 1.0), (Ec, Ev, dNs)
 
 
