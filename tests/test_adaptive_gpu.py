@@ -189,7 +189,7 @@ def check_against_plain(ad, plain, one_shot, p, min_chunks, what):
         want[first == k] = plain[k][0][first == k]
     assert_images_equal(ad["frame"], want, f"{what}: frozen pixels vs plain previews, the rest vs the one-shot frame")
     spp = p.samples_per_px
-    n_of = np.array([0] + [min(16 * k, spp) for k in range(1, bounds[-1] + 1)])
+    n_of = np.array([0] + [min(p.chunk_spp * k, spp) for k in range(1, bounds[-1] + 1)])
     counts = np.where(first != 0, n_of[first], spp)
     assert (ad["counts"] == counts).all()
     last = ad["summaries"][-1]

@@ -206,6 +206,59 @@ def test_refusals_leave_the_scene_usable(gpu, oracle):
     ds.close()
 
 
+BIG = 2 ** 19 + 1  # more than 512 rays per CU on any device of up to 1,024 CUs: query_bounds_kernel's grid-stride loop takes a second trip
+# Every refusal query_bounds names: (what it is, the columns patched, their value, what the message must say)
+REFUSALS = [("a NaN origin", [0], float("nan"), "NaN or infinite origin, direction or time"),
+            ("an infinite direction", [5], float("inf"), "NaN or infinite origin, direction or time"),
+            ("a zero direction", [4, 5, 6], 0.0, "a zero direction"),
+            ("an origin beyond the limit", [1], 2e9, "beyond RAYZ_QUERY_MAX_ORIGIN"),
+            ("a direction below the scale", [4, 5, 6], -1e-12, "RAYZ_QUERY_MIN_DIR"),
+            ("a direction above the scale", [6], -1e10, "RAYZ_QUERY_MAX_DIR"),
+            ("a NaN tmax", [7], float("nan"), "a NaN tmax"),
+            ("time 1.5", [3], 1.5, r"time 1\.5 outside \[0, 1\]"),
+            ("time -0.5", [3], -0.5, r"time -0\.5 outside \[0, 1\]")]
+
+
+def test_a_refusal_is_found_anywhere_in_a_large_batch(gpu, oracle):
+    """One bad ray among 2^19 + 1 valid ones, in the last lane of a wave and the first of the next (63, 64), in the last thread of
+    a block and the first of the next (255, 256), deep in the grid (2^17), and in the last two rays (2^19 − 1; 2^19, which any grid
+    of up to 2,048 blocks reaches only on a second trip of its loop): the flag has to survive the loop, the shuffle, the LDS step
+    and the atomic from wherever it is raised.  The batch is built once on the device and one row is patched per run.  The clean
+    batch is then accepted: its first three rays are the 3-ray batch of test_refusals_leave_the_scene_usable and answer as that
+    does, and a sample of the jittered rest answers as the brute force."""
+    t = tracer.threeSpheres(32, seed=1)
+    sd = t.scene_desc()
+    ds = render.DeviceScene(sd)
+    good = np.array([0, 1, 3, 0.5, 0, 0, -1, np.inf])
+    rng = np.random.default_rng(19)
+    rays = np.tile(good, (BIG, 1))
+    rays[3:, 0:3] += rng.uniform(-0.25, 0.25, (BIG - 3, 3))
+    rays[3:, 3] = rng.uniform(0, 1, BIG - 3)
+    rays[3:, 4:6] += rng.uniform(-0.25, 0.25, (BIG - 3, 2))
+    rays = narrow(rays, F32)
+    clean = torch.tensor(rays, dtype=torch.float32, device="cuda")
+    batch = clean.clone()
+    for at in (63, 64, 255, 256, 2 ** 17, 2 ** 19 - 1, 2 ** 19):
+        for what, cols, value, says in REFUSALS:
+            batch[at, cols] = value
+            with pytest.raises(capi.RayzHipError, match=rf"status {capi.ERR_BAD_ARG}\): query rays: .*{says}"):
+                ds.query(batch, tmin=TMIN, outputs=("index",))
+                pytest.fail(f"{what} at ray {at} of {BIG} was accepted")
+            batch[at] = clean[at]
+    assert torch.equal(batch, clean)
+    r = ds.query(batch, tmin=TMIN)
+    ds.query_sync()
+    got = {k: getattr(r, k).cpu().numpy() for k in render.QUERY_OUTPUTS}
+    small = run_query(ds, rays[:3], F32, AUTO)
+    for k in render.QUERY_OUTPUTS:
+        assert np.array_equal(got[k][:3], small[k], equal_nan=True), k
+    sample = np.concatenate([np.arange(0, BIG, 1021), [BIG - 1]])
+    idx, tt, _, _ = brute_force(oracle, sd, rays[sample], TMIN, F32)
+    assert np.array_equal(got["index"][sample], idx) and np.array_equal(got["t"][sample].astype(np.float64), tt)
+    assert np.array_equal(small["index"], idx[:1].repeat(3)) and (idx >= 0).any()
+    ds.close()
+
+
 def _frame(ds, cam, p):
     out = torch.full((render.shard_rows(p), p.width, 3), float("nan"), device="cuda")
     torch.cuda.synchronize()
