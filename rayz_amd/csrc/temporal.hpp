@@ -1,5 +1,6 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
-// temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp).
+// temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp) and
+// the one procedure of a step of either kind, temporal_run_step.
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
@@ -87,19 +88,28 @@ void temporal_stepped(RayzTemporal* tm, const RayzCameraDesc* cam, const float* 
     std::memcpy(tm->from, from, sizeof(tm->from));
 }
 
+// The parameters a step takes where the caller gives none.
+RayzTemporalParams temporal_params_or_default(const RayzTemporalParams* params) {
+    return params ? *params
+                  : RayzTemporalParams{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
+                                       RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
+}
+
+// What a step of either kind does once its own parameters and buffers are checked: the last checks — of the guides and the
+// camera, of the handle and of its mode (moments: the kind of handle this step takes) — and then the step on the handle's stream
+// behind the previous one.  launch(stream, the plain step's arguments, is_static) completes the mode's arguments and launches.
 // Every argument is checked before the handle, and nothing here touches a device until all of them passed.
-int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, const float* d_in,
-                  const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, void* stream_arg) {
-    RayzTemporalParams p{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
-                         RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
-    if (params) p = *params;
-    RAYZ_TRY(temporal_params_check(p, spp));
-    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
-    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
+template <class Launch>
+int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& p, const RayzCameraDesc* cam, uint32_t spp,
+                      const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out,
+                      void* stream_arg, const Launch& launch) {
     float M[9], from[3];
     RAYZ_TRY(temporal_frame_check(g, cam, M, from));
     RAYZ_TRY(frame_handle_check(tm));
-    if (tm->moments) return fail(RAYZ_ERR_STATE, "a temporal handle in moments mode takes rayz_hip_temporal_step_moments");
+    if (tm->moments != moments)
+        return fail(RAYZ_ERR_STATE, "%s",
+                    moments ? "a plain temporal handle takes rayz_hip_temporal_step (rayz_hip_temporal_track_moments first)"
+                            : "a temporal handle in moments mode takes rayz_hip_temporal_step_moments");
     hipStream_t st;
     RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
     DeviceScope scope(tm->device);
@@ -108,10 +118,22 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     const TemporalArgs a = temporal_args(tm, p, spp, d_in, d_var, g, d_out, d_var_out, d_len_out);
     tm->timed = false; // (a step that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(tm, 0, st));
-    temporal_launch_step(st, a, is_static);
+    launch(st, a, is_static);
     RAYZ_TRY(frame_handle_launched(tm, 1, st));
     temporal_stepped(tm, cam, M, from);
     return RAYZ_OK;
+}
+
+int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, const float* d_in,
+                  const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, void* stream_arg) {
+    const RayzTemporalParams p = temporal_params_or_default(params);
+    RAYZ_TRY(temporal_params_check(p, spp));
+    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
+    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
+    const auto launch = [](hipStream_t st, const TemporalArgs& a, bool is_static) {
+        temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
+    };
+    return temporal_run_step(tm, false, p, cam, spp, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch);
 }
 
 int temporal_reset(RayzTemporal* tm) {

@@ -8,7 +8,7 @@
 // moments step writes and never reads, holds {m1.r, m1.g, m1.b, 0} instead — the raw first moment, what the colour would be had no
 // feedback ever been given.  Every accepted tap reads it too (one more 16-byte record per tap, in the second round of loads), it is
 // blended exactly as the colour is, and §4.16's step 3 takes it where it takes the colour.  LDS, the vote and the barriers are the
-// moments step's.
+// moments step's; the launch is temporal_kernel.hpp's temporal_launch_step, as every step's.
 //
 // The WRITE replaces {c.r, c.g, c.b} of the history side the last step wrote with the caller's pixel and leaves the length in
 // c.w: a streaming kernel on the 32x8 tiles, 12 bytes read and one 16-byte record read and written per pixel, no LDS.  A pixel with
@@ -37,13 +37,7 @@ __global__ __launch_bounds__(256) void temporal_feedback_write_kernel(dn4* __res
     if (tf_finite(r) && tf_finite(g) && tf_finite(b)) c[p] = dn4{r, g, b, was.w};
 }
 
-// ---- host side: the launches (temporal_moments.hpp owns the validation) ----------------------------------------------------------
-inline void temporal_feedback_launch_step(hipStream_t st, const TemporalMomentsArgs& m, bool is_static) {
-    const dim3 grid = denoise_grid(m.t.width, m.t.height), block(256);
-    if (is_static) hipLaunchKernelGGL((temporal_feedback_step_kernel<true>), grid, block, 0, st, m);
-    else hipLaunchKernelGGL((temporal_feedback_step_kernel<false>), grid, block, 0, st, m);
-}
-
+// ---- host side: the write's launch (the steps': temporal_kernel.hpp; temporal_moments.hpp owns the validation) -------------------
 inline void temporal_feedback_launch_write(hipStream_t st, dn4* c, const float* rgb, uint32_t width, uint32_t height) {
     hipLaunchKernelGGL(temporal_feedback_write_kernel, denoise_grid(width, height), dim3(256), 0, st, c, rgb, width, height);
 }

@@ -11,8 +11,13 @@
 // position is data-dependent, and a tile's taps need not lie in a tile.
 //
 // The arithmetic is a contract (§4.15): + - x, the FMAs written below, correctly rounded divides, floor, comparisons — so that
-// tests/temporal_mirror.cpp restates it bit for bit.  What a tap decides is in ta_accepts(), what it adds in ta_add(); the static
+// tests/temporal_mirror.cpp restates it bit for bit.  What a tap decides is in ta_accepts(), what it adds in TaAcc::add(); the static
 // form (the camera did not move: the one tap is the pixel's own record) is a template flag of the same kernel.
+//
+// ta_gather() is the single statement of §4.15 steps 1-4 up to the sums for all three modes — the reprojection through M, the
+// tap positions and weights, the two rounds of loads, the acceptance, the sums in tap order — and ta_blend_head() / ta_blend()
+// that of the blend weight, the capped length and the blend itself: the moments and the feedback step (§4.16, §4.17;
+// temporal_moments_kernel.hpp, temporal_feedback_kernel.hpp) call them with their own record lists and blend their own channels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -48,10 +53,6 @@ struct TemporalArgs {
     float spp, am, nm, cm, r2;         // f32 of samples per pixel, alpha_min, n_max, normal_cos_min; r2 = f32(max_rel_dist)²
 };
 
-struct TaAcc {
-    float B, Hr, Hg, Hb, Vr, Vg, Vb, N;
-};
-
 // A tap's guide records against the current pixel's id, n, P and lim = r2·|P − from|²: is this history pixel the same surface?
 __device__ __forceinline__ bool ta_accepts(const TemporalArgs& a, const dn4 g, const dn4 pp, int32_t id, float nx, float ny, float nz,
                                            float Px, float Py, float Pz, float lim) {
@@ -61,17 +62,96 @@ __device__ __forceinline__ bool ta_accepts(const TemporalArgs& a, const dn4 g, c
     return dn_dot(dx, dy, dz, dx, dy, dz) <= lim;
 }
 
-// An accepted tap of bilinear weight b: its colour + length and variance records join the sums, in tap order.
-__device__ __forceinline__ void ta_add(const dn4 c, const dn4 v, float b, TaAcc& acc) {
-    acc.B = acc.B + b;
-    acc.Hr = __builtin_fmaf(b, c.x, acc.Hr);
-    acc.Vr = __builtin_fmaf(b, v.x, acc.Vr);
-    acc.Hg = __builtin_fmaf(b, c.y, acc.Hg);
-    acc.Vg = __builtin_fmaf(b, v.y, acc.Vg);
-    acc.Hb = __builtin_fmaf(b, c.z, acc.Hb);
-    acc.Vb = __builtin_fmaf(b, v.z, acc.Vb);
-    acc.N = __builtin_fmaf(b, c.w, acc.N);
+// The sums over a pixel's accepted taps: their bilinear weights and, for each of the R records a tap adds, the weighted records.
+// The plain step adds {c, v}, the moments step {c, m}, the feedback step {c, m, m1}; record 0 is always c, whose .w is the length.
+// (A lane no mode reads — the .w of v and of m1 — is summed here and dropped by the compiler: it costs no instruction.)
+template <int R> struct TaAcc {
+    float B = 0.0f;
+    float sum[R][4] = {};
+
+    // An accepted tap of bilinear weight b joins the sums.  Only the order of TAPS within one sum is the contract; the sums of
+    // different records and lanes are independent of each other.
+    __device__ __forceinline__ void add(const dn4 (&rec)[R], float b) {
+        B = B + b;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < R; ++r) sum[r][j] = __builtin_fmaf(b, rec[r][j], sum[r][j]);
+    }
+    __device__ __forceinline__ bool found() const { return B >= kTaMinWeight; } // else there is no history: step 4's selection
+    __device__ __forceinline__ float mean(int r, int j) const { return sum[r][j] / B; }
+};
+
+// §4.15 steps 1-3 for one pixel with id >= 0 of a handle with history: the sums over the history taps that are the same surface.
+// rec: the R arrays of the previous side whose records an accepted tap adds.  STATIC (the camera did not move): the one tap is
+// the pixel's own record, with weight 1.
+template <bool STATIC, int R>
+__device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* const* rec, size_t p, int32_t id, float nx, float ny,
+                                              float nz, float Px, float Py, float Pz) {
+    TaAcc<R> acc;
+    const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
+    const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
+    if (STATIC) {
+        if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim)) {
+            dn4 own[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) own[r] = rec[r][p];
+            acc.add(own, 1.0f);
+        }
+        return acc;
+    }
+    const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
+    const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
+    const float ga = __builtin_fmaf(a.M[8], wz, __builtin_fmaf(a.M[7], wy, a.M[6] * wx));
+    if (!(ga > 0.0f)) return acc;
+    const float hx = al / ga, hy = be / ga;
+    if (!(hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height)) return acc; // (so the casts below are in range)
+    const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
+    const float fx = hx - x0, fy = hy - y0;
+    const int ix = (int)x0, iy = (int)y0;
+    // The four taps in two rounds of loads, so that a pixel waits for memory twice and not once per record: first every tap's
+    // guide records, then the records it adds.  A tap outside the frame loads the nearest pixel inside it (a valid address) and
+    // is refused; a refused tap's records are loaded and not used.
+    size_t q[4];
+    bool ok[4];
+    dn4 g[4], pp[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int qx = ix + (t & 1), qy = iy + (t >> 1);
+        ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
+        const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
+        const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
+        q[t] = (size_t)cy * a.width + (size_t)cx;
+        g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
+    }
+    dn4 tap[4][R];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tap[t][r] = rec[r][q[t]];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
+        if (ok[t]) acc.add(tap[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy));
+    return acc;
 }
+
+// §4.15 step 4's head, from the sums of a pixel that found history: the blend weight al, k = 1 − al and the capped new length.
+struct TaBlend {
+    float al, k, N;
+};
+
+template <int R> __device__ __forceinline__ TaBlend ta_blend_head(const TaAcc<R>& acc, const TemporalArgs& a) {
+    const float hN = acc.mean(0, 3);
+    const float Ns = hN + a.spp;
+    const float a0 = a.spp / Ns;
+    const float al = a0 < a.am ? a.am : a0;
+    return TaBlend{al, 1.0f - al, Ns > a.nm ? a.nm : Ns};
+}
+
+// .. and the blend of the current frame's x into the history's h, which the colour, m1 and m2 channels share.
+__device__ __forceinline__ float ta_blend(float al, float x, float h) { return __builtin_fmaf(al, x - h, h); }
 
 template <bool STATIC> __global__ __launch_bounds__(256) void temporal_step_kernel(const TemporalArgs a) {
     const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
@@ -85,63 +165,18 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_step_kern
     const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
     float or_ = cr, og = cg, ob = cb, vr = sr, vg = sg, vb = sb, No = a.spp; // no history: the input, by selection
     if (id >= 0 && a.has_history) {
-        const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
-        const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
-        TaAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        if (STATIC) {
-            if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim)) ta_add(a.prev.c[p], a.prev.v[p], 1.0f, acc);
-        } else {
-            const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
-            const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
-            const float ga = __builtin_fmaf(a.M[8], wz, __builtin_fmaf(a.M[7], wy, a.M[6] * wx));
-            if (ga > 0.0f) {
-                const float hx = al / ga, hy = be / ga;
-                if (hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height) { // (so the casts below are in range)
-                    const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
-                    const float fx = hx - x0, fy = hy - y0;
-                    const int ix = (int)x0, iy = (int)y0;
-                    // The four taps in two rounds of loads, so that a pixel waits for memory twice and not once per record: first
-                    // every tap's guide records, then the colour and variance records.  A tap outside the frame loads the nearest
-                    // pixel inside it (a valid address) and is refused; a refused tap's records are loaded and not used.
-                    size_t q[4];
-                    bool ok[4];
-                    dn4 g[4], pp[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const int qx = ix + (t & 1), qy = iy + (t >> 1);
-                        ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
-                        const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
-                        const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
-                        q[t] = (size_t)cy * a.width + (size_t)cx;
-                        g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
-                    }
-                    dn4 c[4], v[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
-                        c[t] = a.prev.c[q[t]], v[t] = a.prev.v[q[t]];
-                    }
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
-                        if (ok[t]) ta_add(c[t], v[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
-                }
-            }
-        }
-        if (acc.B >= kTaMinWeight) {
-            const float hN = acc.N / acc.B;
-            const float Ns = hN + a.spp;
-            const float a0 = a.spp / Ns;
-            const float alpha = a0 < a.am ? a.am : a0;
-            const float k = 1.0f - alpha;
-            const float a2 = alpha * alpha, k2 = k * k;
-            const float hr = acc.Hr / acc.B, hg = acc.Hg / acc.B, hb = acc.Hb / acc.B;
-            or_ = __builtin_fmaf(alpha, cr - hr, hr);
-            og = __builtin_fmaf(alpha, cg - hg, hg);
-            ob = __builtin_fmaf(alpha, cb - hb, hb);
-            vr = __builtin_fmaf(a2, sr, k2 * (acc.Vr / acc.B));
-            vg = __builtin_fmaf(a2, sg, k2 * (acc.Vg / acc.B));
-            vb = __builtin_fmaf(a2, sb, k2 * (acc.Vb / acc.B));
-            No = Ns > a.nm ? a.nm : Ns;
+        const dn4* const rec[2] = {a.prev.c, a.prev.v};
+        const TaAcc<2> acc = ta_gather<STATIC, 2>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
+        if (acc.found()) {
+            const TaBlend h = ta_blend_head(acc, a);
+            const float a2 = h.al * h.al, k2 = h.k * h.k;
+            or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+            og = ta_blend(h.al, cg, acc.mean(0, 1));
+            ob = ta_blend(h.al, cb, acc.mean(0, 2));
+            vr = __builtin_fmaf(a2, sr, k2 * acc.mean(1, 0));
+            vg = __builtin_fmaf(a2, sg, k2 * acc.mean(1, 1));
+            vb = __builtin_fmaf(a2, sb, k2 * acc.mean(1, 2));
+            No = h.N;
         }
     }
     a.next.c[p] = dn4{or_, og, ob, No};
@@ -153,11 +188,12 @@ template <bool STATIC> __global__ __launch_bounds__(256) void temporal_step_kern
     if (a.len_out) a.len_out[p] = No;
 }
 
-// ---- host side: the launch (temporal.hpp owns the handle, the validation and the stream) ----------------------------------------
-inline void temporal_launch_step(hipStream_t st, const TemporalArgs& a, bool is_static) {
-    const dim3 grid = denoise_grid(a.width, a.height), block(256);
-    if (is_static) hipLaunchKernelGGL((temporal_step_kernel<true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((temporal_step_kernel<false>), grid, block, 0, st, a);
+// ---- host side: the launch of any of the three modes' steps (temporal.hpp owns the handle, the validation and the stream) ------
+// still, moving: the <true> and <false> instantiations of a step kernel template.
+template <class Args>
+inline void temporal_launch_step(hipStream_t st, void (*still)(Args), void (*moving)(Args), bool is_static, const Args& a, uint32_t width,
+                                 uint32_t height) {
+    hipLaunchKernelGGL(is_static ? still : moving, denoise_grid(width, height), dim3(256), 0, st, a);
 }
 
 } // namespace rayz_dev

@@ -1,6 +1,7 @@
 // temporal_moments.hpp — the moments mode of temporal accumulation's handle (rayz_hip_temporal_track_moments, _step_moments;
-// DESIGN.md §4.16; the kernel and its launch: temporal_moments_kernel.hpp; the handle and what both kinds of step share:
-// temporal.hpp) and its feedback mode (rayz_hip_temporal_track_feedback, _feedback; §4.17; temporal_feedback_kernel.hpp).
+// DESIGN.md §4.16; the kernel: temporal_moments_kernel.hpp; the handle and what both kinds of step share — temporal_run_step, the
+// step's procedure —: temporal.hpp; the launch: temporal_kernel.hpp) and its feedback mode (rayz_hip_temporal_track_feedback,
+// _feedback; §4.17; temporal_feedback_kernel.hpp).
 // Included by rayz_hip.hip after temporal.hpp.
 #pragma once
 
@@ -50,14 +51,12 @@ int temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* stream_arg) {
     return RAYZ_OK;
 }
 
-// Every argument is checked before the handle, and nothing here touches a device until all of them passed.
+// Its own checks, then temporal.hpp's temporal_run_step: every argument is checked before the handle.
 int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, const RayzTemporalMomentsParams* mparams,
                           const RayzCameraDesc* cam, uint32_t spp, const float* d_in, const RayzQueryOutputs* g, float* d_out,
                           float* d_var_out, float* d_len_out, float* d_w2_out, void* stream_arg) {
-    RayzTemporalParams p{RAYZ_TEMPORAL_DEFAULT_ALPHA_MIN, RAYZ_TEMPORAL_DEFAULT_N_MAX, RAYZ_TEMPORAL_DEFAULT_NORMAL_COS_MIN,
-                         RAYZ_TEMPORAL_DEFAULT_MAX_REL_DIST};
+    const RayzTemporalParams p = temporal_params_or_default(params);
     RayzTemporalMomentsParams mp{RAYZ_TEMPORAL_MOMENTS_DEFAULT_W2_MAX, RAYZ_TEMPORAL_MOMENTS_DEFAULT_MIN_TAPS};
-    if (params) p = *params;
     if (mparams) mp = *mparams;
     RAYZ_TRY(temporal_params_check(p, spp));
     if (!(mp.w2_max >= 0 && mp.w2_max <= 1)) return fail(RAYZ_ERR_BAD_ARG, "temporal w2_max %g: must lie in [0, 1]", mp.w2_max);
@@ -66,26 +65,17 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
     if (!d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer");
     if (d_out == d_in)
         return fail(RAYZ_ERR_BAD_ARG, "temporal: a moments step cannot run in place (d_rgb_out == d_rgb_in: neighbours read the current frame)");
-    float M[9], from[3];
-    RAYZ_TRY(temporal_frame_check(g, cam, M, from));
-    RAYZ_TRY(frame_handle_check(tm));
-    if (!tm->moments) return fail(RAYZ_ERR_STATE, "a plain temporal handle takes rayz_hip_temporal_step (rayz_hip_temporal_track_moments first)");
-    hipStream_t st;
-    RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
-    DeviceScope scope(tm->device);
-    RAYZ_TRY(frame_handle_wait_previous(tm, st)); // (this step reads what the previous one wrote)
-    const bool is_static = tm->has_history && std::memcmp(cam, &tm->cam, sizeof(RayzCameraDesc)) == 0;
-    TemporalMomentsArgs a{};
-    a.t = temporal_args(tm, p, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out);
-    a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
-    a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
-    tm->timed = false; // (a step that fails half-way leaves no timing)
-    RAYZ_TRY(frame_handle_record(tm, 0, st));
-    if (tm->feedback) temporal_feedback_launch_step(st, a, is_static);
-    else temporal_moments_launch_step(st, a, is_static);
-    RAYZ_TRY(frame_handle_launched(tm, 1, st));
-    temporal_stepped(tm, cam, M, from);
-    return RAYZ_OK;
+    const auto launch = [&](hipStream_t st, const TemporalArgs& t, bool is_static) { // (behind the handle's check: tm is a handle)
+        TemporalMomentsArgs a{};
+        a.t = t;
+        a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
+        a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
+        if (tm->feedback)
+            temporal_launch_step(st, temporal_feedback_step_kernel<true>, temporal_feedback_step_kernel<false>, is_static, a, t.width, t.height);
+        else
+            temporal_launch_step(st, temporal_moments_step_kernel<true>, temporal_moments_step_kernel<false>, is_static, a, t.width, t.height);
+    };
+    return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch);
 }
 
 } // namespace

@@ -2,7 +2,8 @@
 // rayz_hip_temporal_step_moments; the handle and the validation: temporal_moments.hpp; the plain step: temporal_kernel.hpp).
 //
 // ONE launch per step, as the plain step: 32x8 tiles, 256 threads, the taps in two rounds of loads.  The colour and the length are
-// the plain step's, operation for operation (§4.15 steps 1-4); the variance comes from the history instead of from the caller: a
+// the plain step's, operation for operation (§4.15 steps 1-4: temporal_kernel.hpp's ta_gather, ta_blend_head and ta_blend, called
+// here with this mode's records); the variance comes from the history instead of from the caller: a
 // fifth record per pixel, {m2.r, m2.g, m2.b, W2}, carries the second moment of the colour under the same blend and the sum of the
 // squared frame weights, and v = max(m2 − c², 0)·W2 / (1 − W2).  Where the history is too short to say anything (W2 > w2_max: a
 // first frame, a disocclusion) the variance is estimated over the CURRENT frame's 7x7 neighbourhood on the same surface.
@@ -39,30 +40,6 @@ struct TemporalMomentsArgs {
     float* w2_out;     // or NULL
     float wm, mt;      // f32 of w2_max and min_taps
 };
-
-struct TmAcc {
-    float B, Hr, Hg, Hb, N, Qr, Qg, Qb, W;
-    float M1r, M1g, M1b; // the feedback step's sums of m1; unused otherwise
-};
-
-// An accepted tap of bilinear weight b: its colour + length and moment records join the sums, in tap order; in the feedback step
-// its raw first moment f too, exactly as the colour does.
-template <bool FEEDBACK> __device__ __forceinline__ void tm_add(const dn4 c, const dn4 m, const dn4 f, float b, TmAcc& acc) {
-    acc.B = acc.B + b;
-    acc.Hr = __builtin_fmaf(b, c.x, acc.Hr);
-    acc.Qr = __builtin_fmaf(b, m.x, acc.Qr);
-    acc.Hg = __builtin_fmaf(b, c.y, acc.Hg);
-    acc.Qg = __builtin_fmaf(b, m.y, acc.Qg);
-    acc.Hb = __builtin_fmaf(b, c.z, acc.Hb);
-    acc.Qb = __builtin_fmaf(b, m.z, acc.Qb);
-    acc.N = __builtin_fmaf(b, c.w, acc.N);
-    acc.W = __builtin_fmaf(b, m.w, acc.W);
-    if (FEEDBACK) {
-        acc.M1r = __builtin_fmaf(b, f.x, acc.M1r);
-        acc.M1g = __builtin_fmaf(b, f.y, acc.M1g);
-        acc.M1b = __builtin_fmaf(b, f.z, acc.M1b);
-    }
-}
 
 // §4.16 step 3 for one channel: the variance of the accumulated mean from its second moment.
 __device__ __forceinline__ float tm_temporal_var(float m2, float c, float W2) {
@@ -101,74 +78,26 @@ __device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const
         qr = cr * cr, qg = cg * cg, qb = cb * cb, W2 = 1.0f; // .. its square, and the weight of one frame
         fr = cr, fg = cg, fb = cb;
         if (id >= 0 && a.has_history) {
-            const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
-            const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
-            TmAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-            const dn4 none{0.0f, 0.0f, 0.0f, 0.0f};
-            if (STATIC) {
-                if (ta_accepts(a, a.prev.g[p], a.prev.p[p], id, nx, ny, nz, Px, Py, Pz, lim))
-                    tm_add<FEEDBACK>(a.prev.c[p], m.prev_m[p], FEEDBACK ? a.prev.v[p] : none, 1.0f, acc);
-            } else {
-                const float al = __builtin_fmaf(a.M[2], wz, __builtin_fmaf(a.M[1], wy, a.M[0] * wx));
-                const float be = __builtin_fmaf(a.M[5], wz, __builtin_fmaf(a.M[4], wy, a.M[3] * wx));
-                const float ga = __builtin_fmaf(a.M[8], wz, __builtin_fmaf(a.M[7], wy, a.M[6] * wx));
-                if (ga > 0.0f) {
-                    const float hx = al / ga, hy = be / ga;
-                    if (hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height) { // (so the casts below are in range)
-                        const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
-                        const float fx = hx - x0, fy = hy - y0;
-                        const int ix = (int)x0, iy = (int)y0;
-                        // Two rounds of loads, as in the plain step: every tap's guide records, then its colour and moment records
-                        // (and, in the feedback step, its m1 record).
-                        // A tap outside the frame loads the nearest pixel inside it (a valid address) and is refused.
-                        size_t q[4];
-                        bool ok[4];
-                        dn4 g[4], pp[4];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const int qx = ix + (t & 1), qy = iy + (t >> 1);
-                            ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
-                            const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
-                            const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
-                            q[t] = (size_t)cy * a.width + (size_t)cx;
-                            g[t] = a.prev.g[q[t]], pp[t] = a.prev.p[q[t]];
-                        }
-                        dn4 c[4], mm[4], f[4];
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            ok[t] = ok[t] && ta_accepts(a, g[t], pp[t], id, nx, ny, nz, Px, Py, Pz, lim);
-                            c[t] = a.prev.c[q[t]], mm[t] = m.prev_m[q[t]];
-                            f[t] = FEEDBACK ? a.prev.v[q[t]] : none;
-                        }
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
-                            if (ok[t]) tm_add<FEEDBACK>(c[t], mm[t], f[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy), acc);
-                    }
+            // §4.15 steps 1-4 (temporal_kernel.hpp): the taps add the colour + length and moment records and, in the feedback
+            // step, the raw first moment, which the v record holds there.
+            constexpr int R = FEEDBACK ? 3 : 2;
+            const dn4* const rec[3] = {a.prev.c, m.prev_m, a.prev.v};
+            const TaAcc<R> acc = ta_gather<STATIC, R>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
+            if (acc.found()) {
+                const TaBlend h = ta_blend_head(acc, a);
+                or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+                og = ta_blend(h.al, cg, acc.mean(0, 1));
+                ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                qr = ta_blend(h.al, cr * cr, acc.mean(1, 0));
+                qg = ta_blend(h.al, cg * cg, acc.mean(1, 1));
+                qb = ta_blend(h.al, cb * cb, acc.mean(1, 2));
+                W2 = __builtin_fmaf(h.k * h.k, acc.mean(1, 3), h.al * h.al);
+                if constexpr (FEEDBACK) {
+                    fr = ta_blend(h.al, cr, acc.mean(2, 0));
+                    fg = ta_blend(h.al, cg, acc.mean(2, 1));
+                    fb = ta_blend(h.al, cb, acc.mean(2, 2));
                 }
-            }
-            if (acc.B >= kTaMinWeight) {
-                const float hN = acc.N / acc.B;
-                const float Ns = hN + a.spp;
-                const float a0 = a.spp / Ns;
-                const float alpha = a0 < a.am ? a.am : a0;
-                const float k = 1.0f - alpha;
-                const float a2 = alpha * alpha, k2 = k * k;
-                const float hr = acc.Hr / acc.B, hg = acc.Hg / acc.B, hb = acc.Hb / acc.B;
-                or_ = __builtin_fmaf(alpha, cr - hr, hr);
-                og = __builtin_fmaf(alpha, cg - hg, hg);
-                ob = __builtin_fmaf(alpha, cb - hb, hb);
-                const float hqr = acc.Qr / acc.B, hqg = acc.Qg / acc.B, hqb = acc.Qb / acc.B;
-                qr = __builtin_fmaf(alpha, cr * cr - hqr, hqr);
-                qg = __builtin_fmaf(alpha, cg * cg - hqg, hqg);
-                qb = __builtin_fmaf(alpha, cb * cb - hqb, hqb);
-                W2 = __builtin_fmaf(k2, acc.W / acc.B, a2);
-                if (FEEDBACK) {
-                    const float h1r = acc.M1r / acc.B, h1g = acc.M1g / acc.B, h1b = acc.M1b / acc.B;
-                    fr = __builtin_fmaf(alpha, cr - h1r, h1r);
-                    fg = __builtin_fmaf(alpha, cg - h1g, h1g);
-                    fb = __builtin_fmaf(alpha, cb - h1b, h1b);
-                }
-                No = Ns > a.nm ? a.nm : Ns;
+                No = h.N;
             }
         }
         spatial = id >= 0 && W2 > m.wm;
@@ -225,13 +154,6 @@ __device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const
 template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_step_kernel(const TemporalMomentsArgs m) {
     __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
     tm_step<STATIC, false>(m, s_col, s_nrm);
-}
-
-// ---- host side: the launch (temporal_moments.hpp owns the validation) ------------------------------------------------------------
-inline void temporal_moments_launch_step(hipStream_t st, const TemporalMomentsArgs& m, bool is_static) {
-    const dim3 grid = denoise_grid(m.t.width, m.t.height), block(256);
-    if (is_static) hipLaunchKernelGGL((temporal_moments_step_kernel<true>), grid, block, 0, st, m);
-    else hipLaunchKernelGGL((temporal_moments_step_kernel<false>), grid, block, 0, st, m);
 }
 
 } // namespace rayz_dev

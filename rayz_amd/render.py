@@ -646,6 +646,25 @@ class Temporal(_Handle):
                    "rayz_hip_temporal_feedback")
         self._inflight = (self._inflight, rgb)  # (beside the last step's tensors, which the step's kernel may still use)
 
+    def _step_prologue(self, inputs, gbuffer, out, var_out, planes, stream):
+        """What both kinds of step do before their call: `out` and `var_out` (None: new tensors), the optional (height, width)
+        outputs `planes` ((name, False / True / tensor) each), the tensor checks in argument order, the stream's prologue.  Returns
+        (out, var_out, [a plane's tensor or None, ..], the guides' pointers)."""
+        import torch
+
+        frame = (self.height, self.width, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"]
+        if out is None:
+            out = torch.empty(frame, dtype=torch.float32, device=dev)
+        if var_out is None:
+            var_out = torch.empty(frame, dtype=torch.float32, device=dev)
+        planes = [(name, _optional_out(t, frame[:2], dev)) for name, t in planes]
+        _check_frame_tensors("the temporal handle", self._device, frame, inputs, gbuffer, need,
+                             [("out", out, frame), ("var_out", var_out, frame)] + [(name, t, frame[:2]) for name, t in planes])
+        _stream_prologue(stream, self._device)
+        return out, var_out, [t for _, t in planes], _gbuffer_pointers(gbuffer, need)
+
     def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
              stream: int = 0, **params):
         """One frame: `rgb` and `var_rgb` ((height, width, 3) float32 on the handle's device: the frame and the variance of each
@@ -655,21 +674,9 @@ class Temporal(_Handle):
         history length in samples as a third value.  `params`: the fields of RayzTemporalParams (alpha_min, n_max, normal_cos_min,
         max_rel_dist); unnamed ones take capi.TEMPORAL_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
         work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
-        import torch
-
         prm = _params(capi.TemporalParams, capi.TEMPORAL_DEFAULTS, params, "temporal")
-        frame = (self.height, self.width, 3)
-        dev = torch.device("cuda", self._device)
-        need = ["index", "normal", "point"]
-        if out is None:
-            out = torch.empty(frame, dtype=torch.float32, device=dev)
-        if var_out is None:
-            var_out = torch.empty(frame, dtype=torch.float32, device=dev)
-        length = _optional_out(length, frame[:2], dev)
-        _check_frame_tensors("the temporal handle", self._device, frame, [("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, need,
-                             [("out", out, frame), ("var_out", var_out, frame), ("length", length, frame[:2])])
-        _stream_prologue(stream, self._device)
-        o = _gbuffer_pointers(gbuffer, need)
+        out, var_out, (length,), o = self._step_prologue([("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, out, var_out, [("length", length)],
+                                                         stream)
         rc = self._lib.rayz_hip_temporal_step(self._h, C.byref(prm), C.byref(camera), int(spp), C.c_void_p(rgb.data_ptr()),
                                               C.c_void_p(var_rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
                                               C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
@@ -698,20 +705,9 @@ class Temporal(_Handle):
                       "temporal")
         mprm = _params(capi.TemporalMomentsParams, capi.TEMPORAL_MOMENTS_DEFAULTS,
                        {k: v for k, v in params.items() if k in capi.TEMPORAL_MOMENTS_DEFAULTS}, "temporal")
-        frame = (self.height, self.width, 3)
-        dev = torch.device("cuda", self._device)
-        need = ["index", "normal", "point"]
         if out is rgb or (isinstance(out, torch.Tensor) and isinstance(rgb, torch.Tensor) and out.data_ptr() == rgb.data_ptr()):
             raise ValueError("out must not be rgb: a moments step cannot run in place (neighbours read the current frame)")
-        if out is None:
-            out = torch.empty(frame, dtype=torch.float32, device=dev)
-        if var_out is None:
-            var_out = torch.empty(frame, dtype=torch.float32, device=dev)
-        length, w2 = _optional_out(length, frame[:2], dev), _optional_out(w2, frame[:2], dev)
-        _check_frame_tensors("the temporal handle", self._device, frame, [("rgb", rgb)], gbuffer, need,
-                             [("out", out, frame), ("var_out", var_out, frame), ("length", length, frame[:2]), ("w2", w2, frame[:2])])
-        _stream_prologue(stream, self._device)
-        o = _gbuffer_pointers(gbuffer, need)
+        out, var_out, (length, w2), o = self._step_prologue([("rgb", rgb)], gbuffer, out, var_out, [("length", length), ("w2", w2)], stream)
         rc = self._lib.rayz_hip_temporal_step_moments(self._h, C.byref(prm), C.byref(mprm), C.byref(camera), int(spp),
                                                       C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
                                                       C.c_void_p(var_out.data_ptr()),

@@ -4,44 +4,17 @@ the same two properties of their gfx950 code as tests/test_isa_invariants.py hol
 node load still in flight between the box step's two waits, and the kernels stay off the codegen cliffs (no vector spills in f32,
 global and not flat loads in the BVH shading pass, the flat-list kernel's scalar spills inside the guarded limit).  Their names keep
 them out of that file's `trace_kernel` patterns, which count exactly the six product kernels; hence this file."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_asm
+from isa_asm import bodies
 
 
 @pytest.fixture(scope="module")
-def device_asm(tmp_path_factory):
-    from rayz_amd import _build
-
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    asm = tmp_path_factory.mktemp("isa") / "dev.s"
-    flags = [f for f in _build.HIPFLAGS if f not in ("-fPIC", "-Wall", "-Wextra")]
-    subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", str(asm), os.path.join(ROOT, "rayz_amd", "csrc", "rayz_hip.hip")],
-                   check=True, capture_output=True, timeout=600)
-    return asm.read_text()
-
-
-def bodies(asm: str, stem: str):
-    out, name, body = {}, None, []
-    for line in asm.split("\n"):
-        m = re.match(r"^(_ZN8rayz_dev\w*" + stem + r"\w*):", line)
-        if m:
-            name, body = m.group(1), []
-            continue
-        if name is not None:
-            if line.startswith(".Lfunc_end"):
-                out[name] = body
-                name = None
-            elif not line.lstrip().startswith(";"):
-                body.append(line)
-    return out
+def device_asm():
+    return isa_asm.device_asm()
 
 
 def test_no_instruction_touches_the_node_fetch_registers_in_flight(device_asm):
@@ -76,9 +49,7 @@ def test_no_instruction_touches_the_node_fetch_registers_in_flight(device_asm):
 
 
 def test_adaptive_pass_kernels_stay_off_their_codegen_cliffs(device_asm):
-    meta = {}
-    for m in re.finditer(r"\.name:\s+(\S+)\n((?:\s+\.\w+:.*\n)+)", device_asm):
-        meta[m.group(1)] = dict(re.findall(r"\.(\w+):\s+(\S+)", m.group(2)))
+    meta = isa_asm.metadata(device_asm)
     passes = {k: v for k, v in meta.items() if "adaptive_pass_kernel" in k}
     assert len(passes) == 6, sorted(passes)  # flat f32 / f64, BVH f32 / f64 x two node-record formats
     for name, f in passes.items():

@@ -1,36 +1,14 @@
 """The feedback mode's kernels as compiled for gfx950 (cross-compiled, as tests/test_temporal_moments_isa.py does), from their
 metadata: both instantiations of the step exist, no register spilled, no scratch, the moments step's static LDS, at most 128
 vector registers, a workgroup of 256; the write kernel uses no LDS and no scratch."""
-import os
-import re
-import shutil
-import subprocess
+import isa_asm
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE_LDS = 38 * 14 * 2 * 16  # the tile plus a 3-pixel halo, two 16-byte records per position: 17,024 bytes
 VOTE_LDS = 256               # what the workgroup reduction behind __syncthreads_or takes
 
 
-def test_temporal_feedback_kernels_codegen(tmp_path):
-    from rayz_amd import _build
-
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    asm = tmp_path / "dev.s"
-    flags = [f for f in _build.HIPFLAGS if f not in ("-fPIC", "-Wall", "-Wextra")]
-    subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", str(asm), os.path.join(ROOT, "rayz_amd", "csrc", "rayz_hip.hip")],
-                   check=True, capture_output=True, timeout=600)
-    text = asm.read_text()
-    meta = {}
-    kernels = text[text.index("amdhsa.kernels:"):]
-    for entry in re.split(r"\n  - (?=\.\w+:)", kernels)[1:]:  # one YAML list item per kernel; .args holds nested items, scalars are unique
-        fields = dict(re.findall(r"^    \.(\w+):\s+(\S+)$", entry, flags=re.M))
-        fields.update(re.findall(r"^\.(\w+):\s+(\S+)$", entry.split("\n")[0]))
-        if "name" in fields:
-            meta[fields["name"]] = fields
+def test_temporal_feedback_kernels_codegen():
+    meta = isa_asm.metadata(isa_asm.device_asm())
     step = {k: v for k, v in meta.items() if "temporal_feedback_step_kernel" in k}
     assert len(step) == 2 and sum("ILb0E" in k for k in step) == 1 and sum("ILb1E" in k for k in step) == 1, sorted(step)  # moving, static
     for name, f in step.items():

@@ -1,36 +1,14 @@
 """The moments step's kernels as compiled for gfx950 (cross-compiled, as tests/test_denoise_isa.py does), from their metadata: both
 instantiations exist, no register spilled, no scratch, the static LDS that DESIGN.md §6 states, at most 128 vector registers — and
 names that stay out of the other kernels' counts."""
-import os
-import re
-import shutil
-import subprocess
+import isa_asm
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE_LDS = 38 * 14 * 2 * 16  # the tile plus a 3-pixel halo, two 16-byte records per position: 17,024 bytes
 VOTE_LDS = 256               # what the workgroup reduction behind __syncthreads_or takes
 
 
-def test_temporal_moments_kernels_codegen(tmp_path):
-    from rayz_amd import _build
-
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    asm = tmp_path / "dev.s"
-    flags = [f for f in _build.HIPFLAGS if f not in ("-fPIC", "-Wall", "-Wextra")]
-    subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", str(asm), os.path.join(ROOT, "rayz_amd", "csrc", "rayz_hip.hip")],
-                   check=True, capture_output=True, timeout=600)
-    text = asm.read_text()
-    meta = {}
-    kernels = text[text.index("amdhsa.kernels:"):]
-    for entry in re.split(r"\n  - (?=\.\w+:)", kernels)[1:]:  # one YAML list item per kernel; .args holds nested items, scalars are unique
-        fields = dict(re.findall(r"^    \.(\w+):\s+(\S+)$", entry, flags=re.M))
-        fields.update(re.findall(r"^\.(\w+):\s+(\S+)$", entry.split("\n")[0]))
-        if "name" in fields:
-            meta[fields["name"]] = fields
+def test_temporal_moments_kernels_codegen():
+    meta = isa_asm.metadata(isa_asm.device_asm())
     tm = {k: v for k, v in meta.items() if "temporal_moments_step_kernel" in k}
     assert len(tm) == 2 and sum("ILb0E" in k for k in tm) == 1 and sum("ILb1E" in k for k in tm) == 1, sorted(tm)  # moving, static
     plain = [k for k in meta if "temporal_step_kernel" in k]
