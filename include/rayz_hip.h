@@ -254,6 +254,16 @@ int rayz_hip_render_device(RayzScene* scene, const RayzCameraDesc* camera, const
 int rayz_hip_render_device_f64(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
                                double* d_rgb_out, void* hip_stream);
 
+/* The basis of the flat list's reject test.  Both forms find the same candidates up to roundings the filter's
+ * pad covers, and the f64 narrow phase decides: the image is the same, bit for bit.  XZ (e1 in the xz-plane) tests a sphere
+ * pair of a plane run or speed bucket in 6 packed FMAs and a loose y-moving one in 8; XY (e1 in the xy-plane) in 5 and 9.
+ * AUTO prices one scan of the scene under both from its slot counts and takes XY only where it is strictly cheaper.  The
+ * form applies to the one-shot and progressive flat-list renders; adaptive passes, ray queries and the BVH kernels keep XZ.
+ * _get returns the form the next flat-list render uses, never AUTO (host only: no device needed).  Default AUTO. */
+typedef enum RayzScanForm { RAYZ_SCAN_FORM_AUTO = 0, RAYZ_SCAN_FORM_XZ = 1, RAYZ_SCAN_FORM_XY = 2 } RayzScanForm;
+int rayz_hip_scene_set_scan_form(RayzScene* scene, uint32_t form);
+int rayz_hip_scene_get_scan_form(RayzScene* scene, uint32_t* form);
+
 /* Waits for the last render on `scene` and returns its counters. */
 int rayz_hip_scene_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
 
@@ -524,12 +534,21 @@ typedef enum RayzKatOp {
                                  out: r2 - p1^2 - p2^2 per sphere [0..3] (>= 0: candidate; the plane form for classes 2 / 3), the
                                       same value from the general-velocity form the BVH leaves use [4..7], the padded r2 (f32) the
                                       library used [8..11] if want_r2, else 0              src/geom.zig:40-50, DESIGN.md 4.3 */
-    RAYZ_KAT_BUCKET_DISCS = 10 /* one 4-sphere block of a SPEED BUCKET of a y-moving plane run, as the scan loop evaluates it
+    RAYZ_KAT_BUCKET_DISCS = 10, /* one 4-sphere block of a SPEED BUCKET of a y-moving plane run, as the scan loop evaluates it
                                  (ScanGroup<float, 5>: the static plane form, the bucket's speed folded into K2):
                                  in: cx[0..3] cy[4] (the run's height) cz[8..11] radius[12..15] vy[16..19] origin[20..22]
                                      dir[23..25] time[26] v0[27] (the bucket's speed; finite, RAYZ_ERR_BAD_ARG otherwise)
                                  out: r2b - p1^2 - p2^2 per sphere [0..3], K2 = fm(v0, time * e2y, fm(cy, e2y, k2)) [4], the
                                       padded r2b (f32) of radius + |vy - v0| the library used [8..11]      DESIGN.md 4.3 */
+    RAYZ_KAT_SCAN_DISCS_XY = 11, /* RAYZ_KAT_SCAN_DISCS' record (same fields, same checks) through the reject test's XY basis
+                                 (RAYZ_SCAN_FORM_XY: e1 in the xy-plane; a plane run folds its height into K1 and K2 and tests
+                                 a sphere pair in 5 packed FMAs):
+                                 out: r2 - p1^2 - p2^2 per sphere [0..3], the k1 and k2 the block was tested with [4] [5] (a
+                                      plane run's K1 = fm(cy, e1y, k1), K2 = fm(cy, e2y, k2)), e1x [6], e1y [7], the padded r2
+                                      [8..11] if want_r2, else 0                                            DESIGN.md 4.3 */
+    RAYZ_KAT_BUCKET_DISCS_XY = 12 /* RAYZ_KAT_BUCKET_DISCS' record through the XY basis:
+                                 out: r2b - p1^2 - p2^2 per sphere [0..3], K1 = fm(v0, time * e1y, fm(cy, e1y, k1)) [4],
+                                      K2 = fm(v0, time * e2y, fm(cy, e2y, k2)) [5], e1x [6], e1y [7], the padded r2b [8..11] */
 } RayzKatOp;
 #define RAYZ_KAT_IN_STRIDE 48
 #define RAYZ_KAT_OUT_STRIDE 12

@@ -20,7 +20,8 @@ GATHER_ALLOW_DUPLICATE_DEVICES = 0x100  # flag bit, peer-copy only (tests on a o
  DEBUG_LDS_PAD, DEBUG_BVH_TOP_ORDER, DEBUG_BVH_NODES, DEBUG_BVH_SPLIT, DEBUG_BVHX, DEBUG_CHUNK_CAP,
  DEBUG_DENOISE_LDS_STRIDE) = range(13)
 (KAT_REFRACT, KAT_REFLECTANCE, KAT_GET_RAY, KAT_BOX_HIT, KAT_SPHERE_HIT, KAT_SCATTER, KAT_CHECKER, KAT_BACKGROUND,
- KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS) = range(11)
+ KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS, KAT_SCAN_DISCS_XY, KAT_BUCKET_DISCS_XY) = range(13)
+SCAN_FORM_AUTO, SCAN_FORM_XZ, SCAN_FORM_XY = 0, 1, 2  # RayzScanForm: the basis of the flat list's reject test
 KAT_IN_STRIDE, KAT_OUT_STRIDE = 48, 12
 
 OK = 0
@@ -158,6 +159,8 @@ PROTOTYPES = [
      [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
     ("rayz_hip_render_device_f64", C.c_int,
      [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
+    ("rayz_hip_scene_set_scan_form", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("rayz_hip_scene_get_scan_form", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("rayz_hip_scene_sync", C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     ("rayz_hip_render", C.c_int,
      [C.POINTER(SceneDesc), C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,

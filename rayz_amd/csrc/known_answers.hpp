@@ -90,7 +90,7 @@ int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint3
 // ---- known answers: the kernel's device functions on caller inputs ---------------------------------------------
 int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, double* out) {
     return guarded([&] {
-        if (op > RAYZ_KAT_BUCKET_DISCS) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
+        if (op > RAYZ_KAT_BUCKET_DISCS_XY) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
         if (precision > RAYZ_PRECISION_F64) return fail(RAYZ_ERR_BAD_ARG, "bad precision %u", precision);
         if (!n) return (int)RAYZ_OK;
         if (!in || !out) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
@@ -128,7 +128,7 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
                     for (int k = 0; k < 3; ++k) a[14 + k] = w[k] & 0xffffu, a[17 + k] = w[k] >> 16, a[20 + k] = g.glo[k], a[23 + k] = g.cell[k];
                 }
             }
-            if (op == RAYZ_KAT_SCAN_DISCS) { // the padded squares the scan streams would hold for these four spheres
+            if (op == RAYZ_KAT_SCAN_DISCS || op == RAYZ_KAT_SCAN_DISCS_XY) { // the padded squares the scan streams would hold for these four spheres
                 const double cls = a[27];
                 if (!(cls == 0.0 || cls == 1.0 || cls == 2.0 || cls == 3.0))
                     return fail(RAYZ_ERR_BAD_ARG, "record %u: class = %g is not 0, 1, 2 or 3", i, cls);
@@ -151,7 +151,7 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
                 for (int k = 0; k < 4; ++k)
                     a[28 + k] = precision == RAYZ_PRECISION_F32 ? (double)pad_radius2_scan<float>(q[k], S) : (double)pad_radius2_scan<double>(q[k], S);
             }
-            if (op == RAYZ_KAT_BUCKET_DISCS) { // the padded squares a speed bucket of speed v0 would hold for these four spheres
+            if (op == RAYZ_KAT_BUCKET_DISCS || op == RAYZ_KAT_BUCKET_DISCS_XY) { // the padded squares a speed bucket of speed v0 would hold for these four spheres
                 if (!std::isfinite(a[27])) return fail(RAYZ_ERR_BAD_ARG, "record %u: v0 = %g is not finite", i, a[27]);
                 double S = norm3(a + 20);
                 RayzSphere q[4] = {};

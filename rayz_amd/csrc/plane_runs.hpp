@@ -146,4 +146,29 @@ template <class VyOf, class ROf> RunBuckets plan_buckets(const std::vector<uint3
     return out;
 }
 
+// ---- which basis the scan's reject test runs in ---------------------------------------------------
+// The slots one scan tests, by the form that tests them, and the packed FMAs a sphere pair costs there under the XZ basis (e1 in
+// the xz-plane) and the XY basis (e1 in the xy-plane: a plane run folds its height into K1 too).  The scan sits on its VALU-issue
+// bound, so FMAs per slot price it.  XY is chosen only where it is strictly cheaper: a tie keeps the XZ kernel.
+struct ScanSlots {
+    uint64_t plane_static = 0, bucket = 0, plane_movy = 0, loose_static = 0, loose_movy = 0, movg = 0;
+};
+constexpr uint32_t kScanFormAuto = 0, kScanFormXZ = 1, kScanFormXY = 2;
+inline uint64_t scan_price(const ScanSlots& n, uint32_t form) {
+    const bool xy = form == kScanFormXY;
+    return (xy ? 5 : 6) * (n.plane_static + n.bucket) + 7 * (n.plane_movy + n.loose_static) + (xy ? 9 : 8) * n.loose_movy + 12 * n.movg;
+}
+inline uint32_t cheaper_scan_form(const ScanSlots& n) { return scan_price(n, kScanFormXY) < scan_price(n, kScanFormXZ) ? kScanFormXY : kScanFormXZ; }
+// The slots of a layout: plane_slots[c] and class_slots[c] of the static (0) and mov-Y (1) classes (class_slots: runs and the
+// loose spheres' whole group pairs), the mov-Y runs' buckets, the mov-G class's slots.
+inline ScanSlots scan_slots(const uint32_t (&plane_slots)[2], const uint32_t (&class_slots)[2], const std::vector<RunBuckets>& buckets,
+                            uint32_t movg_slots) {
+    ScanSlots n;
+    for (const RunBuckets& b : buckets) n.bucket += b.bucketed;
+    n.plane_static = plane_slots[0], n.plane_movy = plane_slots[1] - n.bucket;
+    n.loose_static = class_slots[0] - plane_slots[0], n.loose_movy = class_slots[1] - plane_slots[1];
+    n.movg = movg_slots;
+    return n;
+}
+
 } // namespace rayz_plane

@@ -326,23 +326,49 @@ __device__ __forceinline__ void narrow_eval(const d4 c, const d4 v, int pool, V<
 // p1² + p2² with p1 = c·e1 + k1 (2 FMAs; a y-velocity never enters it) and p2 = c·e2 + k2 (3 FMAs), so the test
 // r² − p1² − p2² ≥ 0 costs 7 VALU per static sphere, 8 with a y-velocity, 12 with a general one — against
 // 10 / 11 / 13 for the textbook (ud·oc)² − (|oc|² − r²), and needs no c − o.
-template <class R> struct RayBasis {
+// Which axis e1 avoids is a compile-time fact of a basis (and of the kernel that scans with it).  kBasisXZ is the form above.
+// kBasisXY keeps e1 in the xy-plane (e1.z = 0): e1 = (ud.y, −ud.x, 0)/√(ud.x² + ud.y²), e2 = ud × e1.  Its p1 = cx·e1x + cy·e1y + k1
+// has no cz term, and in a plane run (one cy) cy·e1y folds into a per-run K1 as cy·e2y folds into K2: a plane sphere costs
+// p1 = fm(cx, e1x, K1), p2 = fm(cz, e2z, fm(cx, e2x, K2)) and the disc's two: 5 packed FMAs per sphere pair, not 6.  A loose
+// sphere stays at 7, a loose y-moving one pays 9 (vy enters p1 too), a general velocity 12.
+constexpr int kBasisXZ = 0, kBasisXY = 1;
+template <class R, int AX = kBasisXZ> struct RayBasis {
     R e1x, e1z, e2x, e2y, e2z, k1, k2;
 };
-template <class R> __device__ __forceinline__ RayBasis<R> make_basis(V<R> ud, V<R> o) {
-    RayBasis<R> b;
-    const R h2 = fm(ud.z, ud.z, ud.x * ud.x);
-    b.e1x = R(1);
-    b.e1z = R(0);
-    if (h2 > R(1e-30)) { // below that (|ud.x|, |ud.z| < 1e-15) the x axis is perpendicular to ud far inside the slack
-        const R ih = R(1) / sq(h2);
-        b.e1x = ud.z * ih;
-        b.e1z = -(ud.x * ih);
+template <class R> struct RayBasis<R, kBasisXY> {
+    R e1x, e1y, e2x, e2y, e2z, k1, k2;
+};
+// k1 = −o·e1 of the xy basis, as make_basis rounds it (the scan makes it again after a plane run: scan_plane_class).
+template <class R> __device__ __forceinline__ R basis_xy_k1(const RayBasis<R, kBasisXY>& b, R ox, R oy) { return -fm(oy, b.e1y, ox * b.e1x); }
+template <class R, int AX = kBasisXZ> __device__ __forceinline__ RayBasis<R, AX> make_basis(V<R> ud, V<R> o) {
+    RayBasis<R, AX> b;
+    if constexpr (AX == kBasisXY) {
+        const R h2 = fm(ud.y, ud.y, ud.x * ud.x);
+        b.e1x = R(1);
+        b.e1y = R(0);
+        if (h2 > R(1e-30)) { // below that (|ud.x|, |ud.y| < 1e-15) the x axis is perpendicular to ud far inside the slack
+            const R ih = R(1) / sq(h2);
+            b.e1x = ud.y * ih;
+            b.e1y = -(ud.x * ih);
+        }
+        b.e2x = -(ud.z * b.e1y);
+        b.e2y = ud.z * b.e1x;
+        b.e2z = fm(ud.x, b.e1y, -(ud.y * b.e1x));
+        b.k1 = basis_xy_k1<R>(b, o.x, o.y);
+    } else {
+        const R h2 = fm(ud.z, ud.z, ud.x * ud.x);
+        b.e1x = R(1);
+        b.e1z = R(0);
+        if (h2 > R(1e-30)) { // below that (|ud.x|, |ud.z| < 1e-15) the x axis is perpendicular to ud far inside the slack
+            const R ih = R(1) / sq(h2);
+            b.e1x = ud.z * ih;
+            b.e1z = -(ud.x * ih);
+        }
+        b.e2x = ud.y * b.e1z;
+        b.e2y = fm(ud.z, b.e1x, -(ud.x * b.e1z));
+        b.e2z = -(ud.y * b.e1x);
+        b.k1 = -fm(o.z, b.e1z, o.x * b.e1x);
     }
-    b.e2x = ud.y * b.e1z;
-    b.e2y = fm(ud.z, b.e1x, -(ud.x * b.e1z));
-    b.e2z = -(ud.y * b.e1x);
-    b.k1 = -fm(o.z, b.e1z, o.x * b.e1x);
     b.k2 = -fm(o.z, b.e2z, fm(o.y, b.e2y, o.x * b.e2x));
     return b;
 }
@@ -498,6 +524,38 @@ template <class R, bool kCy, bool kVy> struct PackedGroup {
 #pragma unroll
         for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
+    // The xy basis (kBasisXY): cy and vy enter p1 instead of cz.  Plane-run blocks (kCy = false) find the run's K1 in b.k1 as they
+    // find K2 in b.k2.  Stage by stage across the group's pairs, as above.
+    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R, kBasisXY>& b, [[maybe_unused]] R time) const {
+        const R t1y = kVy ? time * b.e1y : R(0), t2y = kVy ? time * b.e2y : R(0);
+        [[maybe_unused]] const pr E1x{b.e1x, b.e1x}, E1y{b.e1y, b.e1y}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
+            K1{b.k1, b.k1}, K2{b.k2, b.k2}, T1y{t1y, t1y}, T2y{t2y, t2y};
+        pr p1[H], p2[H], d[H];
+#pragma unroll
+        for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cx[q], E1x, K1);
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cx[q], E2x, K2);
+        if constexpr (kCy) {
+#pragma unroll
+            for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(cy[q], E1y, p1[q]);
+#pragma unroll
+            for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cy[q], E2y, p2[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(cz[q], E2z, p2[q]);
+        if constexpr (kVy) {
+#pragma unroll
+            for (int q = 0; q < H; ++q) p1[q] = __builtin_elementwise_fma(vy[q], T1y, p1[q]);
+#pragma unroll
+            for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
+#pragma unroll
+        for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
+    }
 };
 // The forms: their stream, and the slot their first block's first sphere has (DevScene's slot order).
 template <class R> struct ScanGroup<R, 0> : PackedGroup<R, true, false> { // static
@@ -544,7 +602,13 @@ template <class R> struct ScanGroup<R, 2> { // mov-G
                         fm(v[k].y, time * b.e2y, fm(v[k].x, time * b.e2x, basis_p2<R>(b, c[k].x, c[k].y, c[k].z))));
         return basis_disc<R>(p1, p2, c[k].w);
     }
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R>& b, R time) const {
+    __device__ __forceinline__ R disc(int k, const RayBasis<R, kBasisXY>& b, R time) const { // (p1 has y where the form above has z)
+        const R p1 = fm(v[k].y, time * b.e1y, fm(v[k].x, time * b.e1x, fm(c[k].y, b.e1y, fm(c[k].x, b.e1x, b.k1))));
+        const R p2 = fm(v[k].z, time * b.e2z,
+                        fm(v[k].y, time * b.e2y, fm(v[k].x, time * b.e2x, fm(c[k].z, b.e2z, fm(c[k].y, b.e2y, fm(c[k].x, b.e2x, b.k2))))));
+        return basis_disc<R>(p1, p2, c[k].w);
+    }
+    template <int AX> __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R, AX>& b, R time) const {
 #pragma unroll
         for (int k = 0; k < G; ++k) out[k] = disc(k, b, time);
     }
@@ -552,10 +616,10 @@ template <class R> struct ScanGroup<R, 2> { // mov-G
 };
 
 // What the scan needs of one ray (one of the NR rays a lane carries).
-template <class R> struct ScanRay {
+template <class R, int AX = kBasisXZ> struct ScanRay {
     V<R> o, d;
     R time;
-    RayBasis<float> basis; // the reject test runs in f32 for both precisions (FilterR): built from ud, o narrowed to f32
+    RayBasis<float, AX> basis; // the reject test runs in f32 for both precisions (FilterR): built from ud, o narrowed to f32
     float ftime;
     double inv_a2; // 1 / (d·d) in f64, for the narrow phase
     R tbest;
@@ -565,8 +629,8 @@ template <class R> struct ScanRay {
 };
 
 // Reject tests of one group for the lane's NR rays; the running maximum feeds the pair's single branch.
-template <class R, int CLS, int NR>
-__device__ __forceinline__ void group_discs(const ScanGroup<float, CLS>& g, ScanRay<R> (&ray)[NR],
+template <class R, int CLS, int NR, int AX>
+__device__ __forceinline__ void group_discs(const ScanGroup<float, CLS>& g, ScanRay<R, AX> (&ray)[NR],
                                             float (&disc)[NR][ScanGroup<float, CLS>::G], float& m, bool first) {
     constexpr int G = ScanGroup<float, CLS>::G;
 #pragma unroll
@@ -577,7 +641,7 @@ __device__ __forceinline__ void group_discs(const ScanGroup<float, CLS>& g, Scan
     }
 }
 // Evaluate every parked candidate of the wave's lanes (round j: lanes with more than j parked slots).
-template <class R, int NR> __device__ __forceinline__ void narrow_flush(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int NR, int AX> __device__ __forceinline__ void narrow_flush(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
 #pragma unroll
@@ -593,8 +657,8 @@ template <class R, int NR> __device__ __forceinline__ void narrow_flush(const De
     }
 }
 // Park one group's candidates (slots first .. first+G-1); a lane whose list is full forces a flush first.
-template <class R, int CLS, int NR>
-__device__ __forceinline__ void group_collect(const DevScene<R>& sc, int first, ScanRay<R> (&ray)[NR],
+template <class R, int CLS, int NR, int AX>
+__device__ __forceinline__ void group_collect(const DevScene<R>& sc, int first, ScanRay<R, AX> (&ray)[NR],
                                               const float (&disc)[NR][ScanGroup<float, CLS>::G], R tmin) {
     constexpr int G = ScanGroup<float, CLS>::G;
 #pragma unroll
@@ -628,9 +692,9 @@ __device__ __forceinline__ void group_collect(const DevScene<R>& sc, int first, 
 // branch, the only user of the slot number, recovers it.  The furthest group a scan loads is the one behind its last pair:
 // rayz_plane::scan_reach, held inside every section's spare groups where the host builds the streams.
 // scan_blocks tests the stream's slots i0 .. i1 (relative to the class's first slot, ScanGroup::slot0).
-template <class R, int CLS, int NR>
+template <class R, int CLS, int NR, int AX>
 __device__ __forceinline__ void scan_blocks(const DevScene<R>& sc, const RAYZ_CONSTANT float* base, int i0, int i1,
-                                            ScanRay<R> (&ray)[NR], R tmin) {
+                                            ScanRay<R, AX> (&ray)[NR], R tmin) {
     typedef ScanGroup<float, CLS> Grp;
     constexpr int G = Grp::G, W = Grp::kWords * G; // words of a group
     const RAYZ_CONSTANT float* at = base + Grp::kWords * i0;
@@ -669,8 +733,8 @@ __device__ __forceinline__ void scan_blocks(const DevScene<R>& sc, const RAYZ_CO
         }
     }
 }
-template <class R, int CLS, int NR>
-__device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int CLS, int NR, int AX>
+__device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay<R, AX> (&ray)[NR], R tmin) {
     if (n == 0) return;
     // the stream's base as a value of its own: read out of the kernel arguments it is one lane of a 16-register block,
     // and a spilled block comes back whole (the f64 kernel paid 20 v_readlane per iteration for this one pointer)
@@ -685,11 +749,20 @@ __device__ __forceinline__ float plane_run_k2(float cy, float e2y, float k2) { r
 __device__ __forceinline__ float bucket_k2(float v0, float cy, float ftime, float e2y, float k2) {
     return fm(v0, ftime * e2y, plane_run_k2(cy, e2y, k2));
 }
+// The xy basis (kBasisXY): e1 has a y component, and a run's or bucket's K1 is made of (e1y, k1) as its K2 is of (e2y, k2).
+__device__ __forceinline__ float plane_run_k1(float cy, float e1y, float k1) { return plane_run_k2(cy, e1y, k1); }
+__device__ __forceinline__ float bucket_k1(float v0, float cy, float ftime, float e1y, float k1) { return bucket_k2(v0, cy, ftime, e1y, k1); }
+// The xy basis's own k1 of a ray whose basis holds a run's K1 in its place: made again from the origin (two FMAs per ray and run;
+// a saved copy is one more register alive through the scan loops, and cost the f32 kernel two spilled VGPRs), bit for bit what
+// scan_begin's make_basis made: the same function of the same narrowed origin.
+template <class R> __device__ __forceinline__ float scan_k1(const ScanRay<R, kBasisXY>& ray) {
+    return basis_xy_k1<float>(ray.basis, (float)ray.o.x, (float)ray.o.y);
+}
 // The static (CLS 0) or mov-Y (CLS 1) class: its plane runs, then its loose spheres.  Per run, K2 = fm(cy, e2y, k2) replaces
 // each ray's k2 (one FMA per ray and run), which is put back before the loose spheres.  The head is read here, every scan
 // (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
-template <class R, int CLS, int NR>
-__device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_class, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int CLS, int NR, int AX>
+__device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_class, ScanRay<R, AX> (&ray)[NR], R tmin) {
     constexpr int P = ScanGroup<float, CLS + 3>::kWords, G = ScanGroup<float, CLS>::G; // words per plane sphere: the run form's
     const RAYZ_CONSTANT float* head = ScanGroup<float, CLS>::stream(sc);
     asm volatile("" : "+s"(head));
@@ -709,11 +782,17 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
                 if (first == end) continue;
             }
 #pragma unroll
-            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = plane_run_k2(cy, ray[r].basis.e2y, k2[r]);
+            for (int r = 0; r < NR; ++r) {
+                ray[r].basis.k2 = plane_run_k2(cy, ray[r].basis.e2y, k2[r]);
+                if constexpr (AX == kBasisXY) ray[r].basis.k1 = plane_run_k1(cy, ray[r].basis.e1y, scan_k1(ray[r]));
+            }
             scan_blocks<R, CLS + 3, NR>(sc, head + kPlaneHeader, first, end, ray, tmin);
         }
 #pragma unroll
-        for (int r = 0; r < NR; ++r) ray[r].basis.k2 = k2[r];
+        for (int r = 0; r < NR; ++r) {
+            ray[r].basis.k2 = k2[r];
+            if constexpr (AX == kBasisXY) ray[r].basis.k1 = scan_k1(ray[r]);
+        }
     }
     if (n_class > plane) scan_blocks<R, CLS, NR>(sc, head + kPlaneHeader + P * (plane + 2 * G), 0, n_class - plane, ray, tmin);
     if constexpr (CLS == 1) { // the speed buckets, after the loose spheres (scan order is free: scan_sphere_classes)
@@ -726,17 +805,23 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
             for (int j = 0; j < nb; ++j) {
                 const float v0 = bk[j].v0, cy = bk[j].cy;
 #pragma unroll
-                for (int r = 0; r < NR; ++r) ray[r].basis.k2 = bucket_k2(v0, cy, ray[r].ftime, ray[r].basis.e2y, k2[r]);
+                for (int r = 0; r < NR; ++r) {
+                    ray[r].basis.k2 = bucket_k2(v0, cy, ray[r].ftime, ray[r].basis.e2y, k2[r]);
+                    if constexpr (AX == kBasisXY) ray[r].basis.k1 = bucket_k1(v0, cy, ray[r].ftime, ray[r].basis.e1y, scan_k1(ray[r]));
+                }
                 scan_blocks<R, 5, NR>(sc, head + bk[j].base, (int)bk[j].first, (int)bk[j].end, ray, tmin);
             }
 #pragma unroll
-            for (int r = 0; r < NR; ++r) ray[r].basis.k2 = k2[r];
+            for (int r = 0; r < NR; ++r) {
+                ray[r].basis.k2 = k2[r];
+                if constexpr (AX == kBasisXY) ray[r].basis.k1 = scan_k1(ray[r]);
+            }
         }
     }
 }
 // Every sphere class in slot order (the slot order only matters to the candidates' parking order; the acceptance rule
 // decides ties by pool index, so the hit is the same in any order).
-template <class R, int NR> __device__ __forceinline__ void scan_sphere_classes(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int NR, int AX> __device__ __forceinline__ void scan_sphere_classes(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
     scan_plane_class<R, 0, NR>(sc, (int)sc.ns_pad, ray, tmin);
     scan_plane_class<R, 1, NR>(sc, (int)sc.ny_pad, ray, tmin);
     scan_class<R, 2, NR>(sc, (int)sc.ng_pad, ray, tmin);
@@ -752,8 +837,8 @@ template <class R> struct TriGroup {
         for (int k = 0; k < kTriGroup; ++k) a[k] = p[3 * k], b[k] = p[3 * k + 1], c[k] = p[3 * k + 2];
     }
     __device__ __forceinline__ void touch() const { asm volatile("" ::"s"(a[0].x)); }
-    template <int NR>
-    __device__ __forceinline__ void test(const DevScene<R>& sc, int i, ScanRay<R> (&ray)[NR], R tmin) const {
+    template <int NR, int AX>
+    __device__ __forceinline__ void test(const DevScene<R>& sc, int i, ScanRay<R, AX> (&ray)[NR], R tmin) const {
         R f[NR][kTriGroup];
         R m = R(-1);
 #pragma unroll
@@ -775,8 +860,8 @@ template <class R> struct TriGroup {
         }
     }
 };
-template <class R, int NR>
-__device__ __forceinline__ void scan_triangles(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int NR, int AX>
+__device__ __forceinline__ void scan_triangles(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
     const int n = (int)sc.nt_pad;
     if (n == 0) return;
     const RAYZ_CONSTANT R* base = (const RAYZ_CONSTANT R*)sc.tri;
@@ -804,12 +889,12 @@ __device__ __forceinline__ void scan_triangles(const DevScene<R>& sc, ScanRay<R>
 // branch.  Hence two spheres per packed FMA (ScanGroup::discs) and one branch per 8 tests (scan_class).
 // NR = rays per lane; the product instantiates NR = 1 (two rays per lane halve the scalar loads per test and
 // were measured no faster).
-template <class R, int NR>
-__device__ __forceinline__ void scan_begin(ScanRay<R>& ray, V<R> o, V<R> d, V<R> ud, R time) {
+template <class R, int NR, int AX>
+__device__ __forceinline__ void scan_begin(ScanRay<R, AX>& ray, V<R> o, V<R> d, V<R> ud, R time) {
     ray.o = o;
     ray.d = d;
     ray.time = time;
-    ray.basis = make_basis<float>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
+    ray.basis = make_basis<float, AX>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
     ray.ftime = (float)time;
     const double ddx = d.x, ddy = d.y, ddz = d.z;
     ray.inv_a2 = 1.0 / fm(ddz, ddz, fm(ddy, ddy, ddx * ddx));
@@ -818,7 +903,7 @@ __device__ __forceinline__ void scan_begin(ScanRay<R>& ray, V<R> o, V<R> d, V<R>
     ray.cand[0] = ray.cand[1] = ray.cand[2] = ray.cand[3] = 0u;
     ray.ncand = 0u;
 }
-template <class R, int NR> __device__ __forceinline__ void scan_spheres(const DevScene<R>& sc, ScanRay<R> (&ray)[NR], R tmin) {
+template <class R, int NR, int AX> __device__ __forceinline__ void scan_spheres(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
     scan_sphere_classes<R, NR>(sc, ray, tmin);
     narrow_flush<R, NR>(sc, ray, tmin);
     scan_triangles<R, NR>(sc, ray, tmin);
@@ -1146,6 +1231,16 @@ template <class R, int NR> constexpr int flat_waves() { return sizeof(R) == 8 ? 
 #include "trace_kernel_flat.hpp"
 #undef RAYZ_TRACE_KERNEL_NAME
 #undef RAYZ_TRACE_KERNEL_ADAPTIVE
+// The same text once more with the xy basis (kBasisXY: 5 packed FMAs per sphere pair in plane runs and buckets, 9 on a loose
+// y-moving sphere): the host launches it for the scenes whose scan it prices lower (rayz_plane::scan_price).  A kernel of its
+// own name, so that trace_kernel's code is what it was.
+#define RAYZ_TRACE_KERNEL_NAME flat_xy_kernel
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#define RAYZ_TRACE_KERNEL_BASIS kBasisXY
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE
+#undef RAYZ_TRACE_KERNEL_BASIS
 #define RAYZ_TRACE_KERNEL_NAME adaptive_pass_kernel // (an adaptive pass's kernel, DESIGN.md §4.14: the same text over the active list)
 #define RAYZ_TRACE_KERNEL_ADAPTIVE true
 #include "trace_kernel_flat.hpp"
@@ -1677,7 +1772,7 @@ __global__ __launch_bounds__(256) void tonemap_kernel(const float* __restrict__ 
 constexpr int kKatIn = 48, kKatOut = 12;
 // One block of the scan in form CLS from a known-answer record (cx[4] at 0, cy[4] at 4, cz[4] at 8, vy[4] at 16, padded r²[4]
 // at 28: the form takes the fields it has), through ScanGroup::discs as the scan loop runs it.
-template <int CLS> __device__ __forceinline__ void kat_block_discs(const double* a, const RayBasis<float>& b, float ft, float (&out)[4]) {
+template <int CLS, int AX> __device__ __forceinline__ void kat_block_discs(const double* a, const RayBasis<float, AX>& b, float ft, float (&out)[4]) {
     ScanGroup<float, CLS> g;
     auto pair = [&](int at, int q) { return f2{(float)a[at + 2 * q], (float)a[at + 2 * q + 1]}; };
     for (int q = 0; q < 2; ++q) g.cx[q] = pair(0, q), g.cy[q] = pair(4, q), g.cz[q] = pair(8, q), g.vy[q] = pair(16, q), g.r2[q] = pair(28, q);
@@ -1843,6 +1938,35 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
         kat_block_discs<5>(a, b, 0.0f, out4);
         for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = (double)(float)a[28 + k];
         r[4] = (double)b.k2;
+        break;
+    }
+    case 11: { // SCAN_DISCS_XY: SCAN_DISCS' record through the xy basis (kBasisXY, flat_xy_kernel's): the run's K1 and K2 put in
+               // the basis as scan_plane_class does -> disc[4] k1|K1 k2|K2 e1x e1y r²[4] (if want_r2, else 0)
+        const V<R> o = v3(20), d = v3(23);
+        const V<R> ud = unit(d);
+        RayBasis<float, kBasisXY> b = make_basis<float, kBasisXY>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
+        const float ft = (float)(R)a[26];
+        const int cls = (int)a[27];
+        if (cls >= 2) b.k1 = plane_run_k1((float)a[4], b.e1y, b.k1), b.k2 = plane_run_k2((float)a[4], b.e2y, b.k2);
+        float out4[4];
+        if (cls == 0) kat_block_discs<0>(a, b, ft, out4);
+        else if (cls == 1) kat_block_discs<1>(a, b, ft, out4);
+        else if (cls == 2) kat_block_discs<3>(a, b, ft, out4);
+        else kat_block_discs<4>(a, b, ft, out4);
+        for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = a[32] != 0.0 ? (double)(float)a[28 + k] : 0.0;
+        r[4] = (double)b.k1, r[5] = (double)b.k2, r[6] = (double)b.e1x, r[7] = (double)b.e1y;
+        break;
+    }
+    case 12: { // BUCKET_DISCS_XY: BUCKET_DISCS' record through the xy basis -> disc[4] K1b K2b e1x e1y r2b[4]
+        const V<R> o = v3(20), d = v3(23);
+        const V<R> ud = unit(d);
+        RayBasis<float, kBasisXY> b = make_basis<float, kBasisXY>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
+        b.k1 = bucket_k1((float)a[27], (float)a[4], (float)(R)a[26], b.e1y, b.k1);
+        b.k2 = bucket_k2((float)a[27], (float)a[4], (float)(R)a[26], b.e2y, b.k2);
+        float out4[4];
+        kat_block_discs<5>(a, b, 0.0f, out4);
+        for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = (double)(float)a[28 + k];
+        r[4] = (double)b.k1, r[5] = (double)b.k2, r[6] = (double)b.e1x, r[7] = (double)b.e1y;
         break;
     }
     default: break;

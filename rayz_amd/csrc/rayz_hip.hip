@@ -56,7 +56,9 @@ struct NarrowBuffers {
     // speed buckets of each mov-Y run (rayz_plane::plan_buckets): the run's slot order is its buckets' members, its other
     // members, its pads
     std::vector<rayz_plane::RunBuckets> buckets;
-    bool ready = false, bvh_ready = false;
+    // the basis one scan of these slots is cheaper in (rayz_plane::cheaper_scan_form): a fact of the layout, priced with it
+    uint32_t scan_form = rayz_plane::kScanFormXZ;
+    bool planned = false, ready = false, bvh_ready = false;
 };
 
 uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
@@ -186,6 +188,7 @@ struct RayzScene {
     hipStream_t last_stream = nullptr;
     bool rendered = false, last_bvh = false;
     int last_experiment = 0; // the last render's BvhLaunchPlan::experiment (0: a product kernel)
+    uint32_t scan_form = rayz_plane::kScanFormAuto; // rayz_hip_scene_set_scan_form: auto = the layout's own (narrow.scan_form)
     RayzRenderStats last{};
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
     DevBuf<unsigned long long> q_counters; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
@@ -233,8 +236,11 @@ void classify(RayzScene* s) {
 uint32_t scan_len(size_t n, uint32_t group) { return round_up((uint32_t)n, 2 * group); }
 uint32_t stream_len(size_t n, uint32_t group) { return scan_len(n, group) + 2 * group; }
 
-int upload_narrow_body(RayzScene* s) {
+// The slot layout of the pool (host only): classes, plane runs, speed buckets, slot counts — and with them the scan's price
+// under either basis.
+void plan_slots(RayzScene* s) {
     NarrowBuffers& nb = s->narrow;
+    if (nb.planned) return;
     classify(s);
     // slot numbering is shared by both precisions: pad to the larger (f32) group size.  Static and mov-Y: plane runs,
     // each padded to whole group pairs, then the loose spheres
@@ -252,6 +258,14 @@ int upload_narrow_body(RayzScene* s) {
     nb.ns_pad = nb.plane_slots[0] + scan_len(nb.loose[0].size(), kStaticGroup);
     nb.ny_pad = nb.plane_slots[1] + scan_len(nb.loose[1].size(), kMovYGroup);
     nb.ng_pad = scan_len(s->cls[2].size(), kMovGGroup);
+    const uint32_t class_slots[2] = {nb.ns_pad, nb.ny_pad};
+    nb.scan_form = rayz_plane::cheaper_scan_form(rayz_plane::scan_slots(nb.plane_slots, class_slots, nb.buckets, nb.ng_pad));
+    nb.planned = true;
+}
+
+int upload_narrow_body(RayzScene* s) {
+    NarrowBuffers& nb = s->narrow;
+    plan_slots(s);
     const size_t slots = (size_t)nb.ns_pad + nb.ny_pad + nb.ng_pad;
     std::vector<d4> slot64(2 * slots, d4{0, 0, 0, 0});
     std::vector<uint32_t> slot_pool(slots, 0u);
@@ -420,6 +434,13 @@ template <class R> int upload(RayzScene* s, SceneBuffers<R>& b, double S) {
     const int rc = upload_body<R>(s, b);
     if (rc != RAYZ_OK) b = SceneBuffers<R>{};
     return rc;
+}
+
+// The basis the scene's next flat-list render scans in.
+uint32_t scene_scan_form(RayzScene* s) {
+    if (s->scan_form != rayz_plane::kScanFormAuto) return s->scan_form;
+    plan_slots(s);
+    return s->narrow.scan_form;
 }
 
 void ensure_bvh(RayzScene* s) {
@@ -942,6 +963,8 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
 
     BvhLaunchPlan<R> plan{};
     plan.kernel = active_list ? adaptive_pass_kernel<R, 1> : trace_kernel<R, 1>;
+    // the xy basis where the scene's layout prices it lower (or the caller asked for it): the same candidates' narrow phase, the same image
+    if (!active_list && !use_bvh && scene_scan_form(s) == rayz_plane::kScanFormXY) plan.kernel = flat_xy_kernel<R, 1>;
     plan.block = 256;
     plan.items_per_lane = 1;
     if (use_bvh) {
@@ -1277,6 +1300,23 @@ int rayz_hip_render_device(RayzScene* s, const RayzCameraDesc* cam, const RayzRe
 int rayz_hip_render_device_f64(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, double* d_out,
                                void* stream) {
     return guarded([&] { return render_device<double>(s, cam, p, d_out, stream, RAYZ_PRECISION_F64); });
+}
+
+int rayz_hip_scene_set_scan_form(RayzScene* s, uint32_t form) {
+    return guarded([&] {
+        if (!s) return fail(RAYZ_ERR_BAD_ARG, "null scene");
+        if (form > RAYZ_SCAN_FORM_XY) return fail(RAYZ_ERR_BAD_ARG, "bad scan form %u", form);
+        s->scan_form = form;
+        return (int)RAYZ_OK;
+    });
+}
+
+int rayz_hip_scene_get_scan_form(RayzScene* s, uint32_t* form) {
+    return guarded([&] {
+        if (!s || !form) return fail(RAYZ_ERR_BAD_ARG, "null argument");
+        *form = scene_scan_form(s);
+        return (int)RAYZ_OK;
+    });
 }
 
 int rayz_hip_scene_sync(RayzScene* s, RayzRenderStats* stats) {

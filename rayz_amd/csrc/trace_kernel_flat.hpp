@@ -1,12 +1,18 @@
 // trace_kernel_flat.hpp — the text of the persistent flat-list trace kernel (described in rayz_device.hpp, which includes this file
-// TWICE: as trace_kernel, the product kernel, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
-// adaptive pass).  One text, two kernels of two NAMES, and not a second template flag on trace_kernel:
+// THREE times: as trace_kernel, the product kernel, as flat_xy_kernel — RAYZ_TRACE_KERNEL_BASIS kBasisXY — the same kernel with
+// the reject test's other basis, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
+// adaptive pass).  One text, three kernels of three NAMES, and not further template flags on trace_kernel:
 // tests/test_isa_invariants.py counts the kernels named trace_kernel.. (six) and holds each to the product's limits, so a kernel
 // of that name is a product kernel; the adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared
 // body FUNCTION: handing the kernel's argument block to it changes the product kernel's register allocation; compiled twice,
 // trace_kernel's ISA is what it was.  No include guard.
 template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
     constexpr bool kAdaptive = RAYZ_TRACE_KERNEL_ADAPTIVE; // work items over the active list (place_item)
+#ifdef RAYZ_TRACE_KERNEL_BASIS
+    constexpr int kBasis = RAYZ_TRACE_KERNEL_BASIS; // the reject test's basis (RayBasis)
+#else
+    constexpr int kBasis = kBasisXZ;
+#endif
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     PathState<R> p[NR];
 #pragma unroll
@@ -32,7 +38,7 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
 
         RAYZ_FPROF(0)
         // ---- nearest hit (full EXEC; idle tail slots recompute their last ray, results unused) ----
-        ScanRay<R> ray[NR];
+        ScanRay<R, kBasis> ray[NR];
         V<R> ud[NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {

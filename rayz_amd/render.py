@@ -231,6 +231,17 @@ class DeviceScene(_Handle):
         capi.check(self._lib, self._lib.rayz_hip_scene_sync(self._h, C.byref(st)), "rayz_hip_scene_sync")
         return st
 
+    @property
+    def scan_form(self) -> int:
+        """The basis the next flat-list render's reject test runs in: capi.SCAN_FORM_XZ or _XY (what AUTO chose, if nothing was set)."""
+        form = C.c_uint32()
+        capi.check(self._lib, self._lib.rayz_hip_scene_get_scan_form(self._h, C.byref(form)), "rayz_hip_scene_get_scan_form")
+        return form.value
+
+    @scan_form.setter
+    def scan_form(self, form: int) -> None:
+        capi.check(self._lib, self._lib.rayz_hip_scene_set_scan_form(self._h, form), "rayz_hip_scene_set_scan_form")
+
     # ---- ray queries (`findHit`, include/rayz_hip.h: rayz_hip_scene_query*) ----
     def query(self, rays, tmin: float = 1e-3, kind: str = "nearest", traversal: int = capi.TRAVERSAL_AUTO,
               outputs=QUERY_OUTPUTS, stream: int = 0) -> "QueryResult":
