@@ -259,8 +259,12 @@ int rayz_hip_render_device_f64(RayzScene* scene, const RayzCameraDesc* camera, c
  * pair of a plane run or speed bucket in 6 packed FMAs and a loose y-moving one in 8; XY (e1 in the xy-plane) in 5 and 9.
  * AUTO prices one scan of the scene under both from its slot counts and takes XY only where it is strictly cheaper.  The
  * form applies to the one-shot and progressive flat-list renders; adaptive passes, ray queries and the BVH kernels keep XZ.
+ * ONE_RADIUS is XY with the scene's one-radius sets scanned in a loop of their own: members of a static plane run or of a speed
+ * bucket whose radii lie within r_min / 16 of each other are tested with the largest of them, held once per set, in blocks of
+ * cx and cz alone.  A scene without such sets renders under it as under XY.  AUTO takes it wherever it takes XY and the scene's
+ * sets hold at least 1,024 spheres (fewer do not pay for the set tables' loads); XY itself never does.
  * _get returns the form the next flat-list render uses, never AUTO (host only: no device needed).  Default AUTO. */
-typedef enum RayzScanForm { RAYZ_SCAN_FORM_AUTO = 0, RAYZ_SCAN_FORM_XZ = 1, RAYZ_SCAN_FORM_XY = 2 } RayzScanForm;
+typedef enum RayzScanForm { RAYZ_SCAN_FORM_AUTO = 0, RAYZ_SCAN_FORM_XZ = 1, RAYZ_SCAN_FORM_XY = 2, RAYZ_SCAN_FORM_ONE_RADIUS = 3 } RayzScanForm;
 int rayz_hip_scene_set_scan_form(RayzScene* scene, uint32_t form);
 int rayz_hip_scene_get_scan_form(RayzScene* scene, uint32_t* form);
 
@@ -546,9 +550,17 @@ typedef enum RayzKatOp {
                                  out: r2 - p1^2 - p2^2 per sphere [0..3], the k1 and k2 the block was tested with [4] [5] (a
                                       plane run's K1 = fm(cy, e1y, k1), K2 = fm(cy, e2y, k2)), e1x [6], e1y [7], the padded r2
                                       [8..11] if want_r2, else 0                                            DESIGN.md 4.3 */
-    RAYZ_KAT_BUCKET_DISCS_XY = 12 /* RAYZ_KAT_BUCKET_DISCS' record through the XY basis:
+    RAYZ_KAT_BUCKET_DISCS_XY = 12, /* RAYZ_KAT_BUCKET_DISCS' record through the XY basis:
                                  out: r2b - p1^2 - p2^2 per sphere [0..3], K1 = fm(v0, time * e1y, fm(cy, e1y, k1)) [4],
                                       K2 = fm(v0, time * e2y, fm(cy, e2y, k2)) [5], e1x [6], e1y [7], the padded r2b [8..11] */
+    RAYZ_KAT_SET_DISCS = 13     /* one 8-sphere block of a ONE-RADIUS SET of a static plane run or a speed bucket, as the set loop
+                                 evaluates it (RAYZ_SCAN_FORM_ONE_RADIUS: the XY basis, cx and cz from the block, one padded R2):
+                                 in: cx[0..7] cz[8..15] cy[16] (the run's height) v0[17] (the bucket's speed; finite) Rp[18] (the
+                                     set's one radius, >= every member's |radius| + |vy - v0|; finite, >= 0) movy[19] (0: a static
+                                     run's set, v0 and vy unused; 1: a bucket's) origin[20..22] dir[23..25] time[26] vy[28..35]
+                                     (RAYZ_ERR_BAD_ARG for a bad v0, Rp or movy)
+                                 out: R2 - p1^2 - p2^2 per sphere [0..7], the K1 and K2 the block was tested with [8] [9], the
+                                      padded R2 (f32) the library used: the largest over the eight members [10]    DESIGN.md 4.3 */
 } RayzKatOp;
 #define RAYZ_KAT_IN_STRIDE 48
 #define RAYZ_KAT_OUT_STRIDE 12

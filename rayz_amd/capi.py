@@ -20,8 +20,8 @@ GATHER_ALLOW_DUPLICATE_DEVICES = 0x100  # flag bit, peer-copy only (tests on a o
  DEBUG_LDS_PAD, DEBUG_BVH_TOP_ORDER, DEBUG_BVH_NODES, DEBUG_BVH_SPLIT, DEBUG_BVHX, DEBUG_CHUNK_CAP,
  DEBUG_DENOISE_LDS_STRIDE) = range(13)
 (KAT_REFRACT, KAT_REFLECTANCE, KAT_GET_RAY, KAT_BOX_HIT, KAT_SPHERE_HIT, KAT_SCATTER, KAT_CHECKER, KAT_BACKGROUND,
- KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS, KAT_SCAN_DISCS_XY, KAT_BUCKET_DISCS_XY) = range(13)
-SCAN_FORM_AUTO, SCAN_FORM_XZ, SCAN_FORM_XY = 0, 1, 2  # RayzScanForm: the basis of the flat list's reject test
+ KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS, KAT_SCAN_DISCS_XY, KAT_BUCKET_DISCS_XY, KAT_SET_DISCS) = range(14)
+SCAN_FORM_AUTO, SCAN_FORM_XZ, SCAN_FORM_XY, SCAN_FORM_ONE_RADIUS = 0, 1, 2, 3  # RayzScanForm: the basis of the flat list's reject test
 KAT_IN_STRIDE, KAT_OUT_STRIDE = 48, 12
 
 OK = 0

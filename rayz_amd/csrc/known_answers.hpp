@@ -90,7 +90,7 @@ int rayz_hip_noise_kat(uint32_t precision, const double* chunk_sums, const uint3
 // ---- known answers: the kernel's device functions on caller inputs ---------------------------------------------
 int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, double* out) {
     return guarded([&] {
-        if (op > RAYZ_KAT_BUCKET_DISCS_XY) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
+        if (op > RAYZ_KAT_SET_DISCS) return fail(RAYZ_ERR_BAD_ARG, "bad known-answer op %u", op);
         if (precision > RAYZ_PRECISION_F64) return fail(RAYZ_ERR_BAD_ARG, "bad precision %u", precision);
         if (!n) return (int)RAYZ_OK;
         if (!in || !out) return fail(RAYZ_ERR_BAD_ARG, "null buffer");
@@ -164,6 +164,24 @@ int rayz_hip_kat(uint32_t op, uint32_t precision, const double* in, uint32_t n, 
                 for (int k = 0; k < 4; ++k)
                     a[28 + k] = precision == RAYZ_PRECISION_F32 ? (double)pad_radius2_bucket<float>(q[k], S, (float)a[27])
                                                                 : (double)pad_radius2_bucket<double>(q[k], S, (float)a[27]);
+            }
+            if (op == RAYZ_KAT_SET_DISCS) { // the padded square a one-radius set of radius Rp would hold for these eight members
+                if (!std::isfinite(a[17])) return fail(RAYZ_ERR_BAD_ARG, "record %u: v0 = %g is not finite", i, a[17]);
+                if (!(a[19] == 0.0 || a[19] == 1.0)) return fail(RAYZ_ERR_BAD_ARG, "record %u: movy = %g is not 0 or 1", i, a[19]);
+                if (!(a[18] >= 0.0 && std::isfinite(a[18]))) return fail(RAYZ_ERR_BAD_ARG, "record %u: Rp = %g is not a finite radius", i, a[18]);
+                double S = norm3(a + 20);
+                RayzSphere q[8] = {};
+                for (int k = 0; k < 8; ++k) {
+                    q[k].center[0] = a[k], q[k].center[1] = a[16], q[k].center[2] = a[8 + k];
+                    q[k].velocity[1] = a[19] != 0.0 ? a[28 + k] : 0.0;
+                    S = std::max(S, norm3(q[k].center) + norm3(q[k].velocity) + a[18]);
+                }
+                float R2 = 0.0f;
+                for (int k = 0; k < 8; ++k) {
+                    const double h = a[19] != 0.0 ? rayz_plane::bucket_h(q[k].velocity[1], (float)a[17]) : 0.0;
+                    R2 = std::max(R2, rayz_plane::pad_radius2_set(q[k].center, q[k].velocity, S, h, a[18], precision != RAYZ_PRECISION_F32));
+                }
+                a[36] = (double)R2;
             }
             if (op == RAYZ_KAT_SPHERE_HIT) {
                 RayzSphere q{};

@@ -81,6 +81,16 @@ static_assert(4 * sizeof(uint32_t) + kMaxPlaneRuns * sizeof(PlaneRun) <= kPlaneH
 //    cx[G] cz[G] r2b[G], back to back][two spare groups]
 // and the head's words 2 and 3 hold that section's word offset and the number of buckets.  Read with scalar loads at every
 // scan, as the run table is and for its reasons.
+// ONE-RADIUS SETS (both streams; rayz_plane::plan_sets): the members of a static run, or of one speed bucket, whose
+// |radius| + h lie within r_min / 16 of each other are tested with ONE padded r², the set's.  A run's or bucket's slots are its
+// sets' (by radius), then the members no set took, in the blocks they always had (a set's slots keep their blocks there too: the
+// XZ and XY kernels, adaptive passes and queries scan those).  Behind everything above, at the next 64-byte boundary, the stream
+// carries the set section, which only flat_one_radius_kernel reads:
+//   [kSetHeader words: sets, bucket records, 0, 0, per run the first slot its old form still tests][RadiusSet records]
+//   [the SpeedBucket records once more, `first` = the first slot the bucket's old form still tests][to a 64-byte boundary]
+//   [the sets' blocks cx[8] cz[8], back to back][two spare groups]
+// Nothing in front of it moves or changes; the kernel finds it from the stream's length, which the head (and the last bucket record)
+// already give (scan_plane_class).
 using rayz_plane::SpeedBucket;
 constexpr int kBucketHeader = 8;
 static_assert(sizeof(SpeedBucket) == 32 && kMaxPlaneRuns <= kBucketHeader, "bucket table layout");
@@ -460,17 +470,23 @@ template <class R> struct BlockSphere { R cx = R(0), cy = R(0), cz = R(0), r2 = 
 // which the run loop (scan_plane_class) puts in the basis's k2 before the run: discs() finds it in b.k2.
 // p2 = fm(cz, e2z, fm(cx, e2x, K2)): 6 packed FMAs per sphere pair instead of 7 (static), 7 instead of 8 (mov-Y).  The same
 // three roundings as basis_p2, in another order, with the same bounds on the partial sums: the pad E stays.
-template <class R, bool kCy, bool kVy> struct PackedGroup {
+//
+// One-radius sets (kR2 = false; rayz_plane::plan_sets): the members of a static run or a speed bucket whose radii
+// lie close together are tested with ONE padded r², the set's, which discs() takes as an argument: a loop-invariant operand of
+// disc = fm(−p2, p2, R2), the one stage that reads no stream field.  Their blocks are cx[GN] cz[GN], GN = 8: one 16-word load.
+template <class R, bool kCy, bool kVy, bool kR2 = true, int GN = group_size<R>()> struct PackedGroup {
     typedef typename VecOf<R>::pair pr;
-    static constexpr int G = group_size<R>(), H = G / 2;
-    static constexpr int kWords = 3 + kCy + kVy; // words of the stream per sphere
+    static constexpr int G = GN, H = G / 2;
+    static constexpr int kWords = 2 + kR2 + kCy + kVy; // words of the stream per sphere
     // word offset of each field inside a block (a field the form lacks: -1)
-    static constexpr int kOffCx = 0, kOffCy = kCy ? G : -1, kOffCz = (1 + kCy) * G, kOffR2 = (2 + kCy) * G, kOffVy = kVy ? (3 + kCy) * G : -1;
+    static constexpr int kOffCx = 0, kOffCy = kCy ? G : -1, kOffCz = (1 + kCy) * G, kOffR2 = kR2 ? (2 + kCy) * G : -1,
+                         kOffVy = kVy ? (2 + kR2 + kCy) * G : -1;
     pr cx[H], cy[H], cz[H], r2[H], vy[H];
     // Host: sphere s at slot k of a section of blocks in this form.
     static void put(R* section, size_t k, const BlockSphere<R>& s = BlockSphere<R>()) {
         R* blk = section + k / G * (kWords * G) + k % G;
-        blk[kOffCx] = s.cx, blk[kOffCz] = s.cz, blk[kOffR2] = s.r2;
+        blk[kOffCx] = s.cx, blk[kOffCz] = s.cz;
+        if constexpr (kR2) blk[kOffR2] = s.r2;
         if constexpr (kCy) blk[kOffCy] = s.cy;
         if constexpr (kVy) blk[kOffVy] = s.vy;
     }
@@ -480,7 +496,8 @@ template <class R, bool kCy, bool kVy> struct PackedGroup {
         for (int q = 0; q < H; ++q) {
             cx[q] = p[kOffCx / 2 + q];
             if constexpr (kCy) cy[q] = p[kOffCy / 2 + q];
-            cz[q] = p[kOffCz / 2 + q], r2[q] = p[kOffR2 / 2 + q];
+            if constexpr (kR2) cz[q] = p[kOffCz / 2 + q], r2[q] = p[kOffR2 / 2 + q];
+            else cz[q] = p[kOffCz / 2 + q];
             if constexpr (kVy) vy[q] = p[kOffVy / 2 + q];
         }
     }
@@ -491,7 +508,8 @@ template <class R, bool kCy, bool kVy> struct PackedGroup {
     __device__ __forceinline__ void opaque() {
 #pragma unroll
         for (int q = 0; q < H; ++q) {
-            asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
+            if constexpr (kR2) asm volatile("" : "+s"(cx[q]), "+s"(cz[q]), "+s"(r2[q]));
+            else asm volatile("" : "+s"(cx[q]), "+s"(cz[q]));
             if constexpr (kCy) asm volatile("" : "+s"(cy[q]));
             if constexpr (kVy) asm volatile("" : "+s"(vy[q]));
         }
@@ -525,8 +543,8 @@ template <class R, bool kCy, bool kVy> struct PackedGroup {
         for (int q = 0; q < H; ++q) out[2 * q] = d[q].x, out[2 * q + 1] = d[q].y;
     }
     // The xy basis (kBasisXY): cy and vy enter p1 instead of cz.  Plane-run blocks (kCy = false) find the run's K1 in b.k1 as they
-    // find K2 in b.k2.  Stage by stage across the group's pairs, as above.
-    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R, kBasisXY>& b, [[maybe_unused]] R time) const {
+    // find K2 in b.k2.  Stage by stage across the group's pairs, as above.  R2all: the one padded r² of a form without the field.
+    __device__ __forceinline__ void discs(R (&out)[G], const RayBasis<R, kBasisXY>& b, [[maybe_unused]] R time, [[maybe_unused]] R R2all = R(0)) const {
         const R t1y = kVy ? time * b.e1y : R(0), t2y = kVy ? time * b.e2y : R(0);
         [[maybe_unused]] const pr E1x{b.e1x, b.e1x}, E1y{b.e1y, b.e1y}, E2x{b.e2x, b.e2x}, E2y{b.e2y, b.e2y}, E2z{b.e2z, b.e2z},
             K1{b.k1, b.k1}, K2{b.k2, b.k2}, T1y{t1y, t1y}, T2y{t2y, t2y};
@@ -549,8 +567,14 @@ template <class R, bool kCy, bool kVy> struct PackedGroup {
 #pragma unroll
             for (int q = 0; q < H; ++q) p2[q] = __builtin_elementwise_fma(vy[q], T2y, p2[q]);
         }
+        if constexpr (kR2) {
 #pragma unroll
-        for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+            for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], r2[q]);
+        } else {
+            const pr RR{R2all, R2all};
+#pragma unroll
+            for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p2[q], p2[q], RR);
+        }
 #pragma unroll
         for (int q = 0; q < H; ++q) d[q] = __builtin_elementwise_fma(-p1[q], p1[q], d[q]);
 #pragma unroll
@@ -579,6 +603,8 @@ template <class R> struct ScanGroup<R, 5> : ScanGroup<R, 3> {
     template <class SC> static __device__ __forceinline__ const RAYZ_CONSTANT R* stream(const SC& sc) { return (const RAYZ_CONSTANT R*)sc.movy; }
     template <class SC> static __device__ __forceinline__ int slot0(const SC& sc) { return (int)sc.ns_pad; }
 };
+// A one-radius set of a static run or of a speed bucket: cx and cz alone, in groups of kSetGroup (scan_sets is told its stream and slots).
+template <class R> struct ScanGroup<R, 6> : PackedGroup<R, false, false, false, (int)rayz_plane::kSetGroup> {};
 template <class R> struct ScanGroup<R, 2> { // mov-G
     typedef typename VecOf<R>::type r4;
     static constexpr int G = kMovGGroup;
@@ -742,6 +768,46 @@ __device__ __forceinline__ void scan_class(const DevScene<R>& sc, int n, ScanRay
     if constexpr (sizeof(R) == 8) asm volatile("" : "+s"(base));
     scan_blocks<R, CLS, NR>(sc, base, 0, n, ray, tmin);
 }
+// The one-radius sets' loop (xy basis only): scan_blocks' order of waits, loads and tests over two-field groups of kSetGroup = 8,
+// each ONE 16-word scalar load into 16 SGPRs (two sets: 32, where the three-field form of 4 holds 24), with the set's padded r²
+// as the loop-invariant operand R2 and one reject decision per 16 tests.  `slot0`: the class's first slot.
+template <class R, int NR>
+__device__ __forceinline__ void scan_sets(const DevScene<R>& sc, const RAYZ_CONSTANT float* base, int i0, int i1, int slot0,
+                                          ScanRay<R, kBasisXY> (&ray)[NR], R tmin, float R2) {
+    typedef ScanGroup<float, 6> Grp;
+    constexpr int G = Grp::G, W = Grp::kWords * G;
+    const RAYZ_CONSTANT float* at = base + Grp::kWords * i0;
+    Grp a, b;
+    a.load(at);
+    for (int left = i1 - i0; left > 0; left -= 2 * G, at += 2 * W) {
+        float da[NR][G], db[NR][G];
+        float m = -1.0f;
+        a.ready(at);
+        b.load(at + W);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            a.discs(da[r], ray[r].basis, ray[r].ftime, R2);
+#pragma unroll
+            for (int k = 0; k < G; ++k) m = (r == 0 && k == 0) ? da[0][0] : mx(m, da[r][k]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        b.ready(at);
+        a.load(at + 2 * W);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            b.discs(db[r], ray[r].basis, ray[r].ftime, R2);
+#pragma unroll
+            for (int k = 0; k < G; ++k) m = mx(m, db[r][k]);
+        }
+        if (__ballot(m >= 0.0f) != 0ull) {
+            const int first = slot0 + i1 - left;
+            group_collect<R, 6, NR>(sc, first, ray, da, tmin);
+            group_collect<R, 6, NR>(sc, first + G, ray, db, tmin);
+        }
+    }
+}
 // A plane run's K2 for one ray: cy·e2y + k2 in ONE rounding (the run loop below and RAYZ_KAT_SCAN_DISCS classes 2 / 3).
 __device__ __forceinline__ float plane_run_k2(float cy, float e2y, float k2) { return fm(cy, e2y, k2); }
 // A speed bucket's K2 for one ray: the run's K2, then v0·(time·e2y) in one more rounding (the bucket loop below and
@@ -761,13 +827,28 @@ template <class R> __device__ __forceinline__ float scan_k1(const ScanRay<R, kBa
 // The static (CLS 0) or mov-Y (CLS 1) class: its plane runs, then its loose spheres.  Per run, K2 = fm(cy, e2y, k2) replaces
 // each ray's k2 (one FMA per ray and run), which is put back before the loose spheres.  The head is read here, every scan
 // (the empty asm keeps the compiler from loading it once per kernel and holding it in spilled SGPRs).
-template <class R, int CLS, int NR, int AX>
+// kSets (flat_one_radius_kernel): the stream's set section (behind everything else; found from what the head and the bucket table
+// say of the stream's length, rayz_hip.hip: append_sets) names the one-radius sets, tested last by scan_sets, and the first slot the
+// old forms still test of each run and bucket.
+template <class R, int CLS, int NR, int AX, bool kSets = false>
 __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_class, ScanRay<R, AX> (&ray)[NR], R tmin) {
     constexpr int P = ScanGroup<float, CLS + 3>::kWords, G = ScanGroup<float, CLS>::G; // words per plane sphere: the run form's
     const RAYZ_CONSTANT float* head = ScanGroup<float, CLS>::stream(sc);
     asm volatile("" : "+s"(head));
     const RAYZ_CONSTANT uint32_t* h = (const RAYZ_CONSTANT uint32_t*)head;
     const int nr = (int)h[0], plane = (int)h[1];
+    [[maybe_unused]] const RAYZ_CONSTANT uint32_t* sh = h; // the set section's header
+    if constexpr (kSets) {
+        uint32_t end = (uint32_t)(kPlaneHeader + P * (plane + 2 * G) + ScanGroup<float, CLS>::kWords * (n_class - plane + 2 * G));
+        if constexpr (CLS == 1) {
+            const uint32_t nb = h[3];
+            const RAYZ_CONSTANT SpeedBucket* bk = (const RAYZ_CONSTANT SpeedBucket*)(head + h[2] + kBucketHeader);
+            end = h[2] + kBucketHeader;
+            if (nb != 0u) end = bk[nb - 1u].base + ScanGroup<float, 5>::kWords * bk[nb - 1u].end;
+            end += ScanGroup<float, 5>::kWords * 2 * G;
+        }
+        sh = h + rayz_plane::set_section(end);
+    }
     if (nr != 0) {
         const RAYZ_CONSTANT PlaneRun* runs = (const RAYZ_CONSTANT PlaneRun*)(h + 4);
         float k2[NR];
@@ -777,7 +858,10 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
             const float cy = runs[j].cy;
             int first = (int)runs[j].first;
             const int end = (int)runs[j].end;
-            if constexpr (CLS == 1) { // the run's first slots belong to its speed buckets (below)
+            if constexpr (kSets) { // .. or to its one-radius sets
+                first = (int)sh[4 + j];
+                if (first == end) continue;
+            } else if constexpr (CLS == 1) { // the run's first slots belong to its speed buckets (below)
                 first = (int)((const RAYZ_CONSTANT uint32_t*)(head + h[2]))[j];
                 if (first == end) continue;
             }
@@ -799,11 +883,14 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
         const int nb = (int)h[3];
         if (nb != 0) {
             const RAYZ_CONSTANT SpeedBucket* bk = (const RAYZ_CONSTANT SpeedBucket*)(head + h[2] + kBucketHeader);
+            if constexpr (kSets) bk = (const RAYZ_CONSTANT SpeedBucket*)(sh + rayz_plane::kSetHeader + 8u * sh[0]); // (first: behind the bucket's sets)
             float k2[NR];
 #pragma unroll
             for (int r = 0; r < NR; ++r) k2[r] = ray[r].basis.k2;
             for (int j = 0; j < nb; ++j) {
                 const float v0 = bk[j].v0, cy = bk[j].cy;
+                if constexpr (kSets)
+                    if (bk[j].first == bk[j].end) continue;
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     ray[r].basis.k2 = bucket_k2(v0, cy, ray[r].ftime, ray[r].basis.e2y, k2[r]);
@@ -818,12 +905,36 @@ __device__ __forceinline__ void scan_plane_class(const DevScene<R>& sc, int n_cl
             }
         }
     }
+    if constexpr (kSets) {
+        static_assert(AX == kBasisXY && sizeof(rayz_plane::RadiusSet) == 32, "the sets are scanned in the xy basis");
+        const int ns = (int)sh[0];
+        if (ns != 0) {
+            const RAYZ_CONSTANT rayz_plane::RadiusSet* st = (const RAYZ_CONSTANT rayz_plane::RadiusSet*)(sh + rayz_plane::kSetHeader);
+            float k2[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) k2[r] = ray[r].basis.k2;
+            for (int j = 0; j < ns; ++j) {
+                const float v0 = st[j].v0, cy = st[j].cy;
+#pragma unroll
+                for (int r = 0; r < NR; ++r) { // a static run's K1, K2, or its bucket's: the very values the old form tests it with
+                    ray[r].basis.k2 = CLS == 1 ? bucket_k2(v0, cy, ray[r].ftime, ray[r].basis.e2y, k2[r]) : plane_run_k2(cy, ray[r].basis.e2y, k2[r]);
+                    ray[r].basis.k1 = CLS == 1 ? bucket_k1(v0, cy, ray[r].ftime, ray[r].basis.e1y, scan_k1(ray[r])) : plane_run_k1(cy, ray[r].basis.e1y, scan_k1(ray[r]));
+                }
+                scan_sets<R, NR>(sc, head + st[j].base, (int)st[j].first, (int)st[j].end, ScanGroup<float, CLS + 3>::slot0(sc), ray, tmin, st[j].R2);
+            }
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                ray[r].basis.k2 = k2[r];
+                ray[r].basis.k1 = scan_k1(ray[r]);
+            }
+        }
+    }
 }
 // Every sphere class in slot order (the slot order only matters to the candidates' parking order; the acceptance rule
 // decides ties by pool index, so the hit is the same in any order).
-template <class R, int NR, int AX> __device__ __forceinline__ void scan_sphere_classes(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
-    scan_plane_class<R, 0, NR>(sc, (int)sc.ns_pad, ray, tmin);
-    scan_plane_class<R, 1, NR>(sc, (int)sc.ny_pad, ray, tmin);
+template <class R, int NR, bool kSets = false, int AX> __device__ __forceinline__ void scan_sphere_classes(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
+    scan_plane_class<R, 0, NR, AX, kSets>(sc, (int)sc.ns_pad, ray, tmin);
+    scan_plane_class<R, 1, NR, AX, kSets>(sc, (int)sc.ny_pad, ray, tmin);
     scan_class<R, 2, NR>(sc, (int)sc.ng_pad, ray, tmin);
 }
 
@@ -903,8 +1014,8 @@ __device__ __forceinline__ void scan_begin(ScanRay<R, AX>& ray, V<R> o, V<R> d, 
     ray.cand[0] = ray.cand[1] = ray.cand[2] = ray.cand[3] = 0u;
     ray.ncand = 0u;
 }
-template <class R, int NR, int AX> __device__ __forceinline__ void scan_spheres(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
-    scan_sphere_classes<R, NR>(sc, ray, tmin);
+template <class R, int NR, bool kSets = false, int AX> __device__ __forceinline__ void scan_spheres(const DevScene<R>& sc, ScanRay<R, AX> (&ray)[NR], R tmin) {
+    scan_sphere_classes<R, NR, kSets>(sc, ray, tmin);
     narrow_flush<R, NR>(sc, ray, tmin);
     scan_triangles<R, NR>(sc, ray, tmin);
 }
@@ -1241,6 +1352,17 @@ template <class R, int NR> constexpr int flat_waves() { return sizeof(R) == 8 ? 
 #undef RAYZ_TRACE_KERNEL_NAME
 #undef RAYZ_TRACE_KERNEL_ADAPTIVE
 #undef RAYZ_TRACE_KERNEL_BASIS
+// .. and a fourth time: the xy basis with the one-radius sets scanned by scan_sets (scan_plane_class's kSets), for scenes that
+// have such sets.  A kernel of its own name for the reasons flat_xy_kernel is one (tests/test_one_radius_isa.py holds it to the limits).
+#define RAYZ_TRACE_KERNEL_NAME flat_one_radius_kernel
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#define RAYZ_TRACE_KERNEL_BASIS kBasisXY
+#define RAYZ_TRACE_KERNEL_SETS true
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE
+#undef RAYZ_TRACE_KERNEL_BASIS
+#undef RAYZ_TRACE_KERNEL_SETS
 #define RAYZ_TRACE_KERNEL_NAME adaptive_pass_kernel // (an adaptive pass's kernel, DESIGN.md §4.14: the same text over the active list)
 #define RAYZ_TRACE_KERNEL_ADAPTIVE true
 #include "trace_kernel_flat.hpp"
@@ -1967,6 +2089,23 @@ template <class R> __global__ __launch_bounds__(64) void kat_kernel(uint32_t op,
         kat_block_discs<5>(a, b, 0.0f, out4);
         for (int k = 0; k < 4; ++k) r[k] = (double)out4[k], r[8 + k] = (double)(float)a[28 + k];
         r[4] = (double)b.k1, r[5] = (double)b.k2, r[6] = (double)b.e1x, r[7] = (double)b.e1y;
+        break;
+    }
+    case 13: { // SET_DISCS: one block of a one-radius set (scan_sets): cx[8] cz[8] cy v0 . movy o(3) d(3) time (+ the set's padded
+               // R2 at 36, from the host) -> disc[8] K1 K2 R2
+        typedef ScanGroup<float, 6> Grp;
+        const V<R> o = v3(20), d = v3(23);
+        const V<R> ud = unit(d);
+        RayBasis<float, kBasisXY> b = make_basis<float, kBasisXY>(V<float>{(float)ud.x, (float)ud.y, (float)ud.z}, V<float>{(float)o.x, (float)o.y, (float)o.z});
+        const float v0 = (float)a[17], cy = (float)a[16], ft = (float)(R)a[26];
+        if (a[19] != 0.0) b.k1 = bucket_k1(v0, cy, ft, b.e1y, b.k1), b.k2 = bucket_k2(v0, cy, ft, b.e2y, b.k2);
+        else b.k1 = plane_run_k1(cy, b.e1y, b.k1), b.k2 = plane_run_k2(cy, b.e2y, b.k2);
+        Grp g;
+        for (int q = 0; q < Grp::H; ++q) g.cx[q] = f2{(float)a[2 * q], (float)a[2 * q + 1]}, g.cz[q] = f2{(float)a[8 + 2 * q], (float)a[9 + 2 * q]};
+        float out8[Grp::G];
+        g.discs(out8, b, 0.0f, (float)a[36]);
+        for (int k = 0; k < Grp::G; ++k) r[k] = (double)out8[k];
+        r[8] = (double)b.k1, r[9] = (double)b.k2, r[10] = (double)(float)a[36];
         break;
     }
     default: break;

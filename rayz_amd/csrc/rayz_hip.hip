@@ -58,6 +58,10 @@ struct NarrowBuffers {
     std::vector<rayz_plane::RunBuckets> buckets;
     // the basis one scan of these slots is cheaper in (rayz_plane::cheaper_scan_form): a fact of the layout, priced with it
     uint32_t scan_form = rayz_plane::kScanFormXZ;
+    // one-radius sets (rayz_plane::plan_sets) of each class: a static run's, or a speed bucket's; a run's or bucket's slot order
+    // is its sets' members, then what no set took.  old_first: the first slot the old form still tests, of each run and bucket
+    std::vector<rayz_plane::ClassSet> sets[2];
+    std::vector<uint32_t> run_old_first[2], bucket_old_first;
     bool planned = false, ready = false, bvh_ready = false;
 };
 
@@ -153,8 +157,7 @@ template <class R> float pad_radius2_scan(const RayzSphere& q, double S) {
 // meets it, and the pad rule above holds for it as for any sphere (its |v| is at most |v| + h).  h is taken against the
 // pool's f64 speed and the f32 one the buckets were cut by, rounded up.
 template <class R> float pad_radius2_bucket(const RayzSphere& q, double S, float v0) {
-    const double vy = q.velocity[1], h0 = std::max(std::fabs(vy - (double)v0), std::fabs((double)(float)vy - (double)v0));
-    const double h = h0 * (1.0 + 0x1p-50) + 1e-300;
+    const double h = rayz_plane::bucket_h(q.velocity[1], v0);
     const double E = (sizeof(R) == 4 ? 32.0 : 40.0) * unit_roundoff<float>() *
                      (norm3(q.center) + norm3(q.velocity) + h + std::fabs(q.radius) + h + S);
     const double rp = std::fabs(q.radius) + h + E;
@@ -255,6 +258,12 @@ void plan_slots(RayzScene* s) {
             [&](uint32_t pool) { return std::fabs(s->spheres[pool].radius); }, kMovYGroup));
         m = nb.buckets.back().order; // slot order from here on
     }
+    // one-radius sets of each static run and of each speed bucket (rayz_plane::plan_class_sets): slot order from here on
+    auto rad = [&](uint32_t pool) { return std::fabs(s->spheres[pool].radius); };
+    auto vy64 = [&](uint32_t pool) { return s->spheres[pool].velocity[1]; };
+    std::vector<uint32_t> none;
+    rayz_plane::plan_class_sets(nb.runs[0], nb.run_members[0], nullptr, rad, vy64, nb.sets[0], nb.run_old_first[0], none);
+    rayz_plane::plan_class_sets(nb.runs[1], nb.run_members[1], &nb.buckets, rad, vy64, nb.sets[1], nb.run_old_first[1], nb.bucket_old_first);
     nb.ns_pad = nb.plane_slots[0] + scan_len(nb.loose[0].size(), kStaticGroup);
     nb.ny_pad = nb.plane_slots[1] + scan_len(nb.loose[1].size(), kMovYGroup);
     nb.ng_pad = scan_len(s->cls[2].size(), kMovGGroup);
@@ -343,7 +352,44 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
                 Run::put(plane, k, rec32(pool));
             }
         for (size_t k = 0; k < nb.loose[c].size(); ++k) Loose::put(loose, k, rec32(nb.loose[c][k]));
-        if (c != 1) return v;
+        // The set section (rayz_device.hpp), behind everything the stream held before it: {sets, copied bucket records, 0, 0, the
+        // first old-form slot of each run}, the set table, the bucket table once more with each bucket's first old-form slot, the
+        // sets' 2-field blocks cx[G'] cz[G'] back to back, two spare groups.  Nothing in front of it changes.
+        auto append_sets = [&](std::vector<float>& v, std::vector<rayz_plane::SpeedBucket> table) {
+            typedef ScanGroup<float, 6> Set;
+            const uint32_t GS = Set::G;
+            const size_t sec = rayz_plane::set_section((uint32_t)v.size());
+            std::vector<rayz_plane::RadiusSet> sets;
+            uint32_t set_slots = 0;
+            for (const rayz_plane::ClassSet& h : nb.sets[c]) set_slots += h.count;
+            const size_t blocks0 = rayz_plane::set_section((uint32_t)(sec + rayz_plane::kSetHeader + 8 * (nb.sets[c].size() + table.size())));
+            v.resize(blocks0 + Set::kWords * (size_t)(set_slots + 2 * GS), 0.0f);
+            float* const blk = v.data() + blocks0;
+            uint32_t at = 0;
+            for (const rayz_plane::ClassSet& h : nb.sets[c]) {
+                for (uint32_t k = 0; k < h.count; ++k) {
+                    const RayzSphere& q = s->spheres[nb.run_members[c][h.run][h.first - nb.runs[c][h.run].first + k]];
+                    Set::put(blk, at + k, {(float)q.center[0], 0.0f, (float)q.center[2], 0.0f, 0.0f});
+                }
+                const float R2 = rayz_plane::class_set_r2(h, nb.runs[c][h.run], nb.run_members[c][h.run], [&](uint32_t pool) { return s->spheres[pool].center; },
+                                                          [&](uint32_t pool) { return s->spheres[pool].velocity; }, b.pad_S, sizeof(R) == 8);
+                reach(at, at + h.count, GS, set_slots + 2 * GS);
+                sets.push_back({h.first, h.first + h.count, (uint32_t)blocks0 + Set::kWords * at - Set::kWords * h.first, R2, nb.runs[c][h.run].cy, h.v0, {0u, 0u}});
+                at += h.count;
+            }
+            for (size_t q = 0; q < table.size(); ++q) table[q].first = nb.bucket_old_first[q];
+            uint32_t hdr[rayz_plane::kSetHeader] = {(uint32_t)sets.size(), (uint32_t)table.size(), 0u, 0u, 0u, 0u, 0u, 0u};
+            for (size_t j = 0; j < nb.run_old_first[c].size(); ++j) hdr[4 + j] = nb.run_old_first[c][j];
+            std::memcpy(v.data() + sec, hdr, sizeof(hdr));
+            if (!sets.empty()) std::memcpy(v.data() + sec + rayz_plane::kSetHeader, sets.data(), sets.size() * sizeof(rayz_plane::RadiusSet));
+            if (!table.empty()) std::memcpy(v.data() + sec + rayz_plane::kSetHeader + 8 * sets.size(), table.data(), table.size() * sizeof(rayz_plane::SpeedBucket));
+        };
+        if (c != 1) {
+            // (the device finds the set section from the head's two slot counts, scan_plane_class)
+            reach_ok = reach_ok && v.size() == kPlaneHeader + (size_t)P * (nb.plane_slots[c] + 2 * G) + (size_t)F * (class_slots - nb.plane_slots[c] + 2 * G);
+            append_sets(v, {});
+            return v;
+        }
         // mov-Y only: the bucket section (rayz_device.hpp) — per run the first slot of its 4-field remainder, the bucket table,
         // the buckets' 3-field blocks cx[G] cz[G] r2b[G] back to back, two spare groups.  Head words 2 and 3: where, how many.
         // (The buckets' slots keep their places in the plane section above, unused.)
@@ -376,6 +422,10 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         std::memcpy(v.data() + 2, where, sizeof(where));
         std::memcpy(v.data() + section, rem_first, sizeof(rem_first));
         if (!table.empty()) std::memcpy(v.data() + section + kBucketHeader, table.data(), table.size() * sizeof(rayz_plane::SpeedBucket));
+        // (the device finds the set section from the bucket table, scan_plane_class: the last bucket's blocks end the old content)
+        const size_t dev_end = (table.empty() ? section + kBucketHeader : table.back().base + Bucket::kWords * (size_t)table.back().end) + Bucket::kWords * 2 * G;
+        reach_ok = reach_ok && dev_end == v.size();
+        append_sets(v, table);
         return v;
     };
     const std::vector<float> stat = blocks(std::integral_constant<int, 0>(), s->narrow.ns_pad),
@@ -440,6 +490,12 @@ template <class R> int upload(RayzScene* s, SceneBuffers<R>& b, double S) {
 uint32_t scene_scan_form(RayzScene* s) {
     if (s->scan_form != rayz_plane::kScanFormAuto) return s->scan_form;
     plan_slots(s);
+    // .. with the one-radius sets in their own loop where the layout's form is XY and the sets are large enough to pay for their
+    // section (rayz_plane::kSetPayoffSlots)
+    uint64_t set_slots = 0;
+    for (const auto& sets : s->narrow.sets)
+        for (const rayz_plane::ClassSet& t : sets) set_slots += t.count;
+    if (s->narrow.scan_form == rayz_plane::kScanFormXY && set_slots >= rayz_plane::kSetPayoffSlots) return rayz_plane::kScanFormOneRadius;
     return s->narrow.scan_form;
 }
 
@@ -965,6 +1021,8 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     plan.kernel = active_list ? adaptive_pass_kernel<R, 1> : trace_kernel<R, 1>;
     // the xy basis where the scene's layout prices it lower (or the caller asked for it): the same candidates' narrow phase, the same image
     if (!active_list && !use_bvh && scene_scan_form(s) == rayz_plane::kScanFormXY) plan.kernel = flat_xy_kernel<R, 1>;
+    // .. and the kernel that scans the one-radius sets in their own two-field loop: the XY basis, the same candidates and more
+    if (!active_list && !use_bvh && scene_scan_form(s) == rayz_plane::kScanFormOneRadius) plan.kernel = flat_one_radius_kernel<R, 1>;
     plan.block = 256;
     plan.items_per_lane = 1;
     if (use_bvh) {
@@ -1305,7 +1363,7 @@ int rayz_hip_render_device_f64(RayzScene* s, const RayzCameraDesc* cam, const Ra
 int rayz_hip_scene_set_scan_form(RayzScene* s, uint32_t form) {
     return guarded([&] {
         if (!s) return fail(RAYZ_ERR_BAD_ARG, "null scene");
-        if (form > RAYZ_SCAN_FORM_XY) return fail(RAYZ_ERR_BAD_ARG, "bad scan form %u", form);
+        if (form > RAYZ_SCAN_FORM_ONE_RADIUS) return fail(RAYZ_ERR_BAD_ARG, "bad scan form %u", form);
         s->scan_form = form;
         return (int)RAYZ_OK;
     });

@@ -1,7 +1,8 @@
 // trace_kernel_flat.hpp — the text of the persistent flat-list trace kernel (described in rayz_device.hpp, which includes this file
-// THREE times: as trace_kernel, the product kernel, as flat_xy_kernel — RAYZ_TRACE_KERNEL_BASIS kBasisXY — the same kernel with
-// the reject test's other basis, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
-// adaptive pass).  One text, three kernels of three NAMES, and not further template flags on trace_kernel:
+// FOUR times: as trace_kernel, the product kernel, as flat_xy_kernel — RAYZ_TRACE_KERNEL_BASIS kBasisXY — the same kernel with
+// the reject test's other basis, as flat_one_radius_kernel — RAYZ_TRACE_KERNEL_SETS true — that one with the one-radius sets in a
+// loop of their own, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
+// adaptive pass).  One text, four kernels of four NAMES, and not further template flags on trace_kernel:
 // tests/test_isa_invariants.py counts the kernels named trace_kernel.. (six) and holds each to the product's limits, so a kernel
 // of that name is a product kernel; the adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared
 // body FUNCTION: handing the kernel's argument block to it changes the product kernel's register allocation; compiled twice,
@@ -12,6 +13,11 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     constexpr int kBasis = RAYZ_TRACE_KERNEL_BASIS; // the reject test's basis (RayBasis)
 #else
     constexpr int kBasis = kBasisXZ;
+#endif
+#ifdef RAYZ_TRACE_KERNEL_SETS
+    constexpr bool kSets = RAYZ_TRACE_KERNEL_SETS; // the one-radius sets in their own loop (scan_plane_class)
+#else
+    constexpr bool kSets = false;
 #endif
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     PathState<R> p[NR];
@@ -48,13 +54,13 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
         RAYZ_FPROF(1)
 #ifdef RAYZ_FLAT_PROFILE
         fiters++;
-        scan_sphere_classes<R, NR>(A.sc, ray, A.tmin);
+        scan_sphere_classes<R, NR, kSets>(A.sc, ray, A.tmin);
         RAYZ_FPROF(2)
         narrow_flush<R, NR>(A.sc, ray, A.tmin);
         scan_triangles<R, NR>(A.sc, ray, A.tmin);
         RAYZ_FPROF(3)
 #else
-        scan_spheres<R, NR>(A.sc, ray, A.tmin);
+        scan_spheres<R, NR, kSets>(A.sc, ray, A.tmin);
 #endif
 
         // ---- shade ----

@@ -233,7 +233,8 @@ class DeviceScene(_Handle):
 
     @property
     def scan_form(self) -> int:
-        """The basis the next flat-list render's reject test runs in: capi.SCAN_FORM_XZ or _XY (what AUTO chose, if nothing was set)."""
+        """The basis the next flat-list render's reject test runs in: capi.SCAN_FORM_XZ, _XY or _ONE_RADIUS (what AUTO chose, if
+        nothing was set: _ONE_RADIUS is XY with the scene's one-radius sets in their own loop, where they are large enough)."""
         form = C.c_uint32()
         capi.check(self._lib, self._lib.rayz_hip_scene_get_scan_form(self._h, C.byref(form)), "rayz_hip_scene_get_scan_form")
         return form.value

@@ -4,7 +4,8 @@
   python tools/isa_diff.py OLD NEW [--allow REGEX ...]     OLD, NEW: a source tree, or a git revision of this repository
   python tools/isa_diff.py HEAD .  --allow '^void rayz_dev::kat_kernel<'
 
-Comments and the per-compilation __hip_cuid symbol are dropped, labels lose their function's number; the text is split at each function's .type line (what
+Comments and the per-compilation __hip_cuid symbol are dropped, labels lose their function's number (and a long branch's
+.Lpost_getpc label its number in the file, which every kernel added in front of it shifts); the text is split at each function's .type line (what
 precedes the first is "(preamble)", the code objects' notes are "(metadata)").  Prints every symbol that differs with the number
 of changed lines, and exits 1 if one of them matches no --allow pattern (patterns are searched in the demangled name).
 """
@@ -25,7 +26,7 @@ def assembly(tree: str, tmp: str, tag: str) -> dict[str, list[str]]:
     out = os.path.join(tmp, tag + ".s")
     subprocess.run([_hipcc(), *HIPFLAGS, "--cuda-device-only", "-S", "-o", out, os.path.join(tree, "rayz_amd", "csrc", "rayz_hip.hip")], check=True)
     # (labels carry the function's number in the file, and so do the comments behind a label: both go)
-    lines = [re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end)\d+", r".\1", l if '"' in l else re.sub(r"\s*;.*", "", l))
+    lines = [re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end|Lpost_getpc)\d+", r".\1", l if '"' in l else re.sub(r"\s*;.*", "", l))
              for l in open(out) if l.strip() and not l.lstrip().startswith(";") and "__hip_cuid" not in l]
     notes = next((i for i, l in enumerate(lines) if l.lstrip().startswith(".amdgpu_metadata")), len(lines))
     parts: dict[str, list[str]] = {}
