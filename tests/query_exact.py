@@ -299,7 +299,7 @@ def _record(S: Scene, e: ExactRay, o, d, R, precision):
     if j < S.ns:
         time = Fr(float(R[3]))
         cd = [_dec(Fr(float(S.c[j, k])) + Fr(float(S.v[j, k])) * time) for k in range(3)]
-        r = Decimal(float(S.r[j]))
+        r = Decimal(abs(float(S.r[j])))  # (the reference normalises p - c: a negative radius is its magnitude)
         e.normal = np.array([float((p_dec[k] - cd[k]) / r) for k in range(3)])
         q = [Fr(float(S.c[j, k])) + Fr(float(S.v[j, k])) * time - o[k] for k in range(3)]
         e.front_face = not t.ge(_dot(d, q) / _dot(d, d))  # t < hb / a: the near root
@@ -422,7 +422,7 @@ def check_exact(sd: capi.SceneDesc, rays, got: dict, exact, precision: int, scen
         worst["point"] = max(worst["point"], perr / dp)
         if i < S.ns:
             cd = [Decimal(float(S.c[i, k])) + Decimal(float(S.v[i, k])) * Decimal(float(rays[n, 3])) for k in range(3)]
-            r = float(S.r[i])
+            r = abs(float(S.r[i]))
             nrm = np.array([float((p_dec[k] - cd[k]) / Decimal(r)) for k in range(3)])
             dn = 2 * (dp + 3 * u * (float(np.abs(S.c[i]).max()) + float(np.abs(S.v[i]).max())) + u * float(np.abs(p_ex).max())) / r + 6 * u
         else:
