@@ -635,14 +635,51 @@ int rayz_hip_scene_query_camera(RayzScene* scene, const RayzCameraDesc* camera, 
  * renders count them (flat list: rays x hittables), kernel_ms = the query kernel's HIP-event time. */
 int rayz_hip_query_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
 
+/* ---- specular-chain G-buffers: guides seen through mirrors and glass -------------------------------
+ * BUILD-DEFINED.  rayz_hip_scene_query_camera with the ray FOLLOWED through mirror-like metals and dielectrics: per pixel,
+ * segment 0 is the camera query's ray; while the nearest hit of a segment is a dielectric, or a metal whose fuzz is at most
+ * `max_fuzz`, and fewer than `max_depth` hits have been followed, the next segment starts at the hit point (time 0, tmax +inf,
+ * the call's tmin) along the direction `Material.scatter` gives with the metal's fuzz taken as 0 and every uniform draw 1.0:
+ * unit(reflect(d, n)) off a metal; through a dielectric the refraction unless eta·sin > 1 (then the reflection), never the
+ * Fresnel reflection.  A metal that absorbs the ray (its reflection points into the surface) ends the chain on that hit.
+ * `outputs` receives the record of the LAST segment exactly as a NEAREST query of that segment's ray writes it — so point,
+ * normal and index are those of the first non-specular surface along the path, or a miss — except `albedo`, which is that
+ * record's albedo multiplied per channel by the albedos of the followed hits (1, 1, 1 for glass).
+ * Reads the same fields of `params` as rayz_hip_scene_query_camera, deals pixels and shards the same way, is asynchronous the
+ * same way (rayz_hip_query_sync waits for it: primary_rays = pixels, segments = the sum of depth + 1 over them), and counts as
+ * the scene's one render or query in flight.  max_depth = 0 is rayz_hip_scene_query_camera bit for bit.
+ * RAYZ_ERR_BAD_ARG before any HIP call: as rayz_hip_scene_query_camera, and max_depth > RAYZ_CHAIN_MAX_DEPTH, a max_fuzz that
+ * is NaN or negative.  `chain` NULL: the defaults.  Added in ABI 5 (additive: no existing symbol or struct changed).
+ * The record is NOT a first-hit record: temporal reprojection (rayz_hip_temporal_*) needs the first-hit point, so a caller that
+ * uses both fills two G-buffers per frame. */
+#define RAYZ_CHAIN_MAX_DEPTH 16u
+#define RAYZ_CHAIN_DEFAULT_DEPTH 4u      /* a hollow glass ball is four interfaces; a parameter, provisional */
+#define RAYZ_CHAIN_DEFAULT_MAX_FUZZ 0.25 /* a parameter, provisional */
+typedef struct RayzChainParams {
+    uint32_t max_depth; /* hits followed at most, 0..RAYZ_CHAIN_MAX_DEPTH */
+    uint32_t _pad;
+    double max_fuzz;    /* a metal whose fuzz (narrowed to the precision) is greater is not followed */
+} RayzChainParams;
+typedef struct RayzChainOutputs { /* DEVICE memory, each optional; entries as RayzQueryOutputs' */
+    uint32_t* key;         /* n: the chain key: 0, then key <- key x 0x9E3779B1 + (index + 1) in uint32 arithmetic for every followed
+                              hit; 0 for a pixel whose first hit was not followed */
+    uint8_t* depth;        /* n: number of hits followed */
+    int32_t* first_index;  /* n: what rayz_hip_scene_query_camera's `index` holds */
+} RayzChainOutputs;
+int rayz_hip_scene_query_camera_chain(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                      const RayzChainParams* chain_or_null, const RayzQueryOutputs* outputs,
+                                      const RayzChainOutputs* chain_outputs_or_null, void* hip_stream);
+
 /* ---- denoising: a G-buffer-guided à-trous filter for low-spp frames -------------------------------------------------
  * BUILD-DEFINED (the reference has no denoiser): an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) on a WHOLE f32
  * frame in DEVICE memory, guided by the G-buffer a rayz_hip_scene_query_camera call of F32 precision filled for the same camera
  * and frame size.  The arithmetic is a contract, DESIGN.md §4.11 (+ - x, explicit FMAs, correctly rounded divides, comparisons;
  * no transcendental), restated bit for bit on the CPU by tests/denoise_mirror.cpp.  Added in ABI 5 (additive: no existing symbol
  * changed); it changes no image any other entry point produces.
- * Limits of this version: whole frames only (rows of a shard are not image neighbours: gather first); f32 only; the guides are
- * FIRST-HIT guides, so what a metallic or dielectric surface reflects or refracts is filtered as if it were painted on it. */
+ * Limits of this version: whole frames only (rows of a shard are not image neighbours: gather first); f32 only.  With the
+ * G-buffer of rayz_hip_scene_query_camera the guides are FIRST-HIT guides, so what a metallic or dielectric surface reflects or
+ * refracts is filtered as if it were painted on it; the G-buffer of rayz_hip_scene_query_camera_chain with its keys
+ * (rayz_hip_denoiser_set_keys) guides the filter by what is SEEN in such a surface instead. */
 typedef struct RayzDenoiser RayzDenoiser; /* opaque: packed guides + two colour buffers for one frame size on one device */
 
 #define RAYZ_DENOISE_ALBEDO 0x1u      /* demodulate: filter c / max(albedo, 2^-8) and multiply it back in (needs gbuffer->albedo) */
@@ -717,6 +754,14 @@ int rayz_hip_denoiser_run_guided_tap(RayzDenoiser* dn, const RayzDenoiseGuidedPa
                                      float* d_var_out_or_null, uint32_t tap_level, float* d_tap_rgb, void* hip_stream);
 /* Waits for the handle's last run and returns its HIP-event times: *levels_or_null = L, the levels it ran; ms_or_null[0] = the
  * pack pass, ms_or_null[1 + l] = level l, for as many of the L + 1 entries as `capacity` holds.  RAYZ_ERR_STATE before any run. */
+/* Surface keys: every LATER run on the handle, of either mode, with or without a tap, reads height*width keys
+ * from `d_keys_or_null` (DEVICE memory) in its pack pass, and a tap whose key differs from the centre pixel's, compared as a
+ * 32-bit integer, is skipped exactly as a tap outside the frame is — before anything else, background taps and the guided
+ * mode's 3x3 variance prefilter included.  rayz_hip_scene_query_camera_chain's `key` keeps "the ground" and "the ground seen in
+ * the ball" apart at the ball's silhouette.  NULL, the initial state, turns keys off: every image is what it was without this
+ * entry, bit for bit (so is one with all keys equal).  The buffer must stay allocated while runs use it.  Changes nothing on a
+ * device.  RAYZ_ERR_STATE: a bad handle. */
+int rayz_hip_denoiser_set_keys(RayzDenoiser* dn, const uint32_t* d_keys_or_null);
 int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);
 int rayz_hip_denoiser_destroy(RayzDenoiser* dn);
 

@@ -37,6 +37,8 @@ DIFFUSE_UNIT_SPHERE, DIFFUSE_UNIT_SPHERE_SURFACE, DIFFUSE_HEMISPHERE = 0, 1, 2
 PRECISION_F32, PRECISION_F64 = 0, 1
 TRAVERSAL_LINEAR, TRAVERSAL_BVH, TRAVERSAL_AUTO = 0, 1, 2
 QUERY_NEAREST, QUERY_ANY = 0, 1
+CHAIN_MAX_DEPTH = 16
+CHAIN_DEFAULTS = {"max_depth": 4, "max_fuzz": 0.25}  # provisional
 DENOISE_ALBEDO = 1
 DENOISE_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 0.5, "sigma_plane": 0.25}
 DENOISE_GUIDED_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE_ALBEDO, "sigma_color": 2.0, "sigma_plane": 0.25,
@@ -101,6 +103,14 @@ class QueryOutputs(C.Structure):
                 ("front_face", C.c_void_p), ("material", C.c_void_p), ("albedo", C.c_void_p), ("hit", C.c_void_p)]
 
 
+class ChainParams(C.Structure):
+    _fields_ = [("max_depth", C.c_uint32), ("_pad", C.c_uint32), ("max_fuzz", C.c_double)]
+
+
+class ChainOutputs(C.Structure):
+    _fields_ = [("key", C.c_void_p), ("depth", C.c_void_p), ("first_index", C.c_void_p)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
                 ("sigma_color", C.c_double), ("sigma_plane", C.c_double)]
@@ -138,6 +148,7 @@ assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
 assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
+assert C.sizeof(ChainParams) == 16 and C.sizeof(ChainOutputs) == 24
 assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32 and C.sizeof(TemporalMomentsParams) == 16
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
@@ -227,6 +238,9 @@ PROTOTYPES = [
     ("rayz_hip_scene_query_camera", C.c_int,
      [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(QueryOutputs), C.c_void_p]),
     ("rayz_hip_query_sync", C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
+    ("rayz_hip_scene_query_camera_chain", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(ChainParams), C.POINTER(QueryOutputs),
+      C.POINTER(ChainOutputs), C.c_void_p]),
     ("rayz_hip_denoiser_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_denoiser_run", C.c_int,
      [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p]),
@@ -235,6 +249,7 @@ PROTOTYPES = [
     ("rayz_hip_denoiser_run_guided_tap", C.c_int,
      [C.c_void_p, C.POINTER(DenoiseGuidedParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_uint32,
       C.c_void_p, C.c_void_p]),
+    ("rayz_hip_denoiser_set_keys", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rayz_hip_denoiser_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]),
     ("rayz_hip_denoiser_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

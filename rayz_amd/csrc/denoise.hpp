@@ -17,8 +17,12 @@
 // dn_vtap(); dn_filter_pixel() visits the taps in one order (j outer, i inner, ascending) whichever form fetches them, so the
 // staging a level uses never changes a value.
 //
-// Guides are FIRST-HIT guides: a mirror or a glass ball is filtered by its own surface's normal and point, not by what it
-// reflects or refracts — the reflection in it is smoothed as if it were a texture of the ball.
+// The guides are whatever G-buffer the caller hands in.  A camera query's are FIRST-HIT guides: a mirror or a glass ball is filtered
+// by its own surface's normal and point, and the reflection in it is smoothed as if it were a texture of the ball.  A chain
+// G-buffer's (rayz_hip_scene_query_camera_chain, §4.18) are those of what is SEEN in the ball; its surface KEYS
+// (rayz_hip_denoiser_set_keys) ride in the gb record's .w slot as raw bits, and a tap whose key differs from the centre pixel's
+// is skipped before anything else — "the ground" and "the ground seen in the ball" never mix.  Without keys the slot holds 0
+// everywhere and the rule never fires.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,7 +41,7 @@ constexpr float kDnVarCap = 4294967296.0f;  // VCAP = 2^32: "no estimate: trust 
 // One level's arguments, of either mode: the plain mode leaves var and vf unused, the guided mode cl.
 struct DenoiseArgs {
     const dn4* __restrict__ ga;   // per pixel {n.x, n.y, n.z, bg ? 1 : 0}
-    const dn4* __restrict__ gb;   // per pixel {P.x, P.y, P.z, 0}
+    const dn4* __restrict__ gb;   // per pixel {P.x, P.y, P.z, the surface key's 32 bits (0 without keys)}
     const dn4* __restrict__ mod;  // per pixel {m.r, m.g, m.b, 0}: read by the last level only
     const dn4* __restrict__ src;  // this level's colours {e.r, e.g, e.b, guided: the variance v, plain: 0}
     dn4* __restrict__ dst;        // next level's colours (not the last level)
@@ -63,6 +67,13 @@ __device__ __forceinline__ float dn_max0(float x) { return x > 0.0f ? x : 0.0f; 
 // §4.13's clamp of a variance: a NaN or anything not below VCAP becomes VCAP, anything not above 0 becomes 0.
 __device__ __forceinline__ float dn_clamp_var(float t) { return !(t < kDnVarCap) ? kDnVarCap : (t > 0.0f ? t : 0.0f); }
 
+// The surface key of a gb record: its .w slot's bits, compared as an integer (never as a float: a key is an arbitrary pattern).
+// (through a float of its own: __builtin_bit_cast on the vector's element `b.w` itself reads the vector's first four bytes, b.x)
+__device__ __forceinline__ uint32_t dn_key(const dn4 b) {
+    const float w = b.w;
+    return __builtin_bit_cast(uint32_t, w);
+}
+
 struct DnAcc {
     float W, r, g, b, V; // (V: the guided mode's variance sum)
 };
@@ -71,12 +82,14 @@ struct DnTap { // the three records of a pixel
     dn4 a, b, c;
 };
 
-// One tap: centre pixel (pa, pb, pc), tap pixel (qa, qb, qc), h = k[i]·k[j].  The guides either skip the tap or give it g = wn·wz;
+// One tap: centre pixel (pa, pb, pc), tap pixel (qa, qb, qc), h = k[i]·k[j].  A tap of another surface key is skipped (§4.18); then
+// the guides either skip the tap or give it g = wn·wz;
 // the colour weight is wc = 1 / (1 + de2·cl / sc2), or in the guided mode 1 / (1 + de2 / den) with den = sc2·(gv + vf) of the
 // CENTRE pixel, which also sums the variance V.
 template <bool GUIDED>
 __device__ __forceinline__ void dn_tap(const dn4 pa, const dn4 pb, const dn4 pc, const dn4 qa, const dn4 qb, const dn4 qc, const float h,
                                        const float den, const DenoiseArgs& a, DnAcc& acc) {
+    if (dn_key(pb) != dn_key(qb)) return;
     const bool bgp = pa.w != 0.0f, bgq = qa.w != 0.0f;
     float g = 1.0f;
     if (bgp || bgq) {
@@ -110,8 +123,11 @@ __device__ __forceinline__ float dn_k(int i) { // k = {1/16, 1/4, 3/8, 1/4, 1/16
 }
 __device__ __forceinline__ float dn_gk(int i) { return i == 0 ? 0.5f : 0.25f; } // gk = {1/4, 1/2, 1/4}
 
-// One tap of the guided mode's 3x3 variance prefilter: the tap's bg flag and variance (the .w slots of its ga and colour records).
-__device__ __forceinline__ void dn_vtap(const bool bgp, const float qbg, const float qv, const float gg, float& G, float& A) {
+// One tap of the guided mode's 3x3 variance prefilter: the tap's surface key, bg flag and variance (the .w slots of its three
+// records); kp is the centre pixel's key.
+__device__ __forceinline__ void dn_vtap(const uint32_t kp, const bool bgp, const uint32_t qk, const float qbg, const float qv, const float gg,
+                                        float& G, float& A) {
+    if (qk != kp) return;
     if ((qbg != 0.0f) != bgp) return;
     G = G + gg;
     A = __builtin_fmaf(gg, qv, A);
@@ -136,12 +152,12 @@ template <bool GUIDED, bool LAST> __device__ __forceinline__ void dn_store(const
 }
 
 // Builds the records: guides, the modulation m and the demodulated colour e = c / m; in the guided mode also the variance slot,
-// v = the clamp of Σ_ch var_ch / m_ch² (var_rgb is not read otherwise).  One thread per pixel.
+// v = the clamp of Σ_ch var_ch / m_ch² (var_rgb is not read otherwise); the surface key's bits, if there are keys.  One thread per pixel.
 template <bool GUIDED>
 __global__ __launch_bounds__(256) void denoise_pack_kernel(const float* __restrict__ rgb, const float* __restrict__ var_rgb,
                                                            const int32_t* __restrict__ index, const float* __restrict__ normal,
                                                            const float* __restrict__ point, const float* __restrict__ albedo /* NULL: m = 1 */,
-                                                           dn4* __restrict__ ga, dn4* __restrict__ gb, dn4* __restrict__ mod,
+                                                           const uint32_t* __restrict__ keys /* NULL: no keys */, dn4* __restrict__ ga, dn4* __restrict__ gb, dn4* __restrict__ mod,
                                                            dn4* __restrict__ col, size_t n_pixels) {
     const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pixels) return;
@@ -157,7 +173,7 @@ __global__ __launch_bounds__(256) void denoise_pack_kernel(const float* __restri
     float v = 0.0f;
     if (GUIDED) v = dn_clamp_var(((var_rgb[3 * p] / (mr * mr)) + (var_rgb[3 * p + 1] / (mg * mg))) + (var_rgb[3 * p + 2] / (mb * mb)));
     ga[p] = dn4{normal[3 * p], normal[3 * p + 1], normal[3 * p + 2], bg ? 1.0f : 0.0f};
-    gb[p] = dn4{point[3 * p], point[3 * p + 1], point[3 * p + 2], 0.0f};
+    gb[p] = dn4{point[3 * p], point[3 * p + 1], point[3 * p + 2], keys ? __builtin_bit_cast(float, keys[p]) : 0.0f};
     mod[p] = dn4{mr, mg, mb, 0.0f};
     col[p] = dn4{rgb[3 * p] / mr, rgb[3 * p + 1] / mg, rgb[3 * p + 2] / mb, v};
 }
@@ -172,7 +188,11 @@ struct DnGlobalTaps {
     __device__ __forceinline__ int stride() const { return a.stride; }
     __device__ __forceinline__ DnTap at(int qx, int qy, int, int) const {
         const size_t q = (size_t)qy * a.width + qx;
-        return DnTap{a.ga[q], a.gb[q], a.src[q]};
+        DnTap t{a.ga[q], a.gb[q], a.src[q]};
+        // the three loads of a tap are issued TOGETHER: left to itself the compiler fetches the record the first rule reads (the key's),
+        // waits, and only then fetches the other two behind the branch — two dependent memory round trips per tap
+        asm volatile("" : "+v"(t.a), "+v"(t.b), "+v"(t.c));
+        return t;
     }
 };
 // .. from the tile staged in LDS, TW records wide, the thread's own at slot c, at the compile-time stride S, every tap unrolled:
@@ -183,7 +203,9 @@ template <int S, int TW> struct DnLdsTaps {
     __device__ __forceinline__ constexpr int stride() const { return S; }
     __device__ __forceinline__ DnTap at(int, int, int dx, int dy) const {
         const int q = c + dy * TW + dx;
-        return DnTap{sa[q], sb[q], sc[q]};
+        DnTap t{sa[q], sb[q], sc[q]};
+        asm("" : "+v"(t.b)); // (the gb record whole, one ds_read_b128, also where only its key is used: the prefilter's taps)
+        return t;
     }
 };
 
@@ -206,7 +228,7 @@ __device__ __forceinline__ DnAcc dn_filter_pixel(const DenoiseArgs& a, const int
                 const int qx = x + i;
                 if (qx < 0 || qx >= (int)a.width) continue;
                 const DnTap q = taps.at(qx, qy, i, j);
-                dn_vtap(bgp, q.a.w, q.c.w, dn_gk(i) * dn_gk(j), G, A);
+                dn_vtap(dn_key(p.b), bgp, dn_key(q.b), q.a.w, q.c.w, dn_gk(i) * dn_gk(j), G, A);
             }
         }
         den = a.sc2 * (A / G + a.vf);
@@ -268,10 +290,10 @@ inline dim3 denoise_grid(uint32_t width, uint32_t height) {
 }
 
 inline void denoise_launch_pack(hipStream_t st, bool guided, const float* rgb, const float* var_rgb /* guided only */, const int32_t* index,
-                                const float* normal, const float* point, const float* albedo, dn4* ga, dn4* gb, dn4* mod, dn4* col,
-                                size_t n_pixels) {
+                                const float* normal, const float* point, const float* albedo, const uint32_t* keys, dn4* ga, dn4* gb, dn4* mod,
+                                dn4* col, size_t n_pixels) {
     hipLaunchKernelGGL(guided ? denoise_pack_kernel<true> : denoise_pack_kernel<false>, dim3((uint32_t)((n_pixels + 255) / 256)), dim3(256), 0,
-                       st, rgb, var_rgb, index, normal, point, albedo, ga, gb, mod, col, n_pixels);
+                       st, rgb, var_rgb, index, normal, point, albedo, keys, ga, gb, mod, col, n_pixels);
 }
 
 typedef void (*DnLevelKernel)(DenoiseArgs);

@@ -9,6 +9,7 @@ struct RayzDenoiser : FrameHandle<5, 10> {
     static constexpr uint32_t kMagic = 0x444e5a52u;
     static constexpr const char* kNoun = "denoiser";
     uint32_t levels_run = 0; // levels of the last COMPLETE run (0: none, or the last run failed half-way: no timing)
+    const uint32_t* keys = nullptr; // the caller's surface keys (rayz_hip_denoiser_set_keys), read by every run's pack pass; NULL: none
 };
 
 namespace {
@@ -57,7 +58,7 @@ int denoiser_run(RayzDenoiser* dn, bool guided, const RayzDenoiseGuidedParams& p
     dn->levels_run = 0; // (a run that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(dn, 0, st));
     denoise_launch_pack(st, guided, d_in, d_var_rgb, g->index, (const float*)g->normal, (const float*)g->point,
-                        demod ? (const float*)g->albedo : nullptr, ga, gb, mod, col[0], (size_t)dn->width * dn->height);
+                        demod ? (const float*)g->albedo : nullptr, dn->keys, ga, gb, mod, col[0], (size_t)dn->width * dn->height);
     RAYZ_TRY(frame_handle_launched(dn, 1, st));
     DenoiseArgs a{};
     a.ga = ga, a.gb = gb, a.mod = mod, a.rgb = d_out, a.var = d_var_out;
@@ -117,6 +118,14 @@ int rayz_hip_denoiser_run_guided_tap(RayzDenoiser* dn, const RayzDenoiseGuidedPa
         if (d_tap_rgb == d_rgb_in || d_tap_rgb == d_rgb_out)
             return fail(RAYZ_ERR_BAD_ARG, "denoise: the tap buffer must be neither d_rgb_in nor d_rgb_out");
         return denoiser_run(dn, true, p, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out_or_null, hip_stream, tap_level, d_tap_rgb);
+    });
+}
+
+int rayz_hip_denoiser_set_keys(RayzDenoiser* dn, const uint32_t* d_keys_or_null) {
+    return guarded([&] {
+        RAYZ_TRY(frame_handle_check(dn));
+        dn->keys = d_keys_or_null;
+        return (int)RAYZ_OK;
     });
 }
 

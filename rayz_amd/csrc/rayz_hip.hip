@@ -11,6 +11,7 @@
 // experiments/ includes).  It stands on host_base.hpp and includes, at its end, one header per feature: handle, internals, entries.
 #include "../../include/rayz_hip.h"
 #include "rayz_device.hpp"
+#include "chain_kernel.hpp"
 #include "bvh_build.hpp"
 #include "denoise.hpp"
 #include "temporal_kernel.hpp"
@@ -194,11 +195,12 @@ struct RayzScene {
     uint32_t scan_form = rayz_plane::kScanFormAuto; // rayz_hip_scene_set_scan_form: auto = the layout's own (narrow.scan_form)
     RayzRenderStats last{};
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
-    DevBuf<unsigned long long> q_counters; // [0] batch head, [2] node tests, [3] sphere tests, [31] LDS flag,
+    DevBuf<unsigned long long> q_counters; // [0] batch head, [1] segments (chain calls), [2] node tests, [3] sphere tests, [31] LDS flag,
                                            // [kQueryBoundBase + k·kQueryBoundStride] the bound check's four words
     DevEvent q_ev0, q_ev1;
     hipStream_t q_stream = nullptr;
-    bool queried = false, q_bvh = false;
+    bool queried = false, q_bvh = false, q_chain = false; // (q_chain: the query in flight is a chain call, chain.hpp)
+    DevBuf<unsigned long long> q_chain_stores; // a chain call's output pointers (ChainStores, chain_kernel.hpp), which its kernel reads from device memory
     RayzRenderStats q_last{};
     // The members free themselves; what is left is to wait for the scene's last launch first.
     ~RayzScene() {
@@ -1434,6 +1436,7 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "known_answers.hpp"
 #include "multi_device.hpp"
 #include "query.hpp"
+#include "chain.hpp"
 #include "frame_handle.hpp"
 #include "denoiser.hpp"
 #include "temporal.hpp"

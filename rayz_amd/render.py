@@ -136,18 +136,22 @@ def _optional_out(out, shape, device):
 
 
 QUERY_OUTPUTS = ("index", "t", "point", "normal", "front_face", "material", "albedo")
+CHAIN_OUTPUTS = ("key", "depth", "first_index")  # what a chain G-buffer carries beside them (DeviceScene.gbuffer(chain=...))
 
 
 class QueryResult:
     """The outputs of a query as torch tensors on the scene's device (None where not requested): index, material (int32),
     t (R), point / normal / albedo (..., 3) of R, front_face and hit (uint8).  Written asynchronously: call
-    DeviceScene.query_sync() (or synchronise the stream) before reading them on the host."""
+    DeviceScene.query_sync() (or synchronise the stream) before reading them on the host.
+    A chain G-buffer (`is_chain`, DeviceScene.gbuffer(chain=...)) holds the record of the LAST segment of every
+    pixel's specular chain, and also key (int32: the chain key's 32 bits), depth (uint8) and first_index (int32)."""
 
     _VEC = ("point", "normal", "albedo")
 
     def __init__(self):
-        for k in QUERY_OUTPUTS + ("hit",):
+        for k in QUERY_OUTPUTS + ("hit",) + CHAIN_OUTPUTS:
             setattr(self, k, None)
+        self.is_chain = False
 
     @classmethod
     def _alloc(cls, shape, dtype, device, outputs):
@@ -279,19 +283,43 @@ class DeviceScene(_Handle):
         return res
 
     def gbuffer(self, camera: capi.CameraDesc, params: capi.RenderParams, outputs=QUERY_OUTPUTS,
-                stream: int = 0) -> "QueryResult":
+                stream: int = 0, chain=False) -> "QueryResult":
         """The camera form: one lens-centre ray per pixel of `params`' shard (getRay(px, py, null)), results shaped
         (rows_in_shard, width, ...) on the scene's device.  Asynchronous on `stream`; the outputs are kept alive by the scene until
-        query_sync() or the next query."""
+        query_sync() or the next query.
+        `chain` True, or a dict of RayzChainParams' fields (max_depth, max_fuzz; unnamed ones take capi.CHAIN_DEFAULTS): the
+        specular-chain G-buffer (`rayz_hip_scene_query_camera_chain`) — every pixel's ray is followed through
+        mirror-like metals and glass, the requested `outputs` are the last segment's record (albedo multiplied by the chain's
+        tint), and the result also carries key, depth and first_index and is marked `is_chain`.  Such a result guides
+        `Denoiser.run` / `run_guided` (its keys are used by default); `Temporal` refuses it: reprojection needs the first-hit
+        point, so a caller of both fills two G-buffers per frame."""
         import torch
 
         rows = shard_rows(params)
         dtype = torch.float64 if params.precision == capi.PRECISION_F64 else torch.float32
-        res = QueryResult._alloc((rows, params.width), dtype, torch.device("cuda", self.device), outputs)
+        dev = torch.device("cuda", self.device)
+        res = QueryResult._alloc((rows, params.width), dtype, dev, outputs)
+        if chain is False or chain is None:
+            self._query_prologue(stream)
+            rc = self._lib.rayz_hip_scene_query_camera(self._h, C.byref(camera), C.byref(params), C.byref(res._outputs()),
+                                                       C.c_void_p(stream or None))
+            capi.check(self._lib, rc, "rayz_hip_scene_query_camera")
+            self._inflight = (None, res)
+            return res
+        if chain is not True and not isinstance(chain, dict):
+            raise ValueError(f"chain must be False, True or a dict of {sorted(capi.CHAIN_DEFAULTS)}, got {chain!r}")
+        prm = _params(capi.ChainParams, capi.CHAIN_DEFAULTS, {} if chain is True else chain, "chain")
+        res.key = torch.empty((rows, params.width), dtype=torch.int32, device=dev)
+        res.depth = torch.empty((rows, params.width), dtype=torch.uint8, device=dev)
+        res.first_index = torch.empty((rows, params.width), dtype=torch.int32, device=dev)
+        res.is_chain = True
+        co = capi.ChainOutputs()
+        if res.key.numel():
+            co.key, co.depth, co.first_index = res.key.data_ptr(), res.depth.data_ptr(), res.first_index.data_ptr()
         self._query_prologue(stream)
-        rc = self._lib.rayz_hip_scene_query_camera(self._h, C.byref(camera), C.byref(params), C.byref(res._outputs()),
-                                                   C.c_void_p(stream or None))
-        capi.check(self._lib, rc, "rayz_hip_scene_query_camera")
+        rc = self._lib.rayz_hip_scene_query_camera_chain(self._h, C.byref(camera), C.byref(params), C.byref(prm), C.byref(res._outputs()),
+                                                         C.byref(co), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_scene_query_camera_chain")
         self._inflight = (None, res)
         return res
 
@@ -530,6 +558,21 @@ class Denoiser(_Handle):
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
 
+    def _set_keys(self, gbuffer, keys):
+        """The surface keys of a run (`rayz_hip_denoiser_set_keys`): `keys` "auto" — the gbuffer's `key` if it is a
+        chain result, else none —, None for none, or a (height, width) int32 tensor on the handle's device.  Returns the tensor."""
+        import torch
+
+        if isinstance(keys, str):
+            if keys != "auto":
+                raise ValueError(f"keys must be 'auto', None or a tensor, got {keys!r}")
+            keys = gbuffer.key if getattr(gbuffer, "is_chain", False) else None
+        if keys is not None:
+            _check_tensor("keys", keys, torch.int32, (self.height, self.width), self._device, "the denoiser")
+        capi.check(self._lib, self._lib.rayz_hip_denoiser_set_keys(self._h, C.c_void_p(keys.data_ptr() if keys is not None else None)),
+                   "rayz_hip_denoiser_set_keys")
+        return keys
+
     def _checked(self, prm, inputs, gbuffer, out, var_out):
         """The tensor checks of a run, in argument order: the (name, tensor) `inputs`, the guides `prm.flags` asks for, `out` (None: a
         new tensor) and the optional `var_out`.  Returns (out, var_out or None, the guides' names)."""
@@ -544,24 +587,27 @@ class Denoiser(_Handle):
         _check_frame_tensors("the denoiser", self._device, frame, inputs, gbuffer, need, [("out", out, frame), ("var_out", var_out, frame[:2])])
         return out, var_out, need
 
-    def run(self, rgb, gbuffer: "QueryResult", out=None, stream: int = 0, **params):
+    def run(self, rgb, gbuffer: "QueryResult", out=None, stream: int = 0, keys="auto", **params):
         """Filters `rgb` ((height, width, 3) float32 on the handle's device) guided by `gbuffer` (index, normal, point and — unless
         flags drops DENOISE_ALBEDO — albedo of a float32 camera query of the same frame) into `out` (default: a new tensor;
         `out=rgb` filters in place).  `params`: the fields of RayzDenoiseParams (levels, normal_power_log2, flags, sigma_color,
-        sigma_plane); unnamed ones take capi.DENOISE_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
+        sigma_plane); unnamed ones take capi.DENOISE_DEFAULTS.  `keys`: surface keys, (height, width) int32 — a tap whose key differs
+        from the centre pixel's is skipped (§4.18); "auto" (the default) takes `gbuffer.key` when the gbuffer is a chain result and
+        none otherwise, None switches them off.  Asynchronous on `stream` (0: the library's stream, after torch's
         work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
         prm = _params(capi.DenoiseParams, capi.DENOISE_DEFAULTS, params, "denoise")
         out, _, need = self._checked(prm, [("rgb", rgb)], gbuffer, out, False)
+        keys = self._set_keys(gbuffer, keys)
         _stream_prologue(stream, self._device)
         o = _gbuffer_pointers(gbuffer, need)
         rc = self._lib.rayz_hip_denoiser_run(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
                                              C.c_void_p(stream or None))
         capi.check(self._lib, rc, "rayz_hip_denoiser_run")
-        self._inflight = (rgb, gbuffer, out)
+        self._inflight = (rgb, gbuffer, out, keys)
         return out
 
     def run_guided(self, rgb, var_rgb, gbuffer: "QueryResult", out=None, var_out=None, stream: int = 0, tap_level: int = 0, tap_out=None,
-                   **params):
+                   keys="auto", **params):
         """The variance-guided filter (`rayz_hip_denoiser_run_guided`): as `run`, with `var_rgb` — (height, width, 3)
         float32, the variance of each channel of `rgb`'s pixel means (`Progressive.noise_rgb()`) — steering the colour weight pixel
         by pixel.  `var_out`: True for a new (height, width) float32 tensor, or such a tensor, to receive the variance left in the
@@ -569,7 +615,7 @@ class Denoiser(_Handle):
         normal_power_log2, flags, sigma_color — in standard deviations —, sigma_plane, var_floor); unnamed ones take
         capi.DENOISE_GUIDED_DEFAULTS.  `tap_level` t > 0 (`rayz_hip_denoiser_run_guided_tap`): the run also writes the re-modulated
         colour after t levels — what a run with levels=t returns — to `tap_out` (default: a new tensor; neither `rgb` nor `out`),
-        which the call returns as a further value; t = 1 is what `Temporal.feedback` takes."""
+        which the call returns as a further value; t = 1 is what `Temporal.feedback` takes.  `keys`: as `run`."""
         import torch
 
         prm = _params(capi.DenoiseGuidedParams, capi.DENOISE_GUIDED_DEFAULTS, params, "denoise")
@@ -581,6 +627,7 @@ class Denoiser(_Handle):
             _check_tensor("tap_out", tap_out, torch.float32, frame, self._device, "the denoiser")
         elif tap_out is not None:
             raise ValueError("tap_out needs tap_level > 0")
+        keys = self._set_keys(gbuffer, keys)
         _stream_prologue(stream, self._device)
         o = _gbuffer_pointers(gbuffer, need)
         if tap_level:
@@ -589,13 +636,13 @@ class Denoiser(_Handle):
                                                             C.c_void_p(var_out.data_ptr() if var_out is not None else None), int(tap_level),
                                                             C.c_void_p(tap_out.data_ptr()), C.c_void_p(stream or None))
             capi.check(self._lib, rc, "rayz_hip_denoiser_run_guided_tap")
-            self._inflight = (rgb, var_rgb, gbuffer, out, var_out, tap_out)
+            self._inflight = (rgb, var_rgb, gbuffer, out, var_out, tap_out, keys)
             return (out, tap_out) if var_out is None else (out, var_out, tap_out)
         rc = self._lib.rayz_hip_denoiser_run_guided(self._h, C.byref(prm), C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()),
                                                     C.byref(o), C.c_void_p(out.data_ptr()),
                                                     C.c_void_p(var_out.data_ptr() if var_out is not None else None), C.c_void_p(stream or None))
         capi.check(self._lib, rc, "rayz_hip_denoiser_run_guided")
-        self._inflight = (rgb, var_rgb, gbuffer, out, var_out)
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, keys)
         return out if var_out is None else (out, var_out)
 
     def timing(self):
@@ -664,6 +711,9 @@ class Temporal(_Handle):
         (out, var_out, [a plane's tensor or None, ..], the guides' pointers)."""
         import torch
 
+        if getattr(gbuffer, "is_chain", False):
+            raise ValueError("the temporal handle needs a first-hit G-buffer (reprojection projects the first-hit point): this one is a "
+                             "chain result; fill a second G-buffer without chain= for the temporal step")
         frame = (self.height, self.width, 3)
         dev = torch.device("cuda", self._device)
         need = ["index", "normal", "point"]

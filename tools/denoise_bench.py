@@ -18,7 +18,13 @@
    defaults, and the guided filter over sigma_color {1, 2, 4, 8} x var_floor {1e-6, 1e-4, 1e-2} x levels {3, 4, 5} — the sweep the
    guided defaults are taken from; then the per-level HIP-event times of both modes on that frame, same process, 5 levels.
 
-    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE] [--guided]"""
+5. --chain: chain guides and surface keys (rayz_hip_scene_query_camera_chain, rayz_hip_denoiser_set_keys) INSTEAD.
+   Configs 2 and 3 at 1920x1080, the 16-spp tracked frame of --guided against --ref-spp; `run` and `run_guided` at their defaults
+   with first-hit guides, with chain guides without keys and with chain guides plus keys, for max_fuzz 0, 0.25, 0.5 (max_depth 4):
+   MSE over the whole frame and over the pixels whose FIRST hit is metal or glass.  Then the keys-off per-level HIP-event times of
+   both modes (what the key compare costs a caller who does not use it is this build against its parent, run alternately).
+
+    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE] [--guided | --chain]"""
 import argparse
 import json
 import os
@@ -163,6 +169,68 @@ def guided(args):
             json.dump(res, f, indent=1)
 
 
+def chain(args):
+    """Section 5 of the module docstring."""
+    res = {}
+    for cfg, make in (("2", lambda: tracer.randomBouncing(1920, seed=42)), ("3", lambda: tracer.randomBouncing(1920, -50, 50, seed=42))):
+        t = make()
+        t.samples_per_px, t.max_bounces = 16, 50
+        t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=2)
+        sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+        p.tmin = 1e-3
+        w, h = p.width, p.height
+        ds = render.DeviceScene(sd)
+        pr = ds.progressive(cam, p, track_noise=True)
+        noisy = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        while not pr.done:
+            pr.step(0, noisy.data_ptr())
+        var = pr.noise_rgb()
+        pr.stats()
+        first = ds.gbuffer(cam, p)
+        ds.query_sync()
+        kinds = torch.tensor([sd.materials[i].kind for i in range(sd.n_materials)], device="cuda")
+        spec = (first.index >= 0) & (kinds[first.material.clamp(min=0).long()] != capi.MAT_DIFFUSE)
+        p.samples_per_px, p.chunk_spp = args.ref_spp, 0
+        ref = torch.empty_like(noisy)
+        torch.cuda.synchronize()
+        ds.render_into(cam, p, ref.data_ptr())
+        ds.sync()
+        err = lambda a: ((a.double() - ref.double()) ** 2).mean(dim=2)  # noqa: E731
+
+        def both(a):  # (a run is asynchronous on the library's stream: wait before torch reads its output)
+            if isinstance(a, tuple):
+                a = a[0]
+            torch.cuda.synchronize()
+            return float(err(a).mean()), float(err(a)[spec].mean())
+
+        dn = render.Denoiser(w, h)
+        rows = {"noisy": both(noisy), "run first-hit": both(dn.run(noisy, first)), "run_guided first-hit": both(dn.run_guided(noisy, var, first))}
+        for fuzz in (0.0, 0.25, 0.5):
+            g = ds.gbuffer(cam, p, chain=dict(max_depth=4, max_fuzz=fuzz))
+            ds.query_sync()
+            for keys, kname in ((None, "no keys"), ("auto", "keys")):
+                rows[f"run chain max_fuzz {fuzz} {kname}"] = both(dn.run(noisy, g, keys=keys))
+                rows[f"run_guided chain max_fuzz {fuzz} {kname}"] = both(dn.run_guided(noisy, var, g, keys=keys))
+        print(f"config {cfg}, {w}x{h}, 16 spp against {args.ref_spp} spp; {float(spec.float().mean()):.3f} of the pixels first hit metal or glass.  "
+              "MSE whole frame | over those pixels (ratio to the noisy frame's)", flush=True)
+        for k, (a, b) in rows.items():
+            print(f"  {k:44s} {a:.6e} ({a / rows['noisy'][0]:.3f}) | {b:.6e} ({b / rows['noisy'][1]:.3f})", flush=True)
+        res[cfg] = rows
+        if cfg == "3":
+            out = torch.empty_like(noisy)
+            for name, fn in (("run", lambda: dn.run(noisy, first, out=out)), ("run_guided", lambda: dn.run_guided(noisy, var, first, out=out))):
+                rows_t = level_times(dn, fn, 5, args.reps, args.warmup)
+                print(f"  keys off, {name}: pack {rows_t[0][0]:.4f} ms, levels " + ", ".join(f"{m:.4f} [{lo:.4f}, {hi:.4f}]" for m, lo, hi in rows_t[1:]) +
+                      f"; sum {sum(r[0] for r in rows_t):.4f} ms", flush=True)
+                res[f"keys_off_{name}_ms"] = [r[0] for r in rows_t]
+        dn.close(), pr.close(), ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -173,10 +241,13 @@ def main():
     ap.add_argument("--sizes", default="1920,3840")
     ap.add_argument("--json", default=None, help="also write the figures to this file")
     ap.add_argument("--guided", action="store_true", help="the variance-guided mode's sweep and level times instead")
+    ap.add_argument("--chain", action="store_true", help="chain guides and surface keys against first-hit guides instead")
     args = ap.parse_args()
     render.init(0)
     if args.guided:
         return guided(args)
+    if args.chain:
+        return chain(args)
     stream = torch.cuda.Stream()
     result = {"levels": args.levels, "reps": args.reps, "sizes": {}}
     keep = None

@@ -3,7 +3,11 @@
 diffuse-bounce rays from their first hits, NEAREST and ANY, through the BVH and the flat list.  Mrays/s from the library's HIP
 events around the query kernel (rayz_hip_query_sync: kernel_ms), median of --reps launches after a warm-up; next to it the
 render's own BVH segment rate on the same scene (segments / kernel_ms of a low-spp render), the yardstick of DESIGN.md §4.10.
-    python tools/query_bench.py [--reps 5] [--bounce 2000000] [--configs 3,5]"""
+    python tools/query_bench.py [--reps 5] [--bounce 2000000] [--configs 3,5]
+--chain: INSTEAD, the specular-chain G-buffer (rayz_hip_scene_query_camera_chain) on configs 2 and 3 at 1920x1080,
+BVH and flat list: its kernel time beside the first-hit G-buffer's in the same process (both by the library's HIP events, median of
+--reps after a warm-up), the mean segments per pixel and the depth histogram, for max_depth 2, 4 and 8 at the default max_fuzz.
+    python tools/query_bench.py --chain [--reps 5]"""
 import argparse
 import os
 import statistics
@@ -59,13 +63,39 @@ def render_segment_rate(t, spp=16):
     return st.segments / st.kernel_ms / 1e6  # Gsegments/s
 
 
+def chain(args):
+    scenes = {"2": lambda: tracer.randomBouncing(1920, seed=42), "3": lambda: tracer.randomBouncing(1920, -50, 50, seed=42)}
+    for cfg, make in scenes.items():
+        t = make()
+        sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+        p.width, p.height, p.tmin = 1920, 1080, 1e-3
+        ds = render.DeviceScene(sd)
+        print(f"config {cfg}: {sd.n_spheres} spheres, 1920x1080", flush=True)
+        for trav, tname in ((capi.TRAVERSAL_BVH, "bvh"), (capi.TRAVERSAL_LINEAR, "flat")):
+            p.traversal = trav
+            first = timed(lambda: ds.gbuffer(cam, p, outputs=render.QUERY_OUTPUTS), ds, args.reps)
+            print(f"  {tname:4s} first-hit G-buffer {first:8.3f} ms", flush=True)
+            for depth in (2, 4, 8):
+                prm = dict(max_depth=depth, max_fuzz=capi.CHAIN_DEFAULTS["max_fuzz"])
+                ms = timed(lambda: ds.gbuffer(cam, p, chain=prm), ds, args.reps)
+                g = ds.gbuffer(cam, p, chain=prm)
+                st = ds.query_sync()
+                hist = torch.bincount(g.depth.flatten().long(), minlength=depth + 1).tolist()
+                print(f"  {tname:4s} chain max_depth {depth}: {ms:8.3f} ms = x{ms / first:.2f} the first-hit G-buffer; "
+                      f"{st.segments / st.primary_rays:.3f} segments per pixel; pixels by depth {hist}", flush=True)
+        ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bounce", type=int, default=2_000_000)
     ap.add_argument("--configs", default="3,5")
+    ap.add_argument("--chain", action="store_true", help="the chain G-buffer beside the first-hit G-buffer instead")
     args = ap.parse_args()
     render.init(0)
+    if args.chain:
+        return chain(args)
     scenes = {"3": lambda: tracer.randomBouncing(1920, -50, 50, seed=42), "5": lambda: tracer.triangleMesh(1920, 224, seed=1)}
     for cfg in args.configs.split(","):
         t = scenes[cfg]()
