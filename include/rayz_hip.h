@@ -268,6 +268,20 @@ typedef enum RayzScanForm { RAYZ_SCAN_FORM_AUTO = 0, RAYZ_SCAN_FORM_XZ = 1, RAYZ
 int rayz_hip_scene_set_scan_form(RayzScene* scene, uint32_t form);
 int rayz_hip_scene_get_scan_form(RayzScene* scene, uint32_t* form);
 
+/* Primary lists.  The spheres a pixel's camera rays can meet at all are a fact of (scene, camera, pixel): with the
+ * lists ON a flat-list launch first builds every pixel's list (one brute-force f64 pass over the pool, inside the launch's events:
+ * kernel_ms includes it) and resolves each path's camera segment from it, through the same f64 narrow phase that decides behind the
+ * scan, instead of scanning the whole list; a pixel with more than 32 candidates keeps the scan.  The lists take 33 u32 words per pixel of the shard (274 MB at
+ * 1920x1080), kept with the scene, and again with each progressive handle that uses them.  The image and the segments counter
+ * are the same, bit for bit.  A second choice beside the scan form, which keeps its meaning.  It applies to one-shot and progressive
+ * flat-list renders of scenes without triangles (a progressive handle builds its lists once); adaptive passes, ray queries, chain
+ * calls and the BVH kernels are untouched.  AUTO takes the lists from 1,024 spheres and 128 samples per pixel of the launch on (a
+ * progressive handle: of its whole schedule, which shares one build).
+ * _get returns whether a flat-list launch of `samples_per_px` would use them (0 / 1; host only).  Default AUTO. */
+typedef enum RayzPrimaryLists { RAYZ_PRIMARY_LISTS_AUTO = 0, RAYZ_PRIMARY_LISTS_OFF = 1, RAYZ_PRIMARY_LISTS_ON = 2 } RayzPrimaryLists;
+int rayz_hip_scene_set_primary_lists(RayzScene* scene, uint32_t mode);
+int rayz_hip_scene_get_primary_lists(RayzScene* scene, uint32_t samples_per_px, uint32_t* on);
+
 /* Waits for the last render on `scene` and returns its counters. */
 int rayz_hip_scene_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
 

@@ -305,6 +305,16 @@ constexpr uint32_t kScanFormOneRadius = 3;
 // the fixed cost comes to about 230 wave cycles and the saving to about a third of a cycle per slot, a break-even
 // near 700 slots; the gate stands well above that estimate.
 constexpr uint64_t kSetPayoffSlots = 1024;
+// AUTO's gates of the primary lists (rayz_hip_scene_set_primary_lists, primary_lists.hpp): the lists are built and
+// used from this many spheres and this many samples per pixel of a launch on.  Measured at 1920x1080, lists OFF -> ON, kernel ms of one launch (profiles/r15/primary_lists/README.md):
+//   spheres, at 256 spp:  100: 61.8 -> 84.1 | 256: 102.1 -> 120.4 | 485: 141.1 -> 152.5 | 1,027: 241.3 -> 229.2 | 1,936: 361.0 -> 330.1
+//                         | 4,097: 661.9 -> 539.2
+//   spp, 10,003 spheres:  4: 37.2 -> 110.3 | 8: 65.7 -> 133.6 | 16: 115.2 -> 172.5 | 32: 211.1 -> 238.5 | 64: 400.6 -> 380.1
+//   spp, 1,027 spheres:   32: 34.5 -> 40.1 | 256: 241.3 -> 229.2
+// The builder's pass is a fixed cost per launch (83 ms at 10,003 spheres) that the saved camera scans repay per sample: the two
+// rows put the break-even near 50 spp at 10,003 spheres and near 100 spp at 1,027, so 128 loses nowhere from 1,024 spheres on.
+constexpr uint32_t kPrimaryMinSpheres = 1024;
+constexpr uint32_t kPrimaryMinSpp = 128;
 inline uint64_t scan_price(const ScanSlots& n, uint32_t form) {
     const bool xy = form == kScanFormXY;
     return (xy ? 5 : 6) * (n.plane_static + n.bucket) + 7 * (n.plane_movy + n.loose_static) + (xy ? 9 : 8) * n.loose_movy + 12 * n.movg;

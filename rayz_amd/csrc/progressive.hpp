@@ -15,6 +15,7 @@ struct RayzProgressive {
     DevBuf<uint32_t> d_starts;              // the handle's own device copy (the scene's table follows the scene's last render)
     DevBytes acc;                           // shard_pixels running sums (r4 of the precision)
     DevBuf<unsigned long long> counters;    // [0] queue head (cleared per pass), [1..3] summed over the passes
+    PrimaryLists primary;                   // the shard's primary lists: built by the first pass that uses them — the camera and params are the handle's
     uint64_t shard_pixels = 0;
     uint32_t chunks_done = 0;
     uint64_t primary_rays = 0;
@@ -128,7 +129,7 @@ int progressive_step(RayzProgressive* pr, uint32_t min_samples, R* d_preview, vo
         pr->last_stream = stream;
         int experiment = 0; // (the passes' counters are not reported)
         const int rc = trace_window<R>(s, *ctx, b, &pr->cam, &pr->params, use_bvh, pr->starts, pr->d_starts, c0, c1, pr->counters,
-                                       sizeof(unsigned long long), ev0, ev1, stream, experiment);
+                                       sizeof(unsigned long long), ev0, ev1, stream, experiment, nullptr, 0, &pr->primary);
         if (rc != RAYZ_OK) {
             pr->spare.push_back(std::move(ev0));
             pr->spare.push_back(std::move(ev1));

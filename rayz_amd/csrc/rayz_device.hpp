@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "plane_runs.hpp"
+#include "primary_lists.hpp"
 
 namespace rayz_dev {
 
@@ -1368,6 +1369,65 @@ template <class R, int NR> constexpr int flat_waves() { return sizeof(R) == 8 ? 
 #include "trace_kernel_flat.hpp"
 #undef RAYZ_TRACE_KERNEL_NAME
 #undef RAYZ_TRACE_KERNEL_ADAPTIVE
+// .. and the three scan forms once more with the camera segments resolved from the pixels' primary lists: kernels
+// of their own names, which the ISA tests of the kernels above do not count (tests/test_primary_lists_isa.py holds these).
+// Their argument block is the trace kernels' with the lists behind it (a block of its own: a field more in TraceArgs changes
+// every other kernel's code object).
+template <class R> struct PrimaryTraceArgs : TraceArgs<R> {
+    const uint32_t* primary; // the shard's primary lists, word j of local pixel i at [j · shard_pixels + i]
+};
+#define RAYZ_TRACE_KERNEL_PRIMARY true
+#define RAYZ_TRACE_KERNEL_ARGS PrimaryTraceArgs<R>
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#define RAYZ_TRACE_KERNEL_NAME primary_xz_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#define RAYZ_TRACE_KERNEL_BASIS kBasisXY
+#define RAYZ_TRACE_KERNEL_NAME primary_xy_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#define RAYZ_TRACE_KERNEL_SETS true
+#define RAYZ_TRACE_KERNEL_NAME primary_one_radius_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_SETS
+#undef RAYZ_TRACE_KERNEL_BASIS
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE
+#undef RAYZ_TRACE_KERNEL_ARGS
+#undef RAYZ_TRACE_KERNEL_PRIMARY
+
+// ---- the primary lists' builder -----------------------------------------------------------------------------
+// One lane per local pixel of the shard (place_item's numbering, rows as they come): every sphere of the pool, by its slot, through
+// rayz_primary::beam_may_hit in f64; the slots that pass are the pixel's list, kNoList its count when more than kListK do.  The
+// loop is wave-uniform (the sphere's record arrives through scalar loads); `real_slots` names the slots that hold a sphere, in
+// slot order: a pad's record is no sphere and may never become a candidate.
+struct PrimaryArgs {
+    rayz_primary::BeamCamera cam;
+    const d4* slot64;
+    const uint32_t* real_slots;
+    uint32_t* lists; // [(kListK + 1) · shard_pixels]
+    uint32_t n_real, width, tile_rows, shard_index, shard_count, shard_pixels;
+};
+__global__ __launch_bounds__(256) void primary_lists_kernel(const PrimaryArgs A) {
+    const uint32_t lane_px = blockIdx.x * 256u + threadIdx.x;
+    const bool live = lane_px < A.shard_pixels;
+    const uint32_t lp = live ? lane_px : A.shard_pixels - 1u; // (the last block's spare lanes repeat the last pixel and store nothing)
+    const uint32_t lr = lp / A.width, px = lp - lr * A.width;
+    const uint32_t tl = lr / A.tile_rows, within = lr - tl * A.tile_rows;
+    const uint32_t py = (tl * A.shard_count + A.shard_index) * A.tile_rows + within;
+    const rayz_primary::PixelBeam beam = rayz_primary::pixel_beam(A.cam, px, py);
+    uint32_t n = 0;
+    for (uint32_t i = 0; i < A.n_real; ++i) {
+        const uint32_t slot = A.real_slots[i];
+        const d4 c4 = A.slot64[2 * slot], v4 = A.slot64[2 * slot + 1];
+        const double c[3] = {c4.x, c4.y, c4.z}, v[3] = {v4.x, v4.y, v4.z};
+        if (rayz_primary::beam_may_hit(beam, c, v, __builtin_sqrt(c4.w))) {
+            if (live && n < rayz_primary::kListK) A.lists[(size_t)(n + 1u) * A.shard_pixels + lp] = slot;
+            ++n;
+        }
+    }
+    if (live) A.lists[lp] = n <= rayz_primary::kListK ? n : rayz_primary::kNoList;
+}
 
 // ---- BVH traversal (src/hit.zig:181-216) ---------------------------------------------------------------
 // The reference recurses left-then-right with a shrinking tmax.  Here each lane walks the same tree with a small

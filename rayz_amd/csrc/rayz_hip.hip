@@ -47,8 +47,10 @@ template <class R> struct SceneBuffers {
 struct NarrowBuffers {
     DevBuf<d4> slot64;
     DevBuf<uint32_t> slot_pool;
+    DevBuf<uint32_t> real_slots; // the slots that hold a sphere (not a pad), ascending: what primary_lists_kernel loops over
     DevBuf<d4> bvh_sph64; // leaf order (BVH traversal only)
     uint32_t ns_pad = 0, ny_pad = 0, ng_pad = 0;
+    uint32_t n_real = 0; // entries of real_slots
     // slot order of the static (0) and mov-Y (1) classes: plane runs first (rayz_plane::plan_runs), then the loose spheres
     std::vector<PlaneRun> runs[2];
     std::vector<std::vector<uint32_t>> run_members[2]; // pool indices of each run
@@ -64,6 +66,13 @@ struct NarrowBuffers {
     std::vector<rayz_plane::ClassSet> sets[2];
     std::vector<uint32_t> run_old_first[2], bucket_old_first;
     bool planned = false, ready = false, bvh_ready = false;
+};
+
+// A shard's primary lists (primary_lists.hpp) and whether they hold the lists of their owner's camera and params: a
+// scene's are rebuilt by every one-shot render that uses them, a progressive handle's are built by its first pass.
+struct PrimaryLists {
+    DevBuf<uint32_t> buf;
+    bool built = false;
 };
 
 uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
@@ -193,6 +202,8 @@ struct RayzScene {
     bool rendered = false, last_bvh = false;
     int last_experiment = 0; // the last render's BvhLaunchPlan::experiment (0: a product kernel)
     uint32_t scan_form = rayz_plane::kScanFormAuto; // rayz_hip_scene_set_scan_form: auto = the layout's own (narrow.scan_form)
+    uint32_t primary_mode = RAYZ_PRIMARY_LISTS_AUTO; // rayz_hip_scene_set_primary_lists
+    PrimaryLists primary;                            // the one-shot renders' lists: rebuilt by every render that uses them
     RayzRenderStats last{};
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
     DevBuf<unsigned long long> q_counters; // [0] batch head, [1] segments (chain calls), [2] node tests, [3] sphere tests, [31] LDS flag,
@@ -280,7 +291,9 @@ int upload_narrow_body(RayzScene* s) {
     const size_t slots = (size_t)nb.ns_pad + nb.ny_pad + nb.ng_pad;
     std::vector<d4> slot64(2 * slots, d4{0, 0, 0, 0});
     std::vector<uint32_t> slot_pool(slots, 0u);
+    std::vector<uint32_t> real_slots;
     auto place = [&](size_t slot, uint32_t pool) {
+        real_slots.push_back((uint32_t)slot);
         const RayzSphere& q = s->spheres[pool];
         slot64[2 * slot] = d4{q.center[0], q.center[1], q.center[2], q.radius * q.radius}; // radius * radius in f64, src/geom.zig:45
         slot64[2 * slot + 1] = d4{q.velocity[0], q.velocity[1], q.velocity[2], 0.0};
@@ -295,6 +308,9 @@ int upload_narrow_body(RayzScene* s) {
     for (size_t k = 0; k < s->cls[2].size(); ++k) place((size_t)nb.ns_pad + nb.ny_pad + k, s->cls[2][k]);
     HIP_TRY(nb.slot64.upload(slot64));
     HIP_TRY(nb.slot_pool.upload(slot_pool));
+    std::sort(real_slots.begin(), real_slots.end());
+    HIP_TRY(nb.real_slots.upload(real_slots));
+    nb.n_real = (uint32_t)real_slots.size();
     nb.ready = true;
     return RAYZ_OK;
 }
@@ -499,6 +515,14 @@ uint32_t scene_scan_form(RayzScene* s) {
         for (const rayz_plane::ClassSet& t : sets) set_slots += t.count;
     if (s->narrow.scan_form == rayz_plane::kScanFormXY && set_slots >= rayz_plane::kSetPayoffSlots) return rayz_plane::kScanFormOneRadius;
     return s->narrow.scan_form;
+}
+
+// Whether a flat-list launch of `spp` samples per pixel resolves its camera segments from primary lists: never
+// with triangles (scan_triangles has no list) or without spheres; AUTO from kPrimaryMinSpheres spheres and kPrimaryMinSpp samples on.
+bool scene_primary_lists(const RayzScene* s, uint32_t spp) {
+    if (s->primary_mode == RAYZ_PRIMARY_LISTS_OFF || !s->triangles.empty() || s->spheres.empty()) return false;
+    if (s->primary_mode == RAYZ_PRIMARY_LISTS_ON) return true;
+    return s->spheres.size() >= rayz_plane::kPrimaryMinSpheres && spp >= rayz_plane::kPrimaryMinSpp;
 }
 
 void ensure_bvh(RayzScene* s) {
@@ -974,7 +998,7 @@ template <class R>
 int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
                  bool use_bvh, const std::vector<uint32_t>& starts, const uint32_t* d_starts, uint32_t c0, uint32_t c1,
                  unsigned long long* counters, size_t reset_bytes, hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream,
-                 int& experiment, const uint32_t* active_list = nullptr, uint32_t n_active = 0) {
+                 int& experiment, const uint32_t* active_list = nullptr, uint32_t n_active = 0, PrimaryLists* lists = nullptr) {
     typedef typename VecOf<R>::type r4;
     const ShardGeometry shard = shard_geometry(p);
     const uint64_t shard_pixels64 = (uint64_t)shard.rows * p->width;
@@ -1025,6 +1049,17 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     if (!active_list && !use_bvh && scene_scan_form(s) == rayz_plane::kScanFormXY) plan.kernel = flat_xy_kernel<R, 1>;
     // .. and the kernel that scans the one-radius sets in their own two-field loop: the XY basis, the same candidates and more
     if (!active_list && !use_bvh && scene_scan_form(s) == rayz_plane::kScanFormOneRadius) plan.kernel = flat_one_radius_kernel<R, 1>;
+    // .. and each of the three with the camera segments from the pixels' primary lists, where the scene takes them (`lists`: the
+    // caller's, built below inside the launch's events unless they hold this camera's already)
+    const bool primary = lists && !active_list && !use_bvh && scene_primary_lists(s, p->samples_per_px);
+    if (primary) {
+        const size_t words = (size_t)(rayz_primary::kListK + 1u) * (size_t)shard_pixels64;
+        if (words > lists->buf.capacity()) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(lists->buf.alloc(words));
+            lists->built = false;
+        }
+    }
     plan.block = 256;
     plan.items_per_lane = 1;
     if (use_bvh) {
@@ -1054,7 +1089,38 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
 
     HIP_TRY(hipMemsetAsync(counters, 0, reset_bytes, stream));
     HIP_TRY(hipEventRecord(ev0, stream));
-    hipLaunchKernelGGL(plan.kernel, dim3((uint32_t)grid), dim3(plan.block), L.lds, stream, A);
+    if (primary && !lists->built) {
+        PrimaryArgs B{};
+        for (int k = 0; k < 3; ++k) {
+            B.cam.from[k] = cam->look_from[k], B.cam.du[k] = cam->px_du[k], B.cam.dv[k] = cam->px_dv[k];
+            B.cam.pxo[k] = cam->px_origin[k], B.cam.defu[k] = cam->defocus_u[k], B.cam.defv[k] = cam->defocus_v[k];
+        }
+        B.cam.defocus = cam->defocus ? 1u : 0u;
+        B.slot64 = s->narrow.slot64, B.real_slots = s->narrow.real_slots, B.lists = lists->buf;
+        B.n_real = s->narrow.n_real;
+        B.width = p->width, B.tile_rows = shard.tile_rows, B.shard_index = p->shard_index, B.shard_count = shard.shard_count;
+        B.shard_pixels = A.shard_pixels;
+        hipLaunchKernelGGL(primary_lists_kernel, dim3((uint32_t)((shard_pixels64 + 255) / 256)), dim3(256), 0, stream, B);
+        HIP_TRY(hipGetLastError());
+        lists->built = true;
+    }
+    if (primary) { // the same launch geometry (the flat kernels have no dynamic LDS), the lists behind the arguments
+        PrimaryTraceArgs<R> P{};
+        static_cast<TraceArgs<R>&>(P) = A;
+        P.primary = lists->buf;
+        const uint32_t form = scene_scan_form(s);
+        void (*kernel)(const PrimaryTraceArgs<R>) = form == rayz_plane::kScanFormOneRadius ? primary_one_radius_kernel<R, 1>
+                                                    : form == rayz_plane::kScanFormXY      ? primary_xy_kernel<R, 1>
+                                                                                           : primary_xz_kernel<R, 1>;
+        // its own occupancy (the persistent grid is one resident wave set of THIS kernel), asked for once per kernel
+        static int occupancy[4] = {0, 0, 0, 0}; // by scan form, of precision R; 0: not asked yet
+        int& blocks_per_cu = occupancy[form & 3u];
+        if (blocks_per_cu == 0) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, plan.block, 0));
+        grid = std::min<uint64_t>((uint64_t)ctx.num_cu * std::max(1, blocks_per_cu), want);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(plan.block), 0, stream, P);
+    } else {
+        hipLaunchKernelGGL(plan.kernel, dim3((uint32_t)grid), dim3(plan.block), L.lds, stream, A);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, stream));
     return RAYZ_OK;
@@ -1102,8 +1168,9 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         HIP_TRY(s->ev0.create());
         HIP_TRY(s->ev1.create());
     }
+    s->primary.built = false; // (no cache across renders: this camera's lists are built by this launch)
     RAYZ_TRY(trace_window<R>(s, ctx, b, cam, p, use_bvh, starts, s->chunk_start, 0, chunks_per_px, s->counters,
-                             32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, s->last_experiment));
+                             32 * sizeof(unsigned long long), s->ev0, s->ev1, stream, s->last_experiment, nullptr, 0, &s->primary));
     hipLaunchKernelGGL(resolve_kernel<R>, dim3((uint32_t)((shard_pixels64 + 255) / 256)), dim3(256), 0, stream,
                        (const r4*)s->partial.get(), d_out, (uint32_t)shard_pixels64, chunks_per_px, p->samples_per_px);
     HIP_TRY(hipGetLastError());
@@ -1375,6 +1442,23 @@ int rayz_hip_scene_get_scan_form(RayzScene* s, uint32_t* form) {
     return guarded([&] {
         if (!s || !form) return fail(RAYZ_ERR_BAD_ARG, "null argument");
         *form = scene_scan_form(s);
+        return (int)RAYZ_OK;
+    });
+}
+
+int rayz_hip_scene_set_primary_lists(RayzScene* s, uint32_t mode) {
+    return guarded([&] {
+        if (!s) return fail(RAYZ_ERR_BAD_ARG, "null scene");
+        if (mode > RAYZ_PRIMARY_LISTS_ON) return fail(RAYZ_ERR_BAD_ARG, "bad primary-lists mode %u", mode);
+        s->primary_mode = mode;
+        return (int)RAYZ_OK;
+    });
+}
+
+int rayz_hip_scene_get_primary_lists(RayzScene* s, uint32_t samples_per_px, uint32_t* on) {
+    return guarded([&] {
+        if (!s || !on) return fail(RAYZ_ERR_BAD_ARG, "null argument");
+        *on = scene_primary_lists(s, samples_per_px) ? 1u : 0u;
         return (int)RAYZ_OK;
     });
 }

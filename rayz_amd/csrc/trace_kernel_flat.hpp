@@ -7,7 +7,19 @@
 // of that name is a product kernel; the adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared
 // body FUNCTION: handing the kernel's argument block to it changes the product kernel's register allocation; compiled twice,
 // trace_kernel's ISA is what it was.  No include guard.
+// RAYZ_TRACE_KERNEL_PRIMARY true — three more times, as primary_xz_kernel, primary_xy_kernel and primary_one_radius_kernel: the
+// three scan forms with each path's CAMERA segment resolved from its pixel's primary list (primary_lists.hpp)
+// instead of a scan.  An iteration of the loop is then either a LIST phase — taken while any lane of the wave holds a fresh path
+// (seg == 0) on a pixel that has a list: those lanes alone take their listed slots through narrow_eval, count the segment and
+// shade; a path that ends there (sky, absorption, depth) is replaced at the top of the next iteration, the chunk retired and the
+// next item popped as ever — or a SCAN phase as before, once every live lane's next segment needs the scan (a later segment,
+// or the camera segment of a pixel without a list).  The refill therefore repeats, wave-cooperative, until every lane holds a
+// path that needs a scan or the queue is drained; nothing else differs: same streams, same sums, same segments counter.
+#ifdef RAYZ_TRACE_KERNEL_ARGS
+template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const RAYZ_TRACE_KERNEL_ARGS A) {
+#else
 template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
+#endif
     constexpr bool kAdaptive = RAYZ_TRACE_KERNEL_ADAPTIVE; // work items over the active list (place_item)
 #ifdef RAYZ_TRACE_KERNEL_BASIS
     constexpr int kBasis = RAYZ_TRACE_KERNEL_BASIS; // the reject test's basis (RayBasis)
@@ -18,6 +30,11 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     constexpr bool kSets = RAYZ_TRACE_KERNEL_SETS; // the one-radius sets in their own loop (scan_plane_class)
 #else
     constexpr bool kSets = false;
+#endif
+#ifdef RAYZ_TRACE_KERNEL_PRIMARY
+    constexpr bool kPrimary = RAYZ_TRACE_KERNEL_PRIMARY; // camera segments from the pixels' primary lists
+#else
+    constexpr bool kPrimary = false;
 #endif
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     PathState<R> p[NR];
@@ -52,21 +69,54 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
             scan_begin<R, NR>(ray[r], p[r].o, p[r].d, ud[r], p[r].time);
         }
         RAYZ_FPROF(1)
+        // ---- list phase (kPrimary): fresh paths on pixels with a list; the scan waits until the wave has none ----
+        bool listed[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) listed[r] = false;
+        bool list_phase = false;
+        if constexpr (kPrimary) {
+            uint32_t lp[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                lp[r] = 0u;
+                if (p[r].alive && p[r].seg == 0u) {
+                    lp[r] = p[r].item - (p[r].item / A.shard_pixels) * A.shard_pixels; // the local pixel (place_item, rows as they come)
+                    listed[r] = A.primary[lp[r]] != rayz_primary::kNoList;
+                }
+                list_phase = list_phase || listed[r];
+            }
+            list_phase = __ballot(list_phase) != 0ull;
+            if (list_phase) {
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    if (listed[r]) { // scan_begin's tbest, ibest and inv_a2; every listed slot decided by the narrow phase
+                        const uint32_t count = A.primary[lp[r]];
+                        for (uint32_t j = 0; j < count; ++j) {
+                            const uint32_t slot = A.primary[(size_t)(j + 1u) * A.shard_pixels + lp[r]];
+                            narrow_eval<R>(A.sc.slot64[2 * slot], A.sc.slot64[2 * slot + 1], (int)A.sc.slot_pool[slot], ray[r].o, ray[r].d,
+                                           ray[r].time, ray[r].inv_a2, A.tmin, ray[r].tbest, ray[r].ibest);
+                        }
+                    }
+                RAYZ_FPROF(0) // (measurement builds: the list phases count as refill)
+            }
+        }
+        if (!list_phase) {
 #ifdef RAYZ_FLAT_PROFILE
-        fiters++;
-        scan_sphere_classes<R, NR, kSets>(A.sc, ray, A.tmin);
-        RAYZ_FPROF(2)
-        narrow_flush<R, NR>(A.sc, ray, A.tmin);
-        scan_triangles<R, NR>(A.sc, ray, A.tmin);
-        RAYZ_FPROF(3)
+            fiters++;
+            scan_sphere_classes<R, NR, kSets>(A.sc, ray, A.tmin);
+            RAYZ_FPROF(2)
+            narrow_flush<R, NR>(A.sc, ray, A.tmin);
+            scan_triangles<R, NR>(A.sc, ray, A.tmin);
+            RAYZ_FPROF(3)
 #else
-        scan_spheres<R, NR, kSets>(A.sc, ray, A.tmin);
+            scan_spheres<R, NR, kSets>(A.sc, ray, A.tmin);
 #endif
+        }
 
         // ---- shade ----
 #pragma unroll
         for (int r = 0; r < NR; ++r)
-            if (p[r].alive) {
+            if (p[r].alive && (!list_phase || listed[r])) {
                 nseg++;
                 p[r].seg++;
                 bool cont = shade<R>(A.sc, p[r].g, p[r].o, p[r].d, ud[r], p[r].time, ray[r].tbest, ray[r].ibest, p[r].thr,

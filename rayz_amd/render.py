@@ -247,6 +247,17 @@ class DeviceScene(_Handle):
     def scan_form(self, form: int) -> None:
         capi.check(self._lib, self._lib.rayz_hip_scene_set_scan_form(self._h, form), "rayz_hip_scene_set_scan_form")
 
+    def set_primary_lists(self, mode: int) -> None:
+        """capi.PRIMARY_LISTS_AUTO, _OFF or _ON: whether flat-list renders resolve each path's camera segment from its pixel's
+        primary list instead of a scan; the frame is the same either way."""
+        capi.check(self._lib, self._lib.rayz_hip_scene_set_primary_lists(self._h, mode), "rayz_hip_scene_set_primary_lists")
+
+    def uses_primary_lists(self, samples_per_px: int) -> bool:
+        """Whether a flat-list launch of that many samples per pixel would use the lists (what AUTO decides, if nothing was set)."""
+        on = C.c_uint32()
+        capi.check(self._lib, self._lib.rayz_hip_scene_get_primary_lists(self._h, samples_per_px, C.byref(on)), "rayz_hip_scene_get_primary_lists")
+        return bool(on.value)
+
     # ---- ray queries (`findHit`, include/rayz_hip.h: rayz_hip_scene_query*) ----
     def query(self, rays, tmin: float = 1e-3, kind: str = "nearest", traversal: int = capi.TRAVERSAL_AUTO,
               outputs=QUERY_OUTPUTS, stream: int = 0) -> "QueryResult":
