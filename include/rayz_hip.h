@@ -779,6 +779,57 @@ int rayz_hip_denoiser_set_keys(RayzDenoiser* dn, const uint32_t* d_keys_or_null)
 int rayz_hip_denoiser_timing(RayzDenoiser* dn, uint32_t* levels_or_null, float* ms_or_null, uint32_t capacity);
 int rayz_hip_denoiser_destroy(RayzDenoiser* dn);
 
+/* ---- guided upscaling: a low-resolution frame under a full-size G-buffer ---------------------------
+ * BUILD-DEFINED.  A frame traced at 1/f of the resolution in each direction (f = 2, 3 or 4; the camera of
+ * render.lowres_camera: every low-resolution pixel sits at the centre of its f x f block of full pixels) is rebuilt at full size:
+ * every full pixel takes the 2x2 low-resolution pixels around it, weighs each by its bilinear weight times the GUIDE weight of
+ * the denoiser's tap — the full pixel's normal and point from `gbuffer_hi` against the low-resolution pixel's from `gbuffer_lo`;
+ * background never mixes with a hit —, interpolates the colour DEMODULATED by the low-resolution albedo and multiplies its own
+ * full-size albedo back in, so texture detail comes back at full resolution and no colour crosses a silhouette.  A pixel whose
+ * 2x2 footprint holds nothing it may mix with (stage 1) tries the 4x4 footprint with the guide weight alone; failing that
+ * (stage 2) it takes the nearest low-resolution pixel's raw colour.  The arithmetic is a contract (§4.20, the rules of §4.11),
+ * restated bit for bit by tests/upscale_mirror.cpp.  Added in ABI 5 (additive: no existing symbol or struct changed).
+ * Limits of this version: whole frames, f32 only; the full size is an exact multiple of the factor; surface keys are not used (a
+ * chain G-buffer is accepted as plain guides). */
+typedef struct RayzUpscaler RayzUpscaler; /* opaque: the packed low-resolution records (80 bytes per low-resolution pixel) */
+
+#define RAYZ_UPSCALE_FORM_AUTO 0u   /* the build's choice */
+#define RAYZ_UPSCALE_FORM_DIRECT 1u /* the 2x2 footprint read through L1 / L2: the only form this version has */
+
+typedef struct RayzUpscaleParams {
+    uint32_t factor;            /* 2..4, and the handle's */
+    uint32_t normal_power_log2; /* as RayzDenoiseParams */
+    uint32_t flags;             /* RAYZ_DENOISE_ALBEDO or 0 */
+    uint32_t form;              /* RAYZ_UPSCALE_FORM_*: how the taps are fetched, never what they give */
+    double sigma_plane;         /* as RayzDenoiseParams */
+} RayzUpscaleParams;
+
+/* `width` x `height` is the FULL frame.  device as rayz_hip_denoiser_create.  RAYZ_ERR_BAD_ARG (before any HIP call): a factor
+ * outside 2..4, a zero size or one that is no multiple of the factor, width*height > RAYZ_DENOISE_MAX_PIXELS. */
+int rayz_hip_upscaler_create(int device, uint32_t width, uint32_t height, uint32_t factor, RayzUpscaler** out);
+/* With (h, w) = (height, width) / factor.  d_rgb_lo: DEVICE memory, h*w*3 floats, the low-resolution frame; d_var_rgb_lo_or_null:
+ * h*w*3 floats, the variance of each channel of its pixel means (rayz_hip_progressive_noise_rgb, or the variance a
+ * rayz_hip_temporal_step writes).  `gbuffer_lo`, `gbuffer_hi`: index, normal and
+ * point are required, albedo with RAYZ_DENOISE_ALBEDO; F32 camera queries at h x w and at height x width.  d_rgb_out:
+ * height*width*3 floats.  d_var_rgb_out_or_null: height*width*3 floats, each full pixel's MARGINAL variance per channel
+ * (neighbouring full pixels share taps: their errors are correlated, §4.20); 2^32 where stage 2 had no estimate; needs
+ * d_var_rgb_lo.  d_stage_out_or_null: height*width bytes, the stage (0, 1 or 2) that produced each pixel.  No output may overlap
+ * an input or another output.  `params` is required (the factor has no default).  Asynchronous on `hip_stream`, one run in flight
+ * per handle, as rayz_hip_denoiser_run.
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): params NULL, a factor outside 2..4,
+ * normal_power_log2 > 16, unknown flag bits, a form this build does not have, a sigma_plane that is not positive (NaN included),
+ * a missing required pointer, a G-buffer without index, normal or point, RAYZ_DENOISE_ALBEDO without the albedo of both
+ * G-buffers, a variance output without the variance input, an output equal to an input or another output.  RAYZ_ERR_STATE: a
+ * bad handle.  RAYZ_ERR_BAD_ARG behind it: a factor that is not the handle's, an output overlapping an input. */
+int rayz_hip_upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, const float* d_rgb_lo,
+                          const float* d_var_rgb_lo_or_null, const RayzQueryOutputs* gbuffer_lo,
+                          const RayzQueryOutputs* gbuffer_hi, float* d_rgb_out, float* d_var_rgb_out_or_null,
+                          uint8_t* d_stage_out_or_null, void* hip_stream);
+/* Waits for the handle's last run and returns its HIP-event times in ms: the pack launches, the reconstruction launch.
+ * RAYZ_ERR_STATE before any run. */
+int rayz_hip_upscaler_timing(RayzUpscaler* up, float* pack_ms_or_null, float* upscale_ms_or_null);
+int rayz_hip_upscaler_destroy(RayzUpscaler* up);
+
 /* ---- temporal accumulation: reproject the history across camera moves -----------------------------
  * BUILD-DEFINED: the temporal stage of SVGF (Schied et al. 2017) for a caller that keeps a scene in device memory and moves the
  * camera.  A step takes the current frame (WHOLE f32 frame in DEVICE memory), its per-channel variance

@@ -46,6 +46,9 @@ DENOISE_GUIDED_DEFAULTS = {"levels": 5, "normal_power_log2": 6, "flags": DENOISE
                            "var_floor": 1e-4}
 NOISE_DEFAULTS = {"rel_error": 0.05, "mean_floor": 0.02}
 ADAPTIVE_DEFAULT_MIN_CHUNKS = 4
+UPSCALE_FORM_AUTO, UPSCALE_FORM_DIRECT = 0, 1
+# the denoiser's guide parameters; flags 0: demodulating by the low-resolution albedo measured far worse than not
+UPSCALE_DEFAULTS = {"normal_power_log2": 6, "flags": 0, "form": UPSCALE_FORM_AUTO, "sigma_plane": 0.25}
 TEMPORAL_DEFAULTS = {"alpha_min": 0.05, "n_max": 65536.0, "normal_cos_min": 0.9, "max_rel_dist": 0.05}  # provisional
 TEMPORAL_MOMENTS_DEFAULTS = {"w2_max": 0.25, "min_taps": 4.0}  # provisional
 
@@ -122,6 +125,11 @@ class DenoiseGuidedParams(C.Structure):
                 ("sigma_color", C.c_double), ("sigma_plane", C.c_double), ("var_floor", C.c_double)]
 
 
+class UpscaleParams(C.Structure):
+    _fields_ = [("factor", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("form", C.c_uint32),
+                ("sigma_plane", C.c_double)]
+
+
 class NoiseParams(C.Structure):
     _fields_ = [("rel_error", C.c_double), ("mean_floor", C.c_double)]
 
@@ -149,6 +157,7 @@ assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
 assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof(DenoiseParams) == 32
 assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
+assert C.sizeof(UpscaleParams) == 24
 assert C.sizeof(ChainParams) == 16 and C.sizeof(ChainOutputs) == 24
 assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32 and C.sizeof(TemporalMomentsParams) == 16
 
@@ -255,6 +264,12 @@ PROTOTYPES = [
     ("rayz_hip_denoiser_set_keys", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rayz_hip_denoiser_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32]),
     ("rayz_hip_denoiser_destroy", C.c_int, [C.c_void_p]),
+    ("rayz_hip_upscaler_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("rayz_hip_upscaler_run", C.c_int,
+     [C.c_void_p, C.POINTER(UpscaleParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p,
+      C.c_void_p, C.c_void_p]),
+    ("rayz_hip_upscaler_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("rayz_hip_upscaler_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_temporal_step", C.c_int,
      [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(CameraDesc), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p,

@@ -82,6 +82,31 @@ struct DnTap { // the three records of a pixel
     dn4 a, b, c;
 };
 
+// The guide half of a tap, which every filter that weighs a pixel q by the guides of a pixel p shares (the à-trous levels below, the
+// upscaler's taps in upscale.hpp): the records' {n, bg} and {P, ·} of the centre (pa, pb) and of the tap (qa, qb).  false: the tap is
+// skipped; true: g = 1 between two background pixels, else wn·wz.
+__device__ __forceinline__ bool dn_guide(const dn4 pa, const dn4 pb, const dn4 qa, const dn4 qb, const uint32_t normal_power_log2,
+                                         const float sp2, float& g) {
+    const bool bgp = pa.w != 0.0f, bgq = qa.w != 0.0f;
+    g = 1.0f;
+    if (bgp || bgq) {
+        if (!(bgp && bgq)) return false; // background never mixes with a hit: the tap is skipped, as one outside the frame is
+    } else {
+        float wn = dn_max0(dn_dot(pa.x, pa.y, pa.z, qa.x, qa.y, qa.z));
+        for (uint32_t k = 0; k < normal_power_log2; ++k) wn = wn * wn;
+        const float vx = qb.x - pb.x, vy = qb.y - pb.y, vz = qb.z - pb.z;
+        const float d2 = dn_dot(vx, vy, vz, vx, vy, vz);
+        const float pl = dn_dot(pa.x, pa.y, pa.z, vx, vy, vz);
+        float wz = 1.0f;
+        if (d2 != 0.0f) {
+            const float u = dn_max0(1.0f - (pl * pl) / (sp2 * d2));
+            wz = u * u;
+        }
+        g = wn * wz;
+    }
+    return true;
+}
+
 // One tap: centre pixel (pa, pb, pc), tap pixel (qa, qb, qc), h = k[i]·k[j].  A tap of another surface key is skipped (§4.18); then
 // the guides either skip the tap or give it g = wn·wz;
 // the colour weight is wc = 1 / (1 + de2·cl / sc2), or in the guided mode 1 / (1 + de2 / den) with den = sc2·(gv + vf) of the
@@ -90,23 +115,8 @@ template <bool GUIDED>
 __device__ __forceinline__ void dn_tap(const dn4 pa, const dn4 pb, const dn4 pc, const dn4 qa, const dn4 qb, const dn4 qc, const float h,
                                        const float den, const DenoiseArgs& a, DnAcc& acc) {
     if (dn_key(pb) != dn_key(qb)) return;
-    const bool bgp = pa.w != 0.0f, bgq = qa.w != 0.0f;
-    float g = 1.0f;
-    if (bgp || bgq) {
-        if (!(bgp && bgq)) return; // background never mixes with a hit: the tap is skipped, as one outside the frame is
-    } else {
-        float wn = dn_max0(dn_dot(pa.x, pa.y, pa.z, qa.x, qa.y, qa.z));
-        for (uint32_t k = 0; k < a.normal_power_log2; ++k) wn = wn * wn;
-        const float vx = qb.x - pb.x, vy = qb.y - pb.y, vz = qb.z - pb.z;
-        const float d2 = dn_dot(vx, vy, vz, vx, vy, vz);
-        const float pl = dn_dot(pa.x, pa.y, pa.z, vx, vy, vz);
-        float wz = 1.0f;
-        if (d2 != 0.0f) {
-            const float u = dn_max0(1.0f - (pl * pl) / (a.sp2 * d2));
-            wz = u * u;
-        }
-        g = wn * wz;
-    }
+    float g;
+    if (!dn_guide(pa, pb, qa, qb, a.normal_power_log2, a.sp2, g)) return;
     const float ex = qc.x - pc.x, ey = qc.y - pc.y, ez = qc.z - pc.z;
     const float de2 = dn_dot(ex, ey, ez, ex, ey, ez);
     const float wc = GUIDED ? 1.0f / (1.0f + de2 / den) : 1.0f / (1.0f + (de2 * a.cl) / a.sc2);

@@ -14,6 +14,7 @@
 #include "chain_kernel.hpp"
 #include "bvh_build.hpp"
 #include "denoise.hpp"
+#include "upscale.hpp"
 #include "temporal_kernel.hpp"
 #include "temporal_moments_kernel.hpp"
 #include "temporal_feedback_kernel.hpp"
@@ -1523,5 +1524,6 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "chain.hpp"
 #include "frame_handle.hpp"
 #include "denoiser.hpp"
+#include "upscaler.hpp"
 #include "temporal.hpp"
 #include "temporal_moments.hpp"

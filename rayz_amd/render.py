@@ -663,6 +663,110 @@ class Denoiser(_Handle):
         return ms[0], [ms[1 + l] for l in range(n.value)]
 
 
+def lowres_camera(camera: capi.CameraDesc, factor: int) -> capi.CameraDesc:
+    """The camera of a frame traced at 1/`factor` of the resolution in each direction: every low-resolution pixel sits at the centre
+    of its factor x factor block of `camera`'s pixels.  `px_du` and `px_dv` are multiplied by the factor and
+    `px_origin` — the centre of pixel (0, 0) — moves by ((factor - 1) / 2)·(px_du + px_dv); everything else is unchanged."""
+    f = int(factor)
+    if f < 1:
+        raise ValueError(f"factor {factor}: must be a positive integer")
+    cam = capi.CameraDesc.from_buffer_copy(camera)
+    for k in range(3):
+        cam.px_du[k] = camera.px_du[k] * f
+        cam.px_dv[k] = camera.px_dv[k] * f
+        cam.px_origin[k] = camera.px_origin[k] + 0.5 * (f - 1) * (camera.px_du[k] + camera.px_dv[k])
+    return cam
+
+
+def lowres_params(params: capi.RenderParams, factor: int) -> capi.RenderParams:
+    """`params` for the frame `lowres_camera` looks at: width and height divided by the factor.  Raises unless both divide exactly,
+    and on a shard other than the whole frame (rows of a shard are not image neighbours)."""
+    f = int(factor)
+    if f < 1:
+        raise ValueError(f"factor {factor}: must be a positive integer")
+    if params.width % f or params.height % f or not params.width or not params.height:
+        raise ValueError(f"frame {params.width}x{params.height} is not a multiple of the factor {f} in both directions")
+    if params.shard_count > 1 or params.shard_index:
+        raise ValueError(f"shard {params.shard_index} of {params.shard_count}: a low-resolution frame is a whole frame")
+    p = capi.RenderParams.from_buffer_copy(params)
+    p.width, p.height = params.width // f, params.height // f
+    return p
+
+
+class Upscaler(_Handle):
+    """Guided upscaling (`rayz_hip_upscaler_*`): rebuilds a `width` x `height` float32 frame from one traced at
+    1/`factor` of the resolution in each direction (`lowres_camera`, `lowres_params`), under the full-size G-buffer.  `device` None:
+    the default device of init()."""
+
+    _destroy = "rayz_hip_upscaler_destroy"  # (waits for the handle's last run)
+
+    def __init__(self, width: int, height: int, factor: int, device: int | None = None):
+        self._lib = capi.load()
+        self._h = C.c_void_p()
+        self.width, self.height, self.factor = int(width), int(height), int(factor)
+        capi.check(self._lib, self._lib.rayz_hip_upscaler_create(-1 if device is None else device, self.width, self.height, self.factor,
+                                                                 C.byref(self._h)), "rayz_hip_upscaler_create")
+        self._device = device if device is not None else _default_device
+        self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
+
+    def run(self, rgb_lo, gbuffer_lo: "QueryResult", gbuffer_hi: "QueryResult", var_rgb=None, out=None, var_out=None, stage=False,
+            stream: int = 0, **params):
+        """`rgb_lo`: (height / factor, width / factor, 3) float32 on the handle's device; `gbuffer_lo`, `gbuffer_hi`: float32 camera
+        queries of the low-resolution and of the full frame (index, normal, point, and albedo with flags=DENOISE_ALBEDO).  Returns `out` (default: a new (height, width, 3) tensor).  With `var_rgb` — the per-channel variance of `rgb_lo`'s
+        pixel means, shaped as it — the call returns (out, var): the per-channel MARGINAL variance of every full pixel (`var_out`: a
+        tensor to receive it).  `stage` True, or a (height, width) uint8 tensor: the stage map (0, 1, 2) is returned as a further
+        value.  `params`: normal_power_log2, flags, form, sigma_plane of RayzUpscaleParams; unnamed ones take capi.UPSCALE_DEFAULTS —
+        flags 0: demodulating by the low-resolution albedo measured far worse than not doing it.
+        No output may share memory with an input.  Asynchronous on `stream`, as `Denoiser.run`."""
+        import torch
+
+        prm = _params(capi.UpscaleParams, capi.UPSCALE_DEFAULTS, params, "upscale")
+        prm.factor = self.factor
+        hi = (self.height, self.width, 3)
+        lo = (self.height // self.factor, self.width // self.factor, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "normal", "point"] + (["albedo"] if prm.flags & capi.DENOISE_ALBEDO else [])
+        if out is None:
+            out = torch.empty(hi, dtype=torch.float32, device=dev)
+        if var_out is not None and var_rgb is None:
+            raise ValueError("var_out needs var_rgb")
+        if var_rgb is not None and var_out is None:
+            var_out = torch.empty(hi, dtype=torch.float32, device=dev)
+        if stage is True:
+            stage = torch.empty(hi[:2], dtype=torch.uint8, device=dev)
+        elif stage is False:
+            stage = None
+        tensors = [("rgb_lo", rgb_lo, torch.float32, lo)]
+        if var_rgb is not None:
+            tensors.append(("var_rgb", var_rgb, torch.float32, lo))
+        for name, g, frame in (("gbuffer_lo", gbuffer_lo, lo), ("gbuffer_hi", gbuffer_hi, hi)):
+            tensors += [(f"{name}.{k}", getattr(g, k), torch.int32 if k == "index" else torch.float32, frame[:2] if k == "index" else frame)
+                        for k in need]
+        tensors.append(("out", out, torch.float32, hi))
+        if var_out is not None:
+            tensors.append(("var_out", var_out, torch.float32, hi))
+        if stage is not None:
+            tensors.append(("stage", stage, torch.uint8, hi[:2]))
+        for t in tensors:
+            _check_tensor(*t, self._device, "the upscaler")
+        _stream_prologue(stream, self._device)
+        rc = self._lib.rayz_hip_upscaler_run(self._h, C.byref(prm), C.c_void_p(rgb_lo.data_ptr()),
+                                             C.c_void_p(var_rgb.data_ptr() if var_rgb is not None else None),
+                                             C.byref(_gbuffer_pointers(gbuffer_lo, need)), C.byref(_gbuffer_pointers(gbuffer_hi, need)),
+                                             C.c_void_p(out.data_ptr()), C.c_void_p(var_out.data_ptr() if var_out is not None else None),
+                                             C.c_void_p(stage.data_ptr() if stage is not None else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_upscaler_run")
+        self._inflight = (rgb_lo, var_rgb, gbuffer_lo, gbuffer_hi, out, var_out, stage)
+        res = (out,) + ((var_out,) if var_out is not None else ()) + ((stage,) if stage is not None else ())
+        return res[0] if len(res) == 1 else res
+
+    def timing(self):
+        """Waits for the last run; its HIP-event times in ms: (pack launches, reconstruction launch) (`rayz_hip_upscaler_timing`)."""
+        pack, up = C.c_float(), C.c_float()
+        capi.check(self._lib, self._lib.rayz_hip_upscaler_timing(self._h, C.byref(pack), C.byref(up)), "rayz_hip_upscaler_timing")
+        return pack.value, up.value
+
+
 class Temporal(_Handle):
     """Temporal accumulation for whole float32 frames of one size (`rayz_hip_temporal_*`): every `step` blends
     the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
