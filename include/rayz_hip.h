@@ -452,6 +452,32 @@ int rayz_hip_adaptive_kat(uint32_t precision, const double* chunk_sums, const ui
                           const RayzNoiseParams* p_or_null, uint32_t* frozen_at_out, double* acc_out, double* q_out,
                           double* frame_out, uint32_t* lists_out, uint32_t* list_sizes_out);
 
+/* ---- sparse renders: a caller's list of pixels, each equal to the frame's own ----------------
+ * Traces the `n_pixels` pixels `d_pixels` lists (DEVICE memory) and nothing else.  d_pixels[j] is a LOCAL row-major pixel of
+ * `params`' shard, local row * width + column, below rayz_hip_shard_rows(params) * width: the numbering of an adaptive list.
+ * Any order; duplicates are allowed.  `params` is the FULL frame's (samples_per_px the total): the chunk schedule, and with it
+ * the summation tree, is the frame's, every sample keeps its stream, and entry j receives the three values
+ * rayz_hip_render_device gives that pixel, bit for bit.  It writes them at pixel slot d_dest[j] of `d_rgb_out` (DEVICE memory of
+ * `dest_pixels` pixel slots, 3 values each) — slot j without `d_dest`, and then dest_pixels must equal n_pixels.  Where two
+ * entries name one slot, one of them stays (which is unspecified; the same pixel gives the same bits either way).  A slot no
+ * entry names is not written.  `d_var_rgb_out_or_null` (dest_pixels * 3 floats, for both precisions) receives, at the same
+ * slots, the per-channel variance of the pixel's mean as rayz_hip_progressive_noise_rgb reports it for a tracked handle that
+ * has folded every chunk: +inf for a schedule of one chunk.  max_bounces = 0 writes +0 without tracing.
+ * The scene is validated and prepared as for rayz_hip_render_device (AUTO traversal included); the trace runs through the
+ * adaptive passes' kernels, so the scan forms and the primary lists do not apply.
+ * THE CALL BLOCKS ONCE: every entry is checked on the device first (pixel below the shard's pixel count, slot below dest_pixels)
+ * and the host waits for that check's 4-byte count; the trace and the resolve behind it are asynchronous on `hip_stream`.
+ * RAYZ_ERR_BAD_ARG, with nothing traced or written: a null camera, params, list or output; a precision that does not match the
+ * entry; dest_pixels against the rules above; n_pixels * chunks beyond the work queue's range; any entry out of range.
+ * n_pixels = 0 is RAYZ_OK and touches nothing.  Afterwards rayz_hip_scene_sync returns this call's counters: primary_rays =
+ * n_pixels * samples_per_px, segments, tests, and kernel_ms between the call's own events (check, trace and resolve). */
+int rayz_hip_scene_render_pixels(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                 const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_dest_or_null, uint32_t dest_pixels,
+                                 float* d_rgb_out, float* d_var_rgb_out_or_null, void* hip_stream);
+int rayz_hip_scene_render_pixels_f64(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                     const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_dest_or_null, uint32_t dest_pixels,
+                                     double* d_rgb_out, float* d_var_rgb_out_or_null, void* hip_stream);
+
 /* ---- several GPUs behind ONE call -------------------------------------------------------------------------
  * The reference's caller makes one call, `tracer.render()` (src/rayz.zig:26, src/renderer.zig:72-101).  These
  * entry points give that one call every GPU of the node: the pool is replicated (one scene per device), image
@@ -825,6 +851,18 @@ int rayz_hip_upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, con
                           const float* d_var_rgb_lo_or_null, const RayzQueryOutputs* gbuffer_lo,
                           const RayzQueryOutputs* gbuffer_hi, float* d_rgb_out, float* d_var_rgb_out_or_null,
                           uint8_t* d_stage_out_or_null, void* hip_stream);
+/* The same run for a LATTICE frame (DESIGN.md 4.20 "Lattice samples", 4.21): low-resolution pixel (i, j) IS full pixel
+ * (factor*i + phase_x, factor*j + phase_y) — the frame render.lattice_pixels lists and rayz_hip_scene_render_pixels traces, with
+ * `gbuffer_lo` the same pixels of `gbuffer_hi` — not the mean of a block.  The position of a full pixel among the samples
+ * follows the phase (4.20), stage 2 takes the nearest sample, and the stages, taps, weights and finish are the run's above.  One
+ * rule is new: a SAMPLED full pixel whose own sample the guides accept with a weight above 0 is written by selection as that
+ * low-resolution pixel's raw colour (variance: its raw variance, clamped to [0, 2^32]; stage 0), whatever the flags — a lattice
+ * sample passes through unchanged.  Arguments, ordering and refusals as rayz_hip_upscaler_run; also RAYZ_ERR_BAD_ARG (before
+ * the handle): a phase that is not below the factor. */
+int rayz_hip_upscaler_run_phase(RayzUpscaler* up, const RayzUpscaleParams* params, uint32_t phase_x, uint32_t phase_y,
+                                const float* d_rgb_lo, const float* d_var_rgb_lo_or_null, const RayzQueryOutputs* gbuffer_lo,
+                                const RayzQueryOutputs* gbuffer_hi, float* d_rgb_out, float* d_var_rgb_out_or_null,
+                                uint8_t* d_stage_out_or_null, void* hip_stream);
 /* Waits for the handle's last run and returns its HIP-event times in ms: the pack launches, the reconstruction launch.
  * RAYZ_ERR_STATE before any run. */
 int rayz_hip_upscaler_timing(RayzUpscaler* up, float* pack_ms_or_null, float* upscale_ms_or_null);

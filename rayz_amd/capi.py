@@ -227,6 +227,12 @@ PROTOTYPES = [
      [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
       C.c_uint32, C.POINTER(NoiseParams), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("rayz_hip_scene_render_pixels", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
+    ("rayz_hip_scene_render_pixels_f64", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+      C.c_void_p]),
     ("rayz_hip_multi_create", C.c_int,
      [C.POINTER(C.c_int), C.c_int, C.POINTER(SceneDesc), C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_multi_destroy", C.c_int, [C.c_void_p]),
@@ -268,6 +274,9 @@ PROTOTYPES = [
     ("rayz_hip_upscaler_run", C.c_int,
      [C.c_void_p, C.POINTER(UpscaleParams), C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p,
       C.c_void_p, C.c_void_p]),
+    ("rayz_hip_upscaler_run_phase", C.c_int,
+     [C.c_void_p, C.POINTER(UpscaleParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.POINTER(QueryOutputs),
+      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_upscaler_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("rayz_hip_upscaler_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -20,6 +20,7 @@
 #include "temporal_feedback_kernel.hpp"
 #include "noise.hpp"
 #include "adaptive.hpp"
+#include "sparse.hpp"
 #include "host_base.hpp"
 
 using namespace rayz_dev;
@@ -206,6 +207,11 @@ struct RayzScene {
     uint32_t primary_mode = RAYZ_PRIMARY_LISTS_AUTO; // rayz_hip_scene_set_primary_lists
     PrimaryLists primary;                            // the one-shot renders' lists: rebuilt by every render that uses them
     RayzRenderStats last{};
+    // sparse renders (rayz_hip_scene_render_pixels, sparse_render.hpp): the check's count, and the call's events — [0], [1] around
+    // its check, trace and resolve, which rayz_hip_scene_sync times when the last render was one (last_sparse); [2], [3] the trace
+    DevBuf<uint32_t> sparse_bad;
+    DevEvent sparse_ev[4];
+    bool last_sparse = false;
     // ray queries (rayz_hip_scene_query*): their own counters and events, so that rayz_hip_scene_sync keeps reporting the last render
     DevBuf<unsigned long long> q_counters; // [0] batch head, [1] segments (chain calls), [2] node tests, [3] sphere tests, [31] LDS flag,
                                            // [kQueryBoundBase + k·kQueryBoundStride] the bound check's four words
@@ -1127,6 +1133,16 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
     return RAYZ_OK;
 }
 
+// The device copy of the schedule `starts` (scene->chunk_start), kept until the schedule changes.
+int scene_schedule(RayzScene* s, const std::vector<uint32_t>& starts, hipStream_t stream) {
+    if (starts == s->chunk_start_host) return RAYZ_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(s->chunk_start.grow(starts.size()));
+    HIP_TRY(hipMemcpy(s->chunk_start, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s->chunk_start_host = starts;
+    return RAYZ_OK;
+}
+
 // Launches one render of `p`'s shard on the scene's device: the trace kernel over every chunk, then resolve_kernel.  The caller
 // has selected that device (DeviceScope).
 template <class R>
@@ -1147,6 +1163,7 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
     s->last.primary_rays = shard_pixels64 * p->samples_per_px;
     s->last_bvh = use_bvh;
     s->last_experiment = 0;
+    s->last_sparse = false;
     if (items64 == 0) {
         s->rendered = false;
         return RAYZ_OK;
@@ -1159,12 +1176,7 @@ int render_impl(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const Ra
         return RAYZ_OK;
     }
     if (!s->counters) HIP_TRY(s->counters.alloc(32));
-    if (starts != s->chunk_start_host) { // the schedule table, kept on the device until it changes
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(s->chunk_start.grow(starts.size()));
-        HIP_TRY(hipMemcpy(s->chunk_start, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        s->chunk_start_host = starts;
-    }
+    RAYZ_TRY(scene_schedule(s, starts, stream));
     if (!s->ev0) {
         HIP_TRY(s->ev0.create());
         HIP_TRY(s->ev1.create());
@@ -1280,7 +1292,8 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
         RayzRenderStats st = s->last;
         RAYZ_TRY(read_counters(*s, s->counters, "trace_kernel_bvh", s->last_bvh, true, st, report));
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+        if (s->last_sparse) HIP_TRY(hipEventElapsedTime(&ms, s->sparse_ev[0], s->sparse_ev[1])); // (the call's check, trace and resolve)
+        else HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
         st.kernel_ms = ms;
         s->last = st;
     }
@@ -1518,6 +1531,7 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 // ---- the features on top of the trace launch (order: see the head of this file) ---------------------------------------------
 #include "progressive.hpp"
 #include "adaptive_passes.hpp"
+#include "sparse_render.hpp"
 #include "known_answers.hpp"
 #include "multi_device.hpp"
 #include "query.hpp"

@@ -152,7 +152,123 @@ template <bool VAR> __global__ __launch_bounds__(256) void upscale_direct_kernel
     if (a.stage) a.stage[p] = (uint8_t)stage;
 }
 
+// ---- the run with a phase (§4.20, "Lattice samples"; rayz_hip_upscaler_run_phase) -----------------------------------------------
+// Low-resolution pixel (i, j) IS full pixel (f·i + phase_x, f·j + phase_y): a sample of a lattice, not the mean of a block.  A
+// sibling of upscale_direct_kernel — its text repeated with the position, the nearest sample and the pass-through of a sampled
+// pixel replaced — so that the kernel above stays the kernel it was; up_tap and dn_guide are shared.
+struct UpscalePhaseArgs {
+    UpscaleArgs a;
+    const float* __restrict__ var_lo; // the caller's low-resolution variance: a sampled pixel's raw variance (VAR only)
+    uint32_t phase_x, phase_y;
+};
+
+// The position along one axis: a = x - phase, i0 = floor(a / f), r = a - f·i0, fx = f32(r) / f32(f).  (a > -f: i0 >= -1)
+__device__ __forceinline__ void up_phase_position(const int x, const int phase, const int f, int& i0, int& r, float& fx) {
+    const int a = x - phase;
+    i0 = a < 0 ? -1 : a / f;
+    r = a - f * i0;
+    fx = (float)r / (float)f;
+}
+
+// The nearest sample along one axis: clamp(floor((2a + f) / 2f), 0, n - 1).
+__device__ __forceinline__ int up_phase_nearest(const int x, const int phase, const int f, const int n) {
+    const int t = 2 * (x - phase) + f;
+    const int i = t < 0 ? 0 : t / (2 * f);
+    return i < n ? i : n - 1;
+}
+
+template <bool VAR> __global__ __launch_bounds__(256) void upscale_phase_kernel(const UpscalePhaseArgs pa_) {
+    const UpscaleArgs& a = pa_.a;
+    const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
+    const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
+    if (x >= (int)a.width || y >= (int)a.height) return;
+    const size_t p = (size_t)y * a.width + x;
+    const bool bg = a.index[p] < 0;
+    const dn4 pa{a.normal[3 * p], a.normal[3 * p + 1], a.normal[3 * p + 2], bg ? 1.0f : 0.0f};
+    const dn4 pb{a.point[3 * p], a.point[3 * p + 1], a.point[3 * p + 2], 0.0f};
+    const int f = (int)a.factor, w = (int)a.lo_width, h = (int)a.lo_height;
+    int i0, j0, rx, ry;
+    float fx, fy;
+    up_phase_position(x, (int)pa_.phase_x, f, i0, rx, fx);
+    up_phase_position(y, (int)pa_.phase_y, f, j0, ry, fy);
+    if (rx == 0 && ry == 0 && i0 < w && j0 < h) { // a SAMPLED pixel (i0, j0 >= 0 here): its own sample passes through, by selection
+        const size_t q = (size_t)j0 * a.lo_width + i0;
+        float g;
+        if (dn_guide(pa, pb, a.ga[q], a.gb[q], a.normal_power_log2, a.sp2, g) && g > 0.0f) {
+            a.rgb[3 * p + 0] = a.rgb_lo[3 * q + 0];
+            a.rgb[3 * p + 1] = a.rgb_lo[3 * q + 1];
+            a.rgb[3 * p + 2] = a.rgb_lo[3 * q + 2];
+            if (VAR) {
+                a.var_out[3 * p + 0] = dn_clamp_var(pa_.var_lo[3 * q + 0]);
+                a.var_out[3 * p + 1] = dn_clamp_var(pa_.var_lo[3 * q + 1]);
+                a.var_out[3 * p + 2] = dn_clamp_var(pa_.var_lo[3 * q + 2]);
+            }
+            if (a.stage) a.stage[p] = 0;
+            return;
+        }
+    }
+    float mr = 1.0f, mg = 1.0f, mb = 1.0f;
+    if (a.albedo && !bg) { // the pack pass's modulation, of the FULL pixel
+        const float lo = 0.00390625f; // 2^-8
+        const float ar = a.albedo[3 * p], ag = a.albedo[3 * p + 1], ab = a.albedo[3 * p + 2];
+        mr = ar > lo ? ar : lo;
+        mg = ag > lo ? ag : lo;
+        mb = ab > lo ? ab : lo;
+    }
+    UpAcc acc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t stage = 0;
+    // stage 0: the 2x2 footprint, bilinear weight x guide weight
+#pragma unroll
+    for (int dj = 0; dj < 2; ++dj) {
+        const int qy = j0 + dj;
+        const float by = dj ? fy : 1.0f - fy;
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int qx = i0 + di;
+            const float b = (di ? fx : 1.0f - fx) * by;
+            if (qx < 0 || qx >= w || qy < 0 || qy >= h || b == 0.0f) continue;
+            up_tap<VAR>(a, pa, pb, qx, qy, b, acc);
+        }
+    }
+    if (!(acc.W > 0.0f)) { // stage 1 (rare): the 4x4 footprint, guide weight alone
+        stage = 1;
+        acc = UpAcc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int dj = -1; dj <= 2; ++dj) {
+            const int qy = j0 + dj;
+            if (qy < 0 || qy >= h) continue;
+            for (int di = -1; di <= 2; ++di) {
+                const int qx = i0 + di;
+                if (qx < 0 || qx >= w) continue;
+                up_tap<VAR>(a, pa, pb, qx, qy, 1.0f, acc);
+            }
+        }
+    }
+    if (acc.W > 0.0f) {
+        a.rgb[3 * p + 0] = (acc.r / acc.W) * mr;
+        a.rgb[3 * p + 1] = (acc.g / acc.W) * mg;
+        a.rgb[3 * p + 2] = (acc.b / acc.W) * mb;
+        if (VAR) {
+            const float W2 = acc.W * acc.W;
+            a.var_out[3 * p + 0] = (acc.vr / W2) * (mr * mr);
+            a.var_out[3 * p + 1] = (acc.vg / W2) * (mg * mg);
+            a.var_out[3 * p + 2] = (acc.vb / W2) * (mb * mb);
+        }
+    } else { // stage 2: the nearest sample's raw colour, and "no estimate" as its variance
+        stage = 2;
+        const size_t q = (size_t)up_phase_nearest(y, (int)pa_.phase_y, f, h) * a.lo_width + (size_t)up_phase_nearest(x, (int)pa_.phase_x, f, w);
+        a.rgb[3 * p + 0] = a.rgb_lo[3 * q + 0];
+        a.rgb[3 * p + 1] = a.rgb_lo[3 * q + 1];
+        a.rgb[3 * p + 2] = a.rgb_lo[3 * q + 2];
+        if (VAR) a.var_out[3 * p + 0] = a.var_out[3 * p + 1] = a.var_out[3 * p + 2] = kDnVarCap;
+    }
+    if (a.stage) a.stage[p] = (uint8_t)stage;
+}
+
 // ---- host side: the launches (upscaler.hpp owns the handle, the validation and the stream) --------------------------------------
+inline void upscale_launch_phase(hipStream_t st, bool with_var, const UpscalePhaseArgs& a) {
+    hipLaunchKernelGGL(with_var ? upscale_phase_kernel<true> : upscale_phase_kernel<false>, denoise_grid(a.a.width, a.a.height), dim3(256), 0, st, a);
+}
+
 inline void upscale_launch_pack_var(hipStream_t st, const float* var_rgb, const dn4* mod, dn4* var, size_t n_pixels) {
     hipLaunchKernelGGL(upscale_pack_var_kernel, dim3((uint32_t)((n_pixels + 255) / 256)), dim3(256), 0, st, var_rgb, mod, var, n_pixels);
 }

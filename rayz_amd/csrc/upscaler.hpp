@@ -55,11 +55,14 @@ int upscale_alias_check(const float* d_rgb_lo, const float* d_var_lo, const Rayz
 }
 
 // Every argument is checked before the handle, and nothing here touches a device until all of them passed.
-int upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, const float* d_rgb_lo, const float* d_var_lo, const RayzQueryOutputs* lo,
-                 const RayzQueryOutputs* hi, float* d_out, float* d_var_out, uint8_t* d_stage, void* stream_arg) {
+// `phase` (rayz_hip_upscaler_run_phase): {phase_x, phase_y} of a lattice frame, or null for the run of block means.
+int upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, const uint32_t* phase, const float* d_rgb_lo, const float* d_var_lo,
+                 const RayzQueryOutputs* lo, const RayzQueryOutputs* hi, float* d_out, float* d_var_out, uint8_t* d_stage, void* stream_arg) {
     if (!params) return fail(RAYZ_ERR_BAD_ARG, "upscale: null params (the factor has no default)");
     const RayzUpscaleParams& p = *params;
     RAYZ_TRY(upscale_factor_check(p.factor));
+    if (phase && (phase[0] >= p.factor || phase[1] >= p.factor))
+        return fail(RAYZ_ERR_BAD_ARG, "upscale phase (%u, %u): both below the factor %u", phase[0], phase[1], p.factor);
     if (p.normal_power_log2 > 16) return fail(RAYZ_ERR_BAD_ARG, "upscale normal_power_log2 %u > 16", p.normal_power_log2);
     if (p.flags & ~(uint32_t)RAYZ_DENOISE_ALBEDO) return fail(RAYZ_ERR_BAD_ARG, "unknown upscale flag bits 0x%x", p.flags & ~(uint32_t)RAYZ_DENOISE_ALBEDO);
     if (p.form > RAYZ_UPSCALE_FORM_DIRECT) return fail(RAYZ_ERR_BAD_ARG, "upscale form %u: this build has the direct form only (0 or 1)", p.form);
@@ -96,7 +99,13 @@ int upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, const float*
     a.rgb = d_out, a.var_out = d_var_out, a.stage = d_stage;
     a.width = up->full_width, a.height = up->full_height, a.lo_width = up->width, a.lo_height = up->height, a.factor = up->factor;
     a.normal_power_log2 = p.normal_power_log2, a.sp2 = sp2;
-    upscale_launch(st, with_var, a);
+    if (phase) {
+        UpscalePhaseArgs pa{};
+        pa.a = a, pa.var_lo = d_var_lo, pa.phase_x = phase[0], pa.phase_y = phase[1];
+        upscale_launch_phase(st, with_var, pa);
+    } else {
+        upscale_launch(st, with_var, a);
+    }
     RAYZ_TRY(frame_handle_launched(up, 2, st));
     up->ran = true;
     return RAYZ_OK;
@@ -135,7 +144,17 @@ int rayz_hip_upscaler_run(RayzUpscaler* up, const RayzUpscaleParams* params, con
                           const RayzQueryOutputs* gbuffer_lo, const RayzQueryOutputs* gbuffer_hi, float* d_rgb_out,
                           float* d_var_rgb_out_or_null, uint8_t* d_stage_out_or_null, void* hip_stream) {
     return guarded([&] {
-        return upscaler_run(up, params, d_rgb_lo, d_var_rgb_lo_or_null, gbuffer_lo, gbuffer_hi, d_rgb_out, d_var_rgb_out_or_null,
+        return upscaler_run(up, params, nullptr, d_rgb_lo, d_var_rgb_lo_or_null, gbuffer_lo, gbuffer_hi, d_rgb_out, d_var_rgb_out_or_null,
+                            d_stage_out_or_null, hip_stream);
+    });
+}
+
+int rayz_hip_upscaler_run_phase(RayzUpscaler* up, const RayzUpscaleParams* params, uint32_t phase_x, uint32_t phase_y, const float* d_rgb_lo,
+                                const float* d_var_rgb_lo_or_null, const RayzQueryOutputs* gbuffer_lo, const RayzQueryOutputs* gbuffer_hi,
+                                float* d_rgb_out, float* d_var_rgb_out_or_null, uint8_t* d_stage_out_or_null, void* hip_stream) {
+    return guarded([&] {
+        const uint32_t phase[2] = {phase_x, phase_y};
+        return upscaler_run(up, params, phase, d_rgb_lo, d_var_rgb_lo_or_null, gbuffer_lo, gbuffer_hi, d_rgb_out, d_var_rgb_out_or_null,
                             d_stage_out_or_null, hip_stream);
     });
 }

@@ -172,6 +172,18 @@ class QueryResult:
             setattr(r, k, t)
         return r
 
+    def lattice(self, f: int, phase) -> "QueryResult":
+        """The G-buffer of the lattice frame `lattice_pixels(width, height, f, phase)` renders: every field present, strided
+        `[py::f, px::f]` and made contiguous.  A lattice sample is a pixel of this frame, so its guides are this frame's own."""
+        px, py = _check_phase(f, phase)
+        r = QueryResult()
+        for k in QUERY_OUTPUTS + ("hit",) + CHAIN_OUTPUTS:
+            t = getattr(self, k)
+            if t is not None:
+                setattr(r, k, t[py::f, px::f].contiguous())
+        r.is_chain = self.is_chain
+        return r
+
     def _outputs(self) -> capi.QueryOutputs:
         o = capi.QueryOutputs()
         for k in QUERY_OUTPUTS + ("hit",):
@@ -196,6 +208,7 @@ class DeviceScene(_Handle):
         capi.check(self._lib, rc, "rayz_hip_scene_create")
         self._device = device
         self._inflight = None  # (rays, outputs) of the last query: kept alive until query_sync (the kernel may still use them)
+        self._sparse_inflight = None  # the tensors of the last render_pixels: kept alive until sync()
 
     @property
     def device(self) -> int:
@@ -230,9 +243,51 @@ class DeviceScene(_Handle):
         chunks (default capi.ADAPTIVE_DEFAULT_MIN_CHUNKS)."""
         return Progressive(self, camera, params, track_noise=track_noise, adaptive=adaptive, min_chunks=min_chunks)
 
+    def render_pixels(self, camera: capi.CameraDesc, params: capi.RenderParams, pixels, dest=None, out=None, var=False, stream: int = 0):
+        """A sparse render (`rayz_hip_scene_render_pixels`): traces the listed pixels only, each to the bits
+        `render_into(camera, params, ...)` gives it.  `pixels`: an int32 torch tensor (n,) on the scene's device, LOCAL row-major
+        pixels of `params`' shard (row * width + column) in any order, duplicates allowed.  Without `dest` entry j goes to row j of
+        `out`, shaped (n, 3) (allocated when None).  With `dest` (int32, (n,)) entry j goes to pixel slot dest[j] of `out`, which
+        must be given: any contiguous tensor of (..., 3) in `params`' precision, e.g. a frame; slots nobody names keep their bits.
+        `var`: True or a float32 tensor shaped as `out` for the per-channel variance of the mean at the same slots (True: a new
+        tensor, NaN where nothing was written).  Returns `out`, or (out, var).  Blocks for the list's range check — an entry out of
+        range is refused with nothing written — then runs asynchronously on `stream`; the tensors are kept alive by the scene until
+        sync(), which returns this call's counters."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        dtype = torch.float64 if params.precision == capi.PRECISION_F64 else torch.float32
+        for name, t in (("pixels", pixels), ("dest", dest)):
+            if t is not None:
+                _check_tensor(name, t, torch.int32, (int(pixels.numel()) if isinstance(pixels, torch.Tensor) else 0,), self.device, "the scene")
+        n = int(pixels.numel())
+        if out is None:
+            if dest is not None:
+                raise ValueError("dest scatters into a frame of the caller's: pass it as `out`")
+            out = torch.empty((n, 3), dtype=dtype, device=dev)
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device.index != self.device:
+            raise ValueError(f"out must be a torch tensor on cuda:{self.device}")
+        if out.dtype != dtype or not out.is_contiguous() or out.dim() < 2 or out.shape[-1] != 3:
+            raise ValueError(f"out must be a contiguous {dtype} tensor shaped (..., 3), got {out.dtype} {tuple(out.shape)}")
+        if var is True:
+            var = torch.full(tuple(out.shape), float("nan"), dtype=torch.float32, device=dev)
+        elif var is False:
+            var = None
+        if var is not None:
+            _check_tensor("var", var, torch.float32, tuple(out.shape), self.device, "the scene")
+        _stream_prologue(stream, self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else None)  # noqa: E731
+        fn = self._lib.rayz_hip_scene_render_pixels_f64 if dtype == torch.float64 else self._lib.rayz_hip_scene_render_pixels
+        rc = fn(self._h, C.byref(camera), C.byref(params), ptr(pixels), n, ptr(dest), out.numel() // 3, ptr(out), ptr(var),
+                C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_scene_render_pixels")
+        self._sparse_inflight = (pixels, dest, out, var)
+        return out if var is None else (out, var)
+
     def sync(self) -> capi.RenderStats:
         st = capi.RenderStats()
         capi.check(self._lib, self._lib.rayz_hip_scene_sync(self._h, C.byref(st)), "rayz_hip_scene_sync")
+        self._sparse_inflight = None
         return st
 
     @property
@@ -663,6 +718,63 @@ class Denoiser(_Handle):
         return ms[0], [ms[1 + l] for l in range(n.value)]
 
 
+# The order in which the f x f phases (px, py) of a lattice are visited: Bayer's ordered-dither matrices for 2 and 4 (every prefix
+# of the sequence is spread as evenly over the block as that many points can be), a table in the same spirit for 3 (three
+# diagonals, each a Latin pattern).  A parameter, not contract: any permutation of the phases rebuilds the frame.
+_PHASE_ORDER = {
+    2: ((0, 2),
+        (3, 1)),
+    3: ((0, 6, 3),
+        (4, 1, 7),
+        (8, 5, 2)),
+    4: ((0, 8, 2, 10),
+        (12, 4, 14, 6),
+        (3, 11, 1, 9),
+        (15, 7, 13, 5)),
+}
+
+
+def phase_sequence(f: int):
+    """All f x f phases (px, py) of an every-f-th-pixel lattice, each once, in the order a still camera should cycle them."""
+    if f not in _PHASE_ORDER:
+        raise ValueError(f"lattice factor {f}: must be 2, 3 or 4")
+    rank = _PHASE_ORDER[f]  # rank[py][px]: when that phase is visited
+    return sorted(((px, py) for py in range(f) for px in range(f)), key=lambda p: rank[p[1]][p[0]])
+
+
+def _check_phase(f: int, phase):
+    px, py = (int(v) for v in phase)
+    if f < 1 or not (0 <= px < f and 0 <= py < f):
+        raise ValueError(f"phase {tuple(phase)} outside the {f}x{f} block")
+    return px, py
+
+
+def lattice_pixels(width: int, height: int, f: int, phase, order: str = "rows", device=None):
+    """Every f-th pixel of an unsharded width x height frame, starting at `phase` = (px, py): the list `DeviceScene.render_pixels`
+    takes, and where each entry belongs.  Returns (pixels, dest), int32 torch tensors on `device` (None: the CPU): pixels[k] =
+    (f·j + py)·width + f·i + px for the lattice pixel (i, j), dest[k] = j·(width / f) + i, its row-major index in the
+    (height / f, width / f) lattice frame.  `order` "rows" lists the lattice row by row; "tiles" deals it in 8x8 tiles of the
+    lattice frame (tile rows first, a tile's pixels row by row), as whole frames are dealt to the waves.  Both list the same set."""
+    import torch
+
+    px, py = _check_phase(f, phase)
+    if width <= 0 or height <= 0 or width % f or height % f:
+        raise ValueError(f"frame {width}x{height}: not a positive multiple of the factor {f} in both directions")
+    if order not in ("rows", "tiles"):
+        raise ValueError(f"order must be 'rows' or 'tiles', got {order!r}")
+    lw, lh = width // f, height // f
+    j, i = np.divmod(np.arange(lw * lh, dtype=np.int64), lw)
+    if order == "tiles":
+        at = np.lexsort((i % 8, j % 8, i // 8, j // 8))  # (the last key sorts first)
+        j, i = j[at], i[at]
+    pixels = (f * j + py) * width + f * i + px
+    dest = j * lw + i
+    if pixels.size and pixels.max() >= 2 ** 31:
+        raise ValueError(f"frame {width}x{height}: pixel indices beyond int32")
+    as_t = lambda a: torch.from_numpy(a.astype(np.int32)).to(device if device is not None else "cpu")  # noqa: E731
+    return as_t(pixels), as_t(dest)
+
+
 def lowres_camera(camera: capi.CameraDesc, factor: int) -> capi.CameraDesc:
     """The camera of a frame traced at 1/`factor` of the resolution in each direction: every low-resolution pixel sits at the centre
     of its factor x factor block of `camera`'s pixels.  `px_du` and `px_dv` are multiplied by the factor and
@@ -710,18 +822,24 @@ class Upscaler(_Handle):
         self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
 
     def run(self, rgb_lo, gbuffer_lo: "QueryResult", gbuffer_hi: "QueryResult", var_rgb=None, out=None, var_out=None, stage=False,
-            stream: int = 0, **params):
+            stream: int = 0, phase=None, **params):
         """`rgb_lo`: (height / factor, width / factor, 3) float32 on the handle's device; `gbuffer_lo`, `gbuffer_hi`: float32 camera
         queries of the low-resolution and of the full frame (index, normal, point, and albedo with flags=DENOISE_ALBEDO).  Returns `out` (default: a new (height, width, 3) tensor).  With `var_rgb` — the per-channel variance of `rgb_lo`'s
         pixel means, shaped as it — the call returns (out, var): the per-channel MARGINAL variance of every full pixel (`var_out`: a
         tensor to receive it).  `stage` True, or a (height, width) uint8 tensor: the stage map (0, 1, 2) is returned as a further
         value.  `params`: normal_power_log2, flags, form, sigma_plane of RayzUpscaleParams; unnamed ones take capi.UPSCALE_DEFAULTS —
         flags 0: demodulating by the low-resolution albedo measured far worse than not doing it.
+        `phase` (px, py): `rgb_lo` is a LATTICE frame (`lattice_pixels`, `DeviceScene.render_pixels`) whose pixel (i, j) is full
+        pixel (factor·i + px, factor·j + py), and `gbuffer_lo` is `gbuffer_hi.lattice(factor, phase)`
+        (`rayz_hip_upscaler_run_phase`): the sampled pixels come back as they are, the others are rebuilt around them.  None: the
+        frame of block means a `lowres_camera` traces.
         No output may share memory with an input.  Asynchronous on `stream`, as `Denoiser.run`."""
         import torch
 
         prm = _params(capi.UpscaleParams, capi.UPSCALE_DEFAULTS, params, "upscale")
         prm.factor = self.factor
+        if phase is not None:
+            phase = _check_phase(self.factor, phase)
         hi = (self.height, self.width, 3)
         lo = (self.height // self.factor, self.width // self.factor, 3)
         dev = torch.device("cuda", self._device)
@@ -750,11 +868,14 @@ class Upscaler(_Handle):
         for t in tensors:
             _check_tensor(*t, self._device, "the upscaler")
         _stream_prologue(stream, self._device)
-        rc = self._lib.rayz_hip_upscaler_run(self._h, C.byref(prm), C.c_void_p(rgb_lo.data_ptr()),
-                                             C.c_void_p(var_rgb.data_ptr() if var_rgb is not None else None),
-                                             C.byref(_gbuffer_pointers(gbuffer_lo, need)), C.byref(_gbuffer_pointers(gbuffer_hi, need)),
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(var_out.data_ptr() if var_out is not None else None),
-                                             C.c_void_p(stage.data_ptr() if stage is not None else None), C.c_void_p(stream or None))
+        args = (C.c_void_p(rgb_lo.data_ptr()), C.c_void_p(var_rgb.data_ptr() if var_rgb is not None else None),
+                C.byref(_gbuffer_pointers(gbuffer_lo, need)), C.byref(_gbuffer_pointers(gbuffer_hi, need)),
+                C.c_void_p(out.data_ptr()), C.c_void_p(var_out.data_ptr() if var_out is not None else None),
+                C.c_void_p(stage.data_ptr() if stage is not None else None), C.c_void_p(stream or None))
+        if phase is None:
+            rc = self._lib.rayz_hip_upscaler_run(self._h, C.byref(prm), *args)
+        else:
+            rc = self._lib.rayz_hip_upscaler_run_phase(self._h, C.byref(prm), phase[0], phase[1], *args)
         capi.check(self._lib, rc, "rayz_hip_upscaler_run")
         self._inflight = (rgb_lo, var_rgb, gbuffer_lo, gbuffer_hi, out, var_out, stage)
         res = (out,) + ((var_out,) if var_out is not None else ()) + ((stage,) if stage is not None else ())

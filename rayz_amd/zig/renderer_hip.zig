@@ -304,6 +304,34 @@ pub extern fn rayz_hip_adaptive_kat(
     list_sizes_out: ?[*]u32,
 ) c_int;
 
+// ---- sparse renders (include/rayz_hip.h, DESIGN.md §4.21): a device list of local pixels, each traced to the bits the whole
+// frame gives it, scattered to the slots d_dest names.  UNCHECKED BY THE TEXT CHECK as the entries above (`void* hip_stream`);
+// tests/test_sparse_cpu.py holds these two prototypes to the header instead.  Lists and outputs are DEVICE memory.
+pub extern fn rayz_hip_scene_render_pixels(
+    scene: *RayzScene,
+    camera: *const RayzCameraDesc,
+    params: *const RayzRenderParams,
+    d_pixels: [*]const u32,
+    n_pixels: u32,
+    d_dest: ?[*]const u32,
+    dest_pixels: u32,
+    d_rgb_out: [*]f32,
+    d_var_rgb_out: ?[*]f32,
+    hip_stream: ?*anyopaque,
+) c_int;
+pub extern fn rayz_hip_scene_render_pixels_f64(
+    scene: *RayzScene,
+    camera: *const RayzCameraDesc,
+    params: *const RayzRenderParams,
+    d_pixels: [*]const u32,
+    n_pixels: u32,
+    d_dest: ?[*]const u32,
+    dest_pixels: u32,
+    d_rgb_out: [*]f64,
+    d_var_rgb_out: ?[*]f32,
+    hip_stream: ?*anyopaque,
+) c_int;
+
 // ---- variance-guided denoising (include/rayz_hip.h, DESIGN.md §4.13): the per-channel variance of a tracked handle steers an
 // à-trous filter pixel by pixel.  UNCHECKED BY THE TEXT CHECK as the noise entries above are, for the same two reasons (a struct
 // beyond the eight render structs; `void* hip_stream`); tests/test_denoise_guided_cpu.py holds this struct and these two
