@@ -282,6 +282,21 @@ typedef enum RayzPrimaryLists { RAYZ_PRIMARY_LISTS_AUTO = 0, RAYZ_PRIMARY_LISTS_
 int rayz_hip_scene_set_primary_lists(RayzScene* scene, uint32_t mode);
 int rayz_hip_scene_get_primary_lists(RayzScene* scene, uint32_t samples_per_px, uint32_t* on);
 
+/* Cell lists.  The spheres that do not move in x or z and are no wider than a cell of a grid laid over their
+ * centres (the MEMBERS) live between two heights for the whole shutter.  With the cells ON a flat-list render asks, per segment,
+ * under which cells the ray's stretch between those heights runs; if they are at most 12, it resolves the segment from those cells'
+ * spheres and the scene's other hittables (the OUTLIERS, at most 8), through the same f64 narrow phase that decides behind the scan,
+ * instead of scanning the whole list.  A wave scans as before once fewer than 16 of its lanes hold such a segment.  The image and
+ * the segments counter are the same, bit for bit.  The table is a fact of the scene alone (4 u32 words per cell, built with the
+ * scene's slots, nothing per launch), so there is no samples-per-pixel gate.  A third choice beside the scan form and the primary
+ * lists, which keep their meaning.  It applies to one-shot and progressive flat-list renders with tmin > 0; adaptive passes, sparse
+ * renders, ray queries, chain calls and the BVH kernels are untouched.  A scene with a triangle, with more than 8 outliers or
+ * without a member has no cells: ON is accepted, _get reports 0 and the render scans.  AUTO takes the cells from 1,023 members on (the 32 x 32 grid of randomBouncing).
+ * _get returns whether such a render would use them (0 / 1; host only).  Default AUTO. */
+typedef enum RayzCellLists { RAYZ_CELL_LISTS_AUTO = 0, RAYZ_CELL_LISTS_OFF = 1, RAYZ_CELL_LISTS_ON = 2 } RayzCellLists;
+int rayz_hip_scene_set_cell_lists(RayzScene* scene, uint32_t mode);
+int rayz_hip_scene_get_cell_lists(RayzScene* scene, uint32_t* on);
+
 /* Waits for the last render on `scene` and returns its counters. */
 int rayz_hip_scene_sync(RayzScene* scene, RayzRenderStats* stats_or_null);
 

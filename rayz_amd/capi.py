@@ -23,6 +23,7 @@ GATHER_ALLOW_DUPLICATE_DEVICES = 0x100  # flag bit, peer-copy only (tests on a o
  KAT_TRIANGLE_HIT, KAT_SCAN_DISCS, KAT_BUCKET_DISCS, KAT_SCAN_DISCS_XY, KAT_BUCKET_DISCS_XY, KAT_SET_DISCS) = range(14)
 SCAN_FORM_AUTO, SCAN_FORM_XZ, SCAN_FORM_XY, SCAN_FORM_ONE_RADIUS = 0, 1, 2, 3  # RayzScanForm: the basis of the flat list's reject test
 PRIMARY_LISTS_AUTO, PRIMARY_LISTS_OFF, PRIMARY_LISTS_ON = 0, 1, 2  # RayzPrimaryLists: camera segments from per-pixel candidate lists
+CELL_LISTS_AUTO, CELL_LISTS_OFF, CELL_LISTS_ON = 0, 1, 2  # RayzCellLists: listable segments from the slab's cells
 KAT_IN_STRIDE, KAT_OUT_STRIDE = 48, 12
 
 OK = 0
@@ -184,6 +185,8 @@ PROTOTYPES = [
     ("rayz_hip_scene_get_scan_form", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("rayz_hip_scene_set_primary_lists", C.c_int, [C.c_void_p, C.c_uint32]),
     ("rayz_hip_scene_get_primary_lists", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("rayz_hip_scene_set_cell_lists", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("rayz_hip_scene_get_cell_lists", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("rayz_hip_scene_sync", C.c_int, [C.c_void_p, C.POINTER(RenderStats)]),
     ("rayz_hip_render", C.c_int,
      [C.POINTER(SceneDesc), C.POINTER(CameraDesc), C.POINTER(RenderParams), C.c_void_p,

@@ -21,6 +21,7 @@
 
 #include "plane_runs.hpp"
 #include "primary_lists.hpp"
+#include "slab_cells.hpp"
 
 namespace rayz_dev {
 
@@ -1395,6 +1396,39 @@ template <class R> struct PrimaryTraceArgs : TraceArgs<R> {
 #undef RAYZ_TRACE_KERNEL_ADAPTIVE
 #undef RAYZ_TRACE_KERNEL_ARGS
 #undef RAYZ_TRACE_KERNEL_PRIMARY
+// .. and the three scan forms a third time with every listable segment resolved from the slab's cells (slab_cells.hpp, DESIGN.md
+// §4.22), and a fresh path's from its pixel's primary list where the launch has lists (`primary` may be null): kernels of their own
+// names again, and in a namespace of their own, rayz_dev_cells: tests/test_sparse_isa.py takes every kernel of rayz_dev it has no record
+// of for a sparse-render kernel (tests/test_slab_cells_isa.py holds these).  Their argument block is the primary kernels' with the grid
+// and the table behind it.
+template <class R> struct CellsTraceArgs : PrimaryTraceArgs<R> {
+    rayz_cells::CellGrid grid;
+    const uint32_t* cells; // [kTableHead outlier slots][grid.nx · grid.nz records of kCellWords], 16-byte aligned
+};
+} // namespace rayz_dev (reopened below)
+namespace rayz_dev_cells {
+using namespace rayz_dev;
+#define RAYZ_TRACE_KERNEL_CELLS true
+#define RAYZ_TRACE_KERNEL_ARGS CellsTraceArgs<R>
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#define RAYZ_TRACE_KERNEL_NAME cells_xz_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#define RAYZ_TRACE_KERNEL_BASIS kBasisXY
+#define RAYZ_TRACE_KERNEL_NAME cells_xy_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#define RAYZ_TRACE_KERNEL_SETS true
+#define RAYZ_TRACE_KERNEL_NAME cells_one_radius_kernel
+#include "trace_kernel_flat.hpp"
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_SETS
+#undef RAYZ_TRACE_KERNEL_BASIS
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE
+#undef RAYZ_TRACE_KERNEL_ARGS
+#undef RAYZ_TRACE_KERNEL_CELLS
+} // namespace rayz_dev_cells
+namespace rayz_dev {
 
 // ---- the primary lists' builder -----------------------------------------------------------------------------
 // One lane per local pixel of the shard (place_item's numbering, rows as they come): every sphere of the pool, by its slot, through

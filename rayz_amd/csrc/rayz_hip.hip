@@ -53,6 +53,12 @@ struct NarrowBuffers {
     DevBuf<d4> bvh_sph64; // leaf order (BVH traversal only)
     uint32_t ns_pad = 0, ny_pad = 0, ng_pad = 0;
     uint32_t n_real = 0; // entries of real_slots
+    // the slab's cells (slab_cells.hpp): a fact of the pool and its slots alone, planned with them and uploaded with
+    // slot64; cell_grid.nx = 0: the scene has none
+    rayz_cells::CellGrid cell_grid{};
+    std::vector<uint32_t> cell_table_host;
+    DevBuf<uint32_t> cell_table;
+    size_t cell_members = 0;
     // slot order of the static (0) and mov-Y (1) classes: plane runs first (rayz_plane::plan_runs), then the loose spheres
     std::vector<PlaneRun> runs[2];
     std::vector<std::vector<uint32_t>> run_members[2]; // pool indices of each run
@@ -206,6 +212,7 @@ struct RayzScene {
     uint32_t scan_form = rayz_plane::kScanFormAuto; // rayz_hip_scene_set_scan_form: auto = the layout's own (narrow.scan_form)
     uint32_t primary_mode = RAYZ_PRIMARY_LISTS_AUTO; // rayz_hip_scene_set_primary_lists
     PrimaryLists primary;                            // the one-shot renders' lists: rebuilt by every render that uses them
+    uint32_t cells_mode = RAYZ_CELL_LISTS_AUTO;      // rayz_hip_scene_set_cell_lists
     RayzRenderStats last{};
     // sparse renders (rayz_hip_scene_render_pixels, sparse_render.hpp): the check's count, and the call's events — [0], [1] around
     // its check, trace and resolve, which rayz_hip_scene_sync times when the last render was one (last_sparse); [2], [3] the trace
@@ -259,6 +266,19 @@ void classify(RayzScene* s) {
 uint32_t scan_len(size_t n, uint32_t group) { return round_up((uint32_t)n, 2 * group); }
 uint32_t stream_len(size_t n, uint32_t group) { return scan_len(n, group) + 2 * group; }
 
+// Every sphere's slot: place(slot, pool index) over the three classes.  A run's members fill its first slots; its pads keep slot_pool
+// 0 (never a candidate: r² = -inf).
+template <class F> void for_each_slot(const RayzScene* s, F&& place) {
+    const NarrowBuffers& nb = s->narrow;
+    const size_t class0[2] = {0, nb.ns_pad};
+    for (int c = 0; c < 2; ++c) {
+        for (size_t j = 0; j < nb.runs[c].size(); ++j)
+            for (size_t k = 0; k < nb.run_members[c][j].size(); ++k) place(class0[c] + nb.runs[c][j].first + k, nb.run_members[c][j][k]);
+        for (size_t k = 0; k < nb.loose[c].size(); ++k) place(class0[c] + nb.plane_slots[c] + k, nb.loose[c][k]);
+    }
+    for (size_t k = 0; k < s->cls[2].size(); ++k) place((size_t)nb.ns_pad + nb.ny_pad + k, s->cls[2][k]);
+}
+
 // The slot layout of the pool (host only): classes, plane runs, speed buckets, slot counts — and with them the scan's price
 // under either basis.
 void plan_slots(RayzScene* s) {
@@ -290,6 +310,20 @@ void plan_slots(RayzScene* s) {
     const uint32_t class_slots[2] = {nb.ns_pad, nb.ny_pad};
     nb.scan_form = rayz_plane::cheaper_scan_form(rayz_plane::scan_slots(nb.plane_slots, class_slots, nb.buckets, nb.ng_pad));
     nb.planned = true;
+    // the cells, over the slots just planned (every gate but AUTO's member count, which scene_cell_lists applies)
+    std::vector<rayz_cells::SphereIn> in(s->spheres.size());
+    for_each_slot(s, [&](size_t slot, uint32_t pool) {
+        const RayzSphere& q = s->spheres[pool];
+        rayz_cells::SphereIn& e = in[pool];
+        for (int k = 0; k < 3; ++k) e.c[k] = q.center[k], e.v[k] = q.velocity[k];
+        e.r = q.radius;
+        e.slot = (uint32_t)slot;
+    });
+    rayz_cells::CellTable t = rayz_cells::build_cells(in, !s->triangles.empty(), 1u);
+    nb.cell_grid = t.grid;
+    nb.cell_table_host = std::move(t.table);
+    nb.cell_members = 0;
+    for (uint8_t m : t.member) nb.cell_members += m;
 }
 
 int upload_narrow_body(RayzScene* s) {
@@ -299,21 +333,15 @@ int upload_narrow_body(RayzScene* s) {
     std::vector<d4> slot64(2 * slots, d4{0, 0, 0, 0});
     std::vector<uint32_t> slot_pool(slots, 0u);
     std::vector<uint32_t> real_slots;
-    auto place = [&](size_t slot, uint32_t pool) {
+    for_each_slot(s, [&](size_t slot, uint32_t pool) {
         real_slots.push_back((uint32_t)slot);
         const RayzSphere& q = s->spheres[pool];
         slot64[2 * slot] = d4{q.center[0], q.center[1], q.center[2], q.radius * q.radius}; // radius * radius in f64, src/geom.zig:45
         slot64[2 * slot + 1] = d4{q.velocity[0], q.velocity[1], q.velocity[2], 0.0};
         slot_pool[slot] = pool;
-    };
-    const size_t class0[2] = {0, nb.ns_pad};
-    for (int c = 0; c < 2; ++c) { // a run's members fill its first slots; its pads keep slot_pool 0 (never a candidate: r² = -inf)
-        for (size_t j = 0; j < nb.runs[c].size(); ++j)
-            for (size_t k = 0; k < nb.run_members[c][j].size(); ++k) place(class0[c] + nb.runs[c][j].first + k, nb.run_members[c][j][k]);
-        for (size_t k = 0; k < nb.loose[c].size(); ++k) place(class0[c] + nb.plane_slots[c] + k, nb.loose[c][k]);
-    }
-    for (size_t k = 0; k < s->cls[2].size(); ++k) place((size_t)nb.ns_pad + nb.ny_pad + k, s->cls[2][k]);
+    });
     HIP_TRY(nb.slot64.upload(slot64));
+    if (nb.cell_grid.nx) HIP_TRY(nb.cell_table.upload(nb.cell_table_host));
     HIP_TRY(nb.slot_pool.upload(slot_pool));
     std::sort(real_slots.begin(), real_slots.end());
     HIP_TRY(nb.real_slots.upload(real_slots));
@@ -530,6 +558,15 @@ bool scene_primary_lists(const RayzScene* s, uint32_t spp) {
     if (s->primary_mode == RAYZ_PRIMARY_LISTS_OFF || !s->triangles.empty() || s->spheres.empty()) return false;
     if (s->primary_mode == RAYZ_PRIMARY_LISTS_ON) return true;
     return s->spheres.size() >= rayz_plane::kPrimaryMinSpheres && spp >= rayz_plane::kPrimaryMinSpp;
+}
+
+// Whether one-shot and progressive flat-list renders resolve their listable segments from the slab's cells: only
+// where the scene has a table (no triangle, at most kMaxOutliers outliers, a member); AUTO from kCellsMinMembers members on.
+bool scene_cell_lists(RayzScene* s) {
+    if (s->cells_mode == RAYZ_CELL_LISTS_OFF) return false;
+    plan_slots(s);
+    if (!s->narrow.cell_grid.nx) return false;
+    return s->cells_mode == RAYZ_CELL_LISTS_ON || s->narrow.cell_members >= rayz_cells::kCellsMinMembers;
 }
 
 void ensure_bvh(RayzScene* s) {
@@ -1001,6 +1038,17 @@ ShardGeometry shard_geometry(const RayzRenderParams* p) {
 // ev0 / ev1 bracket the kernel; `experiment` returns BvhLaunchPlan::experiment.
 // With `active_list` (an adaptive pass): the window's chunks of the list's `n_active` pixels only, through the
 // adaptive_pass_kernel[_bvh] — queue entry k · n_active + j sums chunk c0 + k of pixel active_list[j] into partial[k · n_active + j].
+// The cells kernel of a scan form.  Defined at the very end of this file, and named nowhere else: the compiler emits
+// a kernel where it first meets a reference to it, so these come out behind every other kernel, and the labels it numbers through the
+// whole file (a long branch's) keep their numbers in every kernel from before — tests/test_sparse_isa.py holds those kernels' text
+// label for label.
+void (*cells_kernel_f32(uint32_t form))(const CellsTraceArgs<float>);
+void (*cells_kernel_f64(uint32_t form))(const CellsTraceArgs<double>);
+template <class R> auto cells_kernel(uint32_t form) {
+    if constexpr (sizeof(R) == 8) return cells_kernel_f64(form);
+    else return cells_kernel_f32(form);
+}
+
 template <class R>
 int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const RayzCameraDesc* cam, const RayzRenderParams* p,
                  bool use_bvh, const std::vector<uint32_t>& starts, const uint32_t* d_starts, uint32_t c0, uint32_t c1,
@@ -1111,7 +1159,27 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
         HIP_TRY(hipGetLastError());
         lists->built = true;
     }
-    if (primary) { // the same launch geometry (the flat kernels have no dynamic LDS), the lists behind the arguments
+    // .. and each of the three with every listable segment from the slab's cells (and the primary lists, if the launch has them):
+    // one-shot and progressive renders alone (`lists` names them), and only with a positive tmin — the query keeps the ray's t >= 0
+    if (lists && !active_list && !use_bvh && p->tmin > 0.0 && scene_cell_lists(s)) {
+        CellsTraceArgs<R> P{};
+        static_cast<TraceArgs<R>&>(P) = A;
+        const uint32_t* built_lists = lists->buf;
+        P.primary = primary ? built_lists : nullptr;
+        P.grid = s->narrow.cell_grid;
+        P.cells = s->narrow.cell_table;
+#ifdef RAYZ_CELLS_TUNE // measurement builds only: the thresholds from the environment
+        P.grid.list_lanes = std::getenv("RAYZ_CELLS_LIST_LANES") ? (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_LIST_LANES")) : rayz_cells::kListLanes;
+        P.grid.max_cells = std::getenv("RAYZ_CELLS_MAX_CELLS") ? (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_MAX_CELLS")) : rayz_cells::kMaxCells;
+#endif
+        const uint32_t form = scene_scan_form(s);
+        void (*kernel)(const CellsTraceArgs<R>) = cells_kernel<R>(form);
+        static int occupancy[4] = {0, 0, 0, 0}; // by scan form, of precision R; 0: not asked yet
+        int& blocks_per_cu = occupancy[form & 3u];
+        if (blocks_per_cu == 0) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kernel, plan.block, 0));
+        grid = std::min<uint64_t>((uint64_t)ctx.num_cu * std::max(1, blocks_per_cu), want);
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(plan.block), 0, stream, P);
+    } else if (primary) { // the same launch geometry (the flat kernels have no dynamic LDS), the lists behind the arguments
         PrimaryTraceArgs<R> P{};
         static_cast<TraceArgs<R>&>(P) = A;
         P.primary = lists->buf;
@@ -1262,10 +1330,19 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
         auto report = [&](const unsigned long long* c) { // (measurement builds: the phase profile of the kernel that ran)
 #ifdef RAYZ_FLAT_PROFILE // measurement build only: wave time per phase of trace_kernel
         if (!s->last_bvh && c[9]) {
-            const double tot = (double)(c[4] + c[5] + c[6] + c[7] + c[8]);
+            const double tot = (double)(c[4] + c[5] + c[6] + c[7] + c[8] + c[10]);
             std::fprintf(stderr, "flat phases (share of wave time; ticks per wave-iteration %.0f): refill %.1f%% | setup %.1f%% | scan %.1f%% | "
-                                 "flush %.1f%% | shade %.1f%%\n", tot / (double)c[9], 100.0 * c[4] / tot, 100.0 * c[5] / tot,
-                         100.0 * c[6] / tot, 100.0 * c[7] / tot, 100.0 * c[8] / tot);
+                                 "flush %.1f%% | shade %.1f%% | list phases %.1f%%; ticks: scans+flush %.4g, list %.4g, all %.4g; scans %llu\n",
+                         tot / (double)c[9], 100.0 * c[4] / tot, 100.0 * c[5] / tot, 100.0 * c[6] / tot, 100.0 * c[7] / tot, 100.0 * c[8] / tot,
+                         100.0 * c[10] / tot, (double)(c[6] + c[7]), (double)c[10], tot, c[9]);
+            if (c[11]) { // a cells kernel ran (trace_kernel_flat.hpp: fp)
+                std::fprintf(stderr, "cells: secondary segments %llu, listable %.2f%%; cell-lane segments listed %llu (%.2f entries each); list phases %llu "
+                                     "(%.1f lanes each); live lanes per scan %.1f; cells per listable secondary segment:",
+                             c[11], 100.0 * c[12] / (double)c[11], c[13], (double)c[14] / (double)(c[13] ? c[13] : 1), c[15],
+                             (double)c[16] / (double)(c[15] ? c[15] : 1), (double)c[17] / (double)(c[9] ? c[9] : 1));
+                for (int k = 0; k <= 12; ++k) std::fprintf(stderr, " %d: %.2f%%", k, 100.0 * c[19 + k] / (double)(c[12] ? c[12] : 1));
+                std::fprintf(stderr, "\n");
+            }
         }
 #endif
 #ifdef RAYZ_BVH_PROFILE // measurement build only: per-phase wave time and lane occupancy of the BVH kernel
@@ -1477,6 +1554,23 @@ int rayz_hip_scene_get_primary_lists(RayzScene* s, uint32_t samples_per_px, uint
     });
 }
 
+int rayz_hip_scene_set_cell_lists(RayzScene* s, uint32_t mode) {
+    return guarded([&] {
+        if (!s) return fail(RAYZ_ERR_BAD_ARG, "null scene");
+        if (mode > RAYZ_CELL_LISTS_ON) return fail(RAYZ_ERR_BAD_ARG, "bad cell-lists mode %u", mode);
+        s->cells_mode = mode;
+        return (int)RAYZ_OK;
+    });
+}
+
+int rayz_hip_scene_get_cell_lists(RayzScene* s, uint32_t* on) {
+    return guarded([&] {
+        if (!s || !on) return fail(RAYZ_ERR_BAD_ARG, "null argument");
+        *on = scene_cell_lists(s) ? 1u : 0u;
+        return (int)RAYZ_OK;
+    });
+}
+
 int rayz_hip_scene_sync(RayzScene* s, RayzRenderStats* stats) {
     return guarded([&] { return scene_sync(s, stats); });
 }
@@ -1541,3 +1635,13 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "upscaler.hpp"
 #include "temporal.hpp"
 #include "temporal_moments.hpp"
+
+// ---- the cells kernels, named last (see cells_kernel) ----
+namespace {
+template <class R> void (*cells_kernel_of(uint32_t form))(const CellsTraceArgs<R>) {
+    using namespace rayz_dev_cells;
+    return form == rayz_plane::kScanFormOneRadius ? cells_one_radius_kernel<R, 1> : form == rayz_plane::kScanFormXY ? cells_xy_kernel<R, 1> : cells_xz_kernel<R, 1>;
+}
+void (*cells_kernel_f32(uint32_t form))(const CellsTraceArgs<float>) { return cells_kernel_of<float>(form); }
+void (*cells_kernel_f64(uint32_t form))(const CellsTraceArgs<double>) { return cells_kernel_of<double>(form); }
+} // namespace

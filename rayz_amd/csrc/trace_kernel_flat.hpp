@@ -15,6 +15,14 @@
 // next item popped as ever — or a SCAN phase as before, once every live lane's next segment needs the scan (a later segment,
 // or the camera segment of a pixel without a list).  The refill therefore repeats, wave-cooperative, until every lane holds a
 // path that needs a scan or the queue is drained; nothing else differs: same streams, same sums, same segments counter.
+// RAYZ_TRACE_KERNEL_CELLS true — three more times, as cells_xz_kernel, cells_xy_kernel and cells_one_radius_kernel: the three scan
+// forms with every segment whose ray crosses the members' slab under a handful of cells (slab_cells.hpp) resolved
+// from the outliers and those cells' slots.  After scan_begin each live lane learns whether its next segment is LISTABLE: a fresh
+// path on a pixel with a primary list (where the launch has lists: A.primary may be null), else whatever cells_query says.  With n
+// such lanes of m live ones, the wave runs a list phase for those lanes alone if n >= min(kListLanes, m), else the scan for every
+// live lane, listable or not: a list phase never runs for a few lanes while the rest wait, and no lane waits longer for its scan
+// than the threshold lets it.  The tie rule of accept_root is order-independent and a member sits in exactly one cell: the same
+// tbest and ibest as the scan's, bit for bit.
 #ifdef RAYZ_TRACE_KERNEL_ARGS
 template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const RAYZ_TRACE_KERNEL_ARGS A) {
 #else
@@ -36,6 +44,11 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
 #else
     constexpr bool kPrimary = false;
 #endif
+#ifdef RAYZ_TRACE_KERNEL_CELLS
+    constexpr bool kCells = RAYZ_TRACE_KERNEL_CELLS; // listable segments from the slab's cells (and the primary lists, where launched with them)
+#else
+    constexpr bool kCells = false;
+#endif
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     PathState<R> p[NR];
 #pragma unroll
@@ -43,7 +56,13 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     uint32_t nseg = 0;
     WaveQueue wq; // wave-uniform
 #ifdef RAYZ_FLAT_PROFILE // measurement build only: wave time per phase (refill, ray setup, scan, narrow flush, shade)
-    unsigned long long ft[5] = {0, 0, 0, 0, 0}, ft0 = __builtin_amdgcn_s_memtime(), fiters = 0;
+    // .. list phases (their own slot, 5); fp: wave-uniform counts of the cells kernels — 0 secondary segments, 1 listable ones, 2 segments a
+    // cell lane's list phase resolved, 3 their cell entries, 4 list phases, 5 their lanes, 6 live lanes at scans, 8 + k listable secondary
+    // segments whose box covers k cells (k <= 12)
+    unsigned long long ft[6] = {0, 0, 0, 0, 0, 0}, ft0 = __builtin_amdgcn_s_memtime(), fiters = 0, fp[21] = {};
+    uint32_t fcells[NR]; // per slot: 13 = not listable by the cells
+#pragma unroll
+    for (int r = 0; r < NR; ++r) fcells[r] = 13u;
 #define RAYZ_FPROF(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ft[k] += now_ - ft0; ft0 = now_; }
 #else
 #define RAYZ_FPROF(k)
@@ -97,8 +116,94 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
                                            ray[r].time, ray[r].inv_a2, A.tmin, ray[r].tbest, ray[r].ibest);
                         }
                     }
-                RAYZ_FPROF(0) // (measurement builds: the list phases count as refill)
+                RAYZ_FPROF(5)
             }
+        }
+        if constexpr (kCells) {
+            uint32_t lp[NR];
+            bool prim[NR], any_alive = false;
+            rayz_cells::CellBox box[NR];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                lp[r] = 0u;
+                prim[r] = false;
+                box[r].kind = rayz_cells::kNotListable;
+                if (p[r].alive) {
+                    if (p[r].seg == 0u && A.primary != nullptr) {
+                        lp[r] = p[r].item - (p[r].item / A.shard_pixels) * A.shard_pixels;
+                        prim[r] = A.primary[lp[r]] != rayz_primary::kNoList;
+                    }
+                    if (!prim[r]) // f64 on the widened o and d: bit for bit the ray narrow_eval gets
+                        box[r] = rayz_cells::cells_query(A.grid, A.cells + rayz_cells::kTableHead, (double)ray[r].o.x, (double)ray[r].o.y,
+                                                         (double)ray[r].o.z, (double)ray[r].d.x, (double)ray[r].d.y, (double)ray[r].d.z);
+                    listed[r] = prim[r] || box[r].kind != rayz_cells::kNotListable;
+                }
+#ifdef RAYZ_FLAT_PROFILE
+                fcells[r] = box[r].kind == rayz_cells::kNotListable ? 13u
+                            : box[r].kind == rayz_cells::kNoCells   ? 0u
+                                                                    : (box[r].i1 - box[r].i0 + 1u) * (box[r].j1 - box[r].j0 + 1u);
+#endif
+                list_phase = list_phase || listed[r];
+                any_alive = any_alive || p[r].alive;
+            }
+            const uint32_t n_listed = (uint32_t)__popcll(__ballot(list_phase)), n_alive = (uint32_t)__popcll(__ballot(any_alive));
+            list_phase = n_listed != 0u && n_listed >= (n_alive < rayz_cells::list_lanes(A.grid) ? n_alive : rayz_cells::list_lanes(A.grid));
+            if (list_phase) {
+#pragma unroll
+                for (int r = 0; r < NR; ++r) {
+                    // round one: a primary lane's listed slots, a cell lane's outliers (the head of the table): an indexed list either way
+                    const uint32_t* src = A.cells;
+                    uint32_t stride = 1u, count = 0u;
+                    if (listed[r]) {
+                        count = A.grid.n_outliers;
+                        if (prim[r]) src = A.primary + (size_t)A.shard_pixels + lp[r], stride = A.shard_pixels, count = A.primary[lp[r]];
+                    }
+                    for (uint32_t k = 0; __ballot(k < count) != 0ull; ++k)
+                        if (k < count) {
+                            const uint32_t slot = src[(size_t)k * stride];
+                            narrow_eval<R>(A.sc.slot64[2 * slot], A.sc.slot64[2 * slot + 1], (int)A.sc.slot_pool[slot], ray[r].o, ray[r].d,
+                                           ray[r].time, ray[r].inv_a2, A.tmin, ray[r].tbest, ray[r].ibest);
+                        }
+                    // round two: a cell lane walks its box, one entry per step whatever cell it comes from
+                    bool walking = listed[r] && !prim[r] && box[r].kind == rayz_cells::kSomeCells;
+                    uint32_t ci = box[r].i0, cj = box[r].j0, e = 0u;
+                    uint4 rec{0u, 0u, 0u, 0u}; // the cell at hand: its count and kCellCap slots
+                    static_assert(rayz_cells::kCellWords == 4u, "a cell's record is one 16-byte load");
+                    bool first = true;
+                    for (;;) {
+                        while (walking && e >= rec.x) { // on to the next cell that holds an entry (no listable box holds an overflowed one)
+                            if (!first && ++ci > box[r].i1) {
+                                ci = box[r].i0;
+                                if (++cj > box[r].j1) walking = false;
+                            }
+                            first = false;
+                            if (walking) rec = *(const uint4*)(A.cells + rayz_cells::kTableHead + (size_t)(cj * A.grid.nx + ci) * rayz_cells::kCellWords);
+                            e = 0u;
+                        }
+                        if (__ballot(walking) == 0ull) break;
+                        if (walking) {
+                            const uint32_t slot = e == 0u ? rec.y : e == 1u ? rec.z : rec.w;
+                            ++e;
+                            narrow_eval<R>(A.sc.slot64[2 * slot], A.sc.slot64[2 * slot + 1], (int)A.sc.slot_pool[slot], ray[r].o, ray[r].d,
+                                           ray[r].time, ray[r].inv_a2, A.tmin, ray[r].tbest, ray[r].ibest);
+                        }
+#ifdef RAYZ_FLAT_PROFILE
+                        fp[3] += (unsigned long long)__popcll(__ballot(walking));
+#endif
+                    }
+#ifdef RAYZ_FLAT_PROFILE
+                    fp[2] += (unsigned long long)__popcll(__ballot(listed[r] && !prim[r]));
+#endif
+                }
+#ifdef RAYZ_FLAT_PROFILE
+                fp[4]++;
+                fp[5] += n_listed;
+#endif
+                RAYZ_FPROF(5)
+            }
+#ifdef RAYZ_FLAT_PROFILE
+            else fp[6] += n_alive;
+#endif
         }
         if (!list_phase) {
 #ifdef RAYZ_FLAT_PROFILE
@@ -114,6 +219,17 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
         }
 
         // ---- shade ----
+#ifdef RAYZ_FLAT_PROFILE
+        if constexpr (kCells) { // (the ballots in front of the divergent shading: every lane keeps the same counts)
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const bool secondary = p[r].alive && (!list_phase || listed[r]) && p[r].seg != 0u;
+                fp[0] += (unsigned long long)__popcll(__ballot(secondary));
+                fp[1] += (unsigned long long)__popcll(__ballot(secondary && fcells[r] <= 12u));
+                for (uint32_t k = 0; k <= 12u; ++k) fp[8 + k] += (unsigned long long)__popcll(__ballot(secondary && fcells[r] == k));
+            }
+        }
+#endif
 #pragma unroll
         for (int r = 0; r < NR; ++r)
             if (p[r].alive && (!list_phase || listed[r])) {
@@ -130,6 +246,8 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     if (lane == 0) {
         for (int k = 0; k < 5; ++k) atomicAdd(&A.counters[4 + k], ft[k]);
         atomicAdd(&A.counters[9], fiters);
+        atomicAdd(&A.counters[10], ft[5]);
+        for (int k = 0; k < 21; ++k) atomicAdd(&A.counters[11 + k], fp[k]);
     }
 #endif
     // ---- counters: one atomic per wave ----

@@ -313,6 +313,17 @@ class DeviceScene(_Handle):
         capi.check(self._lib, self._lib.rayz_hip_scene_get_primary_lists(self._h, samples_per_px, C.byref(on)), "rayz_hip_scene_get_primary_lists")
         return bool(on.value)
 
+    def set_cell_lists(self, mode: int) -> None:
+        """capi.CELL_LISTS_AUTO, _OFF or _ON: whether flat-list renders resolve a segment whose ray crosses the small spheres' slab
+        under a handful of cells from those cells instead of a scan; the frame is the same either way."""
+        capi.check(self._lib, self._lib.rayz_hip_scene_set_cell_lists(self._h, mode), "rayz_hip_scene_set_cell_lists")
+
+    def uses_cell_lists(self) -> bool:
+        """Whether a flat-list render would use the cells (what AUTO decides, if nothing was set; False for a scene without cells)."""
+        on = C.c_uint32()
+        capi.check(self._lib, self._lib.rayz_hip_scene_get_cell_lists(self._h, C.byref(on)), "rayz_hip_scene_get_cell_lists")
+        return bool(on.value)
+
     # ---- ray queries (`findHit`, include/rayz_hip.h: rayz_hip_scene_query*) ----
     def query(self, rays, tmin: float = 1e-3, kind: str = "nearest", traversal: int = capi.TRAVERSAL_AUTO,
               outputs=QUERY_OUTPUTS, stream: int = 0) -> "QueryResult":
