@@ -1002,6 +1002,39 @@ int rayz_hip_temporal_track_feedback(RayzTemporal* tm);
  * does not track feedback, or one without history (before the first step, after _reset). */
 int rayz_hip_temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* hip_stream);
 
+/* ---- temporal accumulation, counts step: per-pixel sample counts for sparse frames -------------------
+ * BUILD-DEFINED, additive within ABI 5.  rayz_hip_temporal_step and _step_moments blend every pixel with one `spp`.  A lattice frame
+ * (rayz_hip_scene_render_pixels over every f-th pixel) adds samples to one pixel in f*f and none to the rest, and an adaptive frame
+ * (rayz_hip_progressive_sample_counts) a different number to each.  The COUNTS STEP is the same step with `d_counts` — DEVICE
+ * memory, height*width uint32, the samples the current frame adds to each pixel, 0 allowed — in place of `spp`:
+ *   - a pixel with count n > 0 blends as the scalar step does with spp = n;
+ *   - a pixel with count 0 that finds history KEEPS it: colour, variance (moments: second moment and W2) are the gathered history's
+ *     and the length is its length, by selection; the pixel's input colour and variance are loaded and never used, so a NaN
+ *     there reaches neither the outputs nor the history;
+ *   - a pixel without history takes its input as always and gets the length n; a record of length 0 holds no samples, and later
+ *     steps refuse it as a tap exactly as they refuse a different surface;
+ *   - the moments step's 7x7 neighbourhood counts only positions whose own count is > 0, the centre included.
+ * With every count equal to one spp >= 1 a counts step returns what the scalar step returns, bit for bit; under a still camera a
+ * pixel with count 0 keeps its record's colour, variance / moments and length.  Counts above 2^24 are the caller's error (they
+ * are used as f32) and are not checked.  The handle gains no state: scalar and counts steps may alternate on one handle.  The
+ * arithmetic is a contract (§4.23), restated by tests/temporal_counts_mirror.cpp.
+ * Limits of this version: plain and moments handles only — a handle that tracks feedback refuses both with RAYZ_ERR_STATE;
+ * background pixels are never accumulated, as before. */
+/* rayz_hip_temporal_step with d_counts for spp.  d_rgb_out == d_rgb_in and d_var_out == d_var_rgb are still allowed.
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): what rayz_hip_temporal_step refuses, minus spp; d_counts
+ * NULL; d_counts equal to d_rgb_out, d_var_out or d_length_out.  RAYZ_ERR_STATE: a bad handle, or one in moments mode. */
+int rayz_hip_temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* params_or_null, const RayzCameraDesc* camera,
+                                  const uint32_t* d_counts, const float* d_rgb_in, const float* d_var_rgb, const RayzQueryOutputs* gbuffer,
+                                  float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, void* hip_stream);
+/* rayz_hip_temporal_step_moments with d_counts for spp.  RAYZ_ERR_BAD_ARG: what rayz_hip_temporal_step_moments refuses, minus spp;
+ * d_counts NULL; d_counts equal to d_rgb_out, d_var_out, d_length_out or d_w2_out.  RAYZ_ERR_STATE: a bad handle, one that is not
+ * in moments mode, or one that tracks feedback. */
+int rayz_hip_temporal_step_moments_counts(RayzTemporal* tm, const RayzTemporalParams* params_or_null,
+                                          const RayzTemporalMomentsParams* mparams_or_null, const RayzCameraDesc* camera,
+                                          const uint32_t* d_counts, const float* d_rgb_in, const RayzQueryOutputs* gbuffer,
+                                          float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, float* d_w2_out_or_null,
+                                          void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

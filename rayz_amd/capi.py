@@ -295,6 +295,12 @@ PROTOTYPES = [
       C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_temporal_track_feedback", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_feedback", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_temporal_step_counts", C.c_int,
+     [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(CameraDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p,
+      C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_temporal_step_moments_counts", C.c_int,
+     [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(TemporalMomentsParams), C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
+      C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 

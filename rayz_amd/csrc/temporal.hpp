@@ -99,10 +99,11 @@ RayzTemporalParams temporal_params_or_default(const RayzTemporalParams* params) 
 // camera, of the handle and of its mode (moments: the kind of handle this step takes) — and then the step on the handle's stream
 // behind the previous one.  launch(stream, the plain step's arguments, is_static) completes the mode's arguments and launches.
 // Every argument is checked before the handle, and nothing here touches a device until all of them passed.
+// counts: this is a counts step (§4.23: spp is 0 and the launch brings a count per pixel), which a feedback handle does not take.
 template <class Launch>
 int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& p, const RayzCameraDesc* cam, uint32_t spp,
                       const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out,
-                      void* stream_arg, const Launch& launch) {
+                      void* stream_arg, const Launch& launch, bool counts = false) {
     float M[9], from[3];
     RAYZ_TRY(temporal_frame_check(g, cam, M, from));
     RAYZ_TRY(frame_handle_check(tm));
@@ -110,6 +111,8 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
         return fail(RAYZ_ERR_STATE, "%s",
                     moments ? "a plain temporal handle takes rayz_hip_temporal_step (rayz_hip_temporal_track_moments first)"
                             : "a temporal handle in moments mode takes rayz_hip_temporal_step_moments");
+    if (counts && tm->feedback)
+        return fail(RAYZ_ERR_STATE, "a temporal handle that tracks feedback takes no counts step (its first moment has no rule for a pixel without samples)");
     hipStream_t st;
     RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
     DeviceScope scope(tm->device);
@@ -134,6 +137,32 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
         temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
     };
     return temporal_run_step(tm, false, p, cam, spp, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch);
+}
+
+// What both counts steps (§4.23) check of their counts: every pixel reads its own and, in the moments step, its neighbours', so
+// the array is no output of the step.
+int temporal_counts_check(const uint32_t* d_counts, std::initializer_list<const void*> outputs) {
+    if (!d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: null counts buffer");
+    for (const void* o : outputs)
+        if (o == (const void*)d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: d_counts is also an output of the step");
+    return RAYZ_OK;
+}
+
+// The counts step of a plain handle: temporal_step with a count per pixel for spp (the kernel does not read the arguments' spp).
+int temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, const uint32_t* d_counts,
+                         const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out,
+                         float* d_len_out, void* stream_arg) {
+    const RayzTemporalParams p = temporal_params_or_default(params);
+    RAYZ_TRY(temporal_params_check(p, 1));
+    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
+    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
+    RAYZ_TRY(temporal_counts_check(d_counts, {d_out, d_var_out, d_len_out}));
+    const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) {
+        using namespace rayz_dev_counts;
+        temporal_launch_step(st, temporal_counts_kernel<true>, temporal_counts_kernel<false>, is_static, TemporalCountsArgs{a, d_counts},
+                             a.width, a.height);
+    };
+    return temporal_run_step(tm, false, p, cam, 0, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch, true);
 }
 
 int temporal_reset(RayzTemporal* tm) {
@@ -165,6 +194,15 @@ int rayz_hip_temporal_step(RayzTemporal* tm, const RayzTemporalParams* params_or
     return guarded([&] {
         return temporal_step(tm, params_or_null, camera, spp, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out, d_length_out_or_null,
                              hip_stream);
+    });
+}
+
+int rayz_hip_temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* params_or_null, const RayzCameraDesc* camera,
+                                  const uint32_t* d_counts, const float* d_rgb_in, const float* d_var_rgb, const RayzQueryOutputs* gbuffer,
+                                  float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, void* hip_stream) {
+    return guarded([&] {
+        return temporal_step_counts(tm, params_or_null, camera, d_counts, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out,
+                                    d_length_out_or_null, hip_stream);
     });
 }
 

@@ -84,8 +84,9 @@ template <int R> struct TaAcc {
 
 // §4.15 steps 1-3 for one pixel with id >= 0 of a handle with history: the sums over the history taps that are the same surface.
 // rec: the R arrays of the previous side whose records an accepted tap adds.  STATIC (the camera did not move): the one tap is
-// the pixel's own record, with weight 1.
-template <bool STATIC, int R>
+// the pixel's own record, with weight 1.  LIVE (the counts step, §4.23): a tap is also refused where its record's length is not > 0 —
+// a record that holds no samples; the plain, moments and feedback steps never write one and compile without the test.
+template <bool STATIC, int R, bool LIVE = false>
 __device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* const* rec, size_t p, int32_t id, float nx, float ny,
                                               float nz, float Px, float Py, float Pz) {
     TaAcc<R> acc;
@@ -96,7 +97,7 @@ __device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* 
             dn4 own[R];
 #pragma unroll
             for (int r = 0; r < R; ++r) own[r] = rec[r][p];
-            acc.add(own, 1.0f);
+            if (!LIVE || own[0].w > 0.0f) acc.add(own, 1.0f);
         }
         return acc;
     }
@@ -133,7 +134,7 @@ __device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* 
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
-        if (ok[t]) acc.add(tap[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy));
+        if (ok[t] && (!LIVE || tap[t][0].w > 0.0f)) acc.add(tap[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy));
     return acc;
 }
 
@@ -142,12 +143,17 @@ struct TaBlend {
     float al, k, N;
 };
 
-template <int R> __device__ __forceinline__ TaBlend ta_blend_head(const TaAcc<R>& acc, const TemporalArgs& a) {
+// spp: the samples the current frame adds to this pixel — the step's one count, or in the counts step (§4.23) the pixel's own.
+template <int R> __device__ __forceinline__ TaBlend ta_blend_head(const TaAcc<R>& acc, const TemporalArgs& a, float spp) {
     const float hN = acc.mean(0, 3);
-    const float Ns = hN + a.spp;
-    const float a0 = a.spp / Ns;
+    const float Ns = hN + spp;
+    const float a0 = spp / Ns;
     const float al = a0 < a.am ? a.am : a0;
     return TaBlend{al, 1.0f - al, Ns > a.nm ? a.nm : Ns};
+}
+
+template <int R> __device__ __forceinline__ TaBlend ta_blend_head(const TaAcc<R>& acc, const TemporalArgs& a) {
+    return ta_blend_head(acc, a, a.spp);
 }
 
 // .. and the blend of the current frame's x into the history's h, which the colour, m1 and m2 channels share.

@@ -52,13 +52,14 @@ int temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* stream_arg) {
 }
 
 // Its own checks, then temporal.hpp's temporal_run_step: every argument is checked before the handle.
+// d_counts: NULL for the step with one spp, else the counts step's array (§4.23), which stands for spp (then 0).
 int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, const RayzTemporalMomentsParams* mparams,
-                          const RayzCameraDesc* cam, uint32_t spp, const float* d_in, const RayzQueryOutputs* g, float* d_out,
-                          float* d_var_out, float* d_len_out, float* d_w2_out, void* stream_arg) {
+                          const RayzCameraDesc* cam, uint32_t spp, const uint32_t* d_counts, const float* d_in,
+                          const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, float* d_w2_out, void* stream_arg) {
     const RayzTemporalParams p = temporal_params_or_default(params);
     RayzTemporalMomentsParams mp{RAYZ_TEMPORAL_MOMENTS_DEFAULT_W2_MAX, RAYZ_TEMPORAL_MOMENTS_DEFAULT_MIN_TAPS};
     if (mparams) mp = *mparams;
-    RAYZ_TRY(temporal_params_check(p, spp));
+    RAYZ_TRY(temporal_params_check(p, d_counts ? 1 : spp));
     if (!(mp.w2_max >= 0 && mp.w2_max <= 1)) return fail(RAYZ_ERR_BAD_ARG, "temporal w2_max %g: must lie in [0, 1]", mp.w2_max);
     if (!(mp.min_taps >= 2 && mp.min_taps <= 49)) return fail(RAYZ_ERR_BAD_ARG, "temporal min_taps %g: must lie in [2, 49]", mp.min_taps);
     if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
@@ -70,12 +71,24 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
         a.t = t;
         a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
         a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
-        if (tm->feedback)
+        if (d_counts) { // (never a feedback handle: temporal_run_step refused it)
+            using namespace rayz_dev_counts;
+            temporal_launch_step(st, temporal_counts_moments_kernel<true>, temporal_counts_moments_kernel<false>, is_static,
+                                 TemporalMomentsCountsArgs{a, d_counts}, t.width, t.height);
+        } else if (tm->feedback)
             temporal_launch_step(st, temporal_feedback_step_kernel<true>, temporal_feedback_step_kernel<false>, is_static, a, t.width, t.height);
         else
             temporal_launch_step(st, temporal_moments_step_kernel<true>, temporal_moments_step_kernel<false>, is_static, a, t.width, t.height);
     };
-    return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch);
+    return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch, d_counts != nullptr);
+}
+
+// The counts step of a moments handle (§4.23): its counts' checks, then the step above.
+int temporal_step_moments_counts(RayzTemporal* tm, const RayzTemporalParams* params, const RayzTemporalMomentsParams* mparams,
+                                 const RayzCameraDesc* cam, const uint32_t* d_counts, const float* d_in, const RayzQueryOutputs* g,
+                                 float* d_out, float* d_var_out, float* d_len_out, float* d_w2_out, void* stream_arg) {
+    RAYZ_TRY(temporal_counts_check(d_counts, {d_out, d_var_out, d_len_out, d_w2_out}));
+    return temporal_step_moments(tm, params, mparams, cam, 0, d_counts, d_in, g, d_out, d_var_out, d_len_out, d_w2_out, stream_arg);
 }
 
 } // namespace
@@ -99,8 +112,19 @@ int rayz_hip_temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* p
                                    const float* d_rgb_in, const RayzQueryOutputs* gbuffer, float* d_rgb_out, float* d_var_out,
                                    float* d_length_out_or_null, float* d_w2_out_or_null, void* hip_stream) {
     return guarded([&] {
-        return temporal_step_moments(tm, params_or_null, mparams_or_null, camera, spp, d_rgb_in, gbuffer, d_rgb_out, d_var_out,
+        return temporal_step_moments(tm, params_or_null, mparams_or_null, camera, spp, nullptr, d_rgb_in, gbuffer, d_rgb_out, d_var_out,
                                      d_length_out_or_null, d_w2_out_or_null, hip_stream);
+    });
+}
+
+int rayz_hip_temporal_step_moments_counts(RayzTemporal* tm, const RayzTemporalParams* params_or_null,
+                                          const RayzTemporalMomentsParams* mparams_or_null, const RayzCameraDesc* camera,
+                                          const uint32_t* d_counts, const float* d_rgb_in, const RayzQueryOutputs* gbuffer,
+                                          float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, float* d_w2_out_or_null,
+                                          void* hip_stream) {
+    return guarded([&] {
+        return temporal_step_moments_counts(tm, params_or_null, mparams_or_null, camera, d_counts, d_rgb_in, gbuffer, d_rgb_out,
+                                            d_var_out, d_length_out_or_null, d_w2_out_or_null, hip_stream);
     });
 }
 

@@ -786,6 +786,21 @@ def lattice_pixels(width: int, height: int, f: int, phase, order: str = "rows", 
     return as_t(pixels), as_t(dest)
 
 
+def lattice_counts(width: int, height: int, f: int, phase, spp: int, device=None):
+    """The sample counts of a lattice frame, for `Temporal.step` / `step_moments`: an int32 (height, width) torch
+    tensor on `device` (None: the CPU) with `spp` at the pixels `lattice_pixels(width, height, f, phase)` lists and 0 elsewhere."""
+    import torch
+
+    px, py = _check_phase(f, phase)
+    if width <= 0 or height <= 0 or width % f or height % f:
+        raise ValueError(f"frame {width}x{height}: not a positive multiple of the factor {f} in both directions")
+    if not 0 <= int(spp) <= 1 << 24:
+        raise ValueError(f"spp {spp}: must lie in 0 .. 2^24 (it is used as f32)")
+    counts = np.zeros((height, width), np.int32)
+    counts[py::f, px::f] = int(spp)
+    return torch.from_numpy(counts).to(device if device is not None else "cpu")
+
+
 def lowres_camera(camera: capi.CameraDesc, factor: int) -> capi.CameraDesc:
     """The camera of a frame traced at 1/`factor` of the resolution in each direction: every low-resolution pixel sits at the centre
     of its factor x factor block of `camera`'s pixels.  `px_du` and `px_dv` are multiplied by the factor and
@@ -974,7 +989,19 @@ class Temporal(_Handle):
         _stream_prologue(stream, self._device)
         return out, var_out, [t for _, t in planes], _gbuffer_pointers(gbuffer, need)
 
-    def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
+    def _counts(self, spp):
+        """`spp` of a step: None for an int (the scalar step), or the checked int32 (height, width) tensor of per-pixel sample counts
+        a counts step takes, which the library reads as uint32: no value may be negative."""
+        import torch
+
+        if not isinstance(spp, torch.Tensor):
+            return None
+        _check_tensor("spp", spp, torch.int32, (self.height, self.width), self._device, "the temporal handle")
+        if int(spp.min()) < 0:
+            raise ValueError("spp holds a negative sample count")
+        return spp
+
+    def step(self, rgb, var_rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp, out=None, var_out=None, length=False,
              stream: int = 0, **params):
         """One frame: `rgb` and `var_rgb` ((height, width, 3) float32 on the handle's device: the frame and the variance of each
         channel of its pixel means, `Progressive.noise_rgb()`), `gbuffer` (index, normal, point of a float32 camera query of the same
@@ -982,19 +1009,24 @@ class Temporal(_Handle):
         default; `out=rgb` / `var_out=var_rgb` step in place — and, with `length` True or a (height, width) float32 tensor, the
         history length in samples as a third value.  `params`: the fields of RayzTemporalParams (alpha_min, n_max, normal_cos_min,
         max_rel_dist); unnamed ones take capi.TEMPORAL_DEFAULTS.  Asynchronous on `stream` (0: the library's stream, after torch's
-        work on the device has finished; another stream must itself be ordered after the inputs' producers)."""
+        work on the device has finished; another stream must itself be ordered after the inputs' producers).
+        `spp` may instead be an int32 (height, width) tensor on the handle's device, values >= 0 — the samples this frame adds to
+        each pixel (`lattice_counts`, `Progressive.sample_counts()`): the counts step (`rayz_hip_temporal_step_counts`, §4.23), in
+        which a pixel with count 0 keeps its history whatever `rgb` and `var_rgb` hold there."""
         prm = _params(capi.TemporalParams, capi.TEMPORAL_DEFAULTS, params, "temporal")
+        counts = self._counts(spp)
         out, var_out, (length,), o = self._step_prologue([("rgb", rgb), ("var_rgb", var_rgb)], gbuffer, out, var_out, [("length", length)],
                                                          stream)
-        rc = self._lib.rayz_hip_temporal_step(self._h, C.byref(prm), C.byref(camera), int(spp), C.c_void_p(rgb.data_ptr()),
-                                              C.c_void_p(var_rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
-                                              C.c_void_p(stream or None))
-        capi.check(self._lib, rc, "rayz_hip_temporal_step")
-        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length)
+        name = "rayz_hip_temporal_step" if counts is None else "rayz_hip_temporal_step_counts"
+        rc = getattr(self._lib, name)(self._h, C.byref(prm), C.byref(camera), int(spp) if counts is None else C.c_void_p(counts.data_ptr()),
+                                      C.c_void_p(rgb.data_ptr()), C.c_void_p(var_rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
+                                      C.c_void_p(stream or None))
+        capi.check(self._lib, rc, name)
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length, counts)
         return (out, var_out) if length is None else (out, var_out, length)
 
-    def step_moments(self, rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp: int, out=None, var_out=None, length=False,
+    def step_moments(self, rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp, out=None, var_out=None, length=False,
                      w2=False, stream: int = 0, **params):
         """One frame of a handle in moments mode (`rayz_hip_temporal_step_moments`): as `step` without `var_rgb` —
         the variance of the accumulated mean comes from the history's second moment, or where the history is too short from the
@@ -1003,7 +1035,9 @@ class Temporal(_Handle):
         (height, width) float32 tensor, the history length in samples, then, with `w2` likewise, W2 (the sum of the squared weights
         of the frames in `out`; 1 / W2 is the effective frame count).  `params`: the fields of RayzTemporalParams and of
         RayzTemporalMomentsParams (w2_max, min_taps); unnamed ones take capi.TEMPORAL_DEFAULTS and
-        capi.TEMPORAL_MOMENTS_DEFAULTS.  Asynchronous on `stream`, as `step`."""
+        capi.TEMPORAL_MOMENTS_DEFAULTS.  Asynchronous on `stream`, as `step`.  `spp` may be a tensor of per-pixel sample counts as
+        in `step` (`rayz_hip_temporal_step_moments_counts`, §4.23): a pixel with count 0 keeps its history and is left out of its
+        neighbours' 7x7 estimates; a handle that tracks feedback refuses it."""
         import torch
 
         unknown = set(params) - set(capi.TEMPORAL_DEFAULTS) - set(capi.TEMPORAL_MOMENTS_DEFAULTS)
@@ -1016,14 +1050,16 @@ class Temporal(_Handle):
                        {k: v for k, v in params.items() if k in capi.TEMPORAL_MOMENTS_DEFAULTS}, "temporal")
         if out is rgb or (isinstance(out, torch.Tensor) and isinstance(rgb, torch.Tensor) and out.data_ptr() == rgb.data_ptr()):
             raise ValueError("out must not be rgb: a moments step cannot run in place (neighbours read the current frame)")
+        counts = self._counts(spp)
         out, var_out, (length, w2), o = self._step_prologue([("rgb", rgb)], gbuffer, out, var_out, [("length", length), ("w2", w2)], stream)
-        rc = self._lib.rayz_hip_temporal_step_moments(self._h, C.byref(prm), C.byref(mprm), C.byref(camera), int(spp),
-                                                      C.c_void_p(rgb.data_ptr()), C.byref(o), C.c_void_p(out.data_ptr()),
-                                                      C.c_void_p(var_out.data_ptr()),
-                                                      C.c_void_p(length.data_ptr() if length is not None else None),
-                                                      C.c_void_p(w2.data_ptr() if w2 is not None else None), C.c_void_p(stream or None))
-        capi.check(self._lib, rc, "rayz_hip_temporal_step_moments")
-        self._inflight = (rgb, gbuffer, out, var_out, length, w2)
+        name = "rayz_hip_temporal_step_moments" if counts is None else "rayz_hip_temporal_step_moments_counts"
+        rc = getattr(self._lib, name)(self._h, C.byref(prm), C.byref(mprm), C.byref(camera),
+                                      int(spp) if counts is None else C.c_void_p(counts.data_ptr()), C.c_void_p(rgb.data_ptr()), C.byref(o),
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(var_out.data_ptr()),
+                                      C.c_void_p(length.data_ptr() if length is not None else None),
+                                      C.c_void_p(w2.data_ptr() if w2 is not None else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, name)
+        self._inflight = (rgb, gbuffer, out, var_out, length, w2, counts)
         return (out, var_out) + tuple(t for t in (length, w2) if t is not None)
 
     def reset(self) -> None:

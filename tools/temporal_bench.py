@@ -45,7 +45,19 @@ rayz_hip_denoiser_run_guided_tap) on --moments' one-chunk fram
 (b) Quality.  Per frame, MSE against the --ref-spp frame of: the raw one-chunk frame; moments step + `run_guided`; and moments
     step on a feedback handle + `run_guided(tap_level=1)` with the tap fed back — both at the shipped defaults.
 
-    python tools/temporal_bench.py --feedback [--settle 6] [the switches above]"""
+    python tools/temporal_bench.py --feedback [--settle 6] [the switches above]
+
+--counts measures the counts step (rayz_hip_temporal_step_counts / _step_moments_counts).
+(a) Cost.  The counts step beside the scalar step of the same mode, plain and moments, by the handles' own HIP events in the same
+    process: a first frame, a static step, a panned step, on frames whose counts are an f = 2 lattice's (one pixel in four has 16,
+    the others 0), each beside a device copy of its compulsory bytes — the twin's plus the 4 B per pixel of the count.
+(b) Quality.  Per frame, MSE against the --ref-spp frame of three pipelines of (nearly) equal traced samples: an f = 2 lattice of
+    16 spp cycling `phase_sequence`, rebuilt around its pixels by `Upscaler.run(phase=)` (what a pixel without samples and without
+    history passes through), into a moments counts step, into `run_guided`; a `lowres_camera` frame of 16 spp in two tracked
+    chunks, `Upscaler.run` with its variance, `run_guided`; and a full-resolution frame of 4 spp in one chunk through the moments
+    step and `run_guided`.
+
+    python tools/temporal_bench.py --counts [the switches above]"""
 import argparse
 import json
 import os
@@ -230,6 +242,145 @@ def main_moments(args):
             json.dump(res, f, indent=1)
 
 
+def main_counts(args):
+    """--counts: see the module docstring."""
+    render.init(0)
+    t = tracer.randomBouncing(args.width, -50, 50, seed=42)  # config 3
+    t.samples_per_px, t.max_bounces = 16, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n, f = w * h, 2
+    ds = render.DeviceScene(sd)
+    res = {"mode": "counts", "size": f"{w}x{h}", "frames": args.frames, "pan_px": args.pan, "lattice_spp": 16, "factor": f,
+           "ref_spp": args.ref_spp, "reps": args.reps}
+    phases = render.phase_sequence(f)
+    up = render.Upscaler(w, h, f)
+    mse = lambda a, ref: float(((a.double() - ref.double()) ** 2).mean())  # noqa: E731
+
+    def params(spp, seed, chunk=0, base=p):
+        q = capi.RenderParams.from_buffer_copy(base)
+        q.samples_per_px, q.seed, q.chunk_spp = spp, seed, chunk
+        return q
+
+    def whole(c, q):
+        frame = torch.empty((q.height, q.width, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ds.render_into(c, q, frame.data_ptr())
+        ds.sync()
+        return frame
+
+    seq = []
+    for k in range(args.frames):
+        c = panned(cam, args.pan * k)
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        phase = phases[k % len(phases)]
+        pixels, dest = render.lattice_pixels(w, h, f, phase, device="cuda")
+        lat = torch.full((h // f, w // f, 3), float("nan"), dtype=torch.float32, device="cuda")
+        ds.render_pixels(c, params(16, 1000 + k), pixels, dest=dest, out=lat)
+        ds.sync()
+        rebuilt = up.run(lat, g.lattice(f, phase), g, phase=phase)  # the lattice's pixels as they are, the others around them
+        counts = render.lattice_counts(w, h, f, phase, 16, device="cuda")
+        c_lo, p_lo = render.lowres_camera(c, f), render.lowres_params(p, f)
+        pr = ds.progressive(c_lo, params(16, 1000 + k, 8, p_lo), track_noise=True)
+        lo = torch.empty((h // f, w // f, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        while not pr.done:
+            pr.step(0, lo.data_ptr())
+        lo_var = pr.noise_rgb()
+        pr.stats()
+        pr.close()
+        g_lo = ds.gbuffer(c_lo, p_lo)
+        ds.query_sync()
+        four = whole(c, params(4, 1000 + k))
+        ref = whole(c, params(args.ref_spp, 7))
+        torch.cuda.synchronize()
+        seq.append(dict(cam=c, g=g, phase=phase, rebuilt=rebuilt, counts=counts, lo=lo, lo_var=lo_var, g_lo=g_lo, four=four, ref=ref))
+        print(f"frame {k}: phase {phase}, lattice 16 spp, low resolution 16 spp, full 4 spp, reference {args.ref_spp} spp", flush=True)
+
+    # ---- (a) cost -------------------------------------------------------------------------------------------------------------
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    length, w2 = torch.empty((h, w), dtype=torch.float32, device="cuda"), torch.empty((h, w), dtype=torch.float32, device="cuda")
+    var_in = torch.full((h, w, 3), 0.01, dtype=torch.float32, device="cuda")
+    plain, mom = render.Temporal(w, h), render.Temporal(w, h, moments=True)
+    sixteen = torch.full((h, w), 16, dtype=torch.int32, device="cuda")
+
+    def step(kind, s, spp):
+        if kind.startswith("plain"):
+            plain.step(s["rebuilt"], var_in, s["g"], s["cam"], spp, out=out, var_out=vout, length=length)
+        else:
+            mom.step_moments(s["rebuilt"], s["g"], s["cam"], spp, out=out, var_out=vout, length=length, w2=w2)
+
+    res["copy"], res["cost"] = {}, {}
+    kinds = [("plain", STEP_BYTES, False), ("plain counts", STEP_BYTES + 4, True), ("moments", MOMENTS_STEP_BYTES, False),
+             ("moments counts", MOMENTS_STEP_BYTES + 4, True)]
+    for name, nbytes, _ in kinds:
+        cp = copy_ms(n * nbytes // 2, args.reps, args.warmup)
+        res["copy"][name] = {"ms": cp[0], "min": cp[1], "max": cp[2]}
+        print(f"copy moving a {name} step's compulsory bytes ({n * nbytes / 1e6:.1f} MB read + written): {cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}]",
+              flush=True)
+    for what, last in (("first", None), ("static", 0), ("panned", 1)):
+        row = {}
+        for name, nbytes, counted in kinds:
+            tm = plain if name.startswith("plain") else mom
+            ms = []
+            for r in range(args.warmup + args.reps):
+                tm.reset()
+                # (the history behind a timed step is a full one: every record holds samples, as after a phase cycle)
+                step(name, seq[0], sixteen if counted else 16)
+                if last is not None:
+                    step(name, seq[last], seq[last]["counts"] if counted else 16)
+                x = tm.timing()
+                if r >= args.warmup:
+                    ms.append(x)
+            med, cpm = statistics.median(ms), res["copy"][name]["ms"]
+            row[name] = {"ms": med, "min": min(ms), "max": max(ms), "ratio_to_copy": med / cpm}
+            print(f"{name:14s} step, {what:6s}: {med:.4f} ms [{min(ms):.4f}, {max(ms):.4f}] = {med / cpm:.2f} x the copy of its compulsory bytes",
+                  flush=True)
+        row["plain_counts_over_plain"] = row["plain counts"]["ms"] / row["plain"]["ms"]
+        row["moments_counts_over_moments"] = row["moments counts"]["ms"] / row["moments"]["ms"]
+        print(f"        {what}: counts / scalar: plain {row['plain_counts_over_plain']:.3f}, moments {row['moments_counts_over_moments']:.3f}", flush=True)
+        res["cost"][what] = row
+
+    # ---- (b) quality at the defaults ------------------------------------------------------------------------------------------------
+    dn = render.Denoiser(w, h)
+    den = torch.empty_like(out)
+    full = render.Temporal(w, h, moments=True)
+    mom.reset()
+    rows = []
+    for k, s in enumerate(seq):
+        row = {"frame": k, "mse_four_raw": mse(s["four"], s["ref"])}
+        mom.step_moments(s["rebuilt"], s["g"], s["cam"], s["counts"], out=out, var_out=vout, length=length)
+        dn.run_guided(out, vout, s["g"], out=den)
+        torch.cuda.synchronize()
+        hit = s["g"].index >= 0
+        row.update(mse_lattice=mse(out, s["ref"]), mse_lattice_guided=mse(den, s["ref"]),
+                   lattice_sampled_share=float((length[hit] > 0).float().mean()))
+        up_c, var_c = up.run(s["lo"], s["g_lo"], s["g"], var_rgb=s["lo_var"])
+        dn.run_guided(up_c, var_c, s["g"], out=den)
+        torch.cuda.synchronize()
+        row.update(mse_lowres=mse(up_c, s["ref"]), mse_lowres_guided=mse(den, s["ref"]))
+        full.step_moments(s["four"], s["g"], s["cam"], 4, out=out, var_out=vout)
+        dn.run_guided(out, vout, s["g"], out=den)
+        torch.cuda.synchronize()
+        row.update(mse_full4=mse(out, s["ref"]), mse_full4_guided=mse(den, s["ref"]))
+        rows.append(row)
+        print(f"frame {k:2d}: MSE lattice + counts step {row['mse_lattice']:.4e}, + guided {row['mse_lattice_guided']:.4e} "
+              f"({row['lattice_sampled_share']:.4f} of the hit pixels hold samples); low resolution + upscale {row['mse_lowres']:.4e}, + guided "
+              f"{row['mse_lowres_guided']:.4e}; full 4 spp + moments step {row['mse_full4']:.4e}, + guided {row['mse_full4_guided']:.4e}", flush=True)
+    res["rows"] = rows
+    for key in ("mse_lattice_guided", "mse_lowres_guided", "mse_full4_guided"):
+        res["mean_" + key] = statistics.mean(r[key] for r in rows)
+        print(f"mean over the frames of {key}: {res['mean_' + key]:.4e}", flush=True)
+    plain.close(), mom.close(), full.close(), dn.close(), up.close(), ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
 def event_ms(fn, reps, warmup):
     """Median [min, max] of fn() between two events on torch's current stream (fn enqueues there)."""
     ms = []
@@ -381,7 +532,10 @@ def main():
     ap.add_argument("--moments", action="store_true", help="measure the moments mode (DESIGN.md §4.16) beside the plain step")
     ap.add_argument("--settle", type=int, default=6, help="--moments: static frames behind a 'settled' history (W2 = 1 / settle)")
     ap.add_argument("--feedback", action="store_true", help="measure the feedback of the filtered colour (DESIGN.md §4.17) beside the moments step")
+    ap.add_argument("--counts", action="store_true", help="measure the counts step (DESIGN.md §4.23) beside the scalar steps")
     args = ap.parse_args()
+    if args.counts:
+        return main_counts(args)
     if args.feedback:
         return main_feedback(args)
     if args.moments:
