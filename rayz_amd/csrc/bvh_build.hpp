@@ -273,7 +273,7 @@ inline FlatBvh build(const std::vector<RayzSphere>& spheres, const std::vector<R
 // plane(i) = glo[k] + i·cell[k] with glo, cell f32 (products of a 16-bit index and a 24-bit mantissa are exact in f64).  A
 // lower plane gets the LARGEST index whose plane lies at or below (true plane − pad), an upper one the SMALLEST at or above
 // (true plane + pad): the held box always contains the padded true one.  `pad` covers the rounding of the device's slab
-// test (rayz_device.hpp: bvh_box_hit), which therefore needs no slack of its own.
+// test (bvh_walk.hpp: bvh_box_hit), which therefore needs no slack of its own.
 struct PlaneGrid {
     float glo[3] = {0, 0, 0}, cell[3] = {1, 1, 1};
     double extent = 0; // largest span of the grid (part of the padding's scale)

@@ -8,11 +8,22 @@
 // the chain went through; beside it the chain key (which surfaces, in which order), the depth and the first hit's index.
 //
 // Every segment is the query kernels' own scan (flat list) or walk (BVH): the same device functions in the same order
-// (rayz_device.hpp: scan_sphere_classes / narrow_flush / scan_triangles; bvh_begin / bvh_node_step / bvh_leaf_pair /
+// (flat_scan.hpp: scan_sphere_classes / narrow_flush / scan_triangles; bvh_walk.hpp: bvh_begin / bvh_node_step / bvh_leaf_pair /
 // bvh_candidate_passes), so a chain of depth 0 IS the camera query.  The depth loop is per wave: a lane whose chain has ended
 // idles in the walk (its cursor is kBvhDone) or traces its last ray again in the scan (full EXEC) and stores nothing; the wave
-// leaves when no lane is active.  Included by rayz_hip.hip behind rayz_device.hpp; the host side is chain.hpp.
+// leaves when no lane is active.  Included by rayz_hip.hip; the host side is chain.hpp.
 #pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bvh_walk.hpp"
+#include "device_math.hpp"
+#include "device_types.hpp"
+#include "flat_scan.hpp"
+#include "path_queue.hpp"
+#include "query_kernel.hpp"
+#include "shade.hpp"
 
 namespace rayz_dev {
 

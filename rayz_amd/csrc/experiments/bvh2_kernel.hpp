@@ -1,5 +1,5 @@
 // experiments/bvh2_kernel.hpp — RETIRED: the BVH walk with two paths per lane (trace_kernel_bvh2).  Device code, included by
-// rayz_device.hpp inside namespace rayz_dev, after the product walk it builds on (BvhQuery, bvh_node_step, shade, ..), and only
+// trace_kernels_bvh.hpp inside namespace rayz_dev, after the product walk it builds on (BvhQuery, bvh_node_step, shade, ..), and only
 // under -DRAYZ_EXPERIMENTS: no product build compiles it.  Kept so that its result can be measured again (tools/bvh2_bench.py).
 #pragma once
 

@@ -1,5 +1,5 @@
 // experiments/bvhx_kernel.hpp — RETIRED: the BVH walk with walker and shader waves (trace_kernel_bvhx).  Device code, included by
-// rayz_device.hpp inside namespace rayz_dev, after the product walk it builds on (BvhQuery, bvh_node_step, shade, ..), and only
+// trace_kernels_bvh.hpp inside namespace rayz_dev, after the product walk it builds on (BvhQuery, bvh_node_step, shade, ..), and only
 // under -DRAYZ_EXPERIMENTS: no product build compiles it.  Kept so that its result can be measured again (tools/bvhx_bench.py).
 #pragma once
 

@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "rayz_device.hpp"
+#include "device_types.hpp"
 
 namespace rayz_dev {
 

@@ -1,5 +1,5 @@
 // Plane runs of the flat list's scan: plain C++, shared by the library (rayz_hip.hip, device layout in
-// rayz_device.hpp) and the CPU test of the layout (tests/test_plane_runs.py).
+// device_types.hpp, flat_scan.hpp) and the CPU test of the layout (tests/test_plane_runs.py).
 #pragma once
 #include <stdint.h>
 
@@ -65,7 +65,7 @@ uint32_t plan_runs(const std::vector<uint32_t>& cls, CyOf cy_of, uint32_t group,
 }
 
 // ---- how far a scan reads ----------------------------------------------------------------------------------------------
-// The scan (rayz_device.hpp: scan_blocks) tests the slots [first, end) of a section of a stream in pairs of groups, and while
+// The scan (flat_scan.hpp: scan_blocks) tests the slots [first, end) of a section of a stream in pairs of groups, and while
 // it tests a group it loads the next one: the furthest group it loads is the ONE behind its last pair (the loop before round 7
 // loaded two).  Every section (plane blocks, loose blocks, bucket blocks, the mov-G stream) ends in kScanSpareGroups groups of
 // never-hit pads, so a scan that ends with its section stays inside it.  scan_reach = one past the last slot a scan loads; the

@@ -1,7 +1,7 @@
 // primary_lists.hpp — which spheres a pixel's camera rays can hit at all.  Every path of a pixel starts
 // with a ray from the lens through the pixel's square of the focus plane at a time in [0, 1): the spheres such a ray can meet
 // are a fact of (scene, camera, pixel), not of the sample.  may_hit() is the conservative test primary_lists_kernel
-// (rayz_device.hpp) builds each pixel's list with; the trace kernels compiled with RAYZ_TRACE_KERNEL_PRIMARY resolve a path's
+// (trace_kernels_flat.hpp) builds each pixel's list with; the trace kernels compiled with RAYZ_TRACE_KERNEL_PRIMARY resolve a path's
 // camera segment from the list (narrow_eval decides, as it does behind the scan) instead of scanning the whole flat list.
 // The test only has to be a SUPERSET: it is f64 throughout, host and device, and every inequality carries its margin.
 // Also compiled by the host compiler alone (tests/primary_lists_mirror.cpp).
@@ -28,7 +28,7 @@ constexpr uint32_t kNoList = 0xffffffffu;
 // AUTO's two gates, kPrimaryMinSpheres and kPrimaryMinSpp, stand beside kSetPayoffSlots in plane_runs.hpp with the figures they
 // were read from.
 
-// The camera as camera_ray (rayz_device.hpp) reads it, in f64.
+// The camera as camera_ray (shade.hpp) reads it, in f64.
 struct BeamCamera {
     double from[3], du[3], dv[3], pxo[3], defu[3], defv[3];
     uint32_t defocus;

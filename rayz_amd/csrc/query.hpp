@@ -4,7 +4,7 @@
 
 namespace {
 
-// query_key (rayz_device.hpp) and its inverse on the host: an order-preserving u64 of a double
+// query_key (query_kernel.hpp) and its inverse on the host: an order-preserving u64 of a double
 unsigned long long query_key_host(double x) {
     unsigned long long b;
     std::memcpy(&b, &x, 8);

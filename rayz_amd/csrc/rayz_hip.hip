@@ -7,8 +7,8 @@
 // done by the caller (torch.distributed in bench.py).
 //
 // One translation unit.  This file holds the scene (layout, upload, BVH upload), the chunk schedule and the trace launch: all that
-// decides what a trace kernel is launched with, which bench.py's kernel_sources_sha256 has to cover (rayz_device.hpp, above its
-// experiments/ includes).  It stands on host_base.hpp and includes, at its end, one header per feature: handle, internals, entries.
+// decides what a trace kernel is launched with.  It stands on host_base.hpp and includes, at its end, one header per feature: handle,
+// internals, entries.
 #include "../../include/rayz_hip.h"
 #include "rayz_device.hpp"
 #include "chain_kernel.hpp"
@@ -367,10 +367,10 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         return r4{(R)q.center[0], (R)q.center[1], (R)q.center[2], (R)pad_radius2_scan<R>(q, b.pad_S)};
     };
     // static / mov-Y streams (f32 for both precisions): blocks of G spheres, SoA inside a block (field f of sphere k of
-    // block g at g·W·G + f·G + k).  After the head (kPlaneHeader words: layout and run table, rayz_device.hpp), the plane
+    // block g at g·W·G + f·G + k).  After the head (kPlaneHeader words: layout and run table, device_types.hpp), the plane
     // section — its runs at their slots, W = F − 1 fields (no cy: the run table holds it), two spare groups — then the
     // loose section, W = F, two spare groups.  Pad spheres {0, (0,) 0, r² = -inf, vy = 0}.  The field offsets are the device
-    // forms' own (PackedGroup in rayz_device.hpp): every sphere and pad below is placed by the form's put().
+    // forms' own (PackedGroup in flat_scan.hpp): every sphere and pad below is placed by the form's put().
     const float ninf32 = -std::numeric_limits<float>::infinity();
     auto rec32 = [&](uint32_t pool) { // r2 = the PADDED r² of the conservative filter
         const RayzSphere& q = s->spheres[pool];
@@ -393,7 +393,7 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
         for (const PlaneRun& r : nb.runs[c]) reach(r.first, r.end, G, n_plane); // (a mov-Y run's remainder starts later, ends there)
         reach(0, class_slots - nb.plane_slots[c], G, n_loose);
         std::vector<float> v(kPlaneHeader + (size_t)n_plane * P + (size_t)n_loose * F, 0.0f);
-        const uint32_t head[4] = {(uint32_t)nb.runs[c].size(), nb.plane_slots[c], 0u, 0u}; // the stream's head (rayz_device.hpp)
+        const uint32_t head[4] = {(uint32_t)nb.runs[c].size(), nb.plane_slots[c], 0u, 0u}; // the stream's head (device_types.hpp)
         std::memcpy(v.data(), head, sizeof(head));
         std::memcpy(v.data() + 4, nb.runs[c].data(), nb.runs[c].size() * sizeof(PlaneRun));
         float* const plane = v.data() + kPlaneHeader;
@@ -406,7 +406,7 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
                 Run::put(plane, k, rec32(pool));
             }
         for (size_t k = 0; k < nb.loose[c].size(); ++k) Loose::put(loose, k, rec32(nb.loose[c][k]));
-        // The set section (rayz_device.hpp), behind everything the stream held before it: {sets, copied bucket records, 0, 0, the
+        // The set section (device_types.hpp), behind everything the stream held before it: {sets, copied bucket records, 0, 0, the
         // first old-form slot of each run}, the set table, the bucket table once more with each bucket's first old-form slot, the
         // sets' 2-field blocks cx[G'] cz[G'] back to back, two spare groups.  Nothing in front of it changes.
         auto append_sets = [&](std::vector<float>& v, std::vector<rayz_plane::SpeedBucket> table) {
@@ -444,7 +444,7 @@ template <class R> int upload_body(RayzScene* s, SceneBuffers<R>& b) {
             append_sets(v, {});
             return v;
         }
-        // mov-Y only: the bucket section (rayz_device.hpp) — per run the first slot of its 4-field remainder, the bucket table,
+        // mov-Y only: the bucket section (device_types.hpp) — per run the first slot of its 4-field remainder, the bucket table,
         // the buckets' 3-field blocks cx[G] cz[G] r2b[G] back to back, two spare groups.  Head words 2 and 3: where, how many.
         // (The buckets' slots keep their places in the plane section above, unused.)
         std::vector<rayz_plane::SpeedBucket> table;
@@ -668,7 +668,7 @@ template <class R> int upload_bvh_body(RayzScene* s, SceneBuffers<R>& b) {
                 inner_order.push_back((uint32_t)i);
             }
     }
-    // the boxes go to the device PADDED: the slab test carries no slack of its own (rayz_device.hpp: bvh_box_hit;
+    // the boxes go to the device PADDED: the slab test carries no slack of its own (bvh_walk.hpp: bvh_box_hit;
     // E = 16u·max(S, B) for f32 planes rounded outward, 16u·(max(S, B) + X) for plane indices on a grid of extent X)
     double box_B = 0;
     rayz_bvh::Box all;

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "device_types.hpp"
 #include "noise.hpp"
 
 namespace rayz_dev {

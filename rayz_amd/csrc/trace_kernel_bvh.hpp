@@ -1,6 +1,13 @@
-// trace_kernel_bvh.hpp — the text of the one-path BVH trace kernel (described in rayz_device.hpp, which includes this file TWICE: as
-// trace_kernel_bvh, the product kernel, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel_bvh, the kernel of an
-// adaptive pass; see trace_kernel_flat.hpp for why one text and not one function).  No include guard.
+// trace_kernel_bvh.hpp — the text of the one-path BVH trace kernel.  trace_kernels_bvh.hpp includes it once per kernel, lists the
+// kernels and describes the round; see trace_kernel_flat.hpp for why one text and not one function.  No include guard.  An includer
+// defines RAYZ_TRACE_KERNEL_NAME (required) and, for an adaptive pass's kernel, RAYZ_TRACE_KERNEL_ADAPTIVE true
+// (default false); the text undefines both at its end.
+#ifndef RAYZ_TRACE_KERNEL_NAME
+#error "define RAYZ_TRACE_KERNEL_NAME before including trace_kernel_bvh.hpp"
+#endif
+#ifndef RAYZ_TRACE_KERNEL_ADAPTIVE
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#endif
 template <class R, bool QUANT> __global__ __launch_bounds__(RAYZ_BVH_WG, (bvh_waves<R>() * 256 >= RAYZ_BVH_WG ? bvh_waves<R>() * 256 / RAYZ_BVH_WG : 1))
 void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
     constexpr bool kAdaptive = RAYZ_TRACE_KERNEL_ADAPTIVE; // work items over the active list (place_item)
@@ -238,3 +245,5 @@ void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
         atomicAdd(&A.counters[3], t2);
     }
 }
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE

@@ -1,54 +1,62 @@
-// trace_kernel_flat.hpp — the text of the persistent flat-list trace kernel (described in rayz_device.hpp, which includes this file
-// FOUR times: as trace_kernel, the product kernel, as flat_xy_kernel — RAYZ_TRACE_KERNEL_BASIS kBasisXY — the same kernel with
-// the reject test's other basis, as flat_one_radius_kernel — RAYZ_TRACE_KERNEL_SETS true — that one with the one-radius sets in a
-// loop of their own, and — RAYZ_TRACE_KERNEL_ADAPTIVE true — as adaptive_pass_kernel, the kernel of an
-// adaptive pass).  One text, four kernels of four NAMES, and not further template flags on trace_kernel:
-// tests/test_isa_invariants.py counts the kernels named trace_kernel.. (six) and holds each to the product's limits, so a kernel
-// of that name is a product kernel; the adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared
-// body FUNCTION: handing the kernel's argument block to it changes the product kernel's register allocation; compiled twice,
-// trace_kernel's ISA is what it was.  No include guard.
-// RAYZ_TRACE_KERNEL_PRIMARY true — three more times, as primary_xz_kernel, primary_xy_kernel and primary_one_radius_kernel: the
-// three scan forms with each path's CAMERA segment resolved from its pixel's primary list (primary_lists.hpp)
+// trace_kernel_flat.hpp — the text of the persistent flat-list trace kernel.  trace_kernels_flat.hpp includes it once per kernel,
+// lists the kernels and describes the work items and the summation tree.  No include guard.
+//
+// THE PROTOCOL.  An includer defines RAYZ_TRACE_KERNEL_NAME (required) and whichever of the parameters below its kernel differs
+// in, then includes this file.  The text defaults what was left out and undefines every parameter at its end, so nothing is
+// carried from one kernel to the next:
+//   RAYZ_TRACE_KERNEL_ARGS      the argument block                                            TraceArgs<R>
+//   RAYZ_TRACE_KERNEL_BASIS     the reject test's basis (RayBasis)                            kBasisXZ
+//   RAYZ_TRACE_KERNEL_ADAPTIVE  work items over an adaptive pass's active list (§4.14)        false
+//   RAYZ_TRACE_KERNEL_SETS      the one-radius sets in a loop of their own                    false
+//   RAYZ_TRACE_KERNEL_PRIMARY   camera segments from the pixels' primary lists                false
+//   RAYZ_TRACE_KERNEL_CELLS     listable segments from the slab's cells                       false
+// One text and kernels of their own NAMES, not further template flags on trace_kernel: tests/test_isa_invariants.py counts the
+// kernels named trace_kernel.. (six) and holds each to the product's limits, so a kernel of that name is a product kernel; the
+// adaptive ones are held to the same limits by tests/test_adaptive_isa.py.  Nor a shared body FUNCTION: handing the kernel's
+// argument block to it changes the product kernel's register allocation; compiled once per name, trace_kernel's ISA is what it was.
+//
+// THE PHASES.  An iteration of the loop refills idle slots, sets up each slot's ray (scan_begin), finds its nearest hit and shades.
+// RAYZ_TRACE_KERNEL_PRIMARY: each path's CAMERA segment is resolved from its pixel's primary list (primary_lists.hpp)
 // instead of a scan.  An iteration of the loop is then either a LIST phase — taken while any lane of the wave holds a fresh path
 // (seg == 0) on a pixel that has a list: those lanes alone take their listed slots through narrow_eval, count the segment and
 // shade; a path that ends there (sky, absorption, depth) is replaced at the top of the next iteration, the chunk retired and the
 // next item popped as ever — or a SCAN phase as before, once every live lane's next segment needs the scan (a later segment,
 // or the camera segment of a pixel without a list).  The refill therefore repeats, wave-cooperative, until every lane holds a
 // path that needs a scan or the queue is drained; nothing else differs: same streams, same sums, same segments counter.
-// RAYZ_TRACE_KERNEL_CELLS true — three more times, as cells_xz_kernel, cells_xy_kernel and cells_one_radius_kernel: the three scan
-// forms with every segment whose ray crosses the members' slab under a handful of cells (slab_cells.hpp) resolved
-// from the outliers and those cells' slots.  After scan_begin each live lane learns whether its next segment is LISTABLE: a fresh
-// path on a pixel with a primary list (where the launch has lists: A.primary may be null), else whatever cells_query says.  With n
+// RAYZ_TRACE_KERNEL_CELLS: every segment whose ray crosses the members' slab under a handful of cells (slab_cells.hpp, DESIGN.md
+// §4.22) is resolved from the outliers and those cells' slots.  After scan_begin each live lane learns whether its next segment is
+// LISTABLE: a fresh path on a pixel with a primary list (where the launch has lists: A.primary may be null), else whatever cells_query says.  With n
 // such lanes of m live ones, the wave runs a list phase for those lanes alone if n >= min(kListLanes, m), else the scan for every
 // live lane, listable or not: a list phase never runs for a few lanes while the rest wait, and no lane waits longer for its scan
 // than the threshold lets it.  The tie rule of accept_root is order-independent and a member sits in exactly one cell: the same
 // tbest and ibest as the scan's, bit for bit.
-#ifdef RAYZ_TRACE_KERNEL_ARGS
+#ifndef RAYZ_TRACE_KERNEL_NAME
+#error "define RAYZ_TRACE_KERNEL_NAME before including trace_kernel_flat.hpp"
+#endif
+#ifndef RAYZ_TRACE_KERNEL_ARGS
+#define RAYZ_TRACE_KERNEL_ARGS TraceArgs<R>
+#endif
+#ifndef RAYZ_TRACE_KERNEL_BASIS
+#define RAYZ_TRACE_KERNEL_BASIS kBasisXZ
+#endif
+#ifndef RAYZ_TRACE_KERNEL_ADAPTIVE
+#define RAYZ_TRACE_KERNEL_ADAPTIVE false
+#endif
+#ifndef RAYZ_TRACE_KERNEL_SETS
+#define RAYZ_TRACE_KERNEL_SETS false
+#endif
+#ifndef RAYZ_TRACE_KERNEL_PRIMARY
+#define RAYZ_TRACE_KERNEL_PRIMARY false
+#endif
+#ifndef RAYZ_TRACE_KERNEL_CELLS
+#define RAYZ_TRACE_KERNEL_CELLS false
+#endif
 template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const RAYZ_TRACE_KERNEL_ARGS A) {
-#else
-template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>())) void RAYZ_TRACE_KERNEL_NAME(const TraceArgs<R> A) {
-#endif
     constexpr bool kAdaptive = RAYZ_TRACE_KERNEL_ADAPTIVE; // work items over the active list (place_item)
-#ifdef RAYZ_TRACE_KERNEL_BASIS
-    constexpr int kBasis = RAYZ_TRACE_KERNEL_BASIS; // the reject test's basis (RayBasis)
-#else
-    constexpr int kBasis = kBasisXZ;
-#endif
-#ifdef RAYZ_TRACE_KERNEL_SETS
-    constexpr bool kSets = RAYZ_TRACE_KERNEL_SETS; // the one-radius sets in their own loop (scan_plane_class)
-#else
-    constexpr bool kSets = false;
-#endif
-#ifdef RAYZ_TRACE_KERNEL_PRIMARY
-    constexpr bool kPrimary = RAYZ_TRACE_KERNEL_PRIMARY; // camera segments from the pixels' primary lists
-#else
-    constexpr bool kPrimary = false;
-#endif
-#ifdef RAYZ_TRACE_KERNEL_CELLS
-    constexpr bool kCells = RAYZ_TRACE_KERNEL_CELLS; // listable segments from the slab's cells (and the primary lists, where launched with them)
-#else
-    constexpr bool kCells = false;
-#endif
+    constexpr int kBasis = RAYZ_TRACE_KERNEL_BASIS;        // the reject test's basis (RayBasis)
+    constexpr bool kSets = RAYZ_TRACE_KERNEL_SETS;         // the one-radius sets in their own loop (scan_plane_class)
+    constexpr bool kPrimary = RAYZ_TRACE_KERNEL_PRIMARY;   // camera segments from the pixels' primary lists
+    constexpr bool kCells = RAYZ_TRACE_KERNEL_CELLS;       // listable segments from the slab's cells (and the primary lists, where launched with them)
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     PathState<R> p[NR];
 #pragma unroll
@@ -256,3 +264,10 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     for (int off = 32; off > 0; off >>= 1) tot += __shfl_xor(tot, off);
     if (lane == 0) atomicAdd(&A.counters[1], tot);
 }
+#undef RAYZ_TRACE_KERNEL_NAME
+#undef RAYZ_TRACE_KERNEL_ARGS
+#undef RAYZ_TRACE_KERNEL_BASIS
+#undef RAYZ_TRACE_KERNEL_ADAPTIVE
+#undef RAYZ_TRACE_KERNEL_SETS
+#undef RAYZ_TRACE_KERNEL_PRIMARY
+#undef RAYZ_TRACE_KERNEL_CELLS

@@ -255,7 +255,7 @@ struct Camera {
         return c;
     }
     // getRay(px, py, null): the rng-less form (src/camera.zig:59-77 with rng == null).  The jittered
-    // form is device code (csrc/rayz_device.hpp camera_ray).
+    // form is device code (csrc/shade.hpp camera_ray).
     Ray getRay(size_t px, size_t py) const {
         const double x = (double)px, y = (double)py;
         Ray r;

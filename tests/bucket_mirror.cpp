@@ -30,7 +30,7 @@ static std::vector<double> read_rows(const char* path) {
 
 template <class R> static R fm(R a, R b, R c) { return std::fma(a, b, c); }
 
-template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp: unit(d) in R
+template <class R> static void unit(const double* d, R* u) { // device_math.hpp: unit(d) in R
     const R x = (R)d[0], y = (R)d[1], z = (R)d[2];
     const R m = std::sqrt(fm(z, z, fm(y, y, x * x)));
     const R inv = R(1) / m;
@@ -38,7 +38,7 @@ template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp:
 }
 
 struct Basis { float e1x, e1z, e2x, e2y, e2z, k1, k2; };
-static Basis make_basis(const float* ud, const float* o) { // rayz_device.hpp: make_basis<float>
+static Basis make_basis(const float* ud, const float* o) { // flat_scan.hpp: make_basis<float>
     Basis b;
     const float h2 = fm(ud[2], ud[2], ud[0] * ud[0]);
     b.e1x = 1.0f, b.e1z = 0.0f;
@@ -87,7 +87,7 @@ static float pad_r2b(const double* s, double S, bool f64_rays, float v0) {
     return round_up32(rp * rp);
 }
 
-// rayz_device.hpp: bucket_k2, then ScanGroup<float, 3>::discs
+// flat_scan.hpp: bucket_k2, then ScanGroup<float, 3>::discs
 static float bucket_k2(float v0, float cy, float ft, const Basis& b) { return fm(v0, ft * b.e2y, fm(cy, b.e2y, b.k2)); }
 static float bucket_disc(const Basis& b, float K2, float cx, float cz, float r2b) {
     float p1 = fm(cx, b.e1x, b.k1), p2 = fm(cx, b.e2x, K2);
@@ -104,7 +104,7 @@ static float run_disc(const Basis& b, float cy, float ft, float cx, float cz, fl
     p2 = fm(vy, ft * b.e2y, p2);
     return fm(-p1, p1, fm(-p2, p2, r2));
 }
-// rayz_device.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
+// flat_scan.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
 static bool f64_hit(const double* s, const double* ry, bool f64_rays) {
     const float ft = (float)ry[6];
     double o[3], d[3];

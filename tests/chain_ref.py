@@ -154,7 +154,7 @@ def _fma(a, b, c, rt):
 
 def _tri_record(v0, v1, v2, o, d, t, rt):
     """pt = fm(d, t, o); n = unit(cross3(e1, e2)) with e = (R)(v - v0), flipped to face the ray — the arithmetic of the device's
-    hit record (rayz_device.hpp: cross3, dot3, unit, face_forward), one rounding per operation, FMAs exact."""
+    hit record (device_math.hpp: cross3, dot3, unit; shade.hpp: face_forward), one rounding per operation, FMAs exact."""
     r = lambda x: float(rt(x))  # noqa: E731
     e1, e2 = [r(v1[k] - v0[k]) for k in range(3)], [r(v2[k] - v0[k]) for k in range(3)]
     pt = [_fma(d[k], t, o[k], rt) for k in range(3)]

@@ -1,4 +1,4 @@
-// CPU mirror of the flat list's reject test in its XY basis (rayz_device.hpp: kBasisXY, flat_xy_kernel) and of the
+// CPU mirror of the flat list's reject test in its XY basis (flat_scan.hpp: kBasisXY; trace_kernels_flat.hpp: flat_xy_kernel) and of the
 // host's choice between the two bases (rayz_amd/csrc/plane_runs.hpp: scan_price), for tests/test_flat_xy.py and
 // tests/test_flat_xy_gpu.py.  Built by the tests with g++ -ffp-contract=off: every fm() below is one std::fma, as on the GPU.
 //   price <plane_static> <bucket> <plane_movy> <loose_static> <loose_movy> <movg>   -> both prices and the form chosen
@@ -31,7 +31,7 @@ static std::vector<double> read_rows(const char* path) {
 
 template <class R> static R fm(R a, R b, R c) { return std::fma(a, b, c); }
 
-template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp: unit(d) in R
+template <class R> static void unit(const double* d, R* u) { // device_math.hpp: unit(d) in R
     const R x = (R)d[0], y = (R)d[1], z = (R)d[2];
     const R m = std::sqrt(fm(z, z, fm(y, y, x * x)));
     const R inv = R(1) / m;
@@ -40,7 +40,7 @@ template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp:
 
 // e1 = (e1x, e1w, 0) in the XY basis (e1w = e1y), (e1x, 0, e1w) in the XZ basis (e1w = e1z)
 struct Basis { float e1x, e1w, e2x, e2y, e2z, k1, k2; };
-static Basis make_basis_xy(const float* ud, const float* o) { // rayz_device.hpp: make_basis<float, kBasisXY>
+static Basis make_basis_xy(const float* ud, const float* o) { // flat_scan.hpp: make_basis<float, kBasisXY>
     Basis b;
     const float h2 = fm(ud[1], ud[1], ud[0] * ud[0]);
     b.e1x = 1.0f, b.e1w = 0.0f;
@@ -56,7 +56,7 @@ static Basis make_basis_xy(const float* ud, const float* o) { // rayz_device.hpp
     b.k2 = -fm(o[2], b.e2z, fm(o[1], b.e2y, o[0] * b.e2x));
     return b;
 }
-static Basis make_basis_xz(const float* ud, const float* o) { // rayz_device.hpp: make_basis<float, kBasisXZ>
+static Basis make_basis_xz(const float* ud, const float* o) { // flat_scan.hpp: make_basis<float, kBasisXZ>
     Basis b;
     const float h2 = fm(ud[2], ud[2], ud[0] * ud[0]);
     b.e1x = 1.0f, b.e1w = 0.0f;
@@ -104,7 +104,7 @@ static float pad_r2b(const double* s, double S, bool f64_rays, float v0) {
 }
 
 static float disc_of(float p1, float p2, float r2) { return fm(-p1, p1, fm(-p2, p2, r2)); }
-// ---- the XY forms (rayz_device.hpp: plane_run_k1 / _k2, bucket_k1 / _k2, PackedGroup::discs(RayBasis<R, kBasisXY>), the
+// ---- the XY forms (flat_scan.hpp: plane_run_k1 / _k2, bucket_k1 / _k2, PackedGroup::discs(RayBasis<R, kBasisXY>), the
 // general-velocity ScanGroup<R, 2>::disc), in the device's order of stages ----
 static float run_k(float cy, float ey, float k) { return fm(cy, ey, k); }
 static float bucket_k(float v0, float cy, float ft, float ey, float k) { return fm(v0, ft * ey, fm(cy, ey, k)); }
@@ -161,7 +161,7 @@ static float xz_movg(const Basis& b, float ft, const float* c, const float* v, f
     return disc_of(p1, p2, r2);
 }
 
-// rayz_device.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
+// flat_scan.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
 static bool f64_hit(const double* s, const double* ry, bool f64_rays) {
     const float ft = (float)ry[6];
     double o[3], d[3];

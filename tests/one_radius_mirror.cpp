@@ -28,7 +28,7 @@ static std::vector<double> read_rows(const char* path) {
 
 template <class R> static R fm(R a, R b, R c) { return std::fma(a, b, c); }
 
-template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp: unit(d) in R
+template <class R> static void unit(const double* d, R* u) { // device_math.hpp: unit(d) in R
     const R x = (R)d[0], y = (R)d[1], z = (R)d[2];
     const R m = std::sqrt(fm(z, z, fm(y, y, x * x)));
     const R inv = R(1) / m;
@@ -36,7 +36,7 @@ template <class R> static void unit(const double* d, R* u) { // rayz_device.hpp:
 }
 
 struct Basis { float e1x, e1y, e2x, e2y, e2z, k1, k2; };
-static Basis make_basis(const float* ud, const float* o) { // rayz_device.hpp: make_basis<float, kBasisXY>
+static Basis make_basis(const float* ud, const float* o) { // flat_scan.hpp: make_basis<float, kBasisXY>
     Basis b;
     const float h2 = fm(ud[1], ud[1], ud[0] * ud[0]);
     b.e1x = 1.0f, b.e1y = 0.0f;
@@ -78,7 +78,7 @@ static float pad_r2(const double* s, double S, bool f64_rays, double h, double r
     return round_up32(rp * rp);
 }
 
-// rayz_device.hpp: plane_run_k1 / _k2, bucket_k1 / _k2, then PackedGroup::discs of the xy basis on a block without cy and vy
+// flat_scan.hpp: plane_run_k1 / _k2, bucket_k1 / _k2, then PackedGroup::discs of the xy basis on a block without cy and vy
 static void set_k(const Basis& b, bool movy, float v0, float cy, float ft, float& K1, float& K2) {
     K1 = fm(cy, b.e1y, b.k1), K2 = fm(cy, b.e2y, b.k2);
     if (movy) K1 = fm(v0, ft * b.e1y, K1), K2 = fm(v0, ft * b.e2y, K2);
@@ -89,7 +89,7 @@ static float plane_disc(const Basis& b, float K1, float K2, float cx, float cz, 
     p2 = fm(cz, b.e2z, p2);
     return fm(-p1, p1, fm(-p2, p2, r2));
 }
-// rayz_device.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
+// flat_scan.hpp: narrow_eval's f64 discriminant on the pool's f64 sphere
 static bool f64_hit(const double* s, const double* ry, bool f64_rays) {
     const float ft = (float)ry[6];
     double o[3], d[3];

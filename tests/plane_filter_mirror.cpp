@@ -27,7 +27,7 @@ static std::vector<double> read_rows(const char* path) {
 
 template <class R> static R fm(R a, R b, R c) { return std::fma(a, b, c); }
 
-// the kernel's unit(d) in R (rayz_device.hpp: dot3, sq, 1/m, products)
+// the kernel's unit(d) in R (device_math.hpp: dot3, sq, 1/m, products)
 template <class R> static void unit(const double* d, R* u) {
     const R x = (R)d[0], y = (R)d[1], z = (R)d[2];
     const R m = std::sqrt(fm(z, z, fm(y, y, x * x)));
@@ -36,7 +36,7 @@ template <class R> static void unit(const double* d, R* u) {
 }
 
 struct Basis { float e1x, e1z, e2x, e2y, e2z, k1, k2; };
-static Basis make_basis(const float* ud, const float* o) { // rayz_device.hpp: make_basis<float>
+static Basis make_basis(const float* ud, const float* o) { // flat_scan.hpp: make_basis<float>
     Basis b;
     const float h2 = fm(ud[2], ud[2], ud[0] * ud[0]);
     b.e1x = 1.0f, b.e1z = 0.0f;
@@ -65,7 +65,7 @@ static float pad_r2(const double* s, double S, bool f64_rays) {
     return f;
 }
 
-// The plane form of a block as the device runs it for a plane run (rayz_device.hpp: scan_plane_class puts K2 in the basis,
+// The plane form of a block as the device runs it for a plane run (flat_scan.hpp: scan_plane_class puts K2 in the basis,
 // ScanGroup<float, 3 / 4>::discs), from a KAT record: the ray as kat_kernel narrows it (unit(d) in R, then f32).
 static int discs(const char* path, bool f64_rays) {
     const std::vector<double> rec = read_rows(path);
@@ -159,7 +159,7 @@ int main(int argc, char** argv) {
             for (uint32_t pool : diagonal ? own : cls[c]) {
                 if (cls_of[pool] != c) continue;
                 const double* s = &sph[7 * pool];
-                // the plane form (rayz_device.hpp: ScanGroup<float, 3 / 4>::discs), the sphere's own f32 cy as the run's
+                // the plane form (flat_scan.hpp: ScanGroup<float, 3 / 4>::discs), the sphere's own f32 cy as the run's
                 const float cx = (float)s[0], cy = (float)s[1], cz = (float)s[2], vy = (float)s[4];
                 const float K2 = fm(cy, b.e2y, b.k2);
                 float p1 = fm(cx, b.e1x, b.k1), p2 = fm(cx, b.e2x, K2);
@@ -168,7 +168,7 @@ int main(int argc, char** argv) {
                 if (c == 1) p2 = fm(vy, ft * b.e2y, p2);
                 const bool cand = fm(-p1, p1, fm(-p2, p2, r2[pool])) >= 0.0f;
                 if (fm(-p1, p1, fm(-p2, p2, -INFINITY)) >= 0.0f) ++pad_pass; // a pad slot of the same run
-                // the narrow phase's f64 discriminant (rayz_device.hpp: narrow_eval) on the pool's f64 sphere
+                // the narrow phase's f64 discriminant (flat_scan.hpp: narrow_eval) on the pool's f64 sphere
                 const double qx = fm(s[3], tt, s[0] - ox), qy = fm(s[4], tt, s[1] - oy), qz = fm(s[5], tt, s[2] - oz);
                 const double hb = fm(dz, qz, fm(dy, qy, dx * qx));
                 const double cc = fm(qz, qz, fm(qy, qy, fm(qx, qx, -(s[6] * s[6]))));

@@ -5,7 +5,7 @@
 //   hist    <spheres> <camera> <width> <height> [stride]   JSON: the histogram of the list lengths
 //   check   <spheres> <camera> <samples>                   JSON: every (sample, sphere) pair decided by the f64 quadratic, held to the lists
 //   check32 <spheres> <camera> <samples>                   the same for the ray the f32 kernels trace: the camera narrowed to float, o, d and
-//                                                          the time formed in float in camera_ray<float>'s operation order (rayz_device.hpp)
+//                                                          the time formed in float in camera_ray<float>'s operation order (shade.hpp)
 #include <cmath>
 #include <cstdint>
 #include <cstdio>

@@ -1,4 +1,4 @@
-"""The flat list's reject test in its XY basis (e1 in the xy-plane: DESIGN.md §4.3; rayz_device.hpp: kBasisXY, flat_xy_kernel) and the
+"""The flat list's reject test in its XY basis (e1 in the xy-plane: DESIGN.md §4.3; flat_scan.hpp: kBasisXY; trace_kernels_flat.hpp: flat_xy_kernel) and the
 host's choice between the two bases (rayz_amd/csrc/plane_runs.hpp: scan_price).  CPU checks through a C++ mirror built here
 (tests/flat_xy_mirror.cpp: the device's forms written with fmaf, and the library's own plane_runs.hpp):
   * 0 false negatives against the f64 discriminant, with f32 rays and with f64 rays narrowed, every sphere in the form its place

@@ -1,4 +1,4 @@
-"""The compiled f32 flat_xy_kernel (rayz_device.hpp: trace_kernel_flat.hpp once more, with the reject test's xy basis, DESIGN.md
+"""The compiled f32 flat_xy_kernel (trace_kernels_flat.hpp: trace_kernel_flat.hpp once more, with the reject test's xy basis, DESIGN.md
 §4.3, §6): what its five packed scan loops must look like on gfx950, found as tests/test_scan_feed.py finds trace_kernel's.
   * packed FMAs per iteration (two groups of G spheres, two spheres per v_pk_fma_f32): 5 per sphere pair in the static plane loop
     and the bucket loop, 7 in the mov-Y plane remainder, 7 on loose static spheres, 9 on loose y-moving ones;
@@ -11,7 +11,7 @@ import re
 
 import isa_asm
 
-G = 4  # rayz_device.hpp: group_size<float>()
+G = 4  # device_types.hpp: group_size<float>()
 F32 = "_ZN8rayz_dev14flat_xy_kernelIfLi1EEEvNS_9TraceArgsIT_EE"
 F64 = "_ZN8rayz_dev14flat_xy_kernelIdLi1EEEvNS_9TraceArgsIT_EE"
 PER_PAIR = [5, 7, 7, 9, 5]  # static plane, static loose, mov-Y plane, mov-Y loose, bucket: the scan's order

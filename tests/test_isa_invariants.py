@@ -1,4 +1,4 @@
-"""The BVH box step's node fetch leaves loads IN FLIGHT across compiler-scheduled code (rayz_device.hpp, bvh_node_step: the
+"""The BVH box step's node fetch leaves loads IN FLIGHT across compiler-scheduled code (bvh_walk.hpp, bvh_node_step: the
 inline asm waits for the left child's loads only, a second asm waits for the right child's): the compiler must not read,
 copy or overwrite the registers those loads are still writing.  The source holds them with "+v" operands; this test reads
 the gfx950 ISA of every kernel that contains the step and checks that nothing between the two waits names them."""
@@ -70,6 +70,10 @@ def test_experiments_build_still_compiles():
     only, all three shader-wave counts of the exchange kernel are instantiable."""
     text = isa_asm.device_asm("-DRAYZ_EXPERIMENTS", "-DRAYZ_BVHX_SHADERS=5")
     assert "trace_kernel_bvh2" in text and "trace_kernel_bvhx" in text
-    # .. and they stay out of the product's device header (their sources: rayz_amd/csrc/experiments/), so the move does not quietly revert
-    header = open(os.path.join(ROOT, "rayz_amd", "csrc", "rayz_device.hpp")).read()
-    assert "void trace_kernel_bvh2(" not in header and "void trace_kernel_bvhx(" not in header
+    # .. and they stay out of the product's device headers (their sources: rayz_amd/csrc/experiments/), so the move does not quietly revert
+    csrc = os.path.join(ROOT, "rayz_amd", "csrc")
+    headers = sorted(f for f in os.listdir(csrc) if f.endswith(".hpp"))
+    assert "rayz_device.hpp" in headers and "trace_kernels_bvh.hpp" in headers
+    for name in headers:
+        header = open(os.path.join(csrc, name)).read()
+        assert "void trace_kernel_bvh2(" not in header and "void trace_kernel_bvhx(" not in header, name

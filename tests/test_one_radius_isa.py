@@ -1,4 +1,4 @@
-"""The compiled f32 flat_one_radius_kernel (rayz_device.hpp: trace_kernel_flat.hpp a fourth time, the xy basis with the one-radius
+"""The compiled f32 flat_one_radius_kernel (trace_kernels_flat.hpp: trace_kernel_flat.hpp once more, the xy basis with the one-radius
 sets in scan_sets' loop): what its scan loops must look like on gfx950, found as tests/test_flat_xy_isa.py finds
 flat_xy_kernel's.
   * the five loops flat_xy_kernel has, with its packed-FMA counts (5, 7, 7, 9, 5 per sphere pair over two groups of 4), and the set
@@ -12,7 +12,7 @@ import re
 
 import isa_asm
 
-G, GS = 4, 8  # rayz_device.hpp: group_size<float>(); plane_runs.hpp: kSetGroup
+G, GS = 4, 8  # device_types.hpp: group_size<float>(); plane_runs.hpp: kSetGroup
 F32 = "_ZN8rayz_dev22flat_one_radius_kernelIfLi1EEEvNS_9TraceArgsIT_EE"
 F64 = "_ZN8rayz_dev22flat_one_radius_kernelIdLi1EEEvNS_9TraceArgsIT_EE"
 # static plane, static loose, static sets, mov-Y plane, mov-Y loose, bucket, mov-Y sets: the scan's order

@@ -20,7 +20,7 @@ from rayz_amd import capi, tracer
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-G = 4  # spheres per scan group (rayz_device.hpp: RAYZ_GROUP)
+G = 4  # spheres per scan group (device_types.hpp: RAYZ_GROUP)
 
 
 @pytest.fixture(scope="module")

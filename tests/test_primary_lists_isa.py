@@ -1,4 +1,4 @@
-"""The compiled primary_xz_kernel, primary_xy_kernel and primary_one_radius_kernel (rayz_device.hpp: trace_kernel_flat.hpp with
+"""The compiled primary_xz_kernel, primary_xy_kernel and primary_one_radius_kernel (trace_kernels_flat.hpp: trace_kernel_flat.hpp with
 RAYZ_TRACE_KERNEL_PRIMARY, the three scan forms with the camera segments from the pixels' primary lists) on gfx950:
   * each exists once per precision under a name of its own, none of which the ISA tests of the other trace kernels count, and
     primary_lists_kernel exists once;
@@ -12,7 +12,7 @@ import pytest
 
 import isa_asm
 
-G = 4  # rayz_device.hpp: group_size<float>()
+G = 4  # device_types.hpp: group_size<float>()
 MADE_FROM = {"primary_xz_kernel": "trace_kernel", "primary_xy_kernel": "flat_xy_kernel", "primary_one_radius_kernel": "flat_one_radius_kernel"}
 
 

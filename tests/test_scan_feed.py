@@ -83,7 +83,7 @@ def test_packed_loops_feed_from_a_running_pointer_behind_covered_loads(device_as
 
 
 def loaded_groups(first, end, group):
-    """The groups (by first slot) the scan of slots [first, end) loads, in the loop's order (rayz_device.hpp: scan_blocks): the
+    """The groups (by first slot) the scan of slots [first, end) loads, in the loop's order (flat_scan.hpp: scan_blocks): the
     first group before the loop; per iteration, the pair's second group, then the first of the next pair."""
     at, out = first, [first]
     while at < end:

@@ -1,4 +1,4 @@
-"""The cells kernels (rayz_device.hpp: trace_kernel_flat.hpp with RAYZ_TRACE_KERNEL_CELLS, the three scan forms with every listable
+"""The cells kernels (trace_kernels_flat.hpp: trace_kernel_flat.hpp with RAYZ_TRACE_KERNEL_CELLS, the three scan forms with every listable
 segment resolved from the slab's cells) added kernels and changed none.
 
   * tests/golden/kernels_before_cells.json holds, for each kernel of the build before them, the SHA-256 of its body as

@@ -46,7 +46,7 @@ def fma32(a, b, c):
 
 
 def bucket_discs_f32(rec):
-    """The f32 kernel's bucket form of a RAYZ_KAT_BUCKET_DISCS record (r2b at [28..31]): rayz_device.hpp's unit, make_basis,
+    """The f32 kernel's bucket form of a RAYZ_KAT_BUCKET_DISCS record (r2b at [28..31]): device_math.hpp's unit, flat_scan.hpp's make_basis,
     bucket_k2 and ScanGroup<float, 3>::discs, operation by operation."""
     d = f32(rec[:, 23:26])
     o = f32(rec[:, 20:23])
