@@ -6,7 +6,7 @@
 // thread per full pixel, weighs the 2x2 low-resolution pixels around it by their bilinear weight times the guide weight of the
 // à-trous tap (dn_guide(), shared with the denoiser: the full pixel's guides are the centre, the low-resolution pixel's the tap),
 // and multiplies the full pixel's own modulation back in — texture detail comes from the full-size albedo, only the irradiance
-// is interpolated.  A pixel no tap of its 2x2 footprint may be mixed with (W = 0: a thin feature, a silhouette) tries the 4x4
+// is interpolated.  A pixel no tap of its 2x2 footprint may be mixed with (W < 2^-40: a thin feature, a silhouette) tries the 4x4
 // footprint with the guide weight alone, and failing that takes the nearest low-resolution pixel's raw colour.
 //
 // The arithmetic is a contract (§4.20): + - x, the FMAs written below, correctly rounded divides, comparisons, integer
@@ -41,6 +41,11 @@ struct UpscaleArgs {
 struct UpAcc {
     float W, r, g, b, vr, vg, vb;
 };
+
+// A stage is taken only with W >= 2^-40 (§4.20): the largest of its at most 16 weights is then at least 2^-44, so neither its
+// square nor W·W underflows in f32.  With "W > 0" a footprint of nearly refused taps (cos^64 at a sphere's limb) gave V = W·W = 0
+// and a NaN variance.
+constexpr float kUpMinW = 0x1p-40f;
 
 // The per-channel variance record of the low-resolution frame: ve_ch = clamp_var(var_ch / (m_ch·m_ch)) with the pack pass's m.
 __global__ __launch_bounds__(256) void upscale_pack_var_kernel(const float* __restrict__ var_rgb, const dn4* __restrict__ mod,
@@ -118,7 +123,7 @@ template <bool VAR> __global__ __launch_bounds__(256) void upscale_direct_kernel
             up_tap<VAR>(a, pa, pb, qx, qy, b, acc);
         }
     }
-    if (!(acc.W > 0.0f)) { // stage 1 (rare): the 4x4 footprint, guide weight alone
+    if (!(acc.W >= kUpMinW)) { // stage 1 (rare): the 4x4 footprint, guide weight alone
         stage = 1;
         acc = UpAcc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         for (int dj = -1; dj <= 2; ++dj) {
@@ -131,7 +136,7 @@ template <bool VAR> __global__ __launch_bounds__(256) void upscale_direct_kernel
             }
         }
     }
-    if (acc.W > 0.0f) {
+    if (acc.W >= kUpMinW) {
         a.rgb[3 * p + 0] = (acc.r / acc.W) * mr;
         a.rgb[3 * p + 1] = (acc.g / acc.W) * mg;
         a.rgb[3 * p + 2] = (acc.b / acc.W) * mb;
@@ -230,7 +235,7 @@ template <bool VAR> __global__ __launch_bounds__(256) void upscale_phase_kernel(
             up_tap<VAR>(a, pa, pb, qx, qy, b, acc);
         }
     }
-    if (!(acc.W > 0.0f)) { // stage 1 (rare): the 4x4 footprint, guide weight alone
+    if (!(acc.W >= kUpMinW)) { // stage 1 (rare): the 4x4 footprint, guide weight alone
         stage = 1;
         acc = UpAcc{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         for (int dj = -1; dj <= 2; ++dj) {
@@ -243,7 +248,7 @@ template <bool VAR> __global__ __launch_bounds__(256) void upscale_phase_kernel(
             }
         }
     }
-    if (acc.W > 0.0f) {
+    if (acc.W >= kUpMinW) {
         a.rgb[3 * p + 0] = (acc.r / acc.W) * mr;
         a.rgb[3 * p + 1] = (acc.g / acc.W) * mg;
         a.rgb[3 * p + 2] = (acc.b / acc.W) * mb;

@@ -4,7 +4,8 @@ segment resolved from the slab's cells) added kernels and chan
   * tests/golden/kernels_before_cells.json holds, for each kernel of the build before them, the SHA-256 of its body as
     test_sparse_isa.normalised leaves it, recorded from that build with the compiler the file names: every one is what it was,
     instruction for instruction and label for label.  (Another compiler lays the same source out differently: under one the
-    comparison says nothing, and the test says so instead of failing.)
+    comparison says nothing, and the test says so instead of failing.)  The four upscale_direct_kernel / upscale_phase_kernel
+    entries were recorded again when §4.20's stage rule became W >= 2^-40, a change of those kernels made on purpose.
   * The six new kernels — one per scan form and precision — are the only new ones, under names no other ISA test counts and in
     a namespace of their own, rayz_dev_cells (tests/test_sparse_isa.py takes every kernel of rayz_dev that its record lacks for a
     sparse-render kernel).

@@ -15,8 +15,8 @@
 //       else wn = max0(dot(n_p, n_q)), squared normal_power_log2 times;  v = P_q - P_p;  d2 = dot(v, v);  pl = dot(n_p, v)
 //            wz = d2 == 0 ? 1 : u·u, u = max0(1 - (pl·pl) / (sp2·d2));  g = wn·wz
 //     w = b·g;  W = W + w;  acc_ch = fma(w, e_q,ch, acc_ch);  V_ch = fma(w·w, ve_q,ch, V_ch)
-//   Stage 1, if not W > 0: sums reset, taps (i0 + di, j0 + dj), dj outer, di inner, -1..2, b = 1.
-//   If W > 0: out_ch = (acc_ch / W)·m_p,ch;  var_ch = (V_ch / (W·W))·(m_p,ch·m_p,ch).
+//   Stage 1, if not W >= 2^-40: sums reset, taps (i0 + di, j0 + dj), dj outer, di inner, -1..2, b = 1.
+//   If W >= 2^-40: out_ch = (acc_ch / W)·m_p,ch;  var_ch = (V_ch / (W·W))·(m_p,ch·m_p,ch).
 //   Stage 2 otherwise: out = c of low-resolution pixel (x div f, y div f), var_ch = 2^32.
 //   dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x·b.x));  max0(x) = x > 0 ? x : 0.
 #include <cmath>
@@ -26,6 +26,7 @@
 namespace {
 
 const float VCAP = 4294967296.0f;
+const float WMIN = 9.094947017729282e-13f; // 2^-40
 
 inline float dot3(const float* a, const float* b) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
 inline float max0(float x) { return x > 0.0f ? x : 0.0f; }
@@ -116,7 +117,7 @@ void upscale_mirror(const float* rgb_lo, const float* var_lo, const int32_t* ind
                             if (with_var) s.V[c] = std::fmaf(wt * wt, clamp_var(var_lo[3 * q + c] / (mq[c] * mq[c])), s.V[c]);
                         }
                     }
-                if (s.W > 0.0f) break;
+                if (s.W >= WMIN) break;
             }
             if (stage < 2) {
                 for (int c = 0; c < 3; ++c) {

@@ -18,8 +18,8 @@
 //   Stage 0: taps (i0 + di, j0 + dj), dj outer, di inner, 0..1:  bx = di ? fx : 1 - fx, by likewise, b = bx·by;  skipped when outside
 //     the low-resolution frame, when b == 0 or when not accepted;  w = b·g;  W = W + w;  acc_ch = fma(w, e_q,ch, acc_ch);
 //     V_ch = fma(w·w, ve_q,ch, V_ch)
-//   Stage 1, if not W > 0: sums reset, taps (i0 + di, j0 + dj), dj outer, di inner, -1..2, b = 1.
-//   If W > 0: out_ch = (acc_ch / W)·m_p,ch;  var_ch = (V_ch / (W·W))·(m_p,ch·m_p,ch).
+//   Stage 1, if not W >= 2^-40: sums reset, taps (i0 + di, j0 + dj), dj outer, di inner, -1..2, b = 1.
+//   If W >= 2^-40: out_ch = (acc_ch / W)·m_p,ch;  var_ch = (V_ch / (W·W))·(m_p,ch·m_p,ch).
 //   Stage 2 otherwise: out = c of the NEAREST sample, per axis clamp(floor((2a + f) / 2f), 0, w - 1);  var_ch = 2^32.
 //   dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x·b.x));  max0(x) = x > 0 ? x : 0.
 #include <cmath>
@@ -29,6 +29,7 @@
 namespace {
 
 const float CAP = 4294967296.0f;
+const float LEAST_W = 1.0f / 1099511627776.0f; // 2^-40
 
 float dot(const float* a, const float* b) { return std::fmaf(a[2], b[2], std::fmaf(a[1], b[1], a[0] * b[0])); }
 float positive(float x) { return x > 0.0f ? x : 0.0f; }
@@ -134,13 +135,13 @@ void upscale_phase_mirror(const float* rgb_lo, const float* var_lo, const int32_
             Sums sums;
             for (long dj = 0; dj <= 1; ++dj)
                 for (long di = 0; di <= 1; ++di) sums.tap(s, p, i0 + di, j0 + dj, (di ? fx : 1.0f - fx) * (dj ? fy : 1.0f - fy));
-            if (!(sums.W > 0.0f)) {
+            if (!(sums.W >= LEAST_W)) {
                 stage = 1;
                 sums = Sums();
                 for (long dj = -1; dj <= 2; ++dj)
                     for (long di = -1; di <= 2; ++di) sums.tap(s, p, i0 + di, j0 + dj, 1.0f);
             }
-            if (sums.W > 0.0f) {
+            if (sums.W >= LEAST_W) {
                 for (int ch = 0; ch < 3; ++ch) {
                     const float m = s.hi.modulation(p, ch);
                     out[3 * p + ch] = (sums.acc[ch] / sums.W) * m;

@@ -9,7 +9,10 @@ The scene, in full-pixel units (X, Y) over [0, W) x [0, H):
   - thin strips, each one full pixel wide and far off every other surface along the ground's normal: slanted ones (x = x0 + y div k),
     which the low-resolution samples hit only every few rows — the pixels between two hits find their surface in the 4x4 footprint
     only (stage 1) or not at all (stage 2) —, and vertical ones that fall between the low-resolution samples (stage 2).
-Colours and variances are random (no dyadic structure); a few variances are +inf ("no estimate yet")."""
+Colours and variances are random (no dyadic structure); a few variances are +inf ("no estimate yet").
+
+Every surface above is flat, so a guide weight is 1 within a surface and 0 across two.  `curved_pair` (below) is the scene with
+weights in between: spheres, evaluated at the full pixel centres, the block centres or the samples of a lattice."""
 import numpy as np
 
 from upscale_ref import Guides
@@ -81,6 +84,84 @@ def synthetic_pair(w, h, f, seed):
     g_hi = _evaluate(xs, ys, W, H, consts)
     xs, ys = np.meshgrid((np.arange(w) + 0.5) * f, (np.arange(h) + 0.5) * f)
     g_lo = _evaluate(xs, ys, W, H, consts)
+    irradiance = rng.uniform(0.05, 2.0, (h, w, 3))
+    rgb_lo = (np.where(g_lo.index[..., None] < 0, 1.0, g_lo.albedo) * irradiance).astype(np.float32)
+    var_lo = (rng.uniform(0.0, 0.2, (h, w, 3)) ** 2).astype(np.float32)
+    var_lo[rng.uniform(size=(h, w)) < 0.05] = np.inf
+    return dict(rgb_lo=rgb_lo, var_lo=var_lo, g_lo=g_lo, g_hi=g_hi)
+
+
+# ---- a curved scene: guide weights between 0 and 1 (tests/upscale_f64.py, tests/test_upscale_f64_*.py)
+_S = 0.37        # world units per full pixel
+_GAP = 300.0     # world units between two surfaces' depths: every silhouette is a step far larger than any sphere
+
+
+def _evaluate_curved(X, Y, W, H, consts):
+    """The curved scene at the screen positions X, Y: an orthographic view along +z of spheres as height fields (analytic normals
+    and points, an albedo that varies with the normal), each at a depth of its own, in front of a tilted checkered ground below the
+    horizon Y = 0.45·H and of the background above it; in front of everything, spheres smaller than a low-resolution pixel and thin
+    slanted strips (the features the low-resolution samples miss: stages 1 and 2)."""
+    spheres, strips, a_even, a_odd = consts
+    shape = X.shape
+    K = len(spheres)
+    # the ground, behind everything
+    ng = _unit((0.1, 0.4, -1.0))
+    index = np.zeros(shape, np.int32)
+    normal = np.broadcast_to(ng, shape + (3,)).copy()
+    zg = _GAP * (K + 2) + _S * (0.4 * Y + 0.1 * X)  # (ng is this height field's normal)
+    point = np.stack([_S * X, _S * Y, zg], axis=-1)
+    cell = (np.floor(X / 1.5) + np.floor(Y / 1.5)).astype(np.int64) & 1
+    albedo = np.where(cell[..., None] == 1, a_odd, a_even)
+    ground_point = point.copy()
+    # the background above the horizon
+    m = Y < 0.45 * H
+    index[m] = -1
+    normal[m] = 0.0
+    point[m] = 0.0
+    albedo[m] = 0.0
+    # the spheres, far to near
+    for k in range(K - 1, -1, -1):
+        cx, cy, R, base = spheres[k]
+        dx, dy = X - cx, Y - cy
+        hz2 = R * R - dx * dx - dy * dy
+        m = hz2 > 0
+        hz = np.sqrt(np.where(m, hz2, 1.0))
+        n = np.stack([dx, dy, -hz], axis=-1) / R
+        index[m] = 1 + k
+        normal[m] = n[m]
+        point[m] = np.stack([_S * X, _S * Y, _GAP * (k + 1) - _S * hz], axis=-1)[m]
+        albedo[m] = (np.asarray(base) * (0.55 + 0.45 * n[..., :1] * n[..., 1:2] - 0.3 * n[..., 2:3] * n[..., :1]))[m]
+    # the strips: parallel to the ground, each far in front of it at a depth of its own
+    xi, yi = np.floor(X).astype(np.int64), np.floor(Y).astype(np.int64)
+    for s, (x0, k) in enumerate(strips):
+        m = xi == (x0 + yi // k)
+        index[m] = 100 + s
+        normal[m] = ng
+        point[m] = (ground_point - (1000.0 + 30.0 * s) * ng)[m]
+        albedo[m] = a_even
+    return Guides(index, normal.astype(np.float32), point.astype(np.float32), albedo.astype(np.float32))
+
+
+def curved_pair(w, h, f, seed, phase=None):
+    """As `synthetic_pair`, on the curved scene.  `phase` None: the low-resolution guides are the scene at the block centres;
+    (px, py): at the lattice samples (f·i + px, f·j + py), where they ARE the full G-buffer's (DESIGN.md §4.20 "Lattice samples")."""
+    rng = np.random.default_rng([seed, w, h, f, 77])
+    W, H = f * w, f * h
+    rmax = min(25.0, max(9.0, 0.6 * max(W, H)))
+    spheres = [(rng.uniform(0.0, W), rng.uniform(0.0, H), R, rng.uniform(0.25, 0.95, 3))
+               for R in np.linspace(rmax, 6.0, max(2, min(12, round(W * H / 600))))]
+    # smaller than a low-resolution pixel, centred on a full pixel's centre so that it is seen at all
+    spheres = [(int(rng.integers(0, W)) + 0.5, int(rng.integers(0, H)) + 0.5, 0.45 * f, rng.uniform(0.25, 0.95, 3))
+               for _ in range(max(2, W * H // 400))] + spheres
+    strips = [(int(rng.integers(0, max(W // 2, 1))), 4), (int(rng.integers(0, max(W // 2, 1))), 3), (int(rng.integers(0, max(W - H // 7, 1))), 7)]
+    consts = (spheres, strips, np.array((0.83, 0.79, 0.71)), np.array((0.9, 0.001, 0.31)))
+    xs, ys = np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5)
+    g_hi = _evaluate_curved(xs, ys, W, H, consts)
+    if phase is None:
+        xs, ys = np.meshgrid((np.arange(w) + 0.5) * f, (np.arange(h) + 0.5) * f)
+    else:
+        xs, ys = np.meshgrid(f * np.arange(w) + phase[0] + 0.5, f * np.arange(h) + phase[1] + 0.5)
+    g_lo = _evaluate_curved(xs, ys, W, H, consts)
     irradiance = rng.uniform(0.05, 2.0, (h, w, 3))
     rgb_lo = (np.where(g_lo.index[..., None] < 0, 1.0, g_lo.albedo) * irradiance).astype(np.float32)
     var_lo = (rng.uniform(0.0, 0.2, (h, w, 3)) ** 2).astype(np.float32)
