@@ -1169,9 +1169,15 @@ int trace_window(RayzScene* s, const DeviceCtx& ctx, SceneBuffers<R>& b, const R
         P.primary = primary ? built_lists : nullptr;
         P.grid = s->narrow.cell_grid;
         P.cells = s->narrow.cell_table;
+        // AUTO walks only from kWalkMinMembers members on (a smaller pool's scan is cheaper than a walk); a forced ON always walks
+        if (!(s->cells_mode == RAYZ_CELL_LISTS_ON || s->narrow.cell_members >= rayz_cells::kWalkMinMembers)) P.grid.any_overflowed |= rayz_cells::kNoWalk;
 #ifdef RAYZ_CELLS_TUNE // measurement builds only: the thresholds from the environment
         P.grid.list_lanes = std::getenv("RAYZ_CELLS_LIST_LANES") ? (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_LIST_LANES")) : rayz_cells::kListLanes;
         P.grid.max_cells = std::getenv("RAYZ_CELLS_MAX_CELLS") ? (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_MAX_CELLS")) : rayz_cells::kMaxCells;
+        P.grid.walk_columns = rayz_cells::kWalkColumns;
+        if (std::getenv("RAYZ_CELLS_WALK_COLUMNS")) // (a cap named here overrides AUTO's gate too)
+            P.grid.walk_columns = (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_WALK_COLUMNS")), P.grid.any_overflowed &= ~rayz_cells::kNoWalk;
+        P.grid.one_class = std::getenv("RAYZ_CELLS_ONE_CLASS") ? (uint32_t)std::atoi(std::getenv("RAYZ_CELLS_ONE_CLASS")) : 0u;
 #endif
         const uint32_t form = scene_scan_form(s);
         void (*kernel)(const CellsTraceArgs<R>) = cells_kernel<R>(form);
@@ -1337,11 +1343,23 @@ int scene_sync(RayzScene* s, RayzRenderStats* stats) {
                          tot / (double)c[9], 100.0 * c[4] / tot, 100.0 * c[5] / tot, 100.0 * c[6] / tot, 100.0 * c[7] / tot, 100.0 * c[8] / tot,
                          100.0 * c[10] / tot, (double)(c[6] + c[7]), (double)c[10], tot, c[9]);
             if (c[11]) { // a cells kernel ran (trace_kernel_flat.hpp: fp)
-                std::fprintf(stderr, "cells: secondary segments %llu, listable %.2f%%; cell-lane segments listed %llu (%.2f entries each); list phases %llu "
+                std::fprintf(stderr, "cells: secondary segments %llu, listable by the box %.2f%%, by the walk %.2f%%; cell-lane segments listed %llu (%.2f entries each); list phases %llu "
                                      "(%.1f lanes each); live lanes per scan %.1f; cells per listable secondary segment:",
-                             c[11], 100.0 * c[12] / (double)c[11], c[13], (double)c[14] / (double)(c[13] ? c[13] : 1), c[15],
+                             c[11], 100.0 * c[12] / (double)c[11], 100.0 * c[18] / (double)c[11], c[13], (double)c[14] / (double)(c[13] ? c[13] : 1), c[15],
                              (double)c[16] / (double)(c[15] ? c[15] : 1), (double)c[17] / (double)(c[9] ? c[9] : 1));
+#ifdef RAYZ_FLAT_PROFILE_WALK // (trace_kernel_flat.hpp: the slots hold the walk's histogram instead)
+                static const char* const bins[8] = {"<= 4", "<= 8", "<= 12", "<= 16", "<= 24", "<= 32", "<= 48", "more"};
+                unsigned long long all = 0;
+                for (int k = 0; k < 8; ++k) all += c[19 + k] & ((1ull << 30) - 1ull);
+                std::fprintf(stderr, " (not in this build)\nwalk: secondary segments whose box fails on its count alone %llu (%.2f%%); by columns, share and walk cells each:",
+                             all, 100.0 * (double)all / (double)c[11]);
+                for (int k = 0; k < 8; ++k) {
+                    const unsigned long long n = c[19 + k] & ((1ull << 30) - 1ull), cells = c[19 + k] >> 30;
+                    std::fprintf(stderr, " %s: %.2f%% %.1f |", bins[k], 100.0 * (double)n / (double)(all ? all : 1), (double)cells / (double)(n ? n : 1));
+                }
+#else
                 for (int k = 0; k <= 12; ++k) std::fprintf(stderr, " %d: %.2f%%", k, 100.0 * c[19 + k] / (double)(c[12] ? c[12] : 1));
+#endif
                 std::fprintf(stderr, "\n");
             }
         }

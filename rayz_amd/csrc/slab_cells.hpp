@@ -28,17 +28,29 @@ constexpr uint32_t kCellCap = 3;
 constexpr uint32_t kCellWords = kCellCap + 1u; // a record: the count, then the slots
 constexpr uint32_t kOverflowed = 0xffffffffu;  // .. or this for a fuller cell
 constexpr uint32_t kMaxCells = 12;             // cells a listable ray's box may cover (DESIGN.md §6 has the GPU histogram)
+// Columns of its major axis a walked stretch may cross (the second tier, for a box of more than kMaxCells).  DESIGN.md §6 has the
+// sweep: 96 % of the headline frame's box-unlistable segments cross at most 48 columns, but a long walk holds its list phase's other
+// lanes up, and past 12 columns that costs more than the scans it saves.
+constexpr uint32_t kWalkColumns = 12;
+// AUTO's gate for the walk: the least member count from which a launch walks (a forced ON always does).  A walk costs what its columns
+// cost whatever the pool; the scan it replaces costs in proportion to the pool.  Kernel ms at 1920x1080 and 256 spp, 24 lanes, without
+// the walk -> with it (profiles/r21/cell_walk/gates_walk.jsonl), by members: 1,023: 191.0 -> 256.9 | 1,932: 229.7 -> 285.3 | 4,093:
+// 311.4 -> 338.6 | 6,399: 376.9 -> 377.5 | 9,999: 519.1 -> 466.0.  It breaks even at 6,399 and wins from 9,999: the gate lies between.
+constexpr uint32_t kWalkMinMembers = 8192;
 constexpr uint32_t kMaxOutliers = 8;
 constexpr uint32_t kTableHead = kMaxOutliers;  // the table's first words: the outliers' slots; the cells' records follow, row-major (z rows)
 // Lanes of a wave that must hold a listable segment before the wave runs a list phase instead of a scan (or all its live lanes, if
-// fewer are live): DESIGN.md §6 has the sweep.
-constexpr uint32_t kListLanes = 16;
+// fewer are live): DESIGN.md §6 has the sweeps (24 beats 16 with the walk, and without it at every grid from 16 to 40).
+constexpr uint32_t kListLanes = 24;
 // AUTO's gate: the least member count from which a scene takes the cells.  Measured at 1920x1080 and 256 spp, cells OFF -> ON, kernel
 // ms of one launch on one DeviceScene (profiles/r18/cell_lists/gates.jsonl), by members:
 //   96: 61.5 -> 110.9 | 252: 102.0 -> 135.4 | 481: 141.5 -> 153.5 | 1,023: 229.0 -> 195.6 | 1,932: 322.9 -> 236.0 | 4,093: 542.2 -> 313.3
 //   | 9,999: 1,170 -> 494.8
 // The first size at which ON wins (by 14.6 %, the spread 0.6 %) is the 32 x 32 grid's.  There is no samples-per-pixel gate: the table
 // is built with the scene's slots and costs a launch nothing.
+// Round 21 (profiles/r21/cell_walk/): with kListLanes = 24, and no walk below kWalkMinMembers, OFF -> AUTO at 1,023: 229.4 -> 184.4; OFF ->
+// cells without the walk (tune build) at 1,932: 322.5 -> 229.7 | 4,093: 541.7 -> 311.4.  A FORCED ON walks at any size and loses up to
+// 1,023 (141.5 -> 263.9 at 481, 229.4 -> 251.7 at 1,023; 324.2 -> 276.1 at 1,932, 542.1 -> 329.6 at 4,093).  The first winning size has not moved.
 constexpr uint32_t kCellsMinMembers = 1023;
 constexpr uint32_t kMaxGridSide = 4096; // cells per side at most: the table stays below 2^24 records
 
@@ -55,24 +67,34 @@ struct CellGrid {
     double extent;           // >= |cx| + |cy| + |cz| + |vy| + |r| of every member
     uint32_t nx, nz;
     uint32_t n_outliers;
-    uint32_t any_overflowed; // some cell is marked kOverflowed
+    uint32_t any_overflowed; // bit 0: some cell is marked kOverflowed (the builder's); bit 1, kNoWalk: this launch does not walk (the
+                             // launch's, for kWalkMinMembers — in the word the kernels hold anyway: a further argument costs them spills)
 #ifdef RAYZ_CELLS_TUNE // measurement builds only: the two thresholds as launch arguments (the sweeps of DESIGN.md §6)
     uint32_t list_lanes, max_cells;
+    uint32_t walk_columns, one_class; // .. and the walk's: its column cap (0: no walk) and the lane rule "one class" (long counts as short)
 #endif
 };
 #ifdef RAYZ_CELLS_TUNE
 RAYZ_SC_HD uint32_t list_lanes(const CellGrid& g) { return g.list_lanes; }
 RAYZ_SC_HD uint32_t max_cells(const CellGrid& g) { return g.max_cells; }
+RAYZ_SC_HD uint32_t walk_columns(const CellGrid& g) { return g.walk_columns; }
+RAYZ_SC_HD bool one_class(const CellGrid& g) { return g.one_class != 0u; }
 #else
 RAYZ_SC_HD uint32_t list_lanes(const CellGrid&) { return kListLanes; }
 RAYZ_SC_HD uint32_t max_cells(const CellGrid&) { return kMaxCells; }
+RAYZ_SC_HD uint32_t walk_columns(const CellGrid&) { return kWalkColumns; }
+RAYZ_SC_HD bool one_class(const CellGrid&) { return false; }
 #endif
+constexpr uint32_t kNoWalk = 2u; // CellGrid::any_overflowed, bit 1
+RAYZ_SC_HD bool overflowed_cells(const CellGrid& g) { return (g.any_overflowed & 1u) != 0u; }
+RAYZ_SC_HD bool walks(const CellGrid& g) { return (g.any_overflowed & kNoWalk) == 0u && walk_columns(g) != 0u; }
 
 // The cell coordinate of x along an axis, as a double: one subtraction, one product, one floor, each monotone in x under rounding —
 // so lo <= cx <= hi in f64 gives cell_of(lo) <= cell_of(cx) <= cell_of(hi), and a centre is filed with this very function.
 RAYZ_SC_HD double cell_of(double x, double x0, double inv_cell) { return floor((x - x0) * inv_cell); }
 
 enum : uint32_t { kNoCells = 0, kSomeCells = 1, kNotListable = 2 };
+constexpr uint32_t kWalkMajorX = 4u; // cells_stretch's own flag beside kNotListable: the walk's major axis is x (cells_query strips it)
 struct CellBox {
     uint32_t kind;
     uint32_t i0, i1, j0, j1; // kSomeCells: the cells [i0 .. i1] x [j0 .. j1], inside the grid
@@ -81,12 +103,19 @@ struct CellBox {
 RAYZ_SC_HD double min2(double a, double b) { return a < b ? a : b; }
 RAYZ_SC_HD double max2(double a, double b) { return a > b ? a : b; }
 
-// The cells whose members the ray o + t·d can meet at some t > 0 (any time of the shutter).  `cells`: the table's records (behind its
-// head), read only where some cell is overflowed.  The proof is DESIGN.md §4.22.
-RAYZ_SC_HD CellBox cells_query(const CellGrid& g, const uint32_t* cells, double ox, double oy, double oz, double dx, double dy, double dz) {
+// The stretch of the ray inside the slab and its xz box, the part the box and the walk share.  `count_only`: a kNotListable answer
+// has no other reason than the box's cell count (b's ranges are then the clipped box, and the walk may be asked).
+struct CellStretch {
+    double t0, t1; // the stretch, t0 >= 0
+    double px, pz; // the box's dilations
+};
+RAYZ_SC_HD CellBox cells_stretch(const CellGrid& g, double ox, double oy, double oz, double dx, double dy, double dz, CellStretch& s,
+                                 bool& count_only) {
     CellBox b;
     b.kind = kNotListable;
     b.i0 = b.i1 = b.j0 = b.j1 = 0u;
+    count_only = false;
+    s.t0 = s.t1 = s.px = s.pz = 0.0;
     if (!(dy != 0.0)) return b; // a ray along the slab (or a NaN)
     // what narrow_eval's rounding can add to a member's radius for this origin
     const double eps = kEvalRel * 2.0 * (fabs(ox) + fabs(oy) + fabs(oz) + g.extent);
@@ -118,13 +147,104 @@ RAYZ_SC_HD CellBox cells_query(const CellGrid& g, const uint32_t* cells, double 
     }
     b.i0 = (uint32_t)max2(fi0, 0.0), b.i1 = (uint32_t)min2(fi1, lx);
     b.j0 = (uint32_t)max2(fj0, 0.0), b.j1 = (uint32_t)min2(fj1, lz);
-    if ((uint64_t)(b.i1 - b.i0 + 1u) * (uint64_t)(b.j1 - b.j0 + 1u) > max_cells(g)) return b;
-    if (g.any_overflowed)
-        for (uint32_t j = b.j0; j <= b.j1; ++j)
-            for (uint32_t i = b.i0; i <= b.i1; ++i)
-                if (cells[(size_t)(j * g.nx + i) * kCellWords] == kOverflowed) return b;
+    s.t0 = t0, s.t1 = t1, s.px = px, s.pz = pz;
+    if ((uint64_t)(b.i1 - b.i0 + 1u) * (uint64_t)(b.j1 - b.j0 + 1u) > max_cells(g)) {
+        // the major axis is chosen by the index ranges BEFORE the clip (a stretch that leaves the grid keeps its direction's axis)
+        count_only = true;
+        b.kind = kNotListable | (fi1 - fi0 > fj1 - fj0 ? kWalkMajorX : 0u);
+        return b;
+    }
     b.kind = kSomeCells;
     return b;
+}
+
+RAYZ_SC_HD bool box_overflowed(const CellGrid& g, const uint32_t* cells, const CellBox& b) {
+    for (uint32_t j = b.j0; j <= b.j1; ++j)
+        for (uint32_t i = b.i0; i <= b.i1; ++i)
+            if (cells[(size_t)(j * g.nx + i) * kCellWords] == kOverflowed) return true;
+    return false;
+}
+
+// The cells whose members the ray o + t·d can meet at some t > 0 (any time of the shutter).  `cells`: the table's records (behind its
+// head), read only where some cell is overflowed.  The proof is DESIGN.md §4.22.
+RAYZ_SC_HD CellBox cells_query(const CellGrid& g, const uint32_t* cells, double ox, double oy, double oz, double dx, double dy, double dz) {
+    CellStretch s;
+    bool count_only;
+    CellBox b = cells_stretch(g, ox, oy, oz, dx, dy, dz, s, count_only);
+    if (b.kind != kSomeCells) {
+        b.kind &= 3u;
+        return b;
+    }
+    if (overflowed_cells(g) && box_overflowed(g, cells, b)) b.kind = kNotListable;
+    return b;
+}
+
+// ---- the walk: the second tier, asked only where the box fails on its cell count ----
+// The MAJOR axis is the one of x / z with the wider index range (ties: z); a COLUMN is one index of it.  Column k's cells are those
+// under the part of the stretch whose major coordinate lies in the column's interval dilated by p: the minor coordinate at that
+// sub-stretch's two ends, dilated likewise, through cell_of.  Columns are disjoint, so no cell is named twice, and every range is
+// clipped to the box's, so no cell lies outside it.
+struct CellWalk {
+    uint32_t kind;   // kNotListable, or kSomeCells: the columns [k0 .. k1] (inside the grid)
+    uint32_t xmajor; // the major axis is x (a column is an i, its range runs over j), else z
+    uint32_t k0, k1;
+};
+
+// Column k's minor range [m0 .. m1] for the box b and its stretch s; false: the column names no cell.
+RAYZ_SC_HD bool walk_column(const CellGrid& g, const CellBox& b, const CellStretch& s, bool xmajor, uint32_t k, double ox, double oz,
+                            double dx, double dz, uint32_t& m0, uint32_t& m1) {
+    const double om = xmajor ? ox : oz, dm = xmajor ? dx : dz, on = xmajor ? oz : ox, dn = xmajor ? dz : dx;
+    const double g0m = xmajor ? g.x0 : g.z0, g0n = xmajor ? g.z0 : g.x0;
+    const double cell = 1.0 / g.inv_cell; // exact: a power of two
+    // the column's interval.  A member filed under k has its centre in [e0, e1) up to the rounding of cell_of's subtraction and of
+    // the two edges (kRel·(|x0| + |e0| + |e1|)); an accepted root lies within the box's px of the centre; the two quotients below
+    // err by a few 2^-53 of |om| + |e|, which the kRel share of pm outweighs by 10^6 — so the computed sub-stretch holds the root's t.
+    const double e0 = g0m + (double)k * cell, e1 = g0m + ((double)k + 1.0) * cell;
+    const double pm = (xmajor ? s.px : s.pz) + kRel * (fabs(om) + fabs(g0m) + fabs(e0) + fabs(e1));
+    double s0 = s.t0, s1 = s.t1;
+    double band = INFINITY, ba = 0.0, bb = 0.0; // (a stretch across the major axis has no band)
+    if (dm != 0.0) {
+        const double inv = 1.0 / dm;
+        const double ta = ((e0 - pm) - om) * inv, tb = ((e1 + pm) - om) * inv;
+        s0 = max2(s0, min2(ta, tb)), s1 = min2(s1, max2(ta, tb)); // clipped to the stretch: never a cell outside the box's reach
+        // The BAND, a second bound on the same centres.  The root X lies on the line minor = on + (major − om)·sl, and within rho =
+        // |r| + eps of the centre C in the plane (the distance §4.22 step 2 bounds is Euclidean), so by Cauchy-Schwarz C.minor is
+        // within rho·sqrt(1 + sl²) <= rho·(1 + sl²/2) of the line's minor coordinate at C.major, which lies in [e0, e1].
+        const double sl = dn * inv;
+        ba = on + (e0 - om) * sl, bb = on + (e1 - om) * sl;
+        band = (1.0 + 0.5 * sl * sl) * ((xmajor ? s.pz : s.px) + kRel * (fabs(on) + fabs(ba) + fabs(bb))) +
+               kRel * (1.0 + fabs(sl)) * (fabs(om) + fabs(g0m) + fabs(e0) + fabs(e1));
+    }
+    if (!(s0 <= s1)) return false; // the stretch does not reach this column
+    // the minor coordinate is linear in t: at the root it lies between its values at the sub-stretch's ends (one product, one sum each)
+    const double na = on + s0 * dn, nb = on + s1 * dn;
+    const double pn = (xmajor ? s.pz : s.px) + kRel * (fabs(on) + fabs(na) + fabs(nb));
+    double f0 = cell_of(min2(na, nb) - pn, g0n, g.inv_cell), f1 = cell_of(max2(na, nb) + pn, g0n, g.inv_cell);
+    if (band < INFINITY) // both ranges hold the centre's cell (cell_of is monotone): so does their intersection
+        f0 = max2(f0, cell_of(min2(ba, bb) - band, g0n, g.inv_cell)), f1 = min2(f1, cell_of(max2(ba, bb) + band, g0n, g.inv_cell));
+    const double lo = (double)(xmajor ? b.j0 : b.i0), hi = (double)(xmajor ? b.j1 : b.i1);
+    if (!(f1 >= lo) || !(f0 <= hi) || !(f0 <= f1)) return false; // (also a NaN)
+    m0 = (uint32_t)max2(f0, lo), m1 = (uint32_t)min2(f1, hi);
+    return true;
+}
+
+// The walk of a ray whose box `b` (of cells_stretch) failed on its cell count alone.
+RAYZ_SC_HD CellWalk cells_walk(const CellGrid& g, const uint32_t* cells, const CellBox& b, const CellStretch& s, double ox, double oz,
+                               double dx, double dz) {
+    CellWalk w;
+    w.kind = kNotListable;
+    w.xmajor = (b.kind & kWalkMajorX) ? 1u : 0u;
+    w.k0 = w.xmajor ? b.i0 : b.j0, w.k1 = w.xmajor ? b.i1 : b.j1; // the box's range, clipped to the grid already
+    if (w.k1 - w.k0 + 1u > walk_columns(g)) return w;
+    if (overflowed_cells(g))
+        for (uint32_t k = w.k0; k <= w.k1; ++k) {
+            uint32_t m0, m1;
+            if (!walk_column(g, b, s, w.xmajor != 0u, k, ox, oz, dx, dz, m0, m1)) continue;
+            for (uint32_t m = m0; m <= m1; ++m)
+                if (cells[(size_t)(w.xmajor ? m * g.nx + k : k * g.nx + m) * kCellWords] == kOverflowed) return w;
+        }
+    w.kind = kSomeCells;
+    return w;
 }
 
 } // namespace rayz_cells

@@ -25,10 +25,12 @@
 // path that needs a scan or the queue is drained; nothing else differs: same streams, same sums, same segments counter.
 // RAYZ_TRACE_KERNEL_CELLS: every segment whose ray crosses the members' slab under a handful of cells (slab_cells.hpp, DESIGN.md
 // §4.22) is resolved from the outliers and those cells' slots.  After scan_begin each live lane learns whether its next segment is
-// LISTABLE: a fresh path on a pixel with a primary list (where the launch has lists: A.primary may be null), else whatever cells_query says.  With n
-// such lanes of m live ones, the wave runs a list phase for those lanes alone if n >= min(kListLanes, m), else the scan for every
-// live lane, listable or not: a list phase never runs for a few lanes while the rest wait, and no lane waits longer for its scan
-// than the threshold lets it.  The tie rule of accept_root is order-independent and a member sits in exactly one cell: the same
+// SHORT (a fresh path on a pixel with a primary list, where the launch has lists: A.primary may be null; no cells; a box of at most
+// kMaxCells), LONG (a walk of at most kWalkColumns columns along the stretch, where the launch walks) or SCAN.  With m live lanes and
+// L = min(kListLanes, m) the wave runs a list phase for the short lanes alone if they number L, else for short and long together if
+// those do, else the scan for every live lane: a list phase never runs for a few lanes while the rest wait, no lane waits longer for
+// its scan than the threshold lets it, and a long walk holds up short lanes only where they could not fill a phase themselves.  The
+// tie rule of accept_root is order-independent, a member sits in exactly one cell and a walk names a cell once: the same
 // tbest and ibest as the scan's, bit for bit.
 #ifndef RAYZ_TRACE_KERNEL_NAME
 #error "define RAYZ_TRACE_KERNEL_NAME before including trace_kernel_flat.hpp"
@@ -65,10 +67,16 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
     WaveQueue wq; // wave-uniform
 #ifdef RAYZ_FLAT_PROFILE // measurement build only: wave time per phase (refill, ray setup, scan, narrow flush, shade)
     // .. list phases (their own slot, 5); fp: wave-uniform counts of the cells kernels — 0 secondary segments, 1 listable ones, 2 segments a
-    // cell lane's list phase resolved, 3 their cell entries, 4 list phases, 5 their lanes, 6 live lanes at scans, 8 + k listable secondary
-    // segments whose box covers k cells (k <= 12)
+    // cell lane's list phase resolved, 3 their cell entries, 4 list phases, 5 their lanes, 6 live lanes at scans, 7 walked secondary
+    // segments, 8 + k listable secondary segments whose box covers k cells (k <= 12).  With -DRAYZ_FLAT_PROFILE_WALK the slots 8 .. 15
+    // hold instead the histogram of the secondary segments whose box failed on its cell count alone, by the columns their walk would
+    // cross (<= 4, 8, 12, 16, 24, 32, 48, more; whatever the cap): the count in the low 30 bits, the walk's cells above them.
     unsigned long long ft[6] = {0, 0, 0, 0, 0, 0}, ft0 = __builtin_amdgcn_s_memtime(), fiters = 0, fp[21] = {};
-    uint32_t fcells[NR]; // per slot: 13 = not listable by the cells
+    uint32_t fcells[NR]; // per slot: 13 = not listable by the cells, 14 = walked
+#ifdef RAYZ_FLAT_PROFILE_WALK
+    uint32_t fbin[NR], fwalk[NR]; // per slot: the bin (8: the box did not fail on its count) and the walk's cells
+    unsigned long long fhist[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // per lane
+#endif
 #pragma unroll
     for (int r = 0; r < NR; ++r) fcells[r] = 13u;
 #define RAYZ_FPROF(k) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ft[k] += now_ - ft0; ft0 = now_; }
@@ -128,35 +136,92 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
             }
         }
         if constexpr (kCells) {
-            uint32_t lp[NR];
-            bool prim[NR], any_alive = false;
-            rayz_cells::CellBox box[NR];
+            namespace rc = rayz_cells;
+            // A live lane is SHORT (a primary list, no cells, or a box of at most kMaxCells), LONG (a walk along the stretch) or SCAN.
+            // The walker's state, five integers: the column at hand and the last, the minor index at hand and the column's last, and
+            // `aux` — a box lane's first minor index (its columns are the box's z rows, all of one range), a walk lane's major axis.
+            enum : uint32_t { kNone = 0u, kBoxLane = 1u, kWalkLane = 2u };
+            uint32_t lp[NR], cls[NR], col[NR], col_last[NR], mi[NR], mi_last[NR], aux[NR];
+            bool prim[NR], is_short = false, is_long = false, any_alive = false;
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 lp[r] = 0u;
                 prim[r] = false;
-                box[r].kind = rayz_cells::kNotListable;
+                cls[r] = kNone;
+                col[r] = col_last[r] = aux[r] = 0u;
+                mi[r] = 1u, mi_last[r] = 0u; // (the first step enters the first column)
+                bool shrt = false, lng = false;
+#ifdef RAYZ_FLAT_PROFILE
+                fcells[r] = 13u;
+#ifdef RAYZ_FLAT_PROFILE_WALK
+                fbin[r] = 8u, fwalk[r] = 0u;
+#endif
+#endif
                 if (p[r].alive) {
                     if (p[r].seg == 0u && A.primary != nullptr) {
                         lp[r] = p[r].item - (p[r].item / A.shard_pixels) * A.shard_pixels;
                         prim[r] = A.primary[lp[r]] != rayz_primary::kNoList;
                     }
-                    if (!prim[r]) // f64 on the widened o and d: bit for bit the ray narrow_eval gets
-                        box[r] = rayz_cells::cells_query(A.grid, A.cells + rayz_cells::kTableHead, (double)ray[r].o.x, (double)ray[r].o.y,
-                                                         (double)ray[r].o.z, (double)ray[r].d.x, (double)ray[r].d.y, (double)ray[r].d.z);
-                    listed[r] = prim[r] || box[r].kind != rayz_cells::kNotListable;
-                }
+                    shrt = prim[r];
+                    if (!prim[r]) { // f64 on the widened o and d: bit for bit the ray narrow_eval gets
+                        const double ox = (double)ray[r].o.x, oy = (double)ray[r].o.y, oz = (double)ray[r].o.z;
+                        const double dx = (double)ray[r].d.x, dy = (double)ray[r].d.y, dz = (double)ray[r].d.z;
+                        rc::CellStretch st;
+                        bool count_only;
+                        const rc::CellBox box = rc::cells_stretch(A.grid, ox, oy, oz, dx, dy, dz, st, count_only);
+                        if (box.kind == rc::kNoCells) shrt = true;
+                        else if (box.kind == rc::kSomeCells) {
+                            if (!(rc::overflowed_cells(A.grid) && rc::box_overflowed(A.grid, A.cells + rc::kTableHead, box))) {
+                                shrt = true;
+                                cls[r] = kBoxLane;
+                                col[r] = box.j0 - 1u, col_last[r] = box.j1, aux[r] = box.i0, mi_last[r] = box.i1, mi[r] = box.i1 + 1u;
 #ifdef RAYZ_FLAT_PROFILE
-                fcells[r] = box[r].kind == rayz_cells::kNotListable ? 13u
-                            : box[r].kind == rayz_cells::kNoCells   ? 0u
-                                                                    : (box[r].i1 - box[r].i0 + 1u) * (box[r].j1 - box[r].j0 + 1u);
+                                fcells[r] = (box.i1 - box.i0 + 1u) * (box.j1 - box.j0 + 1u);
 #endif
-                list_phase = list_phase || listed[r];
+                            }
+                        } else if (count_only && rc::walks(A.grid)) {
+                            const rc::CellWalk w = rc::cells_walk(A.grid, A.cells + rc::kTableHead, box, st, ox, oz, dx, dz);
+                            if (w.kind == rc::kSomeCells) {
+                                lng = true;
+                                cls[r] = kWalkLane;
+                                col[r] = w.k0 - 1u, col_last[r] = w.k1, aux[r] = w.xmajor;
+                            }
+                        }
+#ifdef RAYZ_FLAT_PROFILE
+                        if (box.kind == rc::kNoCells) fcells[r] = 0u;
+                        if (lng) fcells[r] = 14u;
+#ifdef RAYZ_FLAT_PROFILE_WALK
+                        if (count_only) {
+                            const bool xm = (box.kind & rc::kWalkMajorX) != 0u;
+                            const uint32_t k0 = xm ? box.i0 : box.j0, k1 = xm ? box.i1 : box.j1, n = k1 - k0 + 1u;
+                            fbin[r] = n <= 4u ? 0u : n <= 8u ? 1u : n <= 12u ? 2u : n <= 16u ? 3u : n <= 24u ? 4u : n <= 32u ? 5u : n <= 48u ? 6u : 7u;
+                            for (uint32_t k = k0; k <= k1; ++k) {
+                                uint32_t m0 = 1u, m1 = 0u;
+                                if (rc::walk_column(A.grid, box, st, xm, k, ox, oz, dx, dz, m0, m1)) fwalk[r] += m1 - m0 + 1u;
+                            }
+                        }
+#endif
+#endif
+                    }
+                }
+                if (rc::one_class(A.grid)) shrt = shrt || lng, lng = false;
+                listed[r] = shrt; // (for now: the rule below may add the long lanes)
+                is_short = is_short || shrt;
+                is_long = is_long || lng;
                 any_alive = any_alive || p[r].alive;
             }
-            const uint32_t n_listed = (uint32_t)__popcll(__ballot(list_phase)), n_alive = (uint32_t)__popcll(__ballot(any_alive));
-            list_phase = n_listed != 0u && n_listed >= (n_alive < rayz_cells::list_lanes(A.grid) ? n_alive : rayz_cells::list_lanes(A.grid));
-            if (list_phase) {
+            const uint32_t n_short = (uint32_t)__popcll(__ballot(is_short)), n_long = (uint32_t)__popcll(__ballot(is_long));
+            const uint32_t n_alive = (uint32_t)__popcll(__ballot(any_alive));
+            const uint32_t need = n_alive < rc::list_lanes(A.grid) ? n_alive : rc::list_lanes(A.grid);
+            // lanes keep company of their own kind: the short ones alone if they suffice, else short and long together, else the scan
+            const bool with_long = n_short < need; // (wave-uniform)
+            const uint32_t n_listed = with_long ? n_short + n_long : n_short;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) listed[r] = listed[r] || (with_long && cls[r] == kWalkLane);
+            list_phase = n_listed != 0u && n_listed >= need;
+            // (the hint: most iterations are list phases; it also keeps the scan loops laid out in the order of the kernels these were
+            // made from, which tests/test_slab_cells_isa.py compares loop by loop)
+            if (__builtin_expect(list_phase, 1)) {
 #pragma unroll
                 for (int r = 0; r < NR; ++r) {
                     // round one: a primary lane's listed slots, a cell lane's outliers (the head of the table): an indexed list either way
@@ -172,21 +237,32 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
                             narrow_eval<R>(A.sc.slot64[2 * slot], A.sc.slot64[2 * slot + 1], (int)A.sc.slot_pool[slot], ray[r].o, ray[r].d,
                                            ray[r].time, ray[r].inv_a2, A.tmin, ray[r].tbest, ray[r].ibest);
                         }
-                    // round two: a cell lane walks its box, one entry per step whatever cell it comes from
-                    bool walking = listed[r] && !prim[r] && box[r].kind == rayz_cells::kSomeCells;
-                    uint32_t ci = box[r].i0, cj = box[r].j0, e = 0u;
+                    // round two: one walker for box and walk lanes, one entry per step whatever cell it comes from
+                    bool walking = listed[r] && cls[r] != kNone;
+                    uint32_t e = 0u;
                     uint4 rec{0u, 0u, 0u, 0u}; // the cell at hand: its count and kCellCap slots
-                    static_assert(rayz_cells::kCellWords == 4u, "a cell's record is one 16-byte load");
-                    bool first = true;
+                    static_assert(rc::kCellWords == 4u, "a cell's record is one 16-byte load");
                     for (;;) {
-                        while (walking && e >= rec.x) { // on to the next cell that holds an entry (no listable box holds an overflowed one)
-                            if (!first && ++ci > box[r].i1) {
-                                ci = box[r].i0;
-                                if (++cj > box[r].j1) walking = false;
+                        while (walking && e >= rec.x) { // on to the next cell that holds an entry (no listed lane's cells hold an overflowed one)
+                            bool have = true;
+                            if (++mi[r] > mi_last[r]) { // on to the next column
+                                if (++col[r] > col_last[r]) walking = false, have = false;
+                                else if (cls[r] == kBoxLane) mi[r] = aux[r];
+                                else { // a walk lane: the column's range from the widened ray again (nothing f64 is held across narrow_eval)
+                                    const double ox = (double)ray[r].o.x, oz = (double)ray[r].o.z, dx = (double)ray[r].d.x, dz = (double)ray[r].d.z;
+                                    rc::CellStretch st;
+                                    bool count_only;
+                                    const rc::CellBox box = rc::cells_stretch(A.grid, ox, (double)ray[r].o.y, oz, dx, (double)ray[r].d.y, dz, st, count_only);
+                                    uint32_t m0 = 1u, m1 = 0u;
+                                    have = rc::walk_column(A.grid, box, st, aux[r] != 0u, col[r], ox, oz, dx, dz, m0, m1);
+                                    mi[r] = have ? m0 : 1u, mi_last[r] = have ? m1 : 0u;
+                                }
                             }
-                            first = false;
-                            if (walking) rec = *(const uint4*)(A.cells + rayz_cells::kTableHead + (size_t)(cj * A.grid.nx + ci) * rayz_cells::kCellWords);
-                            e = 0u;
+                            e = 0u, rec.x = 0u;
+                            if (have) {
+                                const uint32_t at = cls[r] == kWalkLane && aux[r] != 0u ? mi[r] * A.grid.nx + col[r] : col[r] * A.grid.nx + mi[r];
+                                rec = *(const uint4*)(A.cells + rc::kTableHead + (size_t)at * rc::kCellWords);
+                            }
                         }
                         if (__ballot(walking) == 0ull) break;
                         if (walking) {
@@ -234,7 +310,13 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
                 const bool secondary = p[r].alive && (!list_phase || listed[r]) && p[r].seg != 0u;
                 fp[0] += (unsigned long long)__popcll(__ballot(secondary));
                 fp[1] += (unsigned long long)__popcll(__ballot(secondary && fcells[r] <= 12u));
+                fp[7] += (unsigned long long)__popcll(__ballot(secondary && fcells[r] == 14u));
+#ifdef RAYZ_FLAT_PROFILE_WALK
+                if (secondary && fbin[r] < 8u)
+                    for (uint32_t k = 0; k < 8u; ++k) fhist[k] += fbin[r] == k ? 1ull + ((unsigned long long)fwalk[r] << 30) : 0ull;
+#else
                 for (uint32_t k = 0; k <= 12u; ++k) fp[8 + k] += (unsigned long long)__popcll(__ballot(secondary && fcells[r] == k));
+#endif
             }
         }
 #endif
@@ -251,6 +333,12 @@ template <class R, int NR> __global__ __launch_bounds__(256, (flat_waves<R, NR>(
         RAYZ_FPROF(4)
     }
 #ifdef RAYZ_FLAT_PROFILE
+#ifdef RAYZ_FLAT_PROFILE_WALK
+    for (int k = 0; k < 8; ++k) {
+        for (int off = 32; off > 0; off >>= 1) fhist[k] += __shfl_xor(fhist[k], off);
+        fp[8 + k] = fhist[k];
+    }
+#endif
     if (lane == 0) {
         for (int k = 0; k < 5; ++k) atomicAdd(&A.counters[4 + k], ft[k]);
         atomicAdd(&A.counters[9], fiters);

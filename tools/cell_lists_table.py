@@ -5,7 +5,16 @@ DeviceScene, cells OFF / ON / AUTO.  One JSON line per run, printed and appended
   python tools/cell_lists_table.py TREE OUT profile   the default frame, OFF and ON at kMaxCells 4 / 6 / 9 / 12 (a -DRAYZ_FLAT_PROFILE
                                                       -DRAYZ_CELLS_TUNE build of TREE: the phases go to stderr)
   python tools/cell_lists_table.py TREE OUT sweep     kListLanes x kMaxCells on the default frame (a -DRAYZ_CELLS_TUNE build)
-  python tools/cell_lists_table.py TREE OUT gates     OFF against ON at grids 5 .. 50, 256 spp (the product build)
+  python tools/cell_lists_table.py TREE OUT walk      the walk (profiles/r21/cell_walk/): kWalkColumns x the lane rule at 16 lanes, then
+                                                      kListLanes 8 / 16 / 24 at the best two (a -DRAYZ_CELLS_TUNE build)
+  python tools/cell_lists_table.py TREE OUT walk_at COLUMNS:LANES ..  single points of that sweep, two launches each
+  python tools/cell_lists_table.py TREE OUT walk_grid GRID SPP COLUMNS:LANES ..  the same points on another grid, OFF first
+  python tools/cell_lists_table.py TREE OUT walk_profile  the default frame, ON without the walk and with it (a -DRAYZ_FLAT_PROFILE
+                                                      -DRAYZ_CELLS_TUNE build: the phases go to stderr; with
+                                                      -DRAYZ_FLAT_PROFILE_WALK as well, the histogram of the box-unlistable
+                                                      segments by the columns of their walk and the walk's cells per bin; arguments:
+                                                      the caps to run, as COLUMNS or COLUMNS:LANES)
+  python tools/cell_lists_table.py TREE OUT gates [GRID ..]  OFF against ON at grids 5 .. 50 (or those named), 256 spp (the product build)
   python tools/cell_lists_table.py TREE OUT rows      the other benchmark rows under AUTO (run once per build, a tree of the parent
                                                       commit included: it has no cells and ignores the mode)
 
@@ -47,6 +56,7 @@ def run(ds, t, tag, cells, reps=1, **env):
     print(json.dumps(rec), flush=True)
     out_f.write(json.dumps(rec) + "\n")
     out_f.flush()
+    return min(ms)
 
 
 what = sys.argv[3]
@@ -66,8 +76,40 @@ elif what == "sweep":  # the tune build
             run(ds, t, f"headline on", ON, RAYZ_CELLS_MAX_CELLS=mc, RAYZ_CELLS_LIST_LANES=ll)
     for mc in (4, 6):
         run(ds, t, f"headline on", ON, RAYZ_CELLS_MAX_CELLS=mc, RAYZ_CELLS_LIST_LANES=16)
+elif what == "walk":  # the tune build: the walk's column cap x the lane rule, then the lanes at the best two
+    t = scene(50, 1024)
+    ds = render.DeviceScene(t.scene_desc())
+    run(ds, t, "headline off", OFF)
+    ms = {}
+    for wc in (0, 8, 12, 16, 24, 32, 48):
+        for one in (0, 1):
+            if wc or not one:  # (without a walk there is one class anyway)
+                ms[(wc, one)] = run(ds, t, "headline on", ON, RAYZ_CELLS_WALK_COLUMNS=wc, RAYZ_CELLS_ONE_CLASS=one, RAYZ_CELLS_LIST_LANES=16)
+    for wc, one in sorted(ms, key=ms.get)[:2]:
+        for ll in (8, 24):
+            run(ds, t, "headline on", ON, RAYZ_CELLS_WALK_COLUMNS=wc, RAYZ_CELLS_ONE_CLASS=one, RAYZ_CELLS_LIST_LANES=ll)
+elif what == "walk_at":  # the tune build: the configurations named as COLUMNS:LANES
+    t = scene(50, 1024)
+    ds = render.DeviceScene(t.scene_desc())
+    for a in sys.argv[4:]:
+        wc, ll = map(int, a.split(":"))
+        run(ds, t, "headline on", ON, reps=2, RAYZ_CELLS_WALK_COLUMNS=wc, RAYZ_CELLS_ONE_CLASS=0, RAYZ_CELLS_LIST_LANES=ll)
+elif what == "walk_grid":  # the tune build: another grid (GRID SPP) at the configurations named, OFF first
+    t = scene(int(sys.argv[4]), int(sys.argv[5]))
+    ds = render.DeviceScene(t.scene_desc())
+    run(ds, t, f"grid {sys.argv[4]} off", OFF, reps=2)
+    for a in sys.argv[6:]:
+        wc, ll = map(int, a.split(":"))
+        run(ds, t, f"grid {sys.argv[4]} on", ON, reps=2, RAYZ_CELLS_WALK_COLUMNS=wc, RAYZ_CELLS_ONE_CLASS=0, RAYZ_CELLS_LIST_LANES=ll)
+elif what == "walk_profile":  # the profile build: phases to stderr
+    t = scene(50, 1024)
+    ds = render.DeviceScene(t.scene_desc())
+    run(ds, t, "headline on, no walk", ON, RAYZ_CELLS_WALK_COLUMNS=0, RAYZ_CELLS_LIST_LANES=16)
+    for wc in sys.argv[4:] or ("12",):
+        wc, ll = (wc.split(":") + ["16"])[:2]
+        run(ds, t, f"headline on, walk {wc}", ON, RAYZ_CELLS_WALK_COLUMNS=int(wc), RAYZ_CELLS_LIST_LANES=int(ll))
 elif what == "gates":  # the product build: OFF against ON at 256 spp
-    for g in (5, 8, 11, 16, 22, 32, 50):
+    for g in map(int, sys.argv[4:] or (5, 8, 11, 16, 22, 32, 50)):
         t = scene(g, 256)
         ds = render.DeviceScene(t.scene_desc())
         n = t.info().n_spheres
