@@ -881,6 +881,30 @@ int rayz_hip_upscaler_run_phase(RayzUpscaler* up, const RayzUpscaleParams* param
 /* Waits for the handle's last run and returns its HIP-event times in ms: the pack launches, the reconstruction launch.
  * RAYZ_ERR_STATE before any run. */
 int rayz_hip_upscaler_timing(RayzUpscaler* up, float* pack_ms_or_null, float* upscale_ms_or_null);
+/* The FOOTPRINT ALBEDO of a low-resolution frame.  BUILD-DEFINED; f32 only; frames of block means only (the
+ * camera of render.lowres_camera — a lattice sample is a real pixel with an albedo of its own).  A low-resolution pixel is the
+ * mean over its factor x factor block of full pixels, but `gbuffer_lo->albedo` is one point sample at the block's centre, so
+ * demodulating by it is off by the texture's contrast wherever the texture is finer than a low-resolution pixel.  This call
+ * writes, for every low-resolution pixel, the mean of the RAW full-size albedos of its block whose `index` equals the pixel's own
+ * (visited rows first, plain f32 adds, one divide: 4.24, restated bit for bit by tests/footprint_mirror.cpp); (1, 1, 1) for a
+ * background pixel; `gbuffer_lo->albedo`'s own bits where no pixel of the block has that index.  The result is meant to stand in
+ * for `gbuffer_lo->albedo` in a rayz_hip_upscaler_run with RAYZ_DENOISE_ALBEDO (and in the denoiser run of the low-resolution
+ * frame); the run itself is unchanged and RayzUpscaleParams.flags gets no new bit.
+ * The handle supplies the device, the sizes and the factor.  Of `gbuffer_lo` (h x w) and `gbuffer_hi` (height x width) only index
+ * and albedo are read, and both are required.  d_albedo_lo_out: DEVICE memory, h*w*3 floats.  d_count_out_or_null: h*w bytes, the
+ * number of full pixels of the block with the low-resolution pixel's index (for a background pixel: the block's background
+ * pixels).  No output may overlap an input or the other output — writing in place into `gbuffer_lo->albedo` included.
+ * Asynchronous on `hip_stream`; ordered after the handle's previous launch, and the handle's later launches are ordered after it
+ * (one launch in flight per handle, as rayz_hip_upscaler_run).
+ * RAYZ_ERR_BAD_ARG (checked before the handle, without touching a device): a null G-buffer, a null output, a G-buffer without
+ * index or albedo, an output equal to an input or to the other output.  RAYZ_ERR_STATE: a bad handle.  RAYZ_ERR_BAD_ARG behind
+ * it: an output overlapping an input or the other output.  Added within ABI 5 (additive). */
+int rayz_hip_upscaler_footprint_albedo(RayzUpscaler* up, const RayzQueryOutputs* gbuffer_lo, const RayzQueryOutputs* gbuffer_hi,
+                                       float* d_albedo_lo_out, uint8_t* d_count_out_or_null, void* hip_stream);
+/* Waits for the handle's last footprint call and returns its launch's HIP-event time in ms.  Its events are its own:
+ * rayz_hip_upscaler_timing keeps reporting the last RUN whatever footprint calls came in between.  RAYZ_ERR_STATE before any
+ * footprint call. */
+int rayz_hip_upscaler_footprint_timing(RayzUpscaler* up, float* ms);
 int rayz_hip_upscaler_destroy(RayzUpscaler* up);
 
 /* ---- temporal accumulation: reproject the history across camera moves -----------------------------

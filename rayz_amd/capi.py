@@ -281,6 +281,9 @@ PROTOTYPES = [
      [C.c_void_p, C.POINTER(UpscaleParams), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(QueryOutputs), C.POINTER(QueryOutputs),
       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_upscaler_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("rayz_hip_upscaler_footprint_albedo", C.c_int,
+     [C.c_void_p, C.POINTER(QueryOutputs), C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_upscaler_footprint_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("rayz_hip_upscaler_destroy", C.c_int, [C.c_void_p]),
     ("rayz_hip_temporal_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_temporal_step", C.c_int,

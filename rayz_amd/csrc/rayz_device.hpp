@@ -27,3 +27,4 @@
 #include "frame_kernels.hpp"         // resolve_kernel, accumulate_kernel, tonemap_kernel
 #include "known_answers_kernel.hpp"  // kat_block_discs, kat_kernel
 #include "query_kernel.hpp"          // QueryArgs, query_ray, query_store, the three query kernels, query_key
+#include "footprint.hpp"             // footprint_albedo_kernel and its launch (namespace rayz_dev_footprint)

@@ -5,12 +5,14 @@
 
 // The frame of the FrameHandle is the LOW-resolution one (its records are what the handle owns); full = factor x that.
 // buf: ga, gb, mod, col, var of the low-resolution frame.  ev[0]: the run starts; ev[1]: packed; ev[2]: reconstructed.
-struct RayzUpscaler : FrameHandle<5, 3> {
+// ev[3], ev[4]: around the footprint-albedo launch (§4.24), events of its own so that the last run's timing survives it.
+struct RayzUpscaler : FrameHandle<5, 5> {
     static constexpr uint32_t kMagic = 0x55505a52u;
     static constexpr const char* kNoun = "upscaler";
     uint32_t factor = 0;
     uint32_t full_width = 0, full_height = 0;
     bool ran = false; // the last run was launched whole (false: none yet, or it failed half-way: no timing)
+    bool footprint_ran = false; // the same for the last footprint-albedo call
 };
 
 namespace {
@@ -121,6 +123,47 @@ int upscaler_timing(RayzUpscaler* up, float* pack_ms, float* upscale_ms) {
     return RAYZ_OK;
 }
 
+// ---- the footprint albedo (§4.24; kernel and launch: footprint.hpp) -------------------------------------------------------------
+int footprint_alias_check(const RayzQueryOutputs* lo, const RayzQueryOutputs* hi, float* d_out, uint8_t* d_count, size_t n_lo, size_t n_hi) {
+    const UpscaleSpan in[] = {{"gbuffer_lo.index", lo->index, n_lo * 4}, {"gbuffer_lo.albedo", lo->albedo, n_lo * 12},
+                              {"gbuffer_hi.index", hi->index, n_hi * 4}, {"gbuffer_hi.albedo", hi->albedo, n_hi * 12}};
+    const UpscaleSpan out[] = {{"d_albedo_lo_out", d_out, n_lo * 12}, {"d_count_out", d_count, n_lo}};
+    return upscale_alias_check(in, (int)(sizeof(in) / sizeof(in[0])), out, 2);
+}
+
+// Checked in upscaler_run's order: every argument before the handle, nothing touches a device until all of them passed.
+int upscaler_footprint_albedo(RayzUpscaler* up, const RayzQueryOutputs* lo, const RayzQueryOutputs* hi, float* d_out, uint8_t* d_count,
+                              void* stream_arg) {
+    if (!lo || !hi) return fail(RAYZ_ERR_BAD_ARG, "footprint albedo: null G-buffer");
+    if (!d_out) return fail(RAYZ_ERR_BAD_ARG, "footprint albedo: null output");
+    if (!lo->index || !lo->albedo || !hi->index || !hi->albedo)
+        return fail(RAYZ_ERR_BAD_ARG, "footprint albedo: both G-buffers need index and albedo");
+    RAYZ_TRY(footprint_alias_check(lo, hi, d_out, d_count, 1, 1) /* equal pointers */);
+    RAYZ_TRY(frame_handle_check(up));
+    const size_t n_lo = (size_t)up->width * up->height, n_hi = (size_t)up->full_width * up->full_height;
+    RAYZ_TRY(footprint_alias_check(lo, hi, d_out, d_count, n_lo, n_hi));
+    hipStream_t st;
+    RAYZ_TRY(frame_handle_stream(up, stream_arg, st));
+    DeviceScope scope(up->device);
+    RAYZ_TRY(frame_handle_wait_previous(up, st));
+    up->footprint_ran = false;
+    RAYZ_TRY(frame_handle_record(up, 3, st));
+    rayz_dev_footprint::footprint_launch(st, up->factor, lo->index, (const float*)lo->albedo, hi->index, (const float*)hi->albedo, d_out,
+                                         d_count, up->width, up->height);
+    RAYZ_TRY(frame_handle_launched(up, 4, st));
+    up->footprint_ran = true;
+    return RAYZ_OK;
+}
+
+int upscaler_footprint_timing(RayzUpscaler* up, float* ms) {
+    RAYZ_TRY(frame_handle_check(up));
+    if (!up->footprint_ran) return fail(RAYZ_ERR_STATE, "no footprint-albedo call to time");
+    DeviceScope scope(up->device);
+    HIP_TRY(hipEventSynchronize(up->ev[4]));
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, up->ev[3], up->ev[4]));
+    return RAYZ_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -161,6 +204,15 @@ int rayz_hip_upscaler_run_phase(RayzUpscaler* up, const RayzUpscaleParams* param
 
 int rayz_hip_upscaler_timing(RayzUpscaler* up, float* pack_ms_or_null, float* upscale_ms_or_null) {
     return guarded([&] { return upscaler_timing(up, pack_ms_or_null, upscale_ms_or_null); });
+}
+
+int rayz_hip_upscaler_footprint_albedo(RayzUpscaler* up, const RayzQueryOutputs* gbuffer_lo, const RayzQueryOutputs* gbuffer_hi,
+                                       float* d_albedo_lo_out, uint8_t* d_count_out_or_null, void* hip_stream) {
+    return guarded([&] { return upscaler_footprint_albedo(up, gbuffer_lo, gbuffer_hi, d_albedo_lo_out, d_count_out_or_null, hip_stream); });
+}
+
+int rayz_hip_upscaler_footprint_timing(RayzUpscaler* up, float* ms) {
+    return guarded([&] { return upscaler_footprint_timing(up, ms); });
 }
 
 int rayz_hip_upscaler_destroy(RayzUpscaler* up) {

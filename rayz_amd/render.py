@@ -6,6 +6,7 @@ allocation and the host copy out of the timed region.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 
 import numpy as np
@@ -846,9 +847,57 @@ class Upscaler(_Handle):
                                                                  C.byref(self._h)), "rayz_hip_upscaler_create")
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last run: kept alive until the next run or close() (the kernels may still use them)
+        self._inflight_footprint = None  # .. and of the last footprint_albedo call
+
+    def close(self) -> None:
+        super().close()
+        self._inflight_footprint = None
+
+    def footprint_albedo(self, gbuffer_lo: "QueryResult", gbuffer_hi: "QueryResult", out=None, count=False, stream: int = 0):
+        """The albedo a frame of block means should be demodulated by (`rayz_hip_upscaler_footprint_albedo`): for
+        every low-resolution pixel the mean of the full-size albedos of its factor x factor block that lie on its own surface (the
+        same `index`), (1, 1, 1) for a background pixel, `gbuffer_lo.albedo` itself where no pixel of the block is on that surface.
+        `gbuffer_lo`, `gbuffer_hi`: float32 camera queries of the low-resolution and of the full frame; index and albedo are read.
+        Returns `out` (default: a new (height / factor, width / factor, 3) float32 tensor; never `gbuffer_lo.albedo` itself).
+        `count` True, or a (height / factor, width / factor) uint8 tensor: the number of pixels averaged is returned as a further
+        value.  Asynchronous on `stream`, as `run`, and ordered with the handle's runs."""
+        import torch
+
+        hi = (self.height, self.width, 3)
+        lo = (self.height // self.factor, self.width // self.factor, 3)
+        dev = torch.device("cuda", self._device)
+        need = ["index", "albedo"]
+        if out is None:
+            out = torch.empty(lo, dtype=torch.float32, device=dev)
+        if count is True:
+            count = torch.empty(lo[:2], dtype=torch.uint8, device=dev)
+        elif count is False:
+            count = None
+        tensors = []
+        for name, g, frame in (("gbuffer_lo", gbuffer_lo, lo), ("gbuffer_hi", gbuffer_hi, hi)):
+            tensors += [(f"{name}.{k}", getattr(g, k), torch.int32 if k == "index" else torch.float32, frame[:2] if k == "index" else frame)
+                        for k in need]
+        tensors.append(("out", out, torch.float32, lo))
+        if count is not None:
+            tensors.append(("count", count, torch.uint8, lo[:2]))
+        for t in tensors:
+            _check_tensor(*t, self._device, "the upscaler")
+        _stream_prologue(stream, self._device)
+        rc = self._lib.rayz_hip_upscaler_footprint_albedo(self._h, C.byref(_gbuffer_pointers(gbuffer_lo, need)),
+                                                          C.byref(_gbuffer_pointers(gbuffer_hi, need)), C.c_void_p(out.data_ptr()),
+                                                          C.c_void_p(count.data_ptr() if count is not None else None), C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_upscaler_footprint_albedo")
+        self._inflight_footprint = (gbuffer_lo, gbuffer_hi, out, count)
+        return out if count is None else (out, count)
+
+    def footprint_timing(self) -> float:
+        """Waits for the last `footprint_albedo` call; its launch's HIP-event time in ms (`rayz_hip_upscaler_footprint_timing`)."""
+        ms = C.c_float()
+        capi.check(self._lib, self._lib.rayz_hip_upscaler_footprint_timing(self._h, C.byref(ms)), "rayz_hip_upscaler_footprint_timing")
+        return ms.value
 
     def run(self, rgb_lo, gbuffer_lo: "QueryResult", gbuffer_hi: "QueryResult", var_rgb=None, out=None, var_out=None, stage=False,
-            stream: int = 0, phase=None, **params):
+            stream: int = 0, phase=None, footprint=False, **params):
         """`rgb_lo`: (height / factor, width / factor, 3) float32 on the handle's device; `gbuffer_lo`, `gbuffer_hi`: float32 camera
         queries of the low-resolution and of the full frame (index, normal, point, and albedo with flags=DENOISE_ALBEDO).  Returns `out` (default: a new (height, width, 3) tensor).  With `var_rgb` — the per-channel variance of `rgb_lo`'s
         pixel means, shaped as it — the call returns (out, var): the per-channel MARGINAL variance of every full pixel (`var_out`: a
@@ -859,6 +908,9 @@ class Upscaler(_Handle):
         pixel (factor·i + px, factor·j + py), and `gbuffer_lo` is `gbuffer_hi.lattice(factor, phase)`
         (`rayz_hip_upscaler_run_phase`): the sampled pixels come back as they are, the others are rebuilt around them.  None: the
         frame of block means a `lowres_camera` traces.
+        `footprint` True (needs flags=DENOISE_ALBEDO, and no `phase`: a lattice sample is a real pixel with its own albedo): the
+        low-resolution frame is demodulated by `footprint_albedo(gbuffer_lo, gbuffer_hi)` instead of `gbuffer_lo.albedo` (§4.24),
+        computed on the same stream; `gbuffer_lo` itself is not modified.
         No output may share memory with an input.  Asynchronous on `stream`, as `Denoiser.run`."""
         import torch
 
@@ -866,6 +918,11 @@ class Upscaler(_Handle):
         prm.factor = self.factor
         if phase is not None:
             phase = _check_phase(self.factor, phase)
+        if footprint:
+            if phase is not None:
+                raise ValueError("footprint=True with phase=: a lattice sample is a real pixel with its own albedo")
+            if not prm.flags & capi.DENOISE_ALBEDO:
+                raise ValueError("footprint=True needs flags=DENOISE_ALBEDO: without it nothing is demodulated")
         hi = (self.height, self.width, 3)
         lo = (self.height // self.factor, self.width // self.factor, 3)
         dev = torch.device("cuda", self._device)
@@ -893,7 +950,12 @@ class Upscaler(_Handle):
             tensors.append(("stage", stage, torch.uint8, hi[:2]))
         for t in tensors:
             _check_tensor(*t, self._device, "the upscaler")
-        _stream_prologue(stream, self._device)
+        given_lo = gbuffer_lo
+        if footprint:
+            gbuffer_lo = copy.copy(given_lo)  # (shallow: the caller's G-buffer keeps its albedo)
+            gbuffer_lo.albedo = self.footprint_albedo(given_lo, gbuffer_hi, stream=stream)  # (its prologue is the run's)
+        else:
+            _stream_prologue(stream, self._device)
         args = (C.c_void_p(rgb_lo.data_ptr()), C.c_void_p(var_rgb.data_ptr() if var_rgb is not None else None),
                 C.byref(_gbuffer_pointers(gbuffer_lo, need)), C.byref(_gbuffer_pointers(gbuffer_hi, need)),
                 C.c_void_p(out.data_ptr()), C.c_void_p(var_out.data_ptr() if var_out is not None else None),
@@ -903,7 +965,7 @@ class Upscaler(_Handle):
         else:
             rc = self._lib.rayz_hip_upscaler_run_phase(self._h, C.byref(prm), phase[0], phase[1], *args)
         capi.check(self._lib, rc, "rayz_hip_upscaler_run")
-        self._inflight = (rgb_lo, var_rgb, gbuffer_lo, gbuffer_hi, out, var_out, stage)
+        self._inflight = (rgb_lo, var_rgb, given_lo, gbuffer_lo, gbuffer_hi, out, var_out, stage)
         res = (out,) + ((var_out,) if var_out is not None else ()) + ((stage,) if stage is not None else ())
         return res[0] if len(res) == 1 else res
 

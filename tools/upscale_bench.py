@@ -20,8 +20,16 @@
    with flags = 0: no demodulation in the upscaler (the denoiser keeps its defaults).  The cost rows are measured with the flag: the
    costlier state, which reads both albedos.
 
-    python tools/upscale_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--json FILE]"""
+3. With --footprint: the footprint albedo (rayz_hip_upscaler_footprint_albedo).  In the same run and with the same
+   seeds, beside the rows above: (cF) and (bF), which are (c) and (b) with the filtered albedo handed to the upscaler in place of the
+   low-resolution G-buffer's — for (bF) also to the low-resolution run_guided, which demodulates by the same point sample; their
+   device time includes the footprint launch.  And the launch itself, bracketed by the handle's own events
+   (rayz_hip_upscaler_footprint_timing), against a device copy of its compulsory bytes — per full pixel 16 (index and albedo) +
+   (28 + the count's byte) / f² (the low-resolution index and albedo in, the albedo out) —, median [min, max] of --reps after --warmup.
+
+    python tools/upscale_bench.py [--footprint] [--reps 100] [--warmup 10] [--ref-spp 1024] [--json FILE]"""
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -98,6 +106,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ref-spp", type=int, default=1024)
     ap.add_argument("--json", default=None, help="also write the figures to this file")
+    ap.add_argument("--footprint", action="store_true", help="add the rows (cF), (bF) and the footprint launch's cost (DESIGN.md 4.24)")
     args = ap.parse_args()
     render.init(0)
     stream = torch.cuda.Stream()
@@ -134,6 +143,11 @@ def main():
             up = render.Upscaler(W, H, f)
             dn_lo = render.Denoiser(w, h)
             fr = {"budgets": {}}
+            g_lo_f = fp_ms = None
+            if args.footprint:  # the filtered albedo: of the G-buffers alone, the same for both budgets
+                g_lo_f = copy.copy(g_lo)
+                g_lo_f.albedo = up.footprint_albedo(g_lo, g_hi)
+                fp_ms = up.footprint_timing()
             for budget, spp in (("equal spp", SPP), ("equal traced samples", SPP * f * f)):
                 lo, lo_var, lo_ms = trace(ds, cam_lo, p_lo, spp)
                 # (b), (c) with the upscaler's demodulation on (its default) and, as (b0), (c0), off
@@ -155,13 +169,29 @@ def main():
                     s1, s2 = float((stage == 1).float().mean()), float((stage == 2).float().mean())
                     rows["c" + tag] = {"mse": mse(out_c), "mse_upscaled_unfiltered": mse(up_c), "filter_ms": c_up + c_dn,
                                        "total_ms": lo_ms + g_lo_ms + g_hi_ms + c_up + c_dn, "stage1_share": s1, "stage2_share": s2}
+                if args.footprint:  # (bF), (cF): (b), (c) on the filtered albedo; the footprint launch counts as a filter
+                    den_lo = dn_lo.run_guided(lo, lo_var, g_lo_f)
+                    out_b = up.run(den_lo, g_lo_f, g_hi, flags=capi.DENOISE_ALBEDO)
+                    torch.cuda.synchronize()
+                    b_dn = sum(r[0] for r in handle_ms(dn_lo, lambda: dn_lo.run_guided(lo, lo_var, g_lo_f, out=den_lo), 9, 2))
+                    b_up = sum(r[0] for r in handle_ms(up, lambda: up.run(den_lo, g_lo_f, g_hi, out=out_b, flags=capi.DENOISE_ALBEDO), 9, 2))
+                    rows["bF"] = {"mse": mse(out_b), "filter_ms": fp_ms + b_dn + b_up, "total_ms": lo_ms + g_lo_ms + g_hi_ms + fp_ms + b_dn + b_up}
+                    up_c, var_c, stage = up.run(lo, g_lo_f, g_hi, var_rgb=lo_var, stage=True, flags=capi.DENOISE_ALBEDO)
+                    out_c = dn.run_guided(up_c, var_c, g_hi)
+                    torch.cuda.synchronize()
+                    c_up = sum(r[0] for r in handle_ms(up, lambda: up.run(lo, g_lo_f, g_hi, var_rgb=lo_var, out=up_c, var_out=var_c, stage=stage,
+                                                                         flags=capi.DENOISE_ALBEDO), 9, 2))
+                    c_dn = sum(r[0] for r in handle_ms(dn, lambda: dn.run_guided(up_c, var_c, g_hi, out=out_c), 9, 2))
+                    s1, s2 = float((stage == 1).float().mean()), float((stage == 2).float().mean())
+                    rows["cF"] = {"mse": mse(out_c), "mse_upscaled_unfiltered": mse(up_c), "filter_ms": fp_ms + c_up + c_dn,
+                                  "total_ms": lo_ms + g_lo_ms + g_hi_ms + fp_ms + c_up + c_dn, "stage1_share": s1, "stage2_share": s2}
                 # (d) bilinear
                 bil = lambda: torch.nn.functional.interpolate(lo.permute(2, 0, 1)[None], size=(H, W), mode="bilinear", align_corners=False)  # noqa: E731
                 out_d = bil()[0].permute(1, 2, 0).contiguous()
                 d_ms = event_ms(bil, stream, 9, 2)[0]
                 d = {"mse": mse(out_d), "filter_ms": d_ms, "total_ms": lo_ms + d_ms}
                 print(f"  f = {f}, {budget} ({spp} spp at {w}x{h}; trace {lo_ms:.3f} ms, G-buffers {g_lo_ms:.3f} + {g_hi_ms:.3f} ms):", flush=True)
-                for tag, note in (("", "demodulated"), ("0", "flags = 0   ")):
+                for tag, note in (("", "demodulated"), ("0", "flags = 0   ")) + ((("F", "footprint  "),) if args.footprint else ()):
                     b, c = rows["b" + tag], rows["c" + tag]
                     print(f"    (b{tag}) {note} run_guided low -> upscale:        MSE {b['mse']:.6e}  filters {b['filter_ms']:.3f} ms  total "
                           f"{b['total_ms']:.3f} ms = {b['total_ms'] / a['total_ms']:.3f} x (a)", flush=True)
@@ -191,6 +221,26 @@ def main():
                         row[what] = {"ms": tm[0], "min": tm[1], "max": tm[2], "bytes": nbytes, "copy_ms": cp[0], "copy_min": cp[1], "copy_max": cp[2],
                                      "ratio_to_copy": tm[0] / cp[0]}
                     fr["cost"][name] = row
+                if args.footprint:  # the footprint launch against a copy of its compulsory bytes
+                    fp_out = torch.empty_like(g_lo.albedo)
+                    fp_cnt = torch.empty((h, w), dtype=torch.uint8, device="cuda")
+                    fr["footprint_cost"] = {}
+                    for name, cnt in (("albedo only", False), ("albedo + count", fp_cnt)):
+                        for _ in range(args.warmup):
+                            up.footprint_albedo(g_lo, g_hi, out=fp_out, count=cnt)
+                        ms = []
+                        for _ in range(args.reps):
+                            up.footprint_albedo(g_lo, g_hi, out=fp_out, count=cnt)
+                            ms.append(up.footprint_timing())
+                        tm = (statistics.median(ms), min(ms), max(ms))
+                        nbytes = int(n_hi * (16 + (28 + (1 if cnt is not False else 0)) / (f * f)))
+                        src = torch.empty(nbytes // 2, dtype=torch.uint8, device="cuda")
+                        dst = torch.empty_like(src)
+                        cp = event_ms(lambda: dst.copy_(src), stream, args.reps, args.warmup)
+                        print(f"    [footprint, {name}] launch: {tm[0]:.4f} ms [{tm[1]:.4f}, {tm[2]:.4f}]; copy of its {nbytes / 1e6:.1f} MB: {cp[0]:.4f} ms "
+                              f"[{cp[1]:.4f}, {cp[2]:.4f}] ({nbytes / cp[0] / 1e9:.2f} TB/s) = {tm[0] / cp[0]:.2f} x the copy", flush=True)
+                        fr["footprint_cost"][name] = {"ms": tm[0], "min": tm[1], "max": tm[2], "bytes": nbytes, "copy_ms": cp[0], "copy_min": cp[1],
+                                                      "copy_max": cp[2], "ratio_to_copy": tm[0] / cp[0]}
             res["factors"][str(f)] = fr
             up.close()
             dn_lo.close()
