@@ -725,6 +725,46 @@ int rayz_hip_scene_query_camera_chain(RayzScene* scene, const RayzCameraDesc* ca
                                       const RayzChainParams* chain_or_null, const RayzQueryOutputs* outputs,
                                       const RayzChainOutputs* chain_outputs_or_null, void* hip_stream);
 
+/* ---- sampled G-buffers: guide means over the render's own camera rays --------------------------------
+ * BUILD-DEFINED.  rayz_hip_scene_query_camera traces the pixel's centre through the lens centre at time 0; the frame it guides
+ * is made of samples jittered over the pixel, the lens disk and the shutter.  This call traces those: for every pixel (px, py)
+ * (global coordinates) of the shard `params` describes, dealt and stored as rayz_hip_scene_query_camera does it, and with
+ * spp = params->samples_per_px, samples s = 0 .. n-1:
+ *   ray     a Pcg32 seeded with seed_path(params->seed, (py·width + px)·spp + s), then camera_ray (jitter
+ *           x, jitter y, the lens tries if the camera has a defocus disk, time); tmin = params->tmin, tmax = +inf.  It IS the
+ *           camera segment of the render's path s of that pixel, bit for bit.
+ *   record  the NEAREST findHit record of that ray as a query writes it (by params->traversal, AUTO as for queries, in
+ *           params->precision R): hit or miss, t, the normal facing the ray, the albedo (texture_value at the point; (1, 1, 1)
+ *           for a dielectric).
+ *   sums    in R, from +0, one add (one rounding) per sample in sample order: hits (uint32) counts the hit samples;
+ *           A_k += albedo_k on a hit and A_k += 1 on a miss; N_k += normal_k and T += t on a hit only.
+ * Outputs (RayzSampledOutputs: DEVICE memory, each optional, entry = local row · width + column): albedo = A_k / (R)n; normal =
+ * N_k / (R)hits, (0, 0, 0) when hits = 0 — NOT normalised: its length says how far the samples' normals agree; t = T / (R)hits,
+ * +inf when hits = 0; hits.  Every divide is correctly rounded; there is no other arithmetic.  So n = 1 writes the one ray's
+ * NEAREST record (0 + x, x / 1: x but for the sign of a zero), the result does not depend on traversal, node format, shard count
+ * or launch shape, and the guides of a frame rendered with the same `params` are means over that frame's own camera segments.
+ * `sampled` NULL or samples = 0: n = spp.  RAYZ_ERR_BAD_ARG before any HIP call: everything
+ * rayz_hip_scene_query_camera_chain refuses, spp = 0, samples > spp (the ids would run into the next pixel's paths), `outputs`
+ * NULL.  Reads width, height, shard_index, shard_count, tile_rows, precision, traversal, tmin, samples_per_px and seed of
+ * `params` and ignores the rest.  Asynchronous as the camera query; counts as the scene's one render or query in flight;
+ * rayz_hip_query_sync waits for it and reports primary_rays = segments = pixels · n, node and sphere tests as for queries.  It
+ * leaves rayz_hip_scene_sync's counters and every progressive handle alone and changes no frame any other entry point produces.
+ * For n > 1 the scene keeps a workspace of 8 R per pixel of the largest shard asked for.  Added in ABI 5 (additive: no existing
+ * symbol or struct changed). */
+typedef struct RayzSampledParams {
+    uint32_t samples; /* n: 1 .. params->samples_per_px; 0 = samples_per_px */
+    uint32_t _pad;
+} RayzSampledParams;
+typedef struct RayzSampledOutputs { /* DEVICE memory, each optional; R by the precision */
+    void* albedo;   /* 3n R: mean albedo, a miss counting as (1, 1, 1) */
+    void* normal;   /* 3n R: mean over the hit samples of the normal facing the ray; not normalised; 0 when hits = 0 */
+    void* t;        /* n R: mean t over the hit samples; +inf when hits = 0 */
+    uint32_t* hits; /* n: the hit samples */
+} RayzSampledOutputs;
+int rayz_hip_scene_query_camera_sampled(RayzScene* scene, const RayzCameraDesc* camera, const RayzRenderParams* params,
+                                        const RayzSampledParams* sampled_or_null, const RayzSampledOutputs* outputs,
+                                        void* hip_stream);
+
 /* ---- denoising: a G-buffer-guided à-trous filter for low-spp frames -------------------------------------------------
  * BUILD-DEFINED (the reference has no denoiser): an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) on a WHOLE f32
  * frame in DEVICE memory, guided by the G-buffer a rayz_hip_scene_query_camera call of F32 precision filled for the same camera

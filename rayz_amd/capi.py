@@ -116,6 +116,14 @@ class ChainOutputs(C.Structure):
     _fields_ = [("key", C.c_void_p), ("depth", C.c_void_p), ("first_index", C.c_void_p)]
 
 
+class SampledParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class SampledOutputs(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("t", C.c_void_p), ("hits", C.c_void_p)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
                 ("sigma_color", C.c_double), ("sigma_plane", C.c_double)]
@@ -160,6 +168,7 @@ assert C.sizeof(QueryParams) == 24 and C.sizeof(QueryOutputs) == 64 and C.sizeof
 assert C.sizeof(NoiseParams) == 16 and C.sizeof(NoiseSummary) == 40 and C.sizeof(DenoiseGuidedParams) == 40
 assert C.sizeof(UpscaleParams) == 24
 assert C.sizeof(ChainParams) == 16 and C.sizeof(ChainOutputs) == 24
+assert C.sizeof(SampledParams) == 8 and C.sizeof(SampledOutputs) == 32
 assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32 and C.sizeof(TemporalMomentsParams) == 16
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
@@ -262,6 +271,8 @@ PROTOTYPES = [
     ("rayz_hip_scene_query_camera_chain", C.c_int,
      [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(ChainParams), C.POINTER(QueryOutputs),
       C.POINTER(ChainOutputs), C.c_void_p]),
+    ("rayz_hip_scene_query_camera_sampled", C.c_int,
+     [C.c_void_p, C.POINTER(CameraDesc), C.POINTER(RenderParams), C.POINTER(SampledParams), C.POINTER(SampledOutputs), C.c_void_p]),
     ("rayz_hip_denoiser_create", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("rayz_hip_denoiser_run", C.c_int,
      [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p]),

@@ -126,6 +126,7 @@ int query_impl(RayzScene* s, uint32_t kind, uint32_t traversal, double tmin, uin
     s->q_stream = stream;
     s->q_bvh = use_bvh;
     s->q_chain = false;
+    s->q_sampled = false;
     s->q_last = RayzRenderStats{};
     s->q_last.primary_rays = s->q_last.segments = n;
     HIP_TRY(hipMemsetAsync(s->q_counters, 0, 4 * sizeof(unsigned long long), stream));
@@ -162,7 +163,7 @@ int query_sync(RayzScene* s, RayzRenderStats* stats) {
     DeviceScope scope(s->device);
     HIP_TRY(hipStreamSynchronize(s->q_stream));
     RayzRenderStats st = s->q_last; // (its segments: the batch's rays, query_impl; a chain call's: counted by its kernel, chain.hpp)
-    RAYZ_TRY(read_counters(*s, s->q_counters, s->q_chain ? "chain_kernel_bvh" : "query_kernel_bvh", s->q_bvh, s->q_chain, st, nothing_to_inspect));
+    RAYZ_TRY(read_counters(*s, s->q_counters, s->q_chain ? "chain_kernel_bvh" : s->q_sampled ? "sampled_kernel_bvh" : "query_kernel_bvh", s->q_bvh, s->q_chain, st, nothing_to_inspect));
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, s->q_ev0, s->q_ev1));
     st.kernel_ms = ms;

@@ -12,6 +12,7 @@
 #include "../../include/rayz_hip.h"
 #include "rayz_device.hpp"
 #include "chain_kernel.hpp"
+#include "sampled_kernel.hpp"
 #include "bvh_build.hpp"
 #include "denoise.hpp"
 #include "upscale.hpp"
@@ -227,6 +228,8 @@ struct RayzScene {
     hipStream_t q_stream = nullptr;
     bool queried = false, q_bvh = false, q_chain = false; // (q_chain: the query in flight is a chain call, chain.hpp)
     DevBuf<unsigned long long> q_chain_stores; // a chain call's output pointers (ChainStores, chain_kernel.hpp), which its kernel reads from device memory
+    bool q_sampled = false;      // the query in flight is a sampled call (sampled.hpp)
+    DevBytes q_sampled_sums;     // .. and its workspace: the sums of every pixel between two samples (sampled_kernel.hpp)
     RayzRenderStats q_last{};
     // The members free themselves; what is left is to wait for the scene's last launch first.
     ~RayzScene() {
@@ -1649,6 +1652,7 @@ int rayz_hip_tonemap_u8(const float* d_rgb, uint8_t* d_rgb8, size_t n_pixels, vo
 #include "multi_device.hpp"
 #include "query.hpp"
 #include "chain.hpp"
+#include "sampled.hpp"
 #include "frame_handle.hpp"
 #include "denoiser.hpp"
 #include "upscaler.hpp"

@@ -1,13 +1,14 @@
-// chain.hpp — specular-chain G-buffers (rayz_hip_scene_query_camera_chain): the host side.  Kernels:
-// chain_kernel.hpp.  Included by rayz_hip.hip behind query.hpp, whose checks, counters, events and sync it shares: a chain call
-// is the scene's query in flight, and rayz_hip_query_sync waits for it.
+// sampled.hpp — sampled G-buffers (rayz_hip_scene_query_camera_sampled): the host side.  Kernels:
+// sampled_kernel.hpp.  Included by rayz_hip.hip behind query.hpp and chain.hpp, whose checks, counters, events and sync it shares: a
+// sampled call is the scene's query in flight, and rayz_hip_query_sync waits for it.
 #pragma once
 
 namespace {
 
 template <class R>
-int scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzChainParams& ch,
-                             const RayzQueryOutputs* out, const RayzChainOutputs* co, void* stream_arg) {
+int scene_query_camera_sampled(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, uint32_t samples,
+                               const RayzSampledOutputs* out, void* stream_arg) {
+    using namespace rayz_dev_sampled;
     const uint32_t rows = rayz_hip_shard_rows(p);
     const uint64_t pixels = (uint64_t)rows * p->width;
     if (pixels >= (1ull << 31)) return fail(RAYZ_ERR_BAD_ARG, "camera query of %llu pixels", (unsigned long long)pixels);
@@ -28,11 +29,16 @@ int scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const Rayz
         HIP_TRY(s->q_ev0.create());
         HIP_TRY(s->q_ev1.create());
     }
-    // (every later segment starts at a hit point: inside the bound the scene's padding always covers, prepare_scene_bound)
-    bool use_bvh = false;
+    // the sums of a call of more than one sample: 8 R per pixel (a call still using a smaller workspace is waited for first)
+    const size_t sum_bytes = samples > 1u ? (size_t)n * kSumWords * sizeof(R) : 0;
+    if (sum_bytes > s->q_sampled_sums.capacity() || !s->q_sampled_sums) {
+        if (s->last_stream) HIP_TRY(hipStreamSynchronize(s->last_stream));
+        HIP_TRY(s->q_sampled_sums.alloc(sum_bytes));
+    }
+    bool use_bvh = false; // (camera_origin_bound covers the lens disk)
     RAYZ_TRY(prepare_scene_bound<R>(s, b, camera_origin_bound(cam), p->traversal, stream, use_bvh));
 
-    ChainArgs<R> A{};
+    SampledArgs<R> A{};
     A.q.sc = dev_scene<R>(*s, b, use_bvh);
     fill_camera<R>(cam, A.q.cam);
     A.q.rays = nullptr;
@@ -46,24 +52,23 @@ int scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const Rayz
     A.q.shard_count = shard.shard_count;
     A.q.tiled_pixels = shard.tiled_pixels;
     A.q.counters = s->q_counters;
-    ChainStores<R> stores{out->index, (R*)out->t, (R*)out->point, (R*)out->normal, out->front_face, out->material, (R*)out->albedo,
-                          out->hit, co ? co->key : nullptr, co ? co->depth : nullptr, co ? co->first_index : nullptr};
-    ChainStoreWords words;
-    static_assert(sizeof(stores) == sizeof(words), "a ChainStores is kChainStoreWords pointers");
-    std::memcpy(&words, &stores, sizeof(words));
+    A.samples = samples;
+    SampledStores<R> stores{(R*)out->albedo, (R*)out->normal, (R*)out->t, out->hits, (R*)s->q_sampled_sums.get(), p->seed, p->samples_per_px};
+    ChainStoreWords words{}; // (the chain call's way of handing a kernel its words, and its buffer)
+    static_assert(sizeof(stores) == kSampledStoreWords * sizeof(unsigned long long) && kSampledStoreWords <= kChainStoreWords,
+                  "a SampledStores is kSampledStoreWords words");
+    std::memcpy(&words, &stores, sizeof(stores));
     if (!s->q_chain_stores) HIP_TRY(s->q_chain_stores.alloc(kChainStoreWords));
-    A.out = (const ChainStores<R>*)s->q_chain_stores.get();
-    A.max_fuzz = ch.max_fuzz;
-    A.max_depth = ch.max_depth;
+    A.out = (const SampledStores<R>*)s->q_chain_stores.get();
 
-    typedef void (*Kernel)(const ChainArgs<R>);
-    Kernel kernel = chain_kernel<R>;
+    typedef void (*Kernel)(const SampledArgs<R>);
+    Kernel kernel = sampled_kernel<R>;
     int block = 256;
     BvhLds L;
     if (use_bvh) { // the render's LDS layout, as a query's
-        kernel = b.quantized ? chain_kernel_bvh<R, true> : chain_kernel_bvh<R, false>;
+        kernel = b.quantized ? sampled_kernel_bvh<R, true> : sampled_kernel_bvh<R, false>;
         block = (int)kBvhWg;
-        RAYZ_TRY(bvh_lds_layout(kernel, "chain", block, bvh_stack_bytes(s->bvh_dev.depth, kBvhWg), b.quantized, b.n_big_leaves, b.bvh_top, 0, L));
+        RAYZ_TRY(bvh_lds_layout(kernel, "sampled", block, bvh_stack_bytes(s->bvh_dev.depth, kBvhWg), b.quantized, b.n_big_leaves, b.bvh_top, 0, L));
         A.q.bvh_top_words = L.top_words;
         A.q.bvh_big_words = L.big_words;
         A.q.sc.bvh_top = L.top_bytes;
@@ -73,10 +78,10 @@ int scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const Rayz
     s->last_stream = stream;
     s->q_stream = stream;
     s->q_bvh = use_bvh;
-    s->q_chain = true;
-    s->q_sampled = false;
+    s->q_chain = false; // (the segments are known here: pixels · n)
+    s->q_sampled = true;
     s->q_last = RayzRenderStats{};
-    s->q_last.primary_rays = n;
+    s->q_last.primary_rays = s->q_last.segments = (uint64_t)n * samples;
     HIP_TRY(hipMemsetAsync(s->q_counters, 0, 4 * sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(chain_outputs_kernel, dim3(1), dim3(64), 0, stream, words, s->q_chain_stores.get()); // (behind the scene's last query)
     HIP_TRY(hipGetLastError());
@@ -92,8 +97,8 @@ int scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const Rayz
 
 extern "C" {
 
-int rayz_hip_scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzChainParams* chain,
-                                      const RayzQueryOutputs* out, const RayzChainOutputs* chain_out, void* stream) {
+int rayz_hip_scene_query_camera_sampled(RayzScene* s, const RayzCameraDesc* cam, const RayzRenderParams* p, const RayzSampledParams* sampled,
+                                        const RayzSampledOutputs* out, void* stream) {
     // every argument is checked before the first HIP call
     if (!p) return fail(RAYZ_ERR_BAD_ARG, "params is null");
     RAYZ_TRY(check_query_args(s, RAYZ_QUERY_NEAREST, p->precision, p->traversal, p->tmin));
@@ -102,12 +107,13 @@ int rayz_hip_scene_query_camera_chain(RayzScene* s, const RayzCameraDesc* cam, c
     if (!p->width || !p->height) return fail(RAYZ_ERR_BAD_ARG, "width and height must be > 0");
     const uint32_t sc = p->shard_count ? p->shard_count : 1;
     if (p->shard_index >= sc) return fail(RAYZ_ERR_BAD_ARG, "shard_index %u >= shard_count %u", p->shard_index, sc);
-    const RayzChainParams ch = chain ? *chain : RayzChainParams{RAYZ_CHAIN_DEFAULT_DEPTH, 0, RAYZ_CHAIN_DEFAULT_MAX_FUZZ};
-    if (ch.max_depth > RAYZ_CHAIN_MAX_DEPTH) return fail(RAYZ_ERR_BAD_ARG, "chain max_depth %u > %u", ch.max_depth, RAYZ_CHAIN_MAX_DEPTH);
-    if (!(ch.max_fuzz >= 0.0)) return fail(RAYZ_ERR_BAD_ARG, "chain max_fuzz %g: must not be negative or NaN", ch.max_fuzz);
+    if (!p->samples_per_px) return fail(RAYZ_ERR_BAD_ARG, "samples_per_px must be > 0 (it is the stride of the path ids)");
+    const uint32_t samples = sampled && sampled->samples ? sampled->samples : p->samples_per_px;
+    if (samples > p->samples_per_px)
+        return fail(RAYZ_ERR_BAD_ARG, "samples %u > samples_per_px %u: the path ids would run into the next pixel's", samples, p->samples_per_px);
     return guarded([&] {
-        return p->precision == RAYZ_PRECISION_F64 ? scene_query_camera_chain<double>(s, cam, p, ch, out, chain_out, stream)
-                                                  : scene_query_camera_chain<float>(s, cam, p, ch, out, chain_out, stream);
+        return p->precision == RAYZ_PRECISION_F64 ? scene_query_camera_sampled<double>(s, cam, p, samples, out, stream)
+                                                  : scene_query_camera_sampled<float>(s, cam, p, samples, out, stream);
     });
 }
 

@@ -185,6 +185,27 @@ class QueryResult:
         r.is_chain = self.is_chain
         return r
 
+    def with_albedo(self, albedo) -> "QueryResult":
+        """A copy of this G-buffer whose `albedo` is the given tensor — e.g. a sampled G-buffer's (DeviceScene.gbuffer_sampled,
+        DESIGN.md §4.25), so that a filter's DENOISE_ALBEDO divides and multiplies by the mean over the frame's own camera rays.
+        `albedo` must have the shape, dtype and device of this result's albedo (which must be present); every other field is
+        shared with this result, not copied."""
+        import torch
+
+        if self.albedo is None:
+            raise ValueError("with_albedo: this result carries no albedo to take the place of")
+        if not isinstance(albedo, torch.Tensor) or albedo.device != self.albedo.device:
+            raise ValueError(f"with_albedo: albedo must be a torch tensor on {self.albedo.device}")
+        if albedo.dtype != self.albedo.dtype or tuple(albedo.shape) != tuple(self.albedo.shape) or not albedo.is_contiguous():
+            raise ValueError(f"with_albedo: albedo must be contiguous {self.albedo.dtype} {tuple(self.albedo.shape)}, "
+                             f"got {albedo.dtype} {tuple(albedo.shape)}")
+        r = QueryResult()
+        for k in QUERY_OUTPUTS + ("hit",) + CHAIN_OUTPUTS:
+            setattr(r, k, getattr(self, k))
+        r.is_chain = self.is_chain
+        r.albedo = albedo
+        return r
+
     def _outputs(self) -> capi.QueryOutputs:
         o = capi.QueryOutputs()
         for k in QUERY_OUTPUTS + ("hit",):
@@ -192,6 +213,21 @@ class QueryResult:
             if t is not None and t.numel():
                 setattr(o, k, t.data_ptr())
         return o
+
+
+SAMPLED_OUTPUTS = ("albedo", "normal", "t", "hits")
+
+
+class SampledResult:
+    """The outputs of DeviceScene.gbuffer_sampled as torch tensors on the scene's device, None where not
+    requested: albedo and normal (rows, width, 3) and t (rows, width) of R — means over the pixel's samples, the normal not
+    normalised —, hits (rows, width) int32 (the count's 32 bits), and `samples`, the n they are means over.  Written
+    asynchronously: call DeviceScene.query_sync() before reading them on the host."""
+
+    def __init__(self):
+        for k in SAMPLED_OUTPUTS:
+            setattr(self, k, None)
+        self.samples = 0
 
 
 class DeviceScene(_Handle):
@@ -398,6 +434,42 @@ class DeviceScene(_Handle):
         rc = self._lib.rayz_hip_scene_query_camera_chain(self._h, C.byref(camera), C.byref(params), C.byref(prm), C.byref(res._outputs()),
                                                          C.byref(co), C.c_void_p(stream or None))
         capi.check(self._lib, rc, "rayz_hip_scene_query_camera_chain")
+        self._inflight = (None, res)
+        return res
+
+    def gbuffer_sampled(self, camera: capi.CameraDesc, params: capi.RenderParams, samples: int | None = None,
+                        outputs=SAMPLED_OUTPUTS, stream: int = 0) -> "SampledResult":
+        """The sampled G-buffer (`rayz_hip_scene_query_camera_sampled`): per pixel of `params`' shard the means
+        of albedo, normal and t, and the hit count, over the camera segments of the render's own paths 0 .. samples-1 of that
+        pixel — jittered over the pixel, the lens disk and the shutter by `params`' seed and samples_per_px, exactly as
+        `render_into(camera, params, ...)` draws them.  `samples` None: all samples_per_px of them.  `outputs`: any of
+        SAMPLED_OUTPUTS.  Results shaped (rows_in_shard, width[, 3]); asynchronous on `stream`; kept alive by the scene until
+        query_sync() or the next query."""
+        import torch
+
+        outputs = tuple(outputs)
+        for k in outputs:
+            if k not in SAMPLED_OUTPUTS:
+                raise ValueError(f"unknown sampled output {k!r}; choose from {SAMPLED_OUTPUTS}")
+        if samples is not None and (isinstance(samples, bool) or not isinstance(samples, int) or samples < 1):
+            raise ValueError(f"samples must be None or an int >= 1, got {samples!r}")
+        rows = shard_rows(params)
+        dtype = torch.float64 if params.precision == capi.PRECISION_F64 else torch.float32
+        dev = torch.device("cuda", self.device)
+        res = SampledResult()
+        res.samples = int(samples if samples is not None else params.samples_per_px)
+        so = capi.SampledOutputs()
+        for k in outputs:
+            shape = (rows, params.width) + ((3,) if k in ("albedo", "normal") else ())
+            t = torch.empty(shape, dtype=torch.int32 if k == "hits" else dtype, device=dev)
+            setattr(res, k, t)
+            if t.numel():
+                setattr(so, k, t.data_ptr())
+        prm = capi.SampledParams(samples=0 if samples is None else samples)
+        self._query_prologue(stream)
+        rc = self._lib.rayz_hip_scene_query_camera_sampled(self._h, C.byref(camera), C.byref(params), C.byref(prm), C.byref(so),
+                                                           C.c_void_p(stream or None))
+        capi.check(self._lib, rc, "rayz_hip_scene_query_camera_sampled")
         self._inflight = (None, res)
         return res
 

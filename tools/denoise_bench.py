@@ -24,7 +24,14 @@
    MSE over the whole frame and over the pixels whose FIRST hit is metal or glass.  Then the keys-off per-level HIP-event times of
    both modes (what the key compare costs a caller who does not use it is this build against its parent, run alternately).
 
-    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE] [--guided | --chain]"""
+6. --sampled: the sampled albedo (rayz_hip_scene_query_camera_sampled, QueryResult.with_albedo) INSTEAD.  Configs 2
+   (whose camera has a defocus disk) and 3 at 1920x1080, the 16-spp tracked frame of --guided against --ref-spp, same seeds; `run`
+   and `run_guided` at their defaults otherwise, with flags = DENOISE_ALBEDO on the first-hit G-buffer's point-sampled albedo, with
+   flags = 0, and with flags = DENOISE_ALBEDO on the mean albedo over the frame's own 16 camera segments per pixel: MSE over the
+   whole frame, and the two G-buffer queries' kernel times.
+
+    python tools/denoise_bench.py [--reps 100] [--warmup 10] [--ref-spp 1024] [--paths] [--sizes 1920,3840] [--json FILE]
+                                  [--guided | --chain | --sampled]"""
 import argparse
 import json
 import os
@@ -231,6 +238,64 @@ def chain(args):
             json.dump(res, f, indent=1)
 
 
+def sampled(args):
+    """Section 6 of the module docstring."""
+    res = {}
+    for cfg, make in (("2", lambda: tracer.randomBouncing(1920, seed=42)), ("3", lambda: tracer.randomBouncing(1920, -50, 50, seed=42))):
+        t = make()
+        t.samples_per_px, t.max_bounces = 16, 50
+        t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=2)
+        sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+        p.tmin = 1e-3
+        w, h = p.width, p.height
+        ds = render.DeviceScene(sd)
+        pr = ds.progressive(cam, p, track_noise=True)
+        noisy = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        while not pr.done:
+            pr.step(0, noisy.data_ptr())
+        var = pr.noise_rgb()
+        pr.stats()
+        first = ds.gbuffer(cam, p)
+        first_ms = ds.query_sync().kernel_ms
+        smp = ds.gbuffer_sampled(cam, p, outputs=("albedo", "hits"))  # the frame's own camera segments: same seed, same 16 spp
+        smp_ms = ds.query_sync().kernel_ms
+        mixed = float(((smp.hits > 0) & (smp.hits < 16)).float().mean())
+        moved = float(((smp.albedo - first.albedo).abs().amax(dim=2) > 1e-3).float().mean())
+        guide = first.with_albedo(smp.albedo)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.samples_per_px, q.chunk_spp = args.ref_spp, 0
+        ref = torch.empty_like(noisy)
+        torch.cuda.synchronize()
+        ds.render_into(cam, q, ref.data_ptr())
+        ds.sync()
+
+        def mse(a):  # (a run is asynchronous on the library's stream: wait before torch reads its output)
+            if isinstance(a, tuple):
+                a = a[0]
+            torch.cuda.synchronize()
+            return float(((a.double() - ref.double()) ** 2).mean())
+
+        dn = render.Denoiser(w, h)
+        A = capi.DENOISE_ALBEDO
+        rows = {"noisy": mse(noisy)}
+        for name, fn in (("run", lambda g, flags: dn.run(noisy, g, flags=flags)), ("run_guided", lambda g, flags: dn.run_guided(noisy, var, g, flags=flags))):
+            rows[f"{name} point-sampled albedo"] = mse(fn(first, A))
+            rows[f"{name} flags = 0"] = mse(fn(first, 0))
+            rows[f"{name} sampled albedo"] = mse(fn(guide, A))
+        print(f"config {cfg}, {w}x{h}, 16 spp against {args.ref_spp} spp, camera with{'' if cam.defocus else 'out'} a defocus disk; first-hit G-buffer "
+              f"{first_ms:.3f} ms, sampled G-buffer (n = 16, albedo and hits) {smp_ms:.3f} ms; {100 * mixed:.2f} % of the pixels are hit by some samples "
+              f"only, {100 * moved:.2f} % have a sampled albedo more than 1e-3 from the point sample.  MSE (ratio to the noisy frame's)", flush=True)
+        for k, a in rows.items():
+            print(f"  {k:36s} {a:.6e} ({a / rows['noisy']:.4f})", flush=True)
+        res[cfg] = {"rows": rows, "first_ms": first_ms, "sampled_ms": smp_ms, "mixed_share": mixed, "moved_share": moved}
+        dn.close(), pr.close(), ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=100)
@@ -242,10 +307,13 @@ def main():
     ap.add_argument("--json", default=None, help="also write the figures to this file")
     ap.add_argument("--guided", action="store_true", help="the variance-guided mode's sweep and level times instead")
     ap.add_argument("--chain", action="store_true", help="chain guides and surface keys against first-hit guides instead")
+    ap.add_argument("--sampled", action="store_true", help="demodulation by the sampled albedo against the point sample and flags = 0 instead")
     args = ap.parse_args()
     render.init(0)
     if args.guided:
         return guided(args)
+    if args.sampled:
+        return sampled(args)
     if args.chain:
         return chain(args)
     stream = torch.cuda.Stream()

@@ -7,7 +7,13 @@ render's own BVH segment rate on the same scene (segments / kernel_ms of a low-s
 --chain: INSTEAD, the specular-chain G-buffer (rayz_hip_scene_query_camera_chain) on configs 2 and 3 at 1920x1080,
 BVH and flat list: its kernel time beside the first-hit G-buffer's in the same process (both by the library's HIP events, median of
 --reps after a warm-up), the mean segments per pixel and the depth histogram, for max_depth 2, 4 and 8 at the default max_fuzz.
-    python tools/query_bench.py --chain [--reps 5]"""
+    python tools/query_bench.py --chain [--reps 5]
+--sampled: INSTEAD, the sampled G-buffer (rayz_hip_scene_query_camera_sampled) on configs 2 and 3 at 1920x1080, BVH
+and flat list, n = 4 and 16 samples of 16 per pixel: its kernel time beside n times the first-hit G-buffer's — the two launches
+alternating in one process, both by the library's HIP events, median of --reps pairs after a warm-up —, segments per second beside
+the first-hit query's camera-ray rate, and, as context, the 16-spp render on the same scene: its kernel_ms and the share of it that
+16 camera segments per pixel at the sampled query's rate would be.
+    python tools/query_bench.py --sampled [--reps 5]"""
 import argparse
 import os
 import statistics
@@ -86,16 +92,57 @@ def chain(args):
         ds.close()
 
 
+def sampled(args):
+    scenes = {"2": lambda: tracer.randomBouncing(1920, seed=42), "3": lambda: tracer.randomBouncing(1920, -50, 50, seed=42)}
+    spp, pixels = 16, 1920 * 1080
+    for cfg, make in scenes.items():
+        t = make()
+        t.samples_per_px, t.max_bounces = spp, 50
+        t.set_gpu(render_seed=1)
+        sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+        p.width, p.height, p.tmin = 1920, 1080, 1e-3
+        ds = render.DeviceScene(sd)
+        out = torch.empty((1080, 1920, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        print(f"config {cfg}: {sd.n_spheres} spheres, 1920x1080, {spp} samples per pixel, camera with{'' if cam.defocus else 'out'} a defocus disk", flush=True)
+        for trav, tname in ((capi.TRAVERSAL_BVH, "bvh"), (capi.TRAVERSAL_LINEAR, "flat")):
+            p.traversal = trav
+            ds.render_into(cam, p, out.data_ptr())  # (one run: context, timed by the library's events around the kernel alone)
+            rs = ds.sync()
+            for n in (4, 16):
+                first, smp = [], []
+                for k in range(args.reps + 1):  # (the first pair warms up)
+                    ds.gbuffer(cam, p, outputs=("index", "t", "normal", "albedo"))
+                    a = ds.query_sync().kernel_ms
+                    ds.gbuffer_sampled(cam, p, samples=n)
+                    st = ds.query_sync()
+                    if k:
+                        first.append(a)
+                        smp.append(st.kernel_ms)
+                f, s = statistics.median(first), statistics.median(smp)
+                assert st.segments == pixels * n
+                extra = f"; {st.node_tests / st.segments:.1f} box tests and {st.sphere_tests / st.segments:.2f} leaf tests per segment" if trav == capi.TRAVERSAL_BVH else ""
+                print(f"  {tname:4s} n {n:2d}: sampled {s:8.3f} ms [{min(smp):.3f}, {max(smp):.3f}] = {pixels * n / s / 1e3:9.1f} Msegments/s; first-hit "
+                      f"G-buffer {f:.3f} ms [{min(first):.3f}, {max(first):.3f}] = {pixels / f / 1e3:9.1f} Mrays/s, x {n} = {n * f:8.3f} ms; "
+                      f"sampled / (n x first-hit) = {s / (n * f):.3f}{extra}", flush=True)
+            print(f"  {tname:4s} render, {spp} spp, 50 bounces: kernel {rs.kernel_ms:.3f} ms, {rs.segments / rs.primary_rays:.2f} segments per path; "
+                  f"its {spp} camera segments per pixel at the n = 16 sampled rate: {s:.3f} ms = {100 * s / rs.kernel_ms:.1f} % of it", flush=True)
+        ds.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--bounce", type=int, default=2_000_000)
     ap.add_argument("--configs", default="3,5")
     ap.add_argument("--chain", action="store_true", help="the chain G-buffer beside the first-hit G-buffer instead")
+    ap.add_argument("--sampled", action="store_true", help="the sampled G-buffer beside n first-hit G-buffers instead")
     args = ap.parse_args()
     render.init(0)
     if args.chain:
         return chain(args)
+    if args.sampled:
+        return sampled(args)
     scenes = {"3": lambda: tracer.randomBouncing(1920, -50, 50, seed=42), "5": lambda: tracer.triangleMesh(1920, 224, seed=1)}
     for cfg in args.configs.split(","):
         t = scenes[cfg]()

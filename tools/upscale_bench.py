@@ -27,7 +27,14 @@
    (rayz_hip_upscaler_footprint_timing), against a device copy of its compulsory bytes — per full pixel 16 (index and albedo) +
    (28 + the count's byte) / f² (the low-resolution index and albedo in, the albedo out) —, median [min, max] of --reps after --warmup.
 
-    python tools/upscale_bench.py [--footprint] [--reps 100] [--warmup 10] [--ref-spp 1024] [--json FILE]"""
+4. With --sampled: the sampled albedo (rayz_hip_scene_query_camera_sampled, QueryResult.with_albedo).  In the same
+   run and with the same seeds, beside the rows above, (b) and (c) demodulated (flags = RAYZ_DENOISE_ALBEDO) with a G-buffer's
+   albedo replaced by the mean over camera segments: (bH), (cH) the FULL-SIZE G-buffer's, over the 16 segments per pixel a
+   full-size 16-spp frame of the same seed would trace; (bL), (cL) the LOW-RESOLUTION G-buffer's, sampled through lowres_camera —
+   whose pixel IS the f x f block — over the low-resolution frame's own segments (all of its spp); (bS), (cS) both.  MSE only; the
+   sampled queries' kernel times are printed beside the first-hit G-buffers'.
+
+    python tools/upscale_bench.py [--footprint] [--sampled] [--reps 100] [--warmup 10] [--ref-spp 1024] [--json FILE]"""
 import argparse
 import copy
 import json
@@ -106,6 +113,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ref-spp", type=int, default=1024)
     ap.add_argument("--json", default=None, help="also write the figures to this file")
+    ap.add_argument("--sampled", action="store_true", help="add the rows (bH), (cH), (bL), (cL), (bS), (cS) (DESIGN.md 4.25)")
     ap.add_argument("--footprint", action="store_true", help="add the rows (cF), (bF) and the footprint launch's cost (DESIGN.md 4.24)")
     args = ap.parse_args()
     render.init(0)
@@ -136,6 +144,12 @@ def main():
         print(f"  (a) full-resolution {SPP} spp + run_guided: MSE {a['mse']:.6e}; trace {full_ms:.3f} + G-buffer {g_hi_ms:.3f} + filter {dn_ms:.3f} "
               f"= {a['total_ms']:.3f} ms", flush=True)
         res = {"ref_ms": ref_ms, "mse_noisy": mse(full), "a": a, "factors": {}}
+        g_hi_s = None
+        if args.sampled:  # the full-size albedo over the camera segments of the full-size 16-spp frame (p: its seed and spp)
+            s_hi = ds.gbuffer_sampled(cam, p, outputs=("albedo",))
+            res["sampled_hi_ms"] = ds.query_sync().kernel_ms
+            g_hi_s = g_hi.with_albedo(s_hi.albedo)
+            print(f"  sampled full-size G-buffer (n = {SPP}, albedo): {res['sampled_hi_ms']:.3f} ms beside the first-hit G-buffer's {g_hi_ms:.3f} ms", flush=True)
         for f in (2, 4):
             cam_lo, p_lo = render.lowres_camera(cam, f), render.lowres_params(p, f)
             w, h = p_lo.width, p_lo.height
@@ -185,6 +199,22 @@ def main():
                     s1, s2 = float((stage == 1).float().mean()), float((stage == 2).float().mean())
                     rows["cF"] = {"mse": mse(out_c), "mse_upscaled_unfiltered": mse(up_c), "filter_ms": fp_ms + c_up + c_dn,
                                   "total_ms": lo_ms + g_lo_ms + g_hi_ms + fp_ms + c_up + c_dn, "stage1_share": s1, "stage2_share": s2}
+                if args.sampled:  # (b), (c) on sampled albedos: H the full-size one, L the low-resolution one, S both
+                    q_lo = capi.RenderParams.from_buffer_copy(p_lo)
+                    q_lo.samples_per_px = spp  # (the low-resolution frame's own paths: trace() renders these params)
+                    s_lo = ds.gbuffer_sampled(cam_lo, q_lo, outputs=("albedo",))
+                    s_lo_ms = ds.query_sync().kernel_ms
+                    g_lo_s = g_lo.with_albedo(s_lo.albedo)
+                    for tag, gl, gh in (("H", g_lo, g_hi_s), ("L", g_lo_s, g_hi), ("S", g_lo_s, g_hi_s)):
+                        den_lo = dn_lo.run_guided(lo, lo_var, gl)
+                        out_b = up.run(den_lo, gl, gh, flags=capi.DENOISE_ALBEDO)
+                        torch.cuda.synchronize()
+                        rows["b" + tag] = {"mse": mse(out_b)}
+                        up_c, var_c, stage = up.run(lo, gl, gh, var_rgb=lo_var, stage=True, flags=capi.DENOISE_ALBEDO)
+                        out_c = dn.run_guided(up_c, var_c, gh)
+                        torch.cuda.synchronize()
+                        rows["c" + tag] = {"mse": mse(out_c), "mse_upscaled_unfiltered": mse(up_c)}
+                    rows["sampled_lo_ms"] = s_lo_ms
                 # (d) bilinear
                 bil = lambda: torch.nn.functional.interpolate(lo.permute(2, 0, 1)[None], size=(H, W), mode="bilinear", align_corners=False)  # noqa: E731
                 out_d = bil()[0].permute(1, 2, 0).contiguous()
@@ -199,6 +229,12 @@ def main():
                           f"{c['total_ms']:.3f} ms = {c['total_ms'] / a['total_ms']:.3f} x (a); upscaled, unfiltered: MSE "
                           f"{c['mse_upscaled_unfiltered']:.6e}; stage 1: {100 * c['stage1_share']:.4f} %, stage 2: {100 * c['stage2_share']:.4f} % of the pixels",
                           flush=True)
+                if args.sampled:
+                    for tag, note in (("H", "full-size albedo sampled"), ("L", "low-resolution albedo sampled"), ("S", "both sampled")):
+                        b, c = rows["b" + tag], rows["c" + tag]
+                        print(f"    (b{tag}) {note}: MSE {b['mse']:.6e}    (c{tag}): MSE {c['mse']:.6e}; upscaled, unfiltered: MSE {c['mse_upscaled_unfiltered']:.6e}",
+                              flush=True)
+                    print(f"    sampled low-resolution G-buffer (n = {spp}, albedo): {rows['sampled_lo_ms']:.3f} ms", flush=True)
                 print(f"    (d) bilinear interpolate:             MSE {d['mse']:.6e}  filter {d_ms:.3f} ms  total {d['total_ms']:.3f} ms", flush=True)
                 fr["budgets"][budget] = {"spp": spp, "trace_ms": lo_ms, "gbuffer_lo_ms": g_lo_ms, **rows, "d": d}
                 if spp != SPP:
