@@ -1099,6 +1099,32 @@ int rayz_hip_temporal_step_moments_counts(RayzTemporal* tm, const RayzTemporalPa
                                           float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, float* d_w2_out_or_null,
                                           void* hip_stream);
 
+/* ---- temporal accumulation, resampling mode: Catmull-Rom history fetch with bilinear fallback --------
+ * BUILD-DEFINED, additive within ABI 5, opt-in: a handle starts in RAYZ_TEMPORAL_RESAMPLE_BILINEAR, where every step is §4.15's as
+ * before, bit for bit.  Under a camera move that is no whole number of pixels the 2x2 bilinear gather low-passes the accumulated
+ * colour once per frame.  In RAYZ_TEMPORAL_RESAMPLE_CUBIC a moving step fetches the colour history (in moments mode also the
+ * second moment) with a 4x4 Catmull-Rom kernel WHERE all sixteen history pixels (x0 - 1 .. x0 + 2, y0 - 1 .. y0 + 2) lie inside
+ * the frame and are the same surface as the current pixel by §4.15's own acceptance test, clamps the result per channel to the
+ * range of the four central taps — the negative lobes cannot ring — and uses the bilinear gather everywhere else: a static step,
+ * a pixel near the frame's edge or a silhouette, a pixel whose bilinear gather was renormalised.  The variance (moments: W2) and
+ * the history length are interpolated bilinearly in both modes; the blend and the stores are unchanged; a move by whole pixels
+ * gives the bilinear result bit for bit.  The history's layout does not change and the handle gains no device state, so the mode
+ * may be changed between any two steps, with or without history.  The arithmetic is a contract (§4.26), restated by
+ * tests/temporal_cubic_mirror.cpp.
+ * d_taken_or_null: DEVICE memory, height*width bytes, which the caller keeps allocated until another call replaces it (NULL: none).
+ * EVERY later step of the handle, in either mode, writes one byte per pixel there: 1 where the pixel's colour history came from
+ * the sixteen taps, 0 otherwise — a first frame, a static step, a background pixel, a pixel without history, one that fell back,
+ * and every pixel in bilinear mode.  A step refuses a d_taken that equals one of its outputs with RAYZ_ERR_BAD_ARG.
+ * Limits of this version: plain handles take cubic mode through rayz_hip_temporal_step, moments handles through
+ * rayz_hip_temporal_step_moments; a handle in CUBIC mode refuses rayz_hip_temporal_step_counts and _step_moments_counts with
+ * RAYZ_ERR_STATE; a handle that tracks feedback refuses set_resampling(CUBIC), and a CUBIC handle refuses
+ * rayz_hip_temporal_track_feedback, both with RAYZ_ERR_STATE.
+ * RAYZ_ERR_BAD_ARG (checked before the handle): a mode that is neither constant.  RAYZ_ERR_STATE: a bad handle. */
+#define RAYZ_TEMPORAL_RESAMPLE_BILINEAR 0u   /* default: §4.15 as it is */
+#define RAYZ_TEMPORAL_RESAMPLE_CUBIC    1u
+int rayz_hip_temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken_or_null);
+int rayz_hip_temporal_get_resampling(RayzTemporal* tm, uint32_t* mode);
+
 #ifdef __cplusplus
 }
 #endif

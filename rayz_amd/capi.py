@@ -52,6 +52,8 @@ UPSCALE_FORM_AUTO, UPSCALE_FORM_DIRECT = 0, 1
 UPSCALE_DEFAULTS = {"normal_power_log2": 6, "flags": 0, "form": UPSCALE_FORM_AUTO, "sigma_plane": 0.25}
 TEMPORAL_DEFAULTS = {"alpha_min": 0.05, "n_max": 65536.0, "normal_cos_min": 0.9, "max_rel_dist": 0.05}  # provisional
 TEMPORAL_MOMENTS_DEFAULTS = {"w2_max": 0.25, "min_taps": 4.0}  # provisional
+TEMPORAL_RESAMPLE_BILINEAR, TEMPORAL_RESAMPLE_CUBIC = 0, 1  # RAYZ_TEMPORAL_RESAMPLE_* 
+TEMPORAL_RESAMPLING = {"bilinear": TEMPORAL_RESAMPLE_BILINEAR, "cubic": TEMPORAL_RESAMPLE_CUBIC}
 
 D3 = C.c_double * 3
 
@@ -315,6 +317,8 @@ PROTOTYPES = [
     ("rayz_hip_temporal_step_moments_counts", C.c_int,
      [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(TemporalMomentsParams), C.POINTER(CameraDesc), C.c_void_p, C.c_void_p,
       C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rayz_hip_temporal_set_resampling", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("rayz_hip_temporal_get_resampling", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
 ]
 
 

@@ -19,6 +19,7 @@
 #include "temporal_kernel.hpp"
 #include "temporal_moments_kernel.hpp"
 #include "temporal_feedback_kernel.hpp"
+#include "temporal_cubic_kernel.hpp"
 #include "noise.hpp"
 #include "adaptive.hpp"
 #include "sparse.hpp"

@@ -18,6 +18,8 @@ struct RayzTemporal : FrameHandle<2 * 4, 3> {
     DevBuf<dn4> mom[2];     // .. and owns, per ping-pong side, one more record per pixel {m2.r, m2.g, m2.b, W2}; empty otherwise
     bool feedback = false;  // rayz_hip_temporal_track_feedback: a moments handle whose variance records hold the raw first moment
                             // m1 instead, and which takes rayz_hip_temporal_feedback (§4.17)
+    uint32_t resampling = RAYZ_TEMPORAL_RESAMPLE_BILINEAR; // rayz_hip_temporal_set_resampling (§4.26): how a moving step fetches the colour history
+    uint8_t* taken = nullptr; // .. and the caller's device bytes every step writes (1: the pixel took the cubic path), or NULL
 };
 
 namespace {
@@ -99,11 +101,12 @@ RayzTemporalParams temporal_params_or_default(const RayzTemporalParams* params) 
 // camera, of the handle and of its mode (moments: the kind of handle this step takes) — and then the step on the handle's stream
 // behind the previous one.  launch(stream, the plain step's arguments, is_static) completes the mode's arguments and launches.
 // Every argument is checked before the handle, and nothing here touches a device until all of them passed.
-// counts: this is a counts step (§4.23: spp is 0 and the launch brings a count per pixel), which a feedback handle does not take.
+// counts: this is a counts step (§4.23: spp is 0 and the launch brings a count per pixel), which neither a feedback handle nor one in
+// cubic mode (§4.26) takes.  d_w2_out: the moments step's fourth output, which like the other three the handle's taken bytes must not be.
 template <class Launch>
 int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& p, const RayzCameraDesc* cam, uint32_t spp,
                       const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out,
-                      void* stream_arg, const Launch& launch, bool counts = false) {
+                      void* stream_arg, const Launch& launch, bool counts = false, const float* d_w2_out = nullptr) {
     float M[9], from[3];
     RAYZ_TRY(temporal_frame_check(g, cam, M, from));
     RAYZ_TRY(frame_handle_check(tm));
@@ -113,6 +116,11 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
                             : "a temporal handle in moments mode takes rayz_hip_temporal_step_moments");
     if (counts && tm->feedback)
         return fail(RAYZ_ERR_STATE, "a temporal handle that tracks feedback takes no counts step (its first moment has no rule for a pixel without samples)");
+    if (counts && tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
+        return fail(RAYZ_ERR_STATE, "a temporal handle in cubic resampling mode takes no counts step (rayz_hip_temporal_set_resampling back to bilinear first)");
+    if (tm->taken)
+        for (const void* o : {(const void*)d_out, (const void*)d_var_out, (const void*)d_len_out, (const void*)d_w2_out})
+            if (o == (const void*)tm->taken) return fail(RAYZ_ERR_BAD_ARG, "temporal: the handle's d_taken is also an output of the step");
     hipStream_t st;
     RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
     DeviceScope scope(tm->device);
@@ -121,6 +129,9 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
     const TemporalArgs a = temporal_args(tm, p, spp, d_in, d_var, g, d_out, d_var_out, d_len_out);
     tm->timed = false; // (a step that fails half-way leaves no timing)
     RAYZ_TRY(frame_handle_record(tm, 0, st));
+    // (§4.26: only the cubic kernels write the taken bytes themselves; every other step took the sixteen taps nowhere)
+    const bool cubic = tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static;
+    if (tm->taken && !cubic) HIP_TRY(hipMemsetAsync(tm->taken, 0, (size_t)tm->width * tm->height, st));
     launch(st, a, is_static);
     RAYZ_TRY(frame_handle_launched(tm, 1, st));
     temporal_stepped(tm, cam, M, from);
@@ -133,10 +144,31 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     RAYZ_TRY(temporal_params_check(p, spp));
     if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
     if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
-    const auto launch = [](hipStream_t st, const TemporalArgs& a, bool is_static) {
-        temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
+    const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) { // (behind the handle's check: tm is a handle)
+        using namespace rayz_dev_cubic;
+        if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static)
+            hipLaunchKernelGGL(temporal_cubic_step_kernel, denoise_grid(a.width, a.height), dim3(256), 0, st, TemporalCubicArgs{a, tm->taken});
+        else
+            temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
     };
     return temporal_run_step(tm, false, p, cam, spp, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch);
+}
+
+// §4.26's mode and the taken bytes.  The mode is an argument and is checked before the handle, as a step's arguments are.
+int temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken) {
+    if (mode != RAYZ_TEMPORAL_RESAMPLE_BILINEAR && mode != RAYZ_TEMPORAL_RESAMPLE_CUBIC)
+        return fail(RAYZ_ERR_BAD_ARG, "temporal resampling mode %u: must be RAYZ_TEMPORAL_RESAMPLE_BILINEAR or _CUBIC", mode);
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode == RAYZ_TEMPORAL_RESAMPLE_CUBIC && tm->feedback)
+        return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle that tracks feedback has no cubic mode (its raw first moment has no resampling rule)");
+    tm->resampling = mode, tm->taken = d_taken;
+    return RAYZ_OK;
+}
+
+int temporal_get_resampling(RayzTemporal* tm, uint32_t* mode) {
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode) *mode = tm->resampling;
+    return RAYZ_OK;
 }
 
 // What both counts steps (§4.23) check of their counts: every pixel reads its own and, in the moments step, its neighbours', so
@@ -204,6 +236,14 @@ int rayz_hip_temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* pa
         return temporal_step_counts(tm, params_or_null, camera, d_counts, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out,
                                     d_length_out_or_null, hip_stream);
     });
+}
+
+int rayz_hip_temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken_or_null) {
+    return guarded([&] { return temporal_set_resampling(tm, mode, d_taken_or_null); });
+}
+
+int rayz_hip_temporal_get_resampling(RayzTemporal* tm, uint32_t* mode) {
+    return guarded([&] { return temporal_get_resampling(tm, mode); });
 }
 
 int rayz_hip_temporal_reset(RayzTemporal* tm) {

@@ -22,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 #include "denoise.hpp" // dn4, dn_dot, dn_clamp_var, the tile and its grid
 
@@ -82,13 +83,24 @@ template <int R> struct TaAcc {
     __device__ __forceinline__ float mean(int r, int j) const { return sum[r][j] / B; }
 };
 
+// What ta_gather's moving form leaves behind for §4.26 (temporal_cubic_kernel.hpp), where a caller asks for it: the tap position
+// and its fractions, lim, and each of the four taps' verdict and records.  Set where the projection passed (so wherever found()).
+template <int R> struct TaTaps {
+    int ix, iy;
+    float fx, fy, lim;
+    bool ok[4];
+    dn4 tap[4][R];
+};
+struct TaNoTaps {}; // nothing is kept: every step but the cubic ones
+
 // §4.15 steps 1-3 for one pixel with id >= 0 of a handle with history: the sums over the history taps that are the same surface.
 // rec: the R arrays of the previous side whose records an accepted tap adds.  STATIC (the camera did not move): the one tap is
 // the pixel's own record, with weight 1.  LIVE (the counts step, §4.23): a tap is also refused where its record's length is not > 0 —
 // a record that holds no samples; the plain, moments and feedback steps never write one and compile without the test.
-template <bool STATIC, int R, bool LIVE = false>
+// keep: where the moving form leaves its taps (a TaTaps<R>*), or nothing.
+template <bool STATIC, int R, bool LIVE = false, class Keep = TaNoTaps>
 __device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* const* rec, size_t p, int32_t id, float nx, float ny,
-                                              float nz, float Px, float Py, float Pz) {
+                                              float nz, float Px, float Py, float Pz, [[maybe_unused]] Keep* keep = nullptr) {
     TaAcc<R> acc;
     const float wx = Px - a.from[0], wy = Py - a.from[1], wz = Pz - a.from[2];
     const float lim = a.r2 * dn_dot(wx, wy, wz, wx, wy, wz);
@@ -135,6 +147,15 @@ __device__ __forceinline__ TaAcc<R> ta_gather(const TemporalArgs& a, const dn4* 
 #pragma unroll
     for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
         if (ok[t] && (!LIVE || tap[t][0].w > 0.0f)) acc.add(tap[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy));
+    if constexpr (!std::is_same<Keep, TaNoTaps>::value) {
+        keep->ix = ix, keep->iy = iy, keep->fx = fx, keep->fy = fy, keep->lim = lim;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            keep->ok[t] = ok[t];
+#pragma unroll
+            for (int r = 0; r < R; ++r) keep->tap[t][r] = tap[t][r];
+        }
+    }
     return acc;
 }
 

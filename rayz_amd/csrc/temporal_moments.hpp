@@ -30,6 +30,8 @@ int temporal_track_feedback(RayzTemporal* tm) {
     RAYZ_TRY(frame_handle_check(tm));
     if (tm->feedback) return RAYZ_OK;
     if (!tm->moments) return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is not in moments mode (rayz_hip_temporal_track_moments first)");
+    if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
+        return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is in cubic resampling mode (rayz_hip_temporal_set_resampling back to bilinear first)");
     if (tm->has_history)
         return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle has history (call it after track_moments or after rayz_hip_temporal_reset)");
     tm->feedback = true;
@@ -71,16 +73,21 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
         a.t = t;
         a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
         a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
+        using namespace rayz_dev_cubic;
         if (d_counts) { // (never a feedback handle: temporal_run_step refused it)
             using namespace rayz_dev_counts;
             temporal_launch_step(st, temporal_counts_moments_kernel<true>, temporal_counts_moments_kernel<false>, is_static,
                                  TemporalMomentsCountsArgs{a, d_counts}, t.width, t.height);
-        } else if (tm->feedback)
+        } else if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static) // (never a feedback handle: set_resampling refused it)
+            hipLaunchKernelGGL(temporal_cubic_moments_step_kernel, denoise_grid(t.width, t.height), dim3(256), 0, st,
+                               TemporalCubicMomentsArgs{a, tm->taken});
+        else if (tm->feedback)
             temporal_launch_step(st, temporal_feedback_step_kernel<true>, temporal_feedback_step_kernel<false>, is_static, a, t.width, t.height);
         else
             temporal_launch_step(st, temporal_moments_step_kernel<true>, temporal_moments_step_kernel<false>, is_static, a, t.width, t.height);
     };
-    return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch, d_counts != nullptr);
+    return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch, d_counts != nullptr,
+                             d_w2_out);
 }
 
 // The counts step of a moments handle (§4.23): its counts' checks, then the step above.

@@ -56,9 +56,31 @@ __device__ __forceinline__ float tm_spatial_var(float S0, float S1, float S2, fl
     return dn_clamp_var(((dp * S0) / (S0 - 1.0f)) * W2);
 }
 
+// §4.26 (temporal_cubic_kernel.hpp): the colour (NC = 2: and the second record's three channels) of a pixel that found history,
+// from the sixteen taps around the four that ta_gather kept in k — h[r][ch], where the answer is true.
+template <int NC>
+__device__ __forceinline__ bool tc_resample(const TemporalArgs& a, const dn4* const* rec, const TaTaps<2>& k, int32_t id, float nx,
+                                            float ny, float nz, float Px, float Py, float Pz, float (&h)[NC][3]);
+
+// A cubic step's state of one pixel: the taps ta_gather kept, whether the sixteen were taken, and where to say so (or NULL).
+struct TcPixel {
+    TaTaps<2> keep;
+    bool took = false;
+    uint8_t* taken;
+};
+
+// Where ta_gather leaves its taps: in a cubic step's state, or nowhere.
+__device__ __forceinline__ TaTaps<2>* tm_keep(TcPixel* tc) { return &tc->keep; }
+__device__ __forceinline__ TaNoTaps* tm_keep(TaNoTaps*) { return nullptr; }
+
 // The step of one workgroup; s_col and s_nrm: the kernel's two LDS arrays of kTmLdsH·kTmLdsW records.
-template <bool STATIC, bool FEEDBACK>
-__device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const s_col, dn4* const s_nrm) {
+// Cubic = TcPixel (§4.26; the moving form without feedback): ta_gather keeps its taps in *tc, and where tc_resample takes the
+// sixteen taps the colour and m2 are blended into its values instead.
+template <bool STATIC, bool FEEDBACK, class Cubic = TaNoTaps>
+__device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const s_col, dn4* const s_nrm,
+                                        [[maybe_unused]] Cubic* tc = nullptr) {
+    constexpr bool CUBIC = std::is_same<Cubic, TcPixel>::value;
+    static_assert(!(CUBIC && (STATIC || FEEDBACK)), "the cubic path is the moving moments step's");
     const TemporalArgs& a = m.t;
     const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
     const int x = (int)(blockIdx.x * kDnTileW) + tx, y = (int)(blockIdx.y * kDnTileH) + ty;
@@ -82,15 +104,22 @@ __device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const
             // step, the raw first moment, which the v record holds there.
             constexpr int R = FEEDBACK ? 3 : 2;
             const dn4* const rec[3] = {a.prev.c, m.prev_m, a.prev.v};
-            const TaAcc<R> acc = ta_gather<STATIC, R>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
+            const TaAcc<R> acc = ta_gather<STATIC, R>(a, rec, p, id, nx, ny, nz, Px, Py, Pz, tm_keep(tc));
             if (acc.found()) {
                 const TaBlend h = ta_blend_head(acc, a);
-                or_ = ta_blend(h.al, cr, acc.mean(0, 0));
-                og = ta_blend(h.al, cg, acc.mean(0, 1));
-                ob = ta_blend(h.al, cb, acc.mean(0, 2));
-                qr = ta_blend(h.al, cr * cr, acc.mean(1, 0));
-                qg = ta_blend(h.al, cg * cg, acc.mean(1, 1));
-                qb = ta_blend(h.al, cb * cb, acc.mean(1, 2));
+                if constexpr (CUBIC) { // the history's colour and m2: the bilinear means, or tc_resample's values
+                    float hc[2][3] = {{acc.mean(0, 0), acc.mean(0, 1), acc.mean(0, 2)}, {acc.mean(1, 0), acc.mean(1, 1), acc.mean(1, 2)}};
+                    tc->took = tc_resample<2>(a, rec, tc->keep, id, nx, ny, nz, Px, Py, Pz, hc);
+                    or_ = ta_blend(h.al, cr, hc[0][0]), og = ta_blend(h.al, cg, hc[0][1]), ob = ta_blend(h.al, cb, hc[0][2]);
+                    qr = ta_blend(h.al, cr * cr, hc[1][0]), qg = ta_blend(h.al, cg * cg, hc[1][1]), qb = ta_blend(h.al, cb * cb, hc[1][2]);
+                } else {
+                    or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+                    og = ta_blend(h.al, cg, acc.mean(0, 1));
+                    ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                    qr = ta_blend(h.al, cr * cr, acc.mean(1, 0));
+                    qg = ta_blend(h.al, cg * cg, acc.mean(1, 1));
+                    qb = ta_blend(h.al, cb * cb, acc.mean(1, 2));
+                }
                 W2 = __builtin_fmaf(h.k * h.k, acc.mean(1, 3), h.al * h.al);
                 if constexpr (FEEDBACK) {
                     fr = ta_blend(h.al, cr, acc.mean(2, 0));
@@ -149,6 +178,8 @@ __device__ __forceinline__ void tm_step(const TemporalMomentsArgs& m, dn4* const
     a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
     if (a.len_out) a.len_out[p] = No;
     if (m.w2_out) m.w2_out[p] = W2;
+    if constexpr (CUBIC)
+        if (tc->taken) tc->taken[p] = tc->took ? 1 : 0;
 }
 
 template <bool STATIC> __global__ __launch_bounds__(256) void temporal_moments_step_kernel(const TemporalMomentsArgs m) {

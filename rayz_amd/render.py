@@ -1053,11 +1053,14 @@ class Temporal(_Handle):
     the frame it is given into the history reprojected from the previous step's camera and returns the accumulated frame and its
     per-channel variance — what `Denoiser.run_guided` takes.  `device` None: the default device of init().  `moments` True: the
     handle is put into moments mode (`track_moments`, §4.16) and takes `step_moments`, which needs no variance input; with
-    `feedback` True as well it also tracks feedback (`track_feedback`, §4.17) and takes `feedback`."""
+    `feedback` True as well it also tracks feedback (`track_feedback`, §4.17) and takes `feedback`.  `resampling` "cubic": moving
+    steps fetch the colour history with the 4x4 Catmull-Rom kernel where all sixteen history pixels are the same surface, and
+    bilinearly elsewhere (`set_resampling`, §4.26); the default "bilinear" is §4.15 as it is."""
 
     _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
-    def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False, feedback: bool = False):
+    def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False, feedback: bool = False,
+                 resampling: str = "bilinear"):
         self._lib = capi.load()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
@@ -1065,17 +1068,24 @@ class Temporal(_Handle):
                                                                  C.byref(self._h)), "rayz_hip_temporal_create")
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last step: kept alive until the next step or close() (the kernel may still use them)
+        self._taken = None  # the uint8 (height, width) tensor the library writes at every step (set_resampling), or None
         if feedback and not moments:
             self.close()
             raise ValueError("feedback=True needs moments=True: only a moments handle tracks feedback")
-        if moments:
-            try:
+        try:
+            if resampling not in capi.TEMPORAL_RESAMPLING:
+                raise ValueError(f"resampling must be one of {sorted(capi.TEMPORAL_RESAMPLING)}, got {resampling!r}")
+            if feedback and resampling == "cubic":
+                raise ValueError('feedback=True with resampling="cubic": a handle that tracks feedback has no cubic mode')
+            if moments:
                 self.track_moments()
                 if feedback:
                     self.track_feedback()
-            except Exception:
-                self.close()
-                raise
+            if resampling != "bilinear":
+                self.set_resampling(resampling)
+        except Exception:
+            self.close()
+            raise
 
     def track_moments(self) -> None:
         """Puts the handle into moments mode (`rayz_hip_temporal_track_moments`): only while it has no history — after creation
@@ -1087,6 +1097,41 @@ class Temporal(_Handle):
         has no history; a second call does nothing.  From then on `step_moments` takes its variance from that moment, and the
         handle takes `feedback`."""
         capi.check(self._lib, self._lib.rayz_hip_temporal_track_feedback(self._h), "rayz_hip_temporal_track_feedback")
+
+    def set_resampling(self, resampling: str, taken=False) -> None:
+        """How moving steps fetch the colour history from now on (`rayz_hip_temporal_set_resampling`): "bilinear"
+        (the default, §4.15 as it is) or "cubic" — the clamped 4x4 Catmull-Rom kernel where all sixteen history pixels are the
+        same surface, bilinear elsewhere.  May be changed between any two steps.  `taken`: True for a new uint8 (height, width)
+        tensor, or the caller's, which every later step fills with 1 where the pixel took the sixteen taps and 0 elsewhere
+        (`Temporal.taken`); False for none.  Limits: a handle that tracks feedback has no cubic mode, and a cubic handle takes no
+        counts tensor as `spp`."""
+        import torch
+
+        if resampling not in capi.TEMPORAL_RESAMPLING:
+            raise ValueError(f"resampling must be one of {sorted(capi.TEMPORAL_RESAMPLING)}, got {resampling!r}")
+        if taken is True:
+            taken = torch.empty((self.height, self.width), dtype=torch.uint8, device=torch.device("cuda", self._device))
+        elif taken is False or taken is None:
+            taken = None
+        else:
+            _check_tensor("taken", taken, torch.uint8, (self.height, self.width), self._device, "the temporal handle")
+        capi.check(self._lib, self._lib.rayz_hip_temporal_set_resampling(self._h, capi.TEMPORAL_RESAMPLING[resampling],
+                                                                         C.c_void_p(taken.data_ptr() if taken is not None else None)),
+                   "rayz_hip_temporal_set_resampling")
+        self._taken = taken  # (every later step writes it and keeps it in _inflight, so a step still running when it is replaced holds it)
+
+    @property
+    def resampling(self) -> str:
+        """"bilinear" or "cubic": the handle's mode (`rayz_hip_temporal_get_resampling`)."""
+        mode = C.c_uint32()
+        capi.check(self._lib, self._lib.rayz_hip_temporal_get_resampling(self._h, C.byref(mode)), "rayz_hip_temporal_get_resampling")
+        return {v: k for k, v in capi.TEMPORAL_RESAMPLING.items()}[mode.value]
+
+    @property
+    def taken(self):
+        """The uint8 (height, width) tensor `set_resampling(..., taken=...)` named, holding the last step's bytes once that step has
+        finished: 1 where the pixel's colour history came from the sixteen taps.  None: no such tensor."""
+        return self._taken
 
     def feedback(self, rgb, stream: int = 0) -> None:
         """Replaces the colour history the last step left with `rgb` ((height, width, 3) float32 on the handle's device) — SVGF's
@@ -1130,6 +1175,8 @@ class Temporal(_Handle):
 
         if not isinstance(spp, torch.Tensor):
             return None
+        if self.resampling == "cubic":
+            raise ValueError('a handle in "cubic" resampling mode takes no counts tensor as spp (set_resampling("bilinear") first)')
         _check_tensor("spp", spp, torch.int32, (self.height, self.width), self._device, "the temporal handle")
         if int(spp.min()) < 0:
             raise ValueError("spp holds a negative sample count")
@@ -1157,7 +1204,7 @@ class Temporal(_Handle):
                                       C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
                                       C.c_void_p(stream or None))
         capi.check(self._lib, rc, name)
-        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length, counts)
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length, counts, self._taken)  # (the step writes the taken bytes too)
         return (out, var_out) if length is None else (out, var_out, length)
 
     def step_moments(self, rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp, out=None, var_out=None, length=False,
@@ -1193,7 +1240,7 @@ class Temporal(_Handle):
                                       C.c_void_p(length.data_ptr() if length is not None else None),
                                       C.c_void_p(w2.data_ptr() if w2 is not None else None), C.c_void_p(stream or None))
         capi.check(self._lib, rc, name)
-        self._inflight = (rgb, gbuffer, out, var_out, length, w2, counts)
+        self._inflight = (rgb, gbuffer, out, var_out, length, w2, counts, self._taken)
         return (out, var_out) + tuple(t for t in (length, w2) if t is not None)
 
     def reset(self) -> None:

@@ -57,7 +57,21 @@ rayz_hip_denoiser_run_guided_tap) on --moments' one-chunk fram
     chunks, `Upscaler.run` with its variance, `run_guided`; and a full-resolution frame of 4 spp in one chunk through the moments
     step and `run_guided`.
 
-    python tools/temporal_bench.py --counts [the switches above]"""
+    python tools/temporal_bench.py --counts [the switches above]
+
+--cubic measures the cubic resampling mode (rayz_hip_temporal_set_resampling) beside the bilinear one, the two
+alternating in one process on the same frames.
+(a) Cost.  The panned step (frame 1 on frame 0's history) of a plain and of a moments handle in both modes, by the handles' own
+    HIP events, each beside a device copy of the step's compulsory bytes (204 / 208 B per pixel; + 1 with the taken bytes, which the
+    cubic handles here write), and the share of pixels that took the sixteen taps.  With --lib a second build's bilinear step
+    cannot be loaded into the same process; run the tool once per build and compare the "bilinear" rows.
+(b) Quality.  Per frame, MSE against the --ref-spp frame of the temporal step alone and of the step + `run_guided`, bilinear
+    against cubic, on one-chunk frames through moments handles — over the whole frame, over the pixels whose first hit is diffuse
+    and over those whose first hit is metal or glass (as tools/denoise_bench.py --chain splits them).  --pan 3 is the integer pan
+    (fx = 0 up to rounding), --pan 2.5 a fractional one; --motion orbit turns look_from about the focus point by --pan pixel widths
+    per frame, so that look_from and the view direction both change and the image motion depends on depth.  --config 2 | 3.
+
+    python tools/temporal_bench.py --cubic [--config 3] [--motion pan|orbit] [--pan 2.5] [--lib PATH --lib-label NAME] [the switches above]"""
 import argparse
 import json
 import os
@@ -518,6 +532,155 @@ def main_feedback(args):
             json.dump(res, f, indent=1)
 
 
+def orbited(cam, pixels, width, height):
+    """`cam` turned about the centre of its pixel plane (the focus point), around the image's vertical axis, so that look_from
+    moves along its arc by `pixels` pixel widths as measured in that plane: look_from AND the view direction change, a point in the
+    focus plane stays where it is, nearer and farther ones move in opposite directions by amounts that depend on their depth."""
+    import numpy as np
+
+    lf, du, dv, po = (np.array(list(getattr(cam, k))) for k in ("look_from", "px_du", "px_dv", "px_origin"))
+    pivot = po + du * (width / 2) + dv * (height / 2)
+    axis = dv / np.linalg.norm(dv)
+    th = pixels * np.linalg.norm(du) / np.linalg.norm(pivot - lf)
+
+    def rot(v):  # Rodrigues
+        return v * np.cos(th) + np.cross(axis, v) * np.sin(th) + axis * (axis @ v) * (1 - np.cos(th))
+
+    c = capi.CameraDesc.from_buffer_copy(cam)
+    nlf = pivot + rot(lf - pivot)
+    npo = pivot + rot(po - pivot)
+    for name, v in (("look_from", nlf), ("px_origin", npo), ("px_du", rot(du)), ("px_dv", rot(dv)),
+                    ("defocus_u", rot(np.array(list(cam.defocus_u)))), ("defocus_v", rot(np.array(list(cam.defocus_v))))):
+        for j in range(3):
+            getattr(c, name)[j] = float(v[j])
+    return c
+
+
+def main_cubic(args):
+    """--cubic: see the module docstring."""
+    if args.lib:  # an older build: without the mode's two entry points
+        capi.PROTOTYPES[:] = [q for q in capi.PROTOTYPES if "resampling" not in q[0]]
+        capi.LIB_PATH = os.path.abspath(args.lib)
+    render.init(0)
+    t = tracer.randomBouncing(args.width, seed=42) if args.config == 2 else tracer.randomBouncing(args.width, -50, 50, seed=42)
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    assert args.spp <= 16, "--cubic wants an spp of at most 16: one automatic chunk"
+    ds = render.DeviceScene(sd)
+    has_mode = any(name == "rayz_hip_temporal_set_resampling" for name, _, _ in capi.PROTOTYPES) and not args.lib
+    move = (lambda k: orbited(cam, args.pan * k, w, h)) if args.motion == "orbit" else (lambda k: panned(cam, args.pan * k))
+    res = {"mode": "cubic", "config": args.config, "motion": args.motion, "size": f"{w}x{h}", "frames": args.frames, "px_per_frame": args.pan,
+           "spp": args.spp, "ref_spp": args.ref_spp, "reps": args.reps, "build": args.lib_label or ("--lib" if args.lib else "this build")}
+    kinds = torch.tensor([sd.materials[i].kind for i in range(sd.n_materials)], device="cuda")
+    seq = []
+    for k in range(args.frames if not args.cost_only else 2):
+        c = move(k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed, q.chunk_spp = 1000 + k, 0
+        one = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ds.render_into(c, q, one.data_ptr())
+        ds.sync()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        ref = None
+        if not args.cost_only:
+            q.samples_per_px, q.seed = args.ref_spp, 7
+            ref = torch.empty_like(one)
+            torch.cuda.synchronize()
+            ds.render_into(c, q, ref.data_ptr())
+            ds.sync()
+        seq.append((c, one, g, ref))
+        print(f"frame {k}: {args.spp} spp in one chunk" + ("" if ref is None else f", reference {args.ref_spp} spp"), flush=True)
+    var = torch.full((h, w, 3), 1e-3, dtype=torch.float32, device="cuda")  # (the plain step's cost does not depend on the variance's values)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    taken = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+
+    # ---- (a) cost: the moved step, the variants alternating -------------------------------------------------------------------
+    res["cost"] = {}
+    modes = ("bilinear", "cubic") if has_mode else ("bilinear",)
+    handles = {(kind, mode): render.Temporal(w, h, moments=kind == "moments") for kind in ("plain", "moments") for mode in modes}
+    for (kind, mode), tm in handles.items():
+        if has_mode:
+            tm.set_resampling(mode, taken=taken if mode == "cubic" else False)
+
+    def two_steps(kind, tm):
+        tm.reset()
+        for c, one, g, _ in seq[:2]:
+            if kind == "plain":
+                tm.step(one, var, g, c, args.spp, out=out, var_out=vout)
+            else:
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout)
+
+    ms = {k: [] for k in handles}
+    for r in range(args.warmup + args.reps):
+        for (kind, mode), tm in handles.items():
+            two_steps(kind, tm)
+            x = tm.timing()
+            if r >= args.warmup:
+                ms[(kind, mode)].append(x)
+    for kind, nbytes in (("plain", STEP_BYTES), ("moments", MOMENTS_STEP_BYTES)):
+        for mode in modes:
+            per_pixel = nbytes + (1 if mode == "cubic" else 0)  # (the cubic handles here write the taken bytes)
+            cp = copy_ms(n * per_pixel // 2, args.reps, args.warmup)
+            v = ms[(kind, mode)]
+            med = statistics.median(v)
+            share = None
+            if mode == "cubic":
+                two_steps(kind, handles[(kind, mode)])
+                torch.cuda.synchronize()
+                share = float(taken[seq[1][2].index >= 0].float().mean())
+            res["cost"][f"{kind} {mode}"] = {"ms": med, "min": min(v), "max": max(v), "bytes_per_pixel": per_pixel, "copy_ms": cp[0], "copy_min": cp[1],
+                                             "copy_max": cp[2], "ratio_to_copy": med / cp[0], "taken_share_of_hits": share}
+            print(f"{kind} step, {mode:8s}, {args.motion} {args.pan} px: {med:.4f} ms [{min(v):.4f}, {max(v):.4f}] = {med / cp[0]:.2f} x the copy of its "
+                  f"{per_pixel} B per pixel ({cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}])"
+                  + ("" if share is None else f"; {share:.4f} of the hit pixels took the sixteen taps"), flush=True)
+    for tm in handles.values():
+        tm.close()
+
+    # ---- (b) quality: moments handles on the one-chunk frames -------------------------------------------------------------------
+    if not args.cost_only and has_mode:
+        dn = render.Denoiser(w, h)
+        den = torch.empty_like(out)
+        res["rows"] = []
+        tms = {mode: render.Temporal(w, h, moments=True, resampling=mode) for mode in modes}
+        tms["cubic"].set_resampling("cubic", taken=taken)
+        for k, (c, one, g, ref) in enumerate(seq):
+            hit = g.index >= 0
+            spec = hit & (kinds[g.material.clamp(min=0).long()] != capi.MAT_DIFFUSE)  # first hit metal or glass, as denoise_bench.py --chain
+            diff = hit & ~spec
+
+            def mse3(a):
+                err = ((a.double() - ref.double()) ** 2).mean(dim=2)
+                return [float(err.mean()), float(err[diff].mean()), float(err[spec].mean())]
+
+            row = {"frame": k, "raw": mse3(one), "share_diffuse": float(diff.float().mean()), "share_specular": float(spec.float().mean())}
+            for mode, tm in tms.items():
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout)
+                dn.run_guided(out, vout, g, out=den)
+                torch.cuda.synchronize()
+                row[f"temporal_{mode}"], row[f"temporal_guided_{mode}"] = mse3(out), mse3(den)
+            row["taken_share_of_hits"] = float(taken[hit].float().mean())
+            res["rows"].append(row)
+            rel = lambda key: " ".join(f"{a / b:.4f}" for a, b in zip(row[key], row["raw"]))  # noqa: E731
+            print(f"frame {k:2d}: MSE / raw (all | diffuse | metal or glass): temporal bilinear {rel('temporal_bilinear')}, cubic {rel('temporal_cubic')}; "
+                  f"+ guided bilinear {rel('temporal_guided_bilinear')}, cubic {rel('temporal_guided_cubic')}; taken {row['taken_share_of_hits']:.4f}", flush=True)
+        print(f"raw MSE of the last frame (all | diffuse | metal or glass): {row['raw']}; pixel shares: diffuse {row['share_diffuse']:.3f}, "
+              f"metal or glass {row['share_specular']:.3f}", flush=True)
+        for tm in tms.values():
+            tm.close()
+        dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -533,7 +696,17 @@ def main():
     ap.add_argument("--settle", type=int, default=6, help="--moments: static frames behind a 'settled' history (W2 = 1 / settle)")
     ap.add_argument("--feedback", action="store_true", help="measure the feedback of the filtered colour (DESIGN.md §4.17) beside the moments step")
     ap.add_argument("--counts", action="store_true", help="measure the counts step (DESIGN.md §4.23) beside the scalar steps")
+    ap.add_argument("--cubic", action="store_true", help="measure the cubic resampling mode (DESIGN.md §4.26) beside the bilinear one")
+    ap.add_argument("--cost-only", action="store_true", help="--cubic: the cost part alone (two frames, no references)")
+    ap.add_argument("--config", type=int, default=3, choices=(2, 3), help="--cubic: BASELINE config 2 (grid [-11, 11)) or 3 (grid [-50, 50))")
+    ap.add_argument("--motion", default="pan", choices=("pan", "orbit"),
+                    help="--cubic: pan (px_origin moved along px_du by --pan pixels per frame) or orbit (look_from turned about the focus point by --pan "
+                         "pixel widths per frame)")
+    ap.add_argument("--lib-label", default=None, help="--cubic: what to call --lib's build in the output")
+    ap.add_argument("--lib", default=None, help="--cubic: load this build of librayz_hip.so (an older one: its bilinear step alone is timed)")
     args = ap.parse_args()
+    if args.cubic:
+        return main_cubic(args)
     if args.counts:
         return main_counts(args)
     if args.feedback:
