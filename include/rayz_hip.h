@@ -1125,6 +1125,31 @@ int rayz_hip_temporal_step_moments_counts(RayzTemporal* tm, const RayzTemporalPa
 int rayz_hip_temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken_or_null);
 int rayz_hip_temporal_get_resampling(RayzTemporal* tm, uint32_t* mode);
 
+/* ---- temporal accumulation, background mode: history for pixels whose centre ray misses the scene -----
+ * BUILD-DEFINED, additive within ABI 5, opt-in: a handle starts in RAYZ_TEMPORAL_BACKGROUND_INPUT, where a pixel with index < 0
+ * passes its input through as before, bit for bit.  In RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE such a pixel gathers history as a hit
+ * pixel does: a miss sees the sky at infinity, so its place in the previous frame depends only on how the view turned — the 3x3
+ * matrix between the two cameras' pixel grids, computed on the host in f64 (look_from does not enter: the sky has no parallax).
+ * Its four bilinear taps accept the history pixels that were misses themselves (no normal or distance test; in a counts step also
+ * a length > 0); the weight threshold, the renormalisation, the blend and the stores are a hit pixel's.  In a counts step a
+ * background pixel with count 0 that finds history keeps it, so a NaN input reaches neither the outputs nor the history.  In
+ * moments mode its variance is the temporal one where it found history and W2 <= w2_max, and +0 elsewhere: the 7x7 spatial
+ * estimate stays a hit pixel's.  Every pixel with index >= 0 is the INPUT-mode step bit for bit, outputs and history.
+ * The history's layout does not change and the handle gains no device state, so the mode may be changed between any two steps:
+ * an ACCUMULATE step reads the records an INPUT step left, and the other way round.  Plain and moments handles take it through
+ * all four steps (rayz_hip_temporal_step, _step_moments, _step_counts, _step_moments_counts).  The arithmetic is a contract
+ * (§4.27), restated by tests/temporal_background_mirror.cpp.
+ * What it does not know: a sky pixel beside a defocused or motion-blurred silhouette has samples that hit, and those do have
+ * parallax; the mode treats the pixel as sky.  That is why it is not the default.
+ * Limits of this version, all RAYZ_ERR_STATE: a handle that tracks feedback refuses set_background(ACCUMULATE) and an ACCUMULATE
+ * handle refuses rayz_hip_temporal_track_feedback; a handle in cubic resampling mode refuses set_background(ACCUMULATE) and an
+ * ACCUMULATE handle refuses set_resampling(CUBIC) — the sky has no cubic rule yet.
+ * RAYZ_ERR_BAD_ARG (checked before the handle): a mode that is neither constant.  RAYZ_ERR_STATE: a bad handle. */
+#define RAYZ_TEMPORAL_BACKGROUND_INPUT      0u   /* default: every section as it is */
+#define RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE 1u
+int rayz_hip_temporal_set_background(RayzTemporal* tm, uint32_t mode);
+int rayz_hip_temporal_get_background(RayzTemporal* tm, uint32_t* mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,8 @@ TEMPORAL_DEFAULTS = {"alpha_min": 0.05, "n_max": 65536.0, "normal_cos_min": 0.9,
 TEMPORAL_MOMENTS_DEFAULTS = {"w2_max": 0.25, "min_taps": 4.0}  # provisional
 TEMPORAL_RESAMPLE_BILINEAR, TEMPORAL_RESAMPLE_CUBIC = 0, 1  # RAYZ_TEMPORAL_RESAMPLE_* 
 TEMPORAL_RESAMPLING = {"bilinear": TEMPORAL_RESAMPLE_BILINEAR, "cubic": TEMPORAL_RESAMPLE_CUBIC}
+TEMPORAL_BACKGROUND_INPUT, TEMPORAL_BACKGROUND_ACCUMULATE = 0, 1  # RAYZ_TEMPORAL_BACKGROUND_* 
+TEMPORAL_BACKGROUND = {"input": TEMPORAL_BACKGROUND_INPUT, "accumulate": TEMPORAL_BACKGROUND_ACCUMULATE}
 
 D3 = C.c_double * 3
 
@@ -319,6 +321,8 @@ PROTOTYPES = [
       C.POINTER(QueryOutputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rayz_hip_temporal_set_resampling", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("rayz_hip_temporal_get_resampling", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("rayz_hip_temporal_set_background", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("rayz_hip_temporal_get_background", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
 ]
 
 

@@ -1,6 +1,7 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
 // temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp) and
-// the one procedure of a step of either kind, temporal_run_step.
+// the one procedure of a step of either kind, temporal_run_step; the background mode's host part and calls (§4.27; its kernels:
+// temporal_background_kernel.hpp).
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
@@ -20,13 +21,14 @@ struct RayzTemporal : FrameHandle<2 * 4, 3> {
                             // m1 instead, and which takes rayz_hip_temporal_feedback (§4.17)
     uint32_t resampling = RAYZ_TEMPORAL_RESAMPLE_BILINEAR; // rayz_hip_temporal_set_resampling (§4.26): how a moving step fetches the colour history
     uint8_t* taken = nullptr; // .. and the caller's device bytes every step writes (1: the pixel took the cubic path), or NULL
+    uint32_t background = RAYZ_TEMPORAL_BACKGROUND_INPUT; // rayz_hip_temporal_set_background (§4.27): whether a pixel with id < 0 gathers history
 };
 
 namespace {
 
-// The host part of a step (§4.15), f64, every operation written out: M = the inverse of the matrix with columns px_du, px_dv and
-// px_origin − look_from, each entry rounded once to f32, and look_from in f32.  False: det is zero or not finite.
-bool temporal_camera_matrix(const RayzCameraDesc* c, float* M, float* from) {
+// What §4.15's and §4.27's host parts share of a camera with u = px_du, v = px_dv, a = px_origin − look_from, f64, every operation
+// written out: the rows r0 = v×a, r1 = a×u, r2 = u×v; returns det = u·r0.
+double temporal_camera_rows(const RayzCameraDesc* c, double (&r)[3][3]) {
     const double *u = c->px_du, *v = c->px_dv;
     const double a[3] = {c->px_origin[0] - c->look_from[0], c->px_origin[1] - c->look_from[1], c->px_origin[2] - c->look_from[2]};
     auto cross = [](const double* p, const double* q, double* o) {
@@ -34,16 +36,40 @@ bool temporal_camera_matrix(const RayzCameraDesc* c, float* M, float* from) {
         o[1] = p[2] * q[0] - p[0] * q[2];
         o[2] = p[0] * q[1] - p[1] * q[0];
     };
-    double r[3][3];
     cross(v, a, r[0]);
     cross(a, u, r[1]);
     cross(u, v, r[2]);
-    const double det = (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
+    return (u[0] * r[0][0] + u[1] * r[0][1]) + u[2] * r[0][2];
+}
+
+// The host part of a step (§4.15): M = the inverse of the matrix with columns px_du, px_dv and px_origin − look_from, each entry
+// rounded once to f32, and look_from in f32.  False: det is zero or not finite.
+bool temporal_camera_matrix(const RayzCameraDesc* c, float* M, float* from) {
+    double r[3][3];
+    const double det = temporal_camera_rows(c, r);
     if (!(det != 0.0) || !std::isfinite(det)) return false;
     for (int k = 0; k < 3; ++k)
         for (int j = 0; j < 3; ++j) M[3 * k + j] = (float)(r[k][j] / det);
     for (int j = 0; j < 3; ++j) from[j] = (float)c->look_from[j];
     return true;
+}
+
+// The host part of a step in ACCUMULATE mode (§4.27), f64: G = the previous camera's rows over its det, times the matrix with
+// columns px_du, px_dv and px_origin − look_from of this step's camera, each entry rounded once to f32 — this frame's pixel centre
+// (x, y, 1) to s·(x', y', 1) in the previous frame.  prev was a step's camera: its det passed temporal_camera_matrix.
+void temporal_background_matrix(const RayzCameraDesc* prev, const RayzCameraDesc* cam, float* G) {
+    double r[3][3];
+    const double det = temporal_camera_rows(prev, r);
+    const double a[3] = {cam->px_origin[0] - cam->look_from[0], cam->px_origin[1] - cam->look_from[1], cam->px_origin[2] - cam->look_from[2]};
+    const double* c[3] = {cam->px_du, cam->px_dv, a};
+    for (int k = 0; k < 3; ++k)
+        for (int j = 0; j < 3; ++j) G[3 * k + j] = (float)(((r[k][0] * c[j][0] + r[k][1] * c[j][1]) + r[k][2] * c[j][2]) / det);
+}
+
+// G as the background kernels take it: zeros where no pixel reads it (no history, or a static step).
+void temporal_background_args(const RayzTemporal* tm, const RayzCameraDesc* cam, bool is_static, float* G) {
+    std::memset(G, 0, 9 * sizeof(float));
+    if (tm->has_history && !is_static) temporal_background_matrix(&tm->cam, cam, G);
 }
 
 // The checks both kinds of step make of the parameters and the sample count ..
@@ -146,7 +172,12 @@ int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const Rayz
     if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
     const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) { // (behind the handle's check: tm is a handle)
         using namespace rayz_dev_cubic;
-        if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static)
+        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) { // (never a cubic handle: set_background refused it)
+            using namespace rayz_dev_bg;
+            TemporalBgArgs b{a, {}, nullptr};
+            temporal_background_args(tm, cam, is_static, b.G);
+            temporal_launch_step(st, temporal_bg_kernel<true>, temporal_bg_kernel<false>, is_static, b, a.width, a.height);
+        } else if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static)
             hipLaunchKernelGGL(temporal_cubic_step_kernel, denoise_grid(a.width, a.height), dim3(256), 0, st, TemporalCubicArgs{a, tm->taken});
         else
             temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
@@ -161,6 +192,8 @@ int temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken) {
     RAYZ_TRY(frame_handle_check(tm));
     if (mode == RAYZ_TEMPORAL_RESAMPLE_CUBIC && tm->feedback)
         return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle that tracks feedback has no cubic mode (its raw first moment has no resampling rule)");
+    if (mode == RAYZ_TEMPORAL_RESAMPLE_CUBIC && tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE)
+        return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle that accumulates the background has no cubic mode (rayz_hip_temporal_set_background back to input first)");
     tm->resampling = mode, tm->taken = d_taken;
     return RAYZ_OK;
 }
@@ -168,6 +201,25 @@ int temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken) {
 int temporal_get_resampling(RayzTemporal* tm, uint32_t* mode) {
     RAYZ_TRY(frame_handle_check(tm));
     if (mode) *mode = tm->resampling;
+    return RAYZ_OK;
+}
+
+// §4.27's mode.  The mode is an argument and is checked before the handle, as a step's arguments are.
+int temporal_set_background(RayzTemporal* tm, uint32_t mode) {
+    if (mode != RAYZ_TEMPORAL_BACKGROUND_INPUT && mode != RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE)
+        return fail(RAYZ_ERR_BAD_ARG, "temporal background mode %u: must be RAYZ_TEMPORAL_BACKGROUND_INPUT or _ACCUMULATE", mode);
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE && tm->feedback)
+        return fail(RAYZ_ERR_STATE, "temporal set_background: a handle that tracks feedback does not accumulate the background (its steps have no background kernels)");
+    if (mode == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE && tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
+        return fail(RAYZ_ERR_STATE, "temporal set_background: a handle in cubic resampling mode does not accumulate the background (rayz_hip_temporal_set_resampling back to bilinear first)");
+    tm->background = mode;
+    return RAYZ_OK;
+}
+
+int temporal_get_background(RayzTemporal* tm, uint32_t* mode) {
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode) *mode = tm->background;
     return RAYZ_OK;
 }
 
@@ -191,8 +243,14 @@ int temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* params, con
     RAYZ_TRY(temporal_counts_check(d_counts, {d_out, d_var_out, d_len_out}));
     const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) {
         using namespace rayz_dev_counts;
-        temporal_launch_step(st, temporal_counts_kernel<true>, temporal_counts_kernel<false>, is_static, TemporalCountsArgs{a, d_counts},
-                             a.width, a.height);
+        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) {
+            using namespace rayz_dev_bg;
+            TemporalBgArgs b{a, {}, d_counts};
+            temporal_background_args(tm, cam, is_static, b.G);
+            temporal_launch_step(st, temporal_bg_counts_kernel<true>, temporal_bg_counts_kernel<false>, is_static, b, a.width, a.height);
+        } else
+            temporal_launch_step(st, temporal_counts_kernel<true>, temporal_counts_kernel<false>, is_static, TemporalCountsArgs{a, d_counts},
+                                 a.width, a.height);
     };
     return temporal_run_step(tm, false, p, cam, 0, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch, true);
 }
@@ -244,6 +302,14 @@ int rayz_hip_temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d
 
 int rayz_hip_temporal_get_resampling(RayzTemporal* tm, uint32_t* mode) {
     return guarded([&] { return temporal_get_resampling(tm, mode); });
+}
+
+int rayz_hip_temporal_set_background(RayzTemporal* tm, uint32_t mode) {
+    return guarded([&] { return temporal_set_background(tm, mode); });
+}
+
+int rayz_hip_temporal_get_background(RayzTemporal* tm, uint32_t* mode) {
+    return guarded([&] { return temporal_get_background(tm, mode); });
 }
 
 int rayz_hip_temporal_reset(RayzTemporal* tm) {

@@ -1,0 +1,252 @@
+// temporal_background_kernel.hpp — the device code of temporal accumulation's background mode (include/rayz_hip.h:
+// rayz_hip_temporal_set_background; the host side: temporal.hpp, temporal_moments.hpp; the steps it is made from:
+// temporal_kernel.hpp, temporal_moments_kernel.hpp, temporal_counts_kernel.hpp).
+//
+// The plain, the moments and the two counts steps with ONE difference: a pixel whose centre ray misses the scene (id < 0) gathers
+// history too.  A miss sees the sky at infinity, so where it lay in the previous frame depends only on how the view turned: the
+// host gives the 3x3 matrix G that takes this frame's pixel centre (x, y, 1) to s·(x', y', 1) in the previous frame, and bg_gather
+// runs §4.15's taps from there, accepting the history pixels that were misses themselves — no normal and no distance to compare.
+// Everything behind the sums is the hit pixel's arithmetic through the same functions.  A pixel with id >= 0 takes ta_gather and is
+// the INPUT-mode step bit for bit, outputs and history.
+//
+// A background lane takes the same two rounds of loads as a hit lane: the four taps' indices (the .w of their guide records; the
+// point records are not read), then the records the taps add.  G arrives through the kernel arguments and is the same for every
+// lane: scalar operands of the three FMAs per row.  A wave with both kinds of lane runs both gathers, one after the other.
+//
+// Eight kernels, in a namespace of their own: {plain, moments} x {one spp, a count per pixel} x {static, moving}.  COUNTS is a
+// template flag of the two bodies; the existing kernels are not touched and rayz_dev holds exactly the kernels it held.
+#pragma once
+
+#include "temporal_moments_kernel.hpp"
+
+namespace rayz_dev_bg {
+using namespace rayz_dev;
+
+struct TemporalBgArgs {
+    TemporalArgs t;         // the plain step's arguments; with counts, t.spp is not read
+    float G[9];             // this frame's pixel centre -> the previous frame's, up to scale (row-major; not read by a static step)
+    const uint32_t* counts; // the counts kernels: per pixel, the samples the current frame adds (never an output); else not read
+};
+
+struct TemporalBgMomentsArgs {
+    TemporalMomentsArgs m; // the moments step's arguments; with counts, m.t.spp is not read
+    float G[9];
+    const uint32_t* counts;
+};
+
+// §4.27 rules 1 and 2 for one pixel (x, y) with id < 0 of a handle with history: the sums over the history taps that were misses.
+// rec, R, STATIC, LIVE: as ta_gather's.
+template <bool STATIC, int R, bool LIVE>
+__device__ __forceinline__ TaAcc<R> bg_gather(const TemporalArgs& a, const float (&G)[9], const dn4* const* rec, size_t p, int x, int y) {
+    TaAcc<R> acc;
+    if (STATIC) {
+        if (__float_as_int(a.prev.g[p].w) < 0) {
+            dn4 own[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) own[r] = rec[r][p];
+            if (!LIVE || own[0].w > 0.0f) acc.add(own, 1.0f);
+        }
+        return acc;
+    }
+    const float xf = (float)x, yf = (float)y;
+    const float al = __builtin_fmaf(G[1], yf, __builtin_fmaf(G[0], xf, G[2]));
+    const float be = __builtin_fmaf(G[4], yf, __builtin_fmaf(G[3], xf, G[5]));
+    const float ga = __builtin_fmaf(G[7], yf, __builtin_fmaf(G[6], xf, G[8]));
+    if (!(ga > 0.0f)) return acc;
+    const float hx = al / ga, hy = be / ga;
+    if (!(hx > -1.0f && hx < (float)a.width && hy > -1.0f && hy < (float)a.height)) return acc; // (so the casts below are in range)
+    const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
+    const float fx = hx - x0, fy = hy - y0;
+    const int ix = (int)x0, iy = (int)y0;
+    // Two rounds of loads, as ta_gather's: every tap's index, then the records it adds.  A tap outside the frame loads the nearest
+    // pixel inside it (a valid address) and is refused.
+    size_t q[4];
+    bool ok[4];
+    float gw[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int qx = ix + (t & 1), qy = iy + (t >> 1);
+        ok[t] = qx >= 0 && qx < (int)a.width && qy >= 0 && qy < (int)a.height;
+        const int cx = qx < 0 ? 0 : (qx >= (int)a.width ? (int)a.width - 1 : qx);
+        const int cy = qy < 0 ? 0 : (qy >= (int)a.height ? (int)a.height - 1 : qy);
+        q[t] = (size_t)cy * a.width + (size_t)cx;
+        gw[t] = a.prev.g[q[t]].w;
+    }
+    dn4 tap[4][R];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        ok[t] = ok[t] && __float_as_int(gw[t]) < 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) tap[t][r] = rec[r][q[t]];
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) // j outer, i inner: t = 2·j + i
+        if (ok[t] && (!LIVE || tap[t][0].w > 0.0f)) acc.add(tap[t], ((t & 1) ? fx : 1.0f - fx) * ((t >> 1) ? fy : 1.0f - fy));
+    return acc;
+}
+
+// §4.27 on §4.15 (COUNTS: on §4.23's plain step): the step's body with the gather chosen by the pixel's kind.
+template <bool STATIC, bool COUNTS> __device__ __forceinline__ void bg_plain_step(const TemporalBgArgs& ba) {
+    const TemporalArgs& a = ba.t;
+    const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
+    const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
+    if (x >= (int)a.width || y >= (int)a.height) return;
+    const size_t p = (size_t)y * a.width + (size_t)x;
+    const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
+    const float sr = dn_clamp_var(a.var[3 * p]), sg = dn_clamp_var(a.var[3 * p + 1]), sb = dn_clamp_var(a.var[3 * p + 2]);
+    const int32_t id = a.index[p];
+    const float nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
+    const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
+    const float n = COUNTS ? (float)ba.counts[p] : a.spp;
+    float or_ = cr, og = cg, ob = cb, vr = sr, vg = sg, vb = sb, No = n; // no history: the input, by selection
+    if (a.has_history) {
+        const dn4* const rec[2] = {a.prev.c, a.prev.v};
+        TaAcc<2> acc;
+        if (id >= 0)
+            acc = ta_gather<STATIC, 2, COUNTS>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
+        else
+            acc = bg_gather<STATIC, 2, COUNTS>(a, ba.G, rec, p, x, y);
+        if (acc.found()) {
+            const TaBlend h = ta_blend_head(acc, a, n);
+            No = h.N; // (n = 0: hN + 0, capped)
+            if (!COUNTS || n > 0.0f) {
+                const float a2 = h.al * h.al, k2 = h.k * h.k;
+                or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+                og = ta_blend(h.al, cg, acc.mean(0, 1));
+                ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                vr = __builtin_fmaf(a2, sr, k2 * acc.mean(1, 0));
+                vg = __builtin_fmaf(a2, sg, k2 * acc.mean(1, 1));
+                vb = __builtin_fmaf(a2, sb, k2 * acc.mean(1, 2));
+            } else { // no sample: the gathered history, by selection — the input is loaded and never used
+                or_ = acc.mean(0, 0), og = acc.mean(0, 1), ob = acc.mean(0, 2);
+                vr = acc.mean(1, 0), vg = acc.mean(1, 1), vb = acc.mean(1, 2);
+            }
+        }
+    }
+    a.next.c[p] = dn4{or_, og, ob, No};
+    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
+    a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
+    a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
+    a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
+    a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
+    if (a.len_out) a.len_out[p] = No;
+}
+
+// §4.27 on §4.16 (COUNTS: on §4.23's moments step): tm_step's body without its feedback and cubic modes.  The barriers are
+// tm_step's — the vote and the barrier behind the staging are reached by all 256 threads, a thread outside the frame skips only the
+// per-pixel work and the stores — and so is the LDS.  A background pixel never votes for the staging: its variance is the
+// temporal one where it found history that is long enough, and +0 elsewhere.
+template <bool STATIC, bool COUNTS>
+__device__ __forceinline__ void bg_moments_step(const TemporalBgMomentsArgs& ba, dn4* const s_col, dn4* const s_nrm) {
+    const TemporalMomentsArgs& m = ba.m;
+    const TemporalArgs& a = m.t;
+    const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
+    const int x = (int)(blockIdx.x * kDnTileW) + tx, y = (int)(blockIdx.y * kDnTileH) + ty;
+    const bool inside = x < (int)a.width && y < (int)a.height; // NO early return: every thread reaches the vote and the barrier
+    const size_t p = inside ? (size_t)y * a.width + (size_t)x : 0;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f, Px = 0.0f, Py = 0.0f, Pz = 0.0f;
+    float or_ = 0.0f, og = 0.0f, ob = 0.0f, No = 0.0f, qr = 0.0f, qg = 0.0f, qb = 0.0f, W2 = 1.0f, vr = 0.0f, vg = 0.0f, vb = 0.0f;
+    int32_t id = -1;
+    bool spatial = false;
+    if (inside) {
+        const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
+        const float n = COUNTS ? (float)ba.counts[p] : a.spp;
+        id = a.index[p];
+        nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
+        Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
+        or_ = cr, og = cg, ob = cb, No = n;                  // no history: the input, by selection ..
+        qr = cr * cr, qg = cg * cg, qb = cb * cb, W2 = 1.0f; // .. its square, and the weight of one frame
+        bool found = false;
+        if (a.has_history) {
+            const dn4* const rec[2] = {a.prev.c, m.prev_m};
+            TaAcc<2> acc;
+            if (id >= 0)
+                acc = ta_gather<STATIC, 2, COUNTS>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
+            else
+                acc = bg_gather<STATIC, 2, COUNTS>(a, ba.G, rec, p, x, y);
+            found = acc.found();
+            if (found) {
+                const TaBlend h = ta_blend_head(acc, a, n);
+                No = h.N; // (n = 0: hN + 0, capped)
+                if (!COUNTS || n > 0.0f) {
+                    or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+                    og = ta_blend(h.al, cg, acc.mean(0, 1));
+                    ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                    qr = ta_blend(h.al, cr * cr, acc.mean(1, 0));
+                    qg = ta_blend(h.al, cg * cg, acc.mean(1, 1));
+                    qb = ta_blend(h.al, cb * cb, acc.mean(1, 2));
+                    W2 = __builtin_fmaf(h.k * h.k, acc.mean(1, 3), h.al * h.al);
+                } else { // no sample: the gathered means, by selection (al = 0, k = 1) — the input is loaded and never used
+                    or_ = acc.mean(0, 0), og = acc.mean(0, 1), ob = acc.mean(0, 2);
+                    qr = acc.mean(1, 0), qg = acc.mean(1, 1), qb = acc.mean(1, 2), W2 = acc.mean(1, 3);
+                }
+            }
+        }
+        spatial = id >= 0 && W2 > m.wm;
+        if (id >= 0 ? !spatial : (found && !(W2 > m.wm)))
+            vr = tm_temporal_var(qr, or_, W2), vg = tm_temporal_var(qg, og, W2), vb = tm_temporal_var(qb, ob, W2);
+    }
+    // The vote: reached by every thread of the workgroup; its result is the same in all of them.
+    if (__syncthreads_or(spatial ? 1 : 0)) {
+        const int bx = (int)(blockIdx.x * kDnTileW) - kTmHalo, by = (int)(blockIdx.y * kDnTileH) - kTmHalo;
+        for (int t = (int)threadIdx.x; t < kTmLdsW * kTmLdsH; t += 256) { // (t < 532: inside both arrays)
+            const int gx = bx + t % kTmLdsW, gy = by + t / kTmLdsW;
+            dn4 vc{0.0f, 0.0f, 0.0f, __int_as_float(kTmOutside)}, vn{0.0f, 0.0f, 0.0f, 0.0f};
+            if (gx >= 0 && gx < (int)a.width && gy >= 0 && gy < (int)a.height) { // (so q < width·height: inside counts too)
+                const size_t q = (size_t)gy * a.width + (size_t)gx;
+                vc = dn4{a.rgb[3 * q], a.rgb[3 * q + 1], a.rgb[3 * q + 2], __int_as_float(a.index[q])};
+                vn = dn4{a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2], COUNTS ? (float)ba.counts[q] : 1.0f};
+            }
+            s_col[t] = vc, s_nrm[t] = vn;
+        }
+        __syncthreads(); // all 256 threads are here: the branch is the workgroup's, not a thread's
+        if (spatial) {
+            float S0 = 0.0f, S1r = 0.0f, S1g = 0.0f, S1b = 0.0f, S2r = 0.0f, S2g = 0.0f, S2b = 0.0f;
+            const int centre = (ty + kTmHalo) * kTmLdsW + tx + kTmHalo; // taps: centre + j·38 + i stays within [0, 532)
+            for (int j = -kTmHalo; j <= kTmHalo; ++j)
+#pragma unroll
+                for (int i = -kTmHalo; i <= kTmHalo; ++i) {
+                    const int s = centre + j * kTmLdsW + i;
+                    const dn4 qc = s_col[s], qn = s_nrm[s];
+                    if (__float_as_int(qc.w) == id && (!COUNTS || qn.w > 0.0f) &&
+                        ((i == 0 && j == 0) || dn_dot(qn.x, qn.y, qn.z, nx, ny, nz) >= a.cm)) {
+                        S0 = S0 + 1.0f;
+                        S1r = S1r + qc.x, S1g = S1g + qc.y, S1b = S1b + qc.z;
+                        S2r = __builtin_fmaf(qc.x, qc.x, S2r), S2g = __builtin_fmaf(qc.y, qc.y, S2g), S2b = __builtin_fmaf(qc.z, qc.z, S2b);
+                    }
+                }
+            vr = vg = vb = kDnVarCap;
+            if (S0 >= m.mt) vr = tm_spatial_var(S0, S1r, S2r, W2), vg = tm_spatial_var(S0, S1g, S2g, W2), vb = tm_spatial_var(S0, S1b, S2b, W2);
+        }
+    }
+    if (!inside) return; // (behind the last barrier)
+    a.next.c[p] = dn4{or_, og, ob, No};
+    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
+    a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
+    a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
+    m.next_m[p] = dn4{qr, qg, qb, W2};
+    a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
+    a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
+    if (a.len_out) a.len_out[p] = No;
+    if (m.w2_out) m.w2_out[p] = W2;
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_kernel(const TemporalBgArgs a) {
+    bg_plain_step<STATIC, false>(a);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_kernel(const TemporalBgArgs a) {
+    bg_plain_step<STATIC, true>(a);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_moments_kernel(const TemporalBgMomentsArgs a) {
+    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
+    bg_moments_step<STATIC, false>(a, s_col, s_nrm);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_moments_kernel(const TemporalBgMomentsArgs a) {
+    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
+    bg_moments_step<STATIC, true>(a, s_col, s_nrm);
+}
+
+} // namespace rayz_dev_bg

@@ -32,6 +32,8 @@ int temporal_track_feedback(RayzTemporal* tm) {
     if (!tm->moments) return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is not in moments mode (rayz_hip_temporal_track_moments first)");
     if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
         return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is in cubic resampling mode (rayz_hip_temporal_set_resampling back to bilinear first)");
+    if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE)
+        return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle accumulates the background (rayz_hip_temporal_set_background back to input first)");
     if (tm->has_history)
         return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle has history (call it after track_moments or after rayz_hip_temporal_reset)");
     tm->feedback = true;
@@ -74,7 +76,16 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
         a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
         a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
         using namespace rayz_dev_cubic;
-        if (d_counts) { // (never a feedback handle: temporal_run_step refused it)
+        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) { // (never a feedback or a cubic handle: set_background refused them)
+            using namespace rayz_dev_bg;
+            TemporalBgMomentsArgs b{a, {}, d_counts};
+            temporal_background_args(tm, cam, is_static, b.G);
+            if (d_counts)
+                temporal_launch_step(st, temporal_bg_counts_moments_kernel<true>, temporal_bg_counts_moments_kernel<false>, is_static, b,
+                                     t.width, t.height);
+            else
+                temporal_launch_step(st, temporal_bg_moments_kernel<true>, temporal_bg_moments_kernel<false>, is_static, b, t.width, t.height);
+        } else if (d_counts) { // (never a feedback handle: temporal_run_step refused it)
             using namespace rayz_dev_counts;
             temporal_launch_step(st, temporal_counts_moments_kernel<true>, temporal_counts_moments_kernel<false>, is_static,
                                  TemporalMomentsCountsArgs{a, d_counts}, t.width, t.height);

@@ -1055,12 +1055,14 @@ class Temporal(_Handle):
     handle is put into moments mode (`track_moments`, §4.16) and takes `step_moments`, which needs no variance input; with
     `feedback` True as well it also tracks feedback (`track_feedback`, §4.17) and takes `feedback`.  `resampling` "cubic": moving
     steps fetch the colour history with the 4x4 Catmull-Rom kernel where all sixteen history pixels are the same surface, and
-    bilinearly elsewhere (`set_resampling`, §4.26); the default "bilinear" is §4.15 as it is."""
+    bilinearly elsewhere (`set_resampling`, §4.26); the default "bilinear" is §4.15 as it is.  `background` "accumulate": pixels
+    whose centre ray misses the scene gather history too, reprojected by the view's turn alone (`set_background`, §4.27); the
+    default "input" passes them through."""
 
     _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
     def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False, feedback: bool = False,
-                 resampling: str = "bilinear"):
+                 resampling: str = "bilinear", background: str = "input"):
         self._lib = capi.load()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
@@ -1077,12 +1079,18 @@ class Temporal(_Handle):
                 raise ValueError(f"resampling must be one of {sorted(capi.TEMPORAL_RESAMPLING)}, got {resampling!r}")
             if feedback and resampling == "cubic":
                 raise ValueError('feedback=True with resampling="cubic": a handle that tracks feedback has no cubic mode')
+            if background not in capi.TEMPORAL_BACKGROUND:
+                raise ValueError(f"background must be one of {sorted(capi.TEMPORAL_BACKGROUND)}, got {background!r}")
+            if background == "accumulate" and (feedback or resampling == "cubic"):
+                raise ValueError('background="accumulate" with feedback=True or resampling="cubic": neither accumulates the background')
             if moments:
                 self.track_moments()
                 if feedback:
                     self.track_feedback()
             if resampling != "bilinear":
                 self.set_resampling(resampling)
+            if background != "input":
+                self.set_background(background)
         except Exception:
             self.close()
             raise
@@ -1126,6 +1134,24 @@ class Temporal(_Handle):
         mode = C.c_uint32()
         capi.check(self._lib, self._lib.rayz_hip_temporal_get_resampling(self._h, C.byref(mode)), "rayz_hip_temporal_get_resampling")
         return {v: k for k, v in capi.TEMPORAL_RESAMPLING.items()}[mode.value]
+
+    def set_background(self, background: str) -> None:
+        """What steps do from now on with a pixel whose centre ray misses the scene (`rayz_hip_temporal_set_background`, DESIGN.md
+        §4.27): "input" (the default) passes its input through; "accumulate" reprojects it by the turn of the view alone — the sky
+        has no parallax — and blends it into the history of the previous frame's background pixels, in all four kinds of step; in
+        a counts step a background pixel without samples keeps its history.  May be changed between any two steps.  Limits: a
+        handle that tracks feedback or is in "cubic" resampling mode does not accumulate the background."""
+        if background not in capi.TEMPORAL_BACKGROUND:
+            raise ValueError(f"background must be one of {sorted(capi.TEMPORAL_BACKGROUND)}, got {background!r}")
+        capi.check(self._lib, self._lib.rayz_hip_temporal_set_background(self._h, capi.TEMPORAL_BACKGROUND[background]),
+                   "rayz_hip_temporal_set_background")
+
+    @property
+    def background(self) -> str:
+        """"input" or "accumulate": the handle's background mode (`rayz_hip_temporal_get_background`)."""
+        mode = C.c_uint32()
+        capi.check(self._lib, self._lib.rayz_hip_temporal_get_background(self._h, C.byref(mode)), "rayz_hip_temporal_get_background")
+        return {v: k for k, v in capi.TEMPORAL_BACKGROUND.items()}[mode.value]
 
     @property
     def taken(self):

@@ -71,7 +71,18 @@ alternating in one process on the same frames.
     (fx = 0 up to rounding), --pan 2.5 a fractional one; --motion orbit turns look_from about the focus point by --pan pixel widths
     per frame, so that look_from and the view direction both change and the image motion depends on depth.  --config 2 | 3.
 
-    python tools/temporal_bench.py --cubic [--config 3] [--motion pan|orbit] [--pan 2.5] [--lib PATH --lib-label NAME] [the switches above]"""
+    python tools/temporal_bench.py --cubic [--config 3] [--motion pan|orbit] [--pan 2.5] [--lib PATH --lib-label NAME] [the switches above]
+
+--background measures the background mode (rayz_hip_temporal_set_background) beside the input mode, the two
+alternating in one process on the same frames; the input mode runs the kernels it always ran and is the yardstick.
+(a) Cost.  The plain and the moments step in both modes — a first frame, a static step, a moved step — by the handles' own HIP
+    events, each beside a device copy of the step's compulsory bytes (204 / 208 B per pixel), and the ratio accumulate / input.
+(b) Quality.  Per frame, MSE against the --ref-spp frame of the temporal step alone and of the step + `run_guided`, input against
+    accumulate, on one-chunk frames through moments handles — over the whole frame, and split into the background pixels' and
+    the hit pixels' parts of it — and the share of background pixels that found history with their mean history length.
+    --motion, --pan and --config as for --cubic.
+
+    python tools/temporal_bench.py --background [--config 3] [--motion pan|orbit] [--pan 2.5] [--cost-only] [the switches above]"""
 import argparse
 import json
 import os
@@ -681,6 +692,121 @@ def main_cubic(args):
             json.dump(res, f, indent=1)
 
 
+def main_background(args):
+    """--background: see the module docstring."""
+    render.init(0)
+    t = tracer.randomBouncing(args.width, seed=42) if args.config == 2 else tracer.randomBouncing(args.width, -50, 50, seed=42)
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    assert args.spp <= 16, "--background wants an spp of at most 16: one automatic chunk"
+    ds = render.DeviceScene(sd)
+    move = (lambda k: orbited(cam, args.pan * k, w, h)) if args.motion == "orbit" else (lambda k: panned(cam, args.pan * k))
+    res = {"mode": "background", "config": args.config, "motion": args.motion, "size": f"{w}x{h}", "frames": args.frames,
+           "px_per_frame": args.pan, "spp": args.spp, "ref_spp": args.ref_spp, "reps": args.reps}
+    seq = []
+    for k in range(args.frames if not args.cost_only else 2):
+        c = move(k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed, q.chunk_spp = 1000 + k, 0
+        one = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ds.render_into(c, q, one.data_ptr())
+        ds.sync()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        ref = None
+        if not args.cost_only:
+            q.samples_per_px, q.seed = args.ref_spp, 7
+            ref = torch.empty_like(one)
+            torch.cuda.synchronize()
+            ds.render_into(c, q, ref.data_ptr())
+            ds.sync()
+        seq.append((c, one, g, ref))
+        print(f"frame {k}: {args.spp} spp in one chunk, background {float((g.index < 0).float().mean()):.4f} of the pixels"
+              + ("" if ref is None else f", reference {args.ref_spp} spp"), flush=True)
+    var = torch.full((h, w, 3), 1e-3, dtype=torch.float32, device="cuda")  # (the plain step's cost does not depend on the variance's values)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    length = torch.empty((h, w), dtype=torch.float32, device="cuda")
+
+    # ---- (a) cost: first, static and moved, the two modes alternating ------------------------------------------------------------
+    res["cost"] = {}
+    modes = ("input", "accumulate")
+    handles = {(kind, mode): render.Temporal(w, h, moments=kind == "moments", background=mode) for kind in ("plain", "moments") for mode in modes}
+
+    def steps(kind, tm, what):
+        tm.reset()
+        for c, one, g, _ in {"first": seq[:1], "static": [seq[0], seq[0]], "moved": seq[:2]}[what]:
+            if kind == "plain":
+                tm.step(one, var, g, c, args.spp, out=out, var_out=vout)
+            else:
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout)
+
+    for what in ("first", "static", "moved"):
+        ms = {k: [] for k in handles}
+        for r in range(args.warmup + args.reps):
+            for (kind, mode), tm in handles.items():
+                steps(kind, tm, what)
+                x = tm.timing()
+                if r >= args.warmup:
+                    ms[(kind, mode)].append(x)
+        for kind, nbytes in (("plain", STEP_BYTES), ("moments", MOMENTS_STEP_BYTES)):
+            cp = copy_ms(n * nbytes // 2, args.reps, args.warmup)
+            med = {mode: statistics.median(ms[(kind, mode)]) for mode in modes}
+            for mode in modes:
+                v = ms[(kind, mode)]
+                res["cost"][f"{kind} {what} {mode}"] = {"ms": med[mode], "min": min(v), "max": max(v), "bytes_per_pixel": nbytes, "copy_ms": cp[0],
+                                                        "copy_min": cp[1], "copy_max": cp[2], "ratio_to_copy": med[mode] / cp[0],
+                                                        "ratio_to_input": med[mode] / med["input"]}
+                print(f"{kind:7s} step, {what:6s}, {mode:10s}: {med[mode]:.4f} ms [{min(v):.4f}, {max(v):.4f}] = {med[mode] / cp[0]:.2f} x the copy of "
+                      f"its {nbytes} B per pixel ({cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}]), {med[mode] / med['input']:.3f} x the input mode", flush=True)
+    for tm in handles.values():
+        tm.close()
+
+    # ---- (b) quality: moments handles on the one-chunk frames ---------------------------------------------------------------------
+    if not args.cost_only:
+        dn = render.Denoiser(w, h)
+        den = torch.empty_like(out)
+        res["rows"] = []
+        tms = {mode: render.Temporal(w, h, moments=True, background=mode) for mode in modes}
+        for k, (c, one, g, ref) in enumerate(seq):
+            bg = g.index < 0
+
+            def mse2(a):
+                err = ((a.double() - ref.double()) ** 2).mean(dim=2)
+                return [float(err.mean()), float(err[bg].mean()) if bool(bg.any()) else 0.0, float(err[~bg].mean())]
+
+            row = {"frame": k, "raw": mse2(one), "share_background": float(bg.float().mean())}
+            for mode, tm in tms.items():
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout, length=length)
+                dn.run_guided(out, vout, g, out=den)
+                torch.cuda.synchronize()
+                row[f"temporal_{mode}"], row[f"temporal_guided_{mode}"] = mse2(out), mse2(den)
+                if mode == "accumulate":
+                    row["background_found"] = float((length[bg] > args.spp).float().mean()) if bool(bg.any()) else 0.0
+                    row["background_mean_length"] = float(length[bg].mean()) if bool(bg.any()) else 0.0
+            res["rows"].append(row)
+            whole = row["raw"][0]  # every figure as a share of the WHOLE frame's raw MSE: the background's part is err[bg].mean()·share
+            part = lambda key: " ".join(f"{x:.4f}" for x in (row[key][0] / whole, row[key][1] * row["share_background"] / whole,  # noqa: E731
+                                                             row[key][2] * (1 - row["share_background"]) / whole))
+            print(f"frame {k:2d}: MSE / raw of the frame (all | background's part | hit pixels' part): temporal input {part('temporal_input')}, "
+                  f"accumulate {part('temporal_accumulate')}; + guided input {part('temporal_guided_input')}, accumulate "
+                  f"{part('temporal_guided_accumulate')}; background found {row['background_found']:.4f}, mean length "
+                  f"{row['background_mean_length']:.1f}", flush=True)
+        print(f"raw MSE of the last frame (all | background | hit): {row['raw']}; background share {row['share_background']:.4f}", flush=True)
+        for tm in tms.values():
+            tm.close()
+        dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -697,7 +823,8 @@ def main():
     ap.add_argument("--feedback", action="store_true", help="measure the feedback of the filtered colour (DESIGN.md §4.17) beside the moments step")
     ap.add_argument("--counts", action="store_true", help="measure the counts step (DESIGN.md §4.23) beside the scalar steps")
     ap.add_argument("--cubic", action="store_true", help="measure the cubic resampling mode (DESIGN.md §4.26) beside the bilinear one")
-    ap.add_argument("--cost-only", action="store_true", help="--cubic: the cost part alone (two frames, no references)")
+    ap.add_argument("--background", action="store_true", help="measure the background mode (DESIGN.md §4.27) beside the input mode")
+    ap.add_argument("--cost-only", action="store_true", help="--cubic, --background: the cost part alone (two frames, no references)")
     ap.add_argument("--config", type=int, default=3, choices=(2, 3), help="--cubic: BASELINE config 2 (grid [-11, 11)) or 3 (grid [-50, 50))")
     ap.add_argument("--motion", default="pan", choices=("pan", "orbit"),
                     help="--cubic: pan (px_origin moved along px_du by --pan pixels per frame) or orbit (look_from turned about the focus point by --pan "
@@ -705,6 +832,8 @@ def main():
     ap.add_argument("--lib-label", default=None, help="--cubic: what to call --lib's build in the output")
     ap.add_argument("--lib", default=None, help="--cubic: load this build of librayz_hip.so (an older one: its bilinear step alone is timed)")
     args = ap.parse_args()
+    if args.background:
+        return main_background(args)
     if args.cubic:
         return main_cubic(args)
     if args.counts:
