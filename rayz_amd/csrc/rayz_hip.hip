@@ -23,8 +23,7 @@
 #include "noise.hpp"
 #include "adaptive.hpp"
 #include "sparse.hpp"
-#include "temporal_counts_kernel.hpp"
-#include "temporal_background_kernel.hpp"
+#include "temporal_modes_kernel.hpp"
 #include "host_base.hpp"
 
 using namespace rayz_dev;

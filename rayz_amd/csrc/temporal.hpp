@@ -1,7 +1,7 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
 // temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp) and
-// the one procedure of a step of either kind, temporal_run_step; the background mode's host part and calls (§4.27; its kernels:
-// temporal_background_kernel.hpp).
+// the one procedure of a step of either kind, temporal_run_step; the background mode's host part and calls (§4.27); the choice of a
+// plain step's kernel, temporal_launch_plain (the counts, background and cubic kernels: temporal_modes_kernel.hpp).
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
@@ -164,25 +164,49 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
     return RAYZ_OK;
 }
 
-int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, const float* d_in,
-                  const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out, float* d_len_out, void* stream_arg) {
+// What both counts steps (§4.23) check of their counts: every pixel reads its own and, in the moments step, its neighbours', so
+// the array is no output of the step.
+int temporal_counts_check(const uint32_t* d_counts, std::initializer_list<const void*> outputs) {
+    if (!d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: null counts buffer");
+    for (const void* o : outputs)
+        if (o == (const void*)d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: d_counts is also an output of the step");
+    return RAYZ_OK;
+}
+
+// The launch of a plain step: the one place that says which kernel a plain handle's modes, the camera and the kind of step take.
+// (Behind the handle's check.  ACCUMULATE is never a cubic handle: set_background refused it; a counts step is none either:
+// temporal_run_step refused it; and a static step of a cubic handle resamples nothing.)
+void temporal_launch_plain(hipStream_t st, const RayzTemporal* tm, const RayzCameraDesc* cam, const TemporalArgs& a, bool is_static,
+                           const uint32_t* d_counts) {
+    const bool bg = tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE;
+    const bool cubic = tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static;
+    if (!bg && !d_counts && !cubic)
+        return temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
+    TemporalModeArgs m{a, {}, d_counts, tm->taken};
+    if (bg) temporal_background_args(tm, cam, is_static, m.G);
+    void (*still)(TemporalModeArgs) = nullptr; // (the cubic step has no static form)
+    void (*moving)(TemporalModeArgs) = rayz_dev_cubic::temporal_cubic_step_kernel;
+    if (bg && d_counts)
+        still = rayz_dev_bg::temporal_bg_counts_kernel<true>, moving = rayz_dev_bg::temporal_bg_counts_kernel<false>;
+    else if (bg)
+        still = rayz_dev_bg::temporal_bg_kernel<true>, moving = rayz_dev_bg::temporal_bg_kernel<false>;
+    else if (d_counts)
+        still = rayz_dev_counts::temporal_counts_kernel<true>, moving = rayz_dev_counts::temporal_counts_kernel<false>;
+    temporal_launch_step(st, still, moving, is_static, m, a.width, a.height);
+}
+
+// The step of a plain handle.  counts: the counts step (§4.23), a count per pixel for spp (then 0; the kernel does not read the
+// arguments' spp) — d_counts is checked behind the buffers; else d_counts is NULL.
+int temporal_step(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, uint32_t spp, bool counts,
+                  const uint32_t* d_counts, const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out,
+                  float* d_var_out, float* d_len_out, void* stream_arg) {
     const RayzTemporalParams p = temporal_params_or_default(params);
-    RAYZ_TRY(temporal_params_check(p, spp));
+    RAYZ_TRY(temporal_params_check(p, counts ? 1 : spp));
     if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
     if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
-    const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) { // (behind the handle's check: tm is a handle)
-        using namespace rayz_dev_cubic;
-        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) { // (never a cubic handle: set_background refused it)
-            using namespace rayz_dev_bg;
-            TemporalBgArgs b{a, {}, nullptr};
-            temporal_background_args(tm, cam, is_static, b.G);
-            temporal_launch_step(st, temporal_bg_kernel<true>, temporal_bg_kernel<false>, is_static, b, a.width, a.height);
-        } else if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static)
-            hipLaunchKernelGGL(temporal_cubic_step_kernel, denoise_grid(a.width, a.height), dim3(256), 0, st, TemporalCubicArgs{a, tm->taken});
-        else
-            temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
-    };
-    return temporal_run_step(tm, false, p, cam, spp, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch);
+    if (counts) RAYZ_TRY(temporal_counts_check(d_counts, {d_out, d_var_out, d_len_out}));
+    const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) { temporal_launch_plain(st, tm, cam, a, is_static, d_counts); };
+    return temporal_run_step(tm, false, p, cam, spp, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch, counts);
 }
 
 // §4.26's mode and the taken bytes.  The mode is an argument and is checked before the handle, as a step's arguments are.
@@ -223,38 +247,6 @@ int temporal_get_background(RayzTemporal* tm, uint32_t* mode) {
     return RAYZ_OK;
 }
 
-// What both counts steps (§4.23) check of their counts: every pixel reads its own and, in the moments step, its neighbours', so
-// the array is no output of the step.
-int temporal_counts_check(const uint32_t* d_counts, std::initializer_list<const void*> outputs) {
-    if (!d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: null counts buffer");
-    for (const void* o : outputs)
-        if (o == (const void*)d_counts) return fail(RAYZ_ERR_BAD_ARG, "temporal: d_counts is also an output of the step");
-    return RAYZ_OK;
-}
-
-// The counts step of a plain handle: temporal_step with a count per pixel for spp (the kernel does not read the arguments' spp).
-int temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* params, const RayzCameraDesc* cam, const uint32_t* d_counts,
-                         const float* d_in, const float* d_var, const RayzQueryOutputs* g, float* d_out, float* d_var_out,
-                         float* d_len_out, void* stream_arg) {
-    const RayzTemporalParams p = temporal_params_or_default(params);
-    RAYZ_TRY(temporal_params_check(p, 1));
-    if (!d_in || !d_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null colour buffer");
-    if (!d_var || !d_var_out) return fail(RAYZ_ERR_BAD_ARG, "temporal: null variance buffer (rayz_hip_progressive_noise_rgb writes the input)");
-    RAYZ_TRY(temporal_counts_check(d_counts, {d_out, d_var_out, d_len_out}));
-    const auto launch = [&](hipStream_t st, const TemporalArgs& a, bool is_static) {
-        using namespace rayz_dev_counts;
-        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) {
-            using namespace rayz_dev_bg;
-            TemporalBgArgs b{a, {}, d_counts};
-            temporal_background_args(tm, cam, is_static, b.G);
-            temporal_launch_step(st, temporal_bg_counts_kernel<true>, temporal_bg_counts_kernel<false>, is_static, b, a.width, a.height);
-        } else
-            temporal_launch_step(st, temporal_counts_kernel<true>, temporal_counts_kernel<false>, is_static, TemporalCountsArgs{a, d_counts},
-                                 a.width, a.height);
-    };
-    return temporal_run_step(tm, false, p, cam, 0, d_in, d_var, g, d_out, d_var_out, d_len_out, stream_arg, launch, true);
-}
-
 int temporal_reset(RayzTemporal* tm) {
     RAYZ_TRY(frame_handle_check(tm));
     tm->has_history = false; // (the buffers keep their bytes; no step reads them before it has written them)
@@ -282,8 +274,8 @@ int rayz_hip_temporal_step(RayzTemporal* tm, const RayzTemporalParams* params_or
                            const float* d_rgb_in, const float* d_var_rgb, const RayzQueryOutputs* gbuffer, float* d_rgb_out,
                            float* d_var_out, float* d_length_out_or_null, void* hip_stream) {
     return guarded([&] {
-        return temporal_step(tm, params_or_null, camera, spp, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out, d_length_out_or_null,
-                             hip_stream);
+        return temporal_step(tm, params_or_null, camera, spp, false, nullptr, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out,
+                             d_length_out_or_null, hip_stream);
     });
 }
 
@@ -291,8 +283,8 @@ int rayz_hip_temporal_step_counts(RayzTemporal* tm, const RayzTemporalParams* pa
                                   const uint32_t* d_counts, const float* d_rgb_in, const float* d_var_rgb, const RayzQueryOutputs* gbuffer,
                                   float* d_rgb_out, float* d_var_out, float* d_length_out_or_null, void* hip_stream) {
     return guarded([&] {
-        return temporal_step_counts(tm, params_or_null, camera, d_counts, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out,
-                                    d_length_out_or_null, hip_stream);
+        return temporal_step(tm, params_or_null, camera, 0, true, d_counts, d_rgb_in, d_var_rgb, gbuffer, d_rgb_out, d_var_out,
+                             d_length_out_or_null, hip_stream);
     });
 }
 

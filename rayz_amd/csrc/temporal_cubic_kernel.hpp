@@ -3,8 +3,8 @@
 //
 // Two kernels, the moving forms of the plain and of the moments step of a handle in RAYZ_TEMPORAL_RESAMPLE_CUBIC (a static step
 // resamples nothing and launches the existing static kernels).  The moments one is tm_step (temporal_moments_kernel.hpp) with its
-// CUBIC flag; the plain one restates temporal_step_kernel<false>'s few lines around the same calls, because that kernel's body is
-// the __global__ function itself and its code is held instruction-identical.
+// CUBIC flag, below; the plain one is ta_mode_step with its CUBIC flag (temporal_modes_kernel.hpp), because temporal_step_kernel's
+// body is the __global__ function itself and its code is held instruction-identical.
 //
 // Both run ta_gather first, unchanged, and have it keep its four taps: §4.15 steps 1-3 are stated once, and the variance, W2 and the
 // length are the bilinear values in both modes.  Then tc_resample, for a pixel whose four inner taps were all accepted and whose 4x4 window lies
@@ -99,58 +99,10 @@ __device__ __forceinline__ bool tc_resample(const TemporalArgs& a, const dn4* co
 namespace rayz_dev_cubic {
 using namespace rayz_dev;
 
-struct TemporalCubicArgs {
-    TemporalArgs t;
-    uint8_t* taken; // or NULL: one byte per pixel, 1 where the colour history came from the sixteen taps
-};
-
 struct TemporalCubicMomentsArgs {
     TemporalMomentsArgs m;
-    uint8_t* taken;
+    uint8_t* taken; // or NULL: one byte per pixel, 1 where the colour history came from the sixteen taps
 };
-
-// The plain step's moving form (temporal_step_kernel<false>, whose body stays as it is) with the colour history from tc_resample
-// where that takes the sixteen taps.
-__global__ __launch_bounds__(256) void temporal_cubic_step_kernel(const TemporalCubicArgs ca) {
-    const TemporalArgs& a = ca.t;
-    const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
-    const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
-    if (x >= (int)a.width || y >= (int)a.height) return;
-    const size_t p = (size_t)y * a.width + (size_t)x;
-    const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
-    const float sr = dn_clamp_var(a.var[3 * p]), sg = dn_clamp_var(a.var[3 * p + 1]), sb = dn_clamp_var(a.var[3 * p + 2]);
-    const int32_t id = a.index[p];
-    const float nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
-    const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
-    float or_ = cr, og = cg, ob = cb, vr = sr, vg = sg, vb = sb, No = a.spp; // no history: the input, by selection
-    bool took = false;
-    if (id >= 0 && a.has_history) {
-        const dn4* const rec[2] = {a.prev.c, a.prev.v};
-        TaTaps<2> keep;
-        const TaAcc<2> acc = ta_gather<false, 2, false>(a, rec, p, id, nx, ny, nz, Px, Py, Pz, &keep);
-        if (acc.found()) {
-            const TaBlend h = ta_blend_head(acc, a);
-            const float a2 = h.al * h.al, k2 = h.k * h.k;
-            float hc[1][3] = {{acc.mean(0, 0), acc.mean(0, 1), acc.mean(0, 2)}};
-            took = tc_resample<1>(a, rec, keep, id, nx, ny, nz, Px, Py, Pz, hc);
-            or_ = ta_blend(h.al, cr, hc[0][0]);
-            og = ta_blend(h.al, cg, hc[0][1]);
-            ob = ta_blend(h.al, cb, hc[0][2]);
-            vr = __builtin_fmaf(a2, sr, k2 * acc.mean(1, 0));
-            vg = __builtin_fmaf(a2, sg, k2 * acc.mean(1, 1));
-            vb = __builtin_fmaf(a2, sb, k2 * acc.mean(1, 2));
-            No = h.N;
-        }
-    }
-    a.next.c[p] = dn4{or_, og, ob, No};
-    a.next.v[p] = dn4{vr, vg, vb, 0.0f};
-    a.next.g[p] = dn4{nx, ny, nz, __int_as_float(id)};
-    a.next.p[p] = dn4{Px, Py, Pz, 0.0f};
-    a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
-    a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
-    if (a.len_out) a.len_out[p] = No;
-    if (ca.taken) ca.taken[p] = took ? 1 : 0;
-}
 
 __global__ __launch_bounds__(256) void temporal_cubic_moments_step_kernel(const TemporalCubicMomentsArgs a) {
     __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];

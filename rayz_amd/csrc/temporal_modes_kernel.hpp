@@ -1,35 +1,49 @@
-// temporal_background_kernel.hpp — the device code of temporal accumulation's background mode (include/rayz_hip.h:
-// rayz_hip_temporal_set_background; the host side: temporal.hpp, temporal_moments.hpp; the steps it is made from:
-// temporal_kernel.hpp, temporal_moments_kernel.hpp, temporal_counts_kernel.hpp).
+// temporal_modes_kernel.hpp — the device code of temporal accumulation's counts step (include/rayz_hip.h:
+// rayz_hip_temporal_step_counts, rayz_hip_temporal_step_moments_counts), of its background mode (§4.27,
+// rayz_hip_temporal_set_background) and of the plain step of its cubic resampling mode (§4.26, rayz_hip_temporal_set_resampling;
+// tc_resample and the cubic moments kernel: temporal_cubic_kernel.hpp).  The host side: temporal.hpp, temporal_moments.hpp; the
+// steps these are made from: temporal_kernel.hpp, temporal_moments_kernel.hpp.
 //
-// The plain, the moments and the two counts steps with ONE difference: a pixel whose centre ray misses the scene (id < 0) gathers
-// history too.  A miss sees the sky at infinity, so where it lay in the previous frame depends only on how the view turned: the
-// host gives the 3x3 matrix G that takes this frame's pixel centre (x, y, 1) to s·(x', y', 1) in the previous frame, and bg_gather
-// runs §4.15's taps from there, accepting the history pixels that were misses themselves — no normal and no distance to compare.
-// Everything behind the sums is the hit pixel's arithmetic through the same functions.  A pixel with id >= 0 takes ta_gather and is
-// the INPUT-mode step bit for bit, outputs and history.
+// TWO bodies, each written once, and 13 kernels that are one call each.  ta_mode_step is the plain step (§4.15) and tm_mode_step the
+// moments step (§4.16, without its feedback mode), through the same functions — ta_gather, ta_blend_head, ta_blend,
+// tm_temporal_var, tm_spatial_var — and with what a mode changes behind compile-time flags:
 //
-// A background lane takes the same two rounds of loads as a hit lane: the four taps' indices (the .w of their guide records; the
-// point records are not read), then the records the taps add.  G arrives through the kernel arguments and is the same for every
-// lane: scalar operands of the three FMAs per row.  A wave with both kinds of lane runs both gathers, one after the other.
+//   COUNTS (§4.23)  the samples the current frame adds are a number per pixel, read from an array of height·width uint32, and may
+//                   be 0 — a lattice frame (§4.21) samples one pixel in f², an adaptive frame (§4.14) as many as each pixel still
+//                   needs.  A history record of length 0 holds no samples and is refused like a different surface (the gathers'
+//                   LIVE flag); a pixel that got no sample and finds history keeps the gathered history, by selection, so that
+//                   whatever its input holds — NaN included — reaches nothing; and the moments step's 7x7 neighbourhood counts only
+//                   positions that were sampled: the count rides in the free lane of the staged normal record, so the LDS and the
+//                   barriers are the scalar step's.  Per pixel 4 more bytes are read.  With every count equal to one spp >= 1 the
+//                   step returns what the scalar step returns, bit for bit.
+//   BG (§4.27)      a pixel whose centre ray misses the scene (id < 0) gathers history too.  A miss sees the sky at infinity, so
+//                   where it lay in the previous frame depends only on how the view turned: the host gives the 3x3 matrix G that
+//                   takes this frame's pixel centre (x, y, 1) to s·(x', y', 1) in the previous frame, and bg_gather runs §4.15's
+//                   taps from there, accepting the history pixels that were misses themselves — no normal and no distance to
+//                   compare.  Everything behind the sums is the hit pixel's arithmetic.  A pixel with id >= 0 takes ta_gather and
+//                   is the INPUT-mode step bit for bit.  A wave with both kinds of lane runs both gathers, one after the other.
+//   CUBIC (§4.26)   the plain step only, its moving form, and with neither of the other two: ta_gather keeps its four taps and,
+//                   where tc_resample takes the sixteen around them, the colour is blended into its values; the variance and the
+//                   length stay bilinear.  One byte per pixel says which.
 //
-// Eight kernels, in a namespace of their own: {plain, moments} x {one spp, a count per pixel} x {static, moving}.  COUNTS is a
-// template flag of the two bodies; the existing kernels are not touched and rayz_dev holds exactly the kernels it held.
+// These are the kernels OUTSIDE the recorded set: temporal_step_kernel, tm_step and what they call are compiled from text that
+// stays as it is, and the kernels here live in namespaces of their own, so that rayz_dev holds exactly the kernels
+// it held.  Neither body is a symbol of its own: both are forced inline.
 #pragma once
 
-#include "temporal_moments_kernel.hpp"
+#include "temporal_cubic_kernel.hpp"
 
-namespace rayz_dev_bg {
-using namespace rayz_dev;
+namespace rayz_dev {
 
-struct TemporalBgArgs {
-    TemporalArgs t;         // the plain step's arguments; with counts, t.spp is not read
-    float G[9];             // this frame's pixel centre -> the previous frame's, up to scale (row-major; not read by a static step)
-    const uint32_t* counts; // the counts kernels: per pixel, the samples the current frame adds (never an output); else not read
+struct TemporalModeArgs {
+    TemporalArgs t;         // the plain step's arguments; with COUNTS, t.spp is not read
+    float G[9];             // BG: this frame's pixel centre -> the previous frame's, up to scale (row-major; not read by a static step)
+    const uint32_t* counts; // COUNTS: per pixel, the samples the current frame adds (never an output: a pixel reads its neighbours' too)
+    uint8_t* taken;         // CUBIC: or NULL — one byte per pixel, 1 where the colour history came from the sixteen taps
 };
 
-struct TemporalBgMomentsArgs {
-    TemporalMomentsArgs m; // the moments step's arguments; with counts, m.t.spp is not read
+struct TemporalMomentsModeArgs {
+    TemporalMomentsArgs m; // the moments step's arguments; with COUNTS, m.t.spp is not read
     float G[9];
     const uint32_t* counts;
 };
@@ -58,8 +72,8 @@ __device__ __forceinline__ TaAcc<R> bg_gather(const TemporalArgs& a, const float
     const float x0 = __builtin_floorf(hx), y0 = __builtin_floorf(hy);
     const float fx = hx - x0, fy = hy - y0;
     const int ix = (int)x0, iy = (int)y0;
-    // Two rounds of loads, as ta_gather's: every tap's index, then the records it adds.  A tap outside the frame loads the nearest
-    // pixel inside it (a valid address) and is refused.
+    // Two rounds of loads, as ta_gather's: every tap's index (the .w of its guide record; the point records are not read), then the
+    // records it adds.  A tap outside the frame loads the nearest pixel inside it (a valid address) and is refused.
     size_t q[4];
     bool ok[4];
     float gw[4];
@@ -85,9 +99,11 @@ __device__ __forceinline__ TaAcc<R> bg_gather(const TemporalArgs& a, const float
     return acc;
 }
 
-// §4.27 on §4.15 (COUNTS: on §4.23's plain step): the step's body with the gather chosen by the pixel's kind.
-template <bool STATIC, bool COUNTS> __device__ __forceinline__ void bg_plain_step(const TemporalBgArgs& ba) {
-    const TemporalArgs& a = ba.t;
+// §4.15's step with the modes' flags: temporal_step_kernel's body (temporal_kernel.hpp) with n for spp, the gather chosen by the
+// pixel's kind and the history's colour from tc_resample where that takes the sixteen taps.
+template <bool STATIC, bool COUNTS, bool BG, bool CUBIC> __device__ __forceinline__ void ta_mode_step(const TemporalModeArgs& ma) {
+    static_assert(!(CUBIC && (STATIC || COUNTS || BG)), "the cubic path is the moving plain step's, with one spp and no background history");
+    const TemporalArgs& a = ma.t;
     const int x = (int)(blockIdx.x * kDnTileW + threadIdx.x % kDnTileW);
     const int y = (int)(blockIdx.y * kDnTileH + threadIdx.x / kDnTileW);
     if (x >= (int)a.width || y >= (int)a.height) return;
@@ -97,23 +113,31 @@ template <bool STATIC, bool COUNTS> __device__ __forceinline__ void bg_plain_ste
     const int32_t id = a.index[p];
     const float nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
     const float Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
-    const float n = COUNTS ? (float)ba.counts[p] : a.spp;
+    const float n = COUNTS ? (float)ma.counts[p] : a.spp;
     float or_ = cr, og = cg, ob = cb, vr = sr, vg = sg, vb = sb, No = n; // no history: the input, by selection
-    if (a.has_history) {
+    [[maybe_unused]] bool took = false;
+    if ((BG || id >= 0) && a.has_history) {
         const dn4* const rec[2] = {a.prev.c, a.prev.v};
+        typename std::conditional<CUBIC, TaTaps<2>, TaNoTaps>::type keep; // (where ta_gather leaves its taps, or nothing)
         TaAcc<2> acc;
-        if (id >= 0)
-            acc = ta_gather<STATIC, 2, COUNTS>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
-        else
-            acc = bg_gather<STATIC, 2, COUNTS>(a, ba.G, rec, p, x, y);
+        if (!BG || id >= 0)
+            acc = ta_gather<STATIC, 2, COUNTS>(a, rec, p, id, nx, ny, nz, Px, Py, Pz, &keep);
+        else if constexpr (BG)
+            acc = bg_gather<STATIC, 2, COUNTS>(a, ma.G, rec, p, x, y);
         if (acc.found()) {
             const TaBlend h = ta_blend_head(acc, a, n);
             No = h.N; // (n = 0: hN + 0, capped)
             if (!COUNTS || n > 0.0f) {
                 const float a2 = h.al * h.al, k2 = h.k * h.k;
-                or_ = ta_blend(h.al, cr, acc.mean(0, 0));
-                og = ta_blend(h.al, cg, acc.mean(0, 1));
-                ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                if constexpr (CUBIC) { // the history's colour: the bilinear means, or tc_resample's values
+                    float hc[1][3] = {{acc.mean(0, 0), acc.mean(0, 1), acc.mean(0, 2)}};
+                    took = tc_resample<1>(a, rec, keep, id, nx, ny, nz, Px, Py, Pz, hc);
+                    or_ = ta_blend(h.al, cr, hc[0][0]), og = ta_blend(h.al, cg, hc[0][1]), ob = ta_blend(h.al, cb, hc[0][2]);
+                } else {
+                    or_ = ta_blend(h.al, cr, acc.mean(0, 0));
+                    og = ta_blend(h.al, cg, acc.mean(0, 1));
+                    ob = ta_blend(h.al, cb, acc.mean(0, 2));
+                }
                 vr = __builtin_fmaf(a2, sr, k2 * acc.mean(1, 0));
                 vg = __builtin_fmaf(a2, sg, k2 * acc.mean(1, 1));
                 vb = __builtin_fmaf(a2, sb, k2 * acc.mean(1, 2));
@@ -130,15 +154,19 @@ template <bool STATIC, bool COUNTS> __device__ __forceinline__ void bg_plain_ste
     a.rgb_out[3 * p] = or_, a.rgb_out[3 * p + 1] = og, a.rgb_out[3 * p + 2] = ob;
     a.var_out[3 * p] = vr, a.var_out[3 * p + 1] = vg, a.var_out[3 * p + 2] = vb;
     if (a.len_out) a.len_out[p] = No;
+    if constexpr (CUBIC)
+        if (ma.taken) ma.taken[p] = took ? 1 : 0;
 }
 
-// §4.27 on §4.16 (COUNTS: on §4.23's moments step): tm_step's body without its feedback and cubic modes.  The barriers are
-// tm_step's — the vote and the barrier behind the staging are reached by all 256 threads, a thread outside the frame skips only the
-// per-pixel work and the stores — and so is the LDS.  A background pixel never votes for the staging: its variance is the
-// temporal one where it found history that is long enough, and +0 elsewhere.
-template <bool STATIC, bool COUNTS>
-__device__ __forceinline__ void bg_moments_step(const TemporalBgMomentsArgs& ba, dn4* const s_col, dn4* const s_nrm) {
-    const TemporalMomentsArgs& m = ba.m;
+// §4.16's step with the modes' flags: tm_step's body (temporal_moments_kernel.hpp) without its feedback and cubic modes, with n for
+// spp, the gather chosen by the pixel's kind and the neighbourhood over sampled positions.  The barriers are tm_step's — the vote
+// and the barrier behind the staging are reached by all 256 threads, a thread outside the frame skips only the per-pixel work and
+// the stores — and so is the LDS: two arrays of 38 x 14 records and the vote's.  A background pixel never votes for the staging:
+// its variance is the temporal one where it found history that is long enough, and +0 elsewhere (§4.27 rule 3; without BG a miss
+// gathers nothing, found stays false, and the rule is §4.16's: +0).
+template <bool STATIC, bool COUNTS, bool BG>
+__device__ __forceinline__ void tm_mode_step(const TemporalMomentsModeArgs& ma, dn4* const s_col, dn4* const s_nrm) {
+    const TemporalMomentsArgs& m = ma.m;
     const TemporalArgs& a = m.t;
     const int tx = (int)(threadIdx.x % kDnTileW), ty = (int)(threadIdx.x / kDnTileW);
     const int x = (int)(blockIdx.x * kDnTileW) + tx, y = (int)(blockIdx.y * kDnTileH) + ty;
@@ -150,20 +178,20 @@ __device__ __forceinline__ void bg_moments_step(const TemporalBgMomentsArgs& ba,
     bool spatial = false;
     if (inside) {
         const float cr = a.rgb[3 * p], cg = a.rgb[3 * p + 1], cb = a.rgb[3 * p + 2];
-        const float n = COUNTS ? (float)ba.counts[p] : a.spp;
+        const float n = COUNTS ? (float)ma.counts[p] : a.spp;
         id = a.index[p];
         nx = a.normal[3 * p], ny = a.normal[3 * p + 1], nz = a.normal[3 * p + 2];
         Px = a.point[3 * p], Py = a.point[3 * p + 1], Pz = a.point[3 * p + 2];
         or_ = cr, og = cg, ob = cb, No = n;                  // no history: the input, by selection ..
         qr = cr * cr, qg = cg * cg, qb = cb * cb, W2 = 1.0f; // .. its square, and the weight of one frame
         bool found = false;
-        if (a.has_history) {
+        if ((BG || id >= 0) && a.has_history) {
             const dn4* const rec[2] = {a.prev.c, m.prev_m};
             TaAcc<2> acc;
-            if (id >= 0)
+            if (!BG || id >= 0)
                 acc = ta_gather<STATIC, 2, COUNTS>(a, rec, p, id, nx, ny, nz, Px, Py, Pz);
-            else
-                acc = bg_gather<STATIC, 2, COUNTS>(a, ba.G, rec, p, x, y);
+            else if constexpr (BG)
+                acc = bg_gather<STATIC, 2, COUNTS>(a, ma.G, rec, p, x, y);
             found = acc.found();
             if (found) {
                 const TaBlend h = ta_blend_head(acc, a, n);
@@ -195,7 +223,7 @@ __device__ __forceinline__ void bg_moments_step(const TemporalBgMomentsArgs& ba,
             if (gx >= 0 && gx < (int)a.width && gy >= 0 && gy < (int)a.height) { // (so q < width·height: inside counts too)
                 const size_t q = (size_t)gy * a.width + (size_t)gx;
                 vc = dn4{a.rgb[3 * q], a.rgb[3 * q + 1], a.rgb[3 * q + 2], __int_as_float(a.index[q])};
-                vn = dn4{a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2], COUNTS ? (float)ba.counts[q] : 1.0f};
+                vn = dn4{a.normal[3 * q], a.normal[3 * q + 1], a.normal[3 * q + 2], COUNTS ? (float)ma.counts[q] : 1.0f};
             }
             s_col[t] = vc, s_nrm[t] = vn;
         }
@@ -231,22 +259,52 @@ __device__ __forceinline__ void bg_moments_step(const TemporalBgMomentsArgs& ba,
     if (m.w2_out) m.w2_out[p] = W2;
 }
 
-template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_kernel(const TemporalBgArgs a) {
-    bg_plain_step<STATIC, false>(a);
+} // namespace rayz_dev
+
+// The kernels live in namespaces of their own: the kernels of rayz_dev are a recorded set (tests/test_slab_cells_isa.py).
+namespace rayz_dev_counts {
+using namespace rayz_dev;
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_counts_kernel(const TemporalModeArgs a) {
+    ta_mode_step<STATIC, true, false, false>(a);
 }
 
-template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_kernel(const TemporalBgArgs a) {
-    bg_plain_step<STATIC, true>(a);
-}
-
-template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_moments_kernel(const TemporalBgMomentsArgs a) {
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_counts_moments_kernel(const TemporalMomentsModeArgs a) {
     __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
-    bg_moments_step<STATIC, false>(a, s_col, s_nrm);
+    tm_mode_step<STATIC, true, false>(a, s_col, s_nrm);
 }
 
-template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_moments_kernel(const TemporalBgMomentsArgs a) {
+} // namespace rayz_dev_counts
+
+// {plain, moments} x {one spp, a count per pixel} x {static, moving}
+namespace rayz_dev_bg {
+using namespace rayz_dev;
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_kernel(const TemporalModeArgs a) {
+    ta_mode_step<STATIC, false, true, false>(a);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_kernel(const TemporalModeArgs a) {
+    ta_mode_step<STATIC, true, true, false>(a);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_moments_kernel(const TemporalMomentsModeArgs a) {
     __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
-    bg_moments_step<STATIC, true>(a, s_col, s_nrm);
+    tm_mode_step<STATIC, false, true>(a, s_col, s_nrm);
+}
+
+template <bool STATIC> __global__ __launch_bounds__(256) void temporal_bg_counts_moments_kernel(const TemporalMomentsModeArgs a) {
+    __shared__ dn4 s_col[kTmLdsH * kTmLdsW], s_nrm[kTmLdsH * kTmLdsW];
+    tm_mode_step<STATIC, true, true>(a, s_col, s_nrm);
 }
 
 } // namespace rayz_dev_bg
+
+namespace rayz_dev_cubic {
+
+// The plain step's moving form (temporal_step_kernel<false>, whose body stays as it is) with the colour history from tc_resample.
+__global__ __launch_bounds__(256) void temporal_cubic_step_kernel(const TemporalModeArgs a) {
+    ta_mode_step<false, false, false, true>(a);
+}
+
+} // namespace rayz_dev_cubic

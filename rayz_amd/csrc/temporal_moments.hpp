@@ -1,7 +1,8 @@
 // temporal_moments.hpp — the moments mode of temporal accumulation's handle (rayz_hip_temporal_track_moments, _step_moments;
 // DESIGN.md §4.16; the kernel: temporal_moments_kernel.hpp; the handle and what both kinds of step share — temporal_run_step, the
-// step's procedure —: temporal.hpp; the launch: temporal_kernel.hpp) and its feedback mode (rayz_hip_temporal_track_feedback,
-// _feedback; §4.17; temporal_feedback_kernel.hpp).
+// step's procedure —: temporal.hpp; the launch: temporal_kernel.hpp), its feedback mode (rayz_hip_temporal_track_feedback,
+// _feedback; §4.17; temporal_feedback_kernel.hpp) and the choice of a moments step's kernel, temporal_launch_moments (the counts
+// and background kernels: temporal_modes_kernel.hpp; the cubic one: temporal_cubic_kernel.hpp).
 // Included by rayz_hip.hip after temporal.hpp.
 #pragma once
 
@@ -55,6 +56,33 @@ int temporal_feedback(RayzTemporal* tm, const float* d_rgb, void* stream_arg) {
     return RAYZ_OK;
 }
 
+// The launch of a moments step: the one place that says which kernel a moments handle's modes, the camera and the kind of step
+// take.  (Behind the handle's check.  ACCUMULATE is never a feedback or a cubic handle: set_background refused them; a counts step
+// is none either: temporal_run_step refused it; a cubic handle is no feedback handle: set_resampling refused it; and a static step
+// of a cubic handle resamples nothing.)
+void temporal_launch_moments(hipStream_t st, const RayzTemporal* tm, const RayzCameraDesc* cam, const TemporalMomentsArgs& a, bool is_static,
+                             const uint32_t* d_counts) {
+    const uint32_t w = a.t.width, h = a.t.height;
+    const bool bg = tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE;
+    if (bg || d_counts) {
+        TemporalMomentsModeArgs m{a, {}, d_counts};
+        if (bg) temporal_background_args(tm, cam, is_static, m.G);
+        void (*still)(TemporalMomentsModeArgs) = rayz_dev_counts::temporal_counts_moments_kernel<true>;
+        void (*moving)(TemporalMomentsModeArgs) = rayz_dev_counts::temporal_counts_moments_kernel<false>;
+        if (bg && d_counts)
+            still = rayz_dev_bg::temporal_bg_counts_moments_kernel<true>, moving = rayz_dev_bg::temporal_bg_counts_moments_kernel<false>;
+        else if (bg)
+            still = rayz_dev_bg::temporal_bg_moments_kernel<true>, moving = rayz_dev_bg::temporal_bg_moments_kernel<false>;
+        temporal_launch_step(st, still, moving, is_static, m, w, h);
+    } else if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static)
+        hipLaunchKernelGGL(rayz_dev_cubic::temporal_cubic_moments_step_kernel, denoise_grid(w, h), dim3(256), 0, st,
+                           rayz_dev_cubic::TemporalCubicMomentsArgs{a, tm->taken});
+    else if (tm->feedback)
+        temporal_launch_step(st, temporal_feedback_step_kernel<true>, temporal_feedback_step_kernel<false>, is_static, a, w, h);
+    else
+        temporal_launch_step(st, temporal_moments_step_kernel<true>, temporal_moments_step_kernel<false>, is_static, a, w, h);
+}
+
 // Its own checks, then temporal.hpp's temporal_run_step: every argument is checked before the handle.
 // d_counts: NULL for the step with one spp, else the counts step's array (§4.23), which stands for spp (then 0).
 int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, const RayzTemporalMomentsParams* mparams,
@@ -75,27 +103,7 @@ int temporal_step_moments(RayzTemporal* tm, const RayzTemporalParams* params, co
         a.t = t;
         a.prev_m = tm->mom[tm->cur], a.next_m = tm->mom[tm->cur ^ 1];
         a.w2_out = d_w2_out, a.wm = (float)mp.w2_max, a.mt = (float)mp.min_taps;
-        using namespace rayz_dev_cubic;
-        if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE) { // (never a feedback or a cubic handle: set_background refused them)
-            using namespace rayz_dev_bg;
-            TemporalBgMomentsArgs b{a, {}, d_counts};
-            temporal_background_args(tm, cam, is_static, b.G);
-            if (d_counts)
-                temporal_launch_step(st, temporal_bg_counts_moments_kernel<true>, temporal_bg_counts_moments_kernel<false>, is_static, b,
-                                     t.width, t.height);
-            else
-                temporal_launch_step(st, temporal_bg_moments_kernel<true>, temporal_bg_moments_kernel<false>, is_static, b, t.width, t.height);
-        } else if (d_counts) { // (never a feedback handle: temporal_run_step refused it)
-            using namespace rayz_dev_counts;
-            temporal_launch_step(st, temporal_counts_moments_kernel<true>, temporal_counts_moments_kernel<false>, is_static,
-                                 TemporalMomentsCountsArgs{a, d_counts}, t.width, t.height);
-        } else if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static) // (never a feedback handle: set_resampling refused it)
-            hipLaunchKernelGGL(temporal_cubic_moments_step_kernel, denoise_grid(t.width, t.height), dim3(256), 0, st,
-                               TemporalCubicMomentsArgs{a, tm->taken});
-        else if (tm->feedback)
-            temporal_launch_step(st, temporal_feedback_step_kernel<true>, temporal_feedback_step_kernel<false>, is_static, a, t.width, t.height);
-        else
-            temporal_launch_step(st, temporal_moments_step_kernel<true>, temporal_moments_step_kernel<false>, is_static, a, t.width, t.height);
+        temporal_launch_moments(st, tm, cam, a, is_static, d_counts);
     };
     return temporal_run_step(tm, true, p, cam, spp, d_in, nullptr, g, d_out, d_var_out, d_len_out, stream_arg, launch, d_counts != nullptr,
                              d_w2_out);

@@ -20,7 +20,7 @@ def _umbrella_lines():
 
 
 UMBRELLA = [m.group(1) for m in (re.match(r'#include "([^"]+)"', line) for line in _umbrella_lines()) if m]
-HEADERS = UMBRELLA + ["chain_kernel.hpp", "noise.hpp", "sparse.hpp", "adaptive.hpp"]  # device headers of features, outside the umbrella
+HEADERS = UMBRELLA + ["chain_kernel.hpp", "noise.hpp", "sparse.hpp", "adaptive.hpp", "temporal_modes_kernel.hpp"]  # device headers of features, outside the umbrella
 
 
 def test_umbrella_holds_only_comment_and_includes():
