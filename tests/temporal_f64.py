@@ -9,6 +9,10 @@ camera's twelve doubles and its 152-byte key.)
 
 `misread=` switches in ONE wrong reading of §4.15 (MISREADINGS); the tests require that each is told apart from the mirror.
 
+`step` takes `spp` as one number — this section — or as an (h, w) integer array of per-pixel sample counts: the counts step, §4.23,
+whose rules act inside the gather and the blend below and are switched on by the array alone (every `if counts:`).  Their text, bounds
+and wrong readings (COUNTS_MISREADINGS) are in tests/temporal_counts_f64.py.
+
 The error bound (first order, carried from step to step, DOUBLED where it is reported or used as a margin).  u = 2^-24; a primed
 quantity is the f32 contract's, δq = |q' − q|.
 
@@ -36,7 +40,8 @@ quantity is the f32 contract's, δq = |q' − q|.
 
       δh <= Σ b_q E_q / B  +  Σ δb_q |c_q − h| / B  +  8u·Σ b_q |c_q| / B        (four FMAs into H, three adds into B, one divide)
 
-  and the same for hv (with the variance's E) and hN (with the length's E).  δB <= Σ δb_q + 3u·B.
+  and the same for hv (with the variance's E) and hN (with the length's E).  δB <= Σ δb_q + 3u·B.  A STATIC step's one tap has
+  b = 1: B = 1 and every mean is fma(1, x, 0) / 1 = x in any order of the operations, so the last term is 0 there (§4.23 (b)).
 
   Blend.  spp is exact.  Ns = hN + spp: δNs <= δhN + u·Ns.  a0 = spp/Ns: δa0 <= a0·δNs/Ns + u·a0.  al = max(a0, am): δal <= δa0.
   c_out = fma(al, c − h, h) = al·c + (1 − al)·h with the difference rounded first:
@@ -64,6 +69,11 @@ MISREADINGS = ("project_with_current_camera", "matrix_transposed", "pixel_centre
                "distance_absolute", "normal_test_abs", "refused_tap_in_B", "no_divide_by_B", "nearest_tap", "variance_b_squared",
                "variance_linear_alpha", "alpha_by_steps", "length_of_nearest_tap", "clamp_length_before_alpha",
                "alpha_min_is_a_ceiling", "background_takes_history", "history_stores_input", "outside_tap_clamped_in")
+# Wrong readings of §4.23 (the counts step), switched in like the others; tests/temporal_counts_f64.py lists and explains them.
+COUNTS_MISREADINGS = ("zero_length_record_accepted", "zero_length_tap_in_B", "static_tap_exempt_from_length_test",
+                      "alpha_min_applied_at_zero_count", "zero_count_takes_input", "zero_count_resets_length",
+                      "length_uncapped_at_zero_count", "variance_from_input_at_zero_count", "count_shared_over_the_frame",
+                      "background_keeps_history")
 
 
 def camera_system(cam):
@@ -102,11 +112,12 @@ def project(lf, A, P, half=False):
 
 class TemporalF64:
     def __init__(self, width, height, misread=None):
-        assert misread is None or misread in MISREADINGS, misread
+        assert misread is None or misread in MISREADINGS + COUNTS_MISREADINGS, misread
         self.width, self.height, self.misread = width, height, misread
         self.has_history = False
         self.key = self.cam = None
         self.last_static = None
+        self.last_passthrough = None  # (h, w) bool: the pixels whose outputs the last step took from its inputs by selection
         self.taps = None  # the per-tap quantities of the last step that read history (see _blend)
         self.hist = None  # dict: c, v (h, w, 3); N, K (h, w); n, P (h, w, 3); id (h, w); Ec, Ev (h, w, 3); EN (h, w); excluded (h, w)
 
@@ -115,7 +126,8 @@ class TemporalF64:
 
     def step(self, rgb, var_rgb, index, normal, point, camera, spp, length=True, bound=False, **params):
         """Returns (colour (h, w, 3), variance (h, w, 3)[, length (h, w)]) in float64; with bound=True two more entries: the bounds
-        (for colour, variance and length, shaped like them) and the `excluded` mask (h, w)."""
+        (for colour, variance and length, shaped like them) and the `excluded` mask (h, w).  `spp` is one number (§4.15) or an (h, w)
+        array of non-negative integers, one sample count per pixel: the counts step, §4.23 (tests/temporal_counts_f64.py)."""
         assert not (bound and self.misread), "the bound belongs to the reference as written"
         mis = lambda name: self.misread == name  # noqa: E731
         prm = {**DEFAULTS, **params}
@@ -125,7 +137,15 @@ class TemporalF64:
             am, nm, cm = f32(prm["alpha_min"]), f32(prm["n_max"]), f32(prm["normal_cos_min"])
             r = np.float32(prm["max_rel_dist"])
             r2 = np.float64(r * r)  # an f32 product
-        spp = float(spp)
+        counts = np.ndim(spp) != 0
+        if counts:
+            spp = np.asarray(spp)
+            assert spp.shape == (h, w) and spp.dtype.kind in "iu" and (spp >= 0).all() and (spp <= 2 ** 24).all(), (spp.shape, spp.dtype)
+            spp = spp.astype(np.float64)  # n = f32(count), exact up to 2^24
+            if mis("count_shared_over_the_frame"):
+                counts, spp = False, float(spp.mean())
+        else:
+            spp = float(spp)
         c = np.asarray(rgb, np.float64).reshape(h, w, 3)
         s = np.asarray(var_rgb, np.float64).reshape(h, w, 3)
         n = np.asarray(normal, np.float64).reshape(h, w, 3)
@@ -136,29 +156,32 @@ class TemporalF64:
         lf, A = camera_system(camera)
         key = camera_key(camera)
         static = self.has_history and key == self.key
+        had = self.has_history
         hit = idx >= 0
         zero3, zero1 = np.zeros((h, w, 3)), np.zeros((h, w))
         has = np.zeros((h, w), bool)
         excluded = np.zeros((h, w), bool)
-        c_out, v_out, N_out, K_out = c.copy(), s.copy(), np.full((h, w), spp), np.ones((h, w))
+        c_out, v_out, N_out, K_out = c.copy(), s.copy(), (spp.copy() if counts else np.full((h, w), spp)), np.ones((h, w))
         Ec, Ev, EN = zero3.copy(), zero3.copy(), zero1.copy()
         if self.has_history:
             with np.errstate(all="ignore"):
                 has, excluded, (c_b, v_b, N_b, K_b), (Ec_b, Ev_b, EN_b) = self._blend(
-                    mis, static, c, s, n, P, idx, hit, lf, A, spp, am, nm, cm, r2)
+                    mis, static, c, s, n, P, idx, hit, lf, A, spp, am, nm, cm, r2, counts)
             sel = lambda m, a, b: np.where(m[..., None] if a.ndim == 3 else m, a, b)  # noqa: E731
             c_out, v_out, N_out, K_out = sel(has, c_b, c_out), sel(has, v_b, v_out), sel(has, N_b, N_out), sel(has, K_b, K_out)
             Ec, Ev, EN = sel(has, Ec_b, Ec), sel(has, Ev_b, Ev), sel(has, EN_b, EN)
         self.hist = dict(c=c.copy() if mis("history_stores_input") else c_out, v=v_out, N=N_out, K=K_out, n=n, P=P, id=idx,
                          Ec=Ec, Ev=Ev, EN=EN, excluded=excluded)
         self.has_history, self.key, self.cam, self.last_static = True, key, (lf, A), static
+        self.last_passthrough = ~has & ~excluded
+        self.last_had = had
         res = (c_out, v_out) + ((N_out,) if length else ())
         if bound:
             res += ((2 * Ec, 2 * Ev) + ((2 * EN,) if length else ()), excluded)
         return res
 
     # ---- steps 2-4 for a handle that has history ------------------------------------------------------------------------------
-    def _blend(self, mis, static, c, s, n, P, idx, hit, lf, A, spp, am, nm, cm, r2):
+    def _blend(self, mis, static, c, s, n, P, idx, hit, lf, A, spp, am, nm, cm, r2, counts=False):
         h, w = self.height, self.width
         H = self.hist
         gy, gx = np.mgrid[0:h, 0:w]
@@ -213,12 +236,26 @@ class TemporalF64:
         dd = np.sum(d * d, axis=-1)
         acc = same & ((np.abs(dn) if mis("normal_test_abs") else dn) >= cm) & (dd <= lim[None])
         tnear = same & rel & ((np.abs(dn - cm) <= 2 * ddn) | (np.abs(dd - lim[None]) <= 2 * (5 * U * dd + dlim[None])))
+        self.length_near = np.zeros((h, w), bool)
+        live = acc  # (the taps §4.15's tests accept)
+        if counts:
+            # §4.23 rule 1: a record of length 0 holds no samples and is refused — the static step's one tap too.  A length is 0
+            # exactly (rule 2 stored a count of 0) or positive; the decision gets the margin every other one has.
+            Nq, ENq = H["N"][qy, qx], H["EN"][qy, qx]
+            lnear = same & rel & (Nq > 0) & (Nq <= 2 * ENq)
+            self.length_near = lnear.any(axis=0)
+            tnear = tnear | lnear
+            if not (mis("zero_length_record_accepted") or (static and mis("static_tap_exempt_from_length_test"))):
+                acc = acc & (Nq > 0)
+            self.refused_empty = (live & ~acc & (b > 0)).any(axis=0)  # a tap with b > 0 that only rule 1 refuses
         near |= tnear.any(axis=0)
         taint = (acc & rel & H["excluded"][qy, qx]).any(axis=0)
 
         ba = np.where(acc, b, 0.0)
         dba = np.where(acc, db, 0.0)
         B = np.sum(np.where(inside & ok[None], b, 0.0), axis=0) if mis("refused_tap_in_B") else np.sum(ba, axis=0)
+        if mis("zero_length_tap_in_B"):
+            B = np.sum(np.where(live, b, 0.0), axis=0)
         dB = np.sum(dba, axis=0) + 3 * U * B
         near |= ok & (np.abs(B - BMIN) <= 2 * dB)
         has = ok & (B >= BMIN)
@@ -228,11 +265,18 @@ class TemporalF64:
             """h = Σ b v_q / B over accepted taps and its bound; val (h, w[, 3])."""
             three = val.ndim == 3
             ex = (lambda z: z[..., None]) if three else (lambda z: z)
-            vq, Eq = val[qy, qx], E[qy, qx]
+            # the records are SELECTED before they meet a weight: a refused record may hold a NaN (§4.23), and 0·NaN is NaN
+            used = ex((weight != 0) | (ba != 0) | (dba != 0))
+            vq, Eq = np.where(used, val[qy, qx], 0.0), np.where(used, E[qy, qx], 0.0)
             hh = np.sum(ex(weight) * vq, axis=0) / ex(norm)
             Eh = (np.sum(ex(ba) * Eq, axis=0) + np.sum(ex(dba) * np.abs(vq - hh[None]), axis=0)
-                  + 8 * U * np.sum(ex(ba) * np.abs(vq), axis=0)) / ex(div)
+                  + rnd * np.sum(ex(ba) * np.abs(vq), axis=0)) / ex(div)
             return hh, Eh
+
+        # A static step's one tap has b = 1, so B = 1 and every mean is fma(1, x, 0) / 1 = x, whatever the order of the operations
+        # (§4.23 (b)): the gather rounds nothing there and δh is the record's own E.  (Without this a kept W2 = 1 of a first frame,
+        # with w2_max = 1, would sit within a margin of 8u that no f32 run can use.)
+        rnd = 0.0 if static else 8 * U
 
         hc, Ehc = gather(H["c"], H["Ec"])
         if mis("variance_b_squared"):
@@ -244,7 +288,7 @@ class TemporalF64:
         if mis("length_of_nearest_tap"):
             best = np.argmax(ba, axis=0)
             hN = np.take_along_axis(H["N"][qy, qx], best[None], axis=0)[0]
-        if mis("background_takes_history"):
+        if mis("background_takes_history") or mis("background_keeps_history"):
             both = ~hit & (H["id"] < 0)
             e3 = both[..., None]
             hc, hv, hN, hK = np.where(e3, H["c"], hc), np.where(e3, H["v"], hv), np.where(both, H["N"], hN), np.where(both, H["K"], hK)
@@ -257,7 +301,20 @@ class TemporalF64:
         a0 = 1.0 / (hK + 1.0) if mis("alpha_by_steps") else spp / Ns
         da0 = a0 * dNs / Ns + U * a0
         al = np.where(a0 > am, am, a0) if mis("alpha_min_is_a_ceiling") else np.where(a0 < am, am, a0)
-        near |= has & ((np.abs(a0 - am) <= 2 * da0) | (np.abs(Ns - nm) <= 2 * dNs))
+        sampled = np.ones((h, w), bool)
+        if counts:
+            # §4.23 rule 4: history found and n = 0.  al = 0 by selection — a0 < am is not decided and has no margin — and the input
+            # is never read: c_out = h (δh), v_out = hv (δhv), N_out = hN > nm ? nm : hN (δhN, the margin on nm is 2·δhN).
+            sampled = spp > 0
+            dNs = np.where(sampled, dNs, EhN)
+            if not mis("alpha_min_applied_at_zero_count"):
+                al, da0 = np.where(sampled, al, 0.0), np.where(sampled, da0, 0.0)
+                near |= has & np.where(sampled, np.abs(a0 - am) <= 2 * da0, False)
+            else:
+                near |= has & (np.abs(a0 - am) <= 2 * da0)
+            near |= has & (np.abs(Ns - nm) <= 2 * dNs)
+        else:
+            near |= has & ((np.abs(a0 - am) <= 2 * da0) | (np.abs(Ns - nm) <= 2 * dNs))
         k = 1.0 - al
         a3, k3 = al[..., None], k[..., None]
         diff = c - hc
@@ -271,10 +328,25 @@ class TemporalF64:
             v_b = a3 * a3 * s + k3 * k3 * hv
         Ev = s * da2[..., None] + hv * dk2[..., None] + k3 * k3 * Ehv + U * k3 * k3 * hv + U * v_b
         N_b = np.where(Ns > nm, nm, Ns)
+        if counts:
+            kept = ~sampled  # rule 4, by selection on the VALUE: the input of such a pixel may be a NaN
+            k3 = kept[..., None]
+            if not (mis("alpha_min_applied_at_zero_count") or mis("zero_count_takes_input")):
+                c_b, Ec = np.where(k3, hc, c_b), np.where(k3, Ehc, Ec)
+            if mis("zero_count_takes_input"):
+                c_b, Ec = np.where(k3, c, c_b), np.where(k3, 0.0, Ec)
+            if mis("zero_count_takes_input") or mis("variance_from_input_at_zero_count"):
+                v_b, Ev = np.where(k3, s, v_b), np.where(k3, 0.0, Ev)
+            elif not mis("alpha_min_applied_at_zero_count"):
+                v_b, Ev = np.where(k3, hv, v_b), np.where(k3, Ehv, Ev)
+            if mis("zero_count_resets_length"):
+                N_b = np.where(kept, 0.0, N_b)
+            if mis("length_uncapped_at_zero_count"):
+                N_b = np.where(kept, hN, N_b)
         excluded = hit & (near | (has & taint))
         # what a step that rides the same taps needs (tests/temporal_moments_f64.py); nothing above depends on it
         self.taps = dict(b=b, db=db, ba=ba, dba=dba, qy=qy, qx=qx, inside=inside, ok=ok, div=div, has=has, al=al, da0=da0, hc=hc,
-                         near=near, taint=taint, gather=gather)
+                         near=near, taint=taint, gather=gather, sampled=sampled, acc=acc)
         return has, excluded, (c_b, v_b, N_b, hK + 1.0), (Ec, Ev, dNs)
 
 

@@ -9,7 +9,10 @@ their bounds and the `excluded` mask from it, and reads the per-tap quantities i
 `feedback(rgb)` is §4.17's write: finite pixels replace the colour of the side the last step wrote — which is the inner
 reference's colour history, whose bound becomes 0 there, the image being the same f32 numbers in both runs — and nothing else.
 
-`misread=` switches in ONE wrong reading of §4.16 (MISREADINGS) or, on a feedback handle, of §4.17 (FEEDBACK_MISREADINGS).
+`misread=` switches in ONE wrong reading of §4.16 (MISREADINGS) or, on a feedback handle, of §4.17 (FEEDBACK_MISREADINGS).  `step`
+takes `spp` as one number or as an (h, w) integer array, the counts step of §4.23: the inner reference gets the array, m2 and W2 are
+kept by selection where a pixel without samples found history, and step 4's neighbourhood runs over sampled positions
+(tests/temporal_counts_f64.py has the text, the bounds and the wrong readings, COUNTS_MISREADINGS).
 
 The error bound (first order, carried from step to step, DOUBLED where it is reported or used as a margin; u = 2^-24; δq = |q' − q|
 for the f32 contract's q').  The input colour c and the guides are the same f32 numbers in both runs.  From tests/temporal_f64.py:
@@ -48,7 +51,9 @@ What is dropped is second order, so the reported bounds are 2·E and every decis
 
 Exclusions (bound=True returns two masks).  `excluded` is §4.15's, taint included: colour, length and W2 of a pixel are excluded
 exactly there — m2, W2 and m1 ride the same taps.  The VARIANCE of a pixel is excluded there and, besides, (a) where W2_out lies
-within 2·δW2_out of wm and δW2_out > 0 (with δW2_out = 0 both runs hold the same number and decide alike), and (b) where the pixel
+within 2·δW2_out of wm and δW2_out > 0 (with δW2_out = 0 both runs hold the same number and decide alike) and the estimate the
+reference selected has a finite bound in some channel (where it has none nothing is held to the value, so nothing needs excluding:
+with w2_max = 1 a W2_out within its margin of 1 has den <= 2δden, and the pixel stays in the comparison), and (b) where the pixel
 takes, or within that margin may take, the spatial estimate and one of its 7x7 taps inside the frame, of the same index and not
 the centre, has dot(n(q), n) within 2·3u·Σ|n_i n'_i| of cm.  A variance-only exclusion spreads no taint: no later step reads v_out
 (§4.16: "written, never read"; §4.17: the record holds m1)."""
@@ -65,6 +70,9 @@ MISREADINGS = ("m2_from_blended_colour", "m2_blend_linear_in_c", "m2_of_squared_
                "background_gets_the_cap", "spatial_over_accumulated_colour")
 FEEDBACK_MISREADINGS = ("variance_from_fedback_colour", "write_overwrites_m1", "write_overwrites_length", "write_to_older_side",
                         "m1_from_own_record", "nonfinite_feedback_stored")
+# Wrong readings of §4.23's moments step; tests/temporal_counts_f64.py lists and explains them.
+COUNTS_MISREADINGS = ("neighbourhood_counts_unsampled", "centre_counted_without_samples", "m2_from_input_at_zero_count",
+                      "w2_reset_at_zero_count", "w2_blended_at_zero_count")
 NAMES = ("colour", "variance", "length", "W2")
 # What the less obvious names switch in.  m2_from_blended_colour: m2_out = c_out².  m2_blend_linear_in_c: m2_out = fma(al, c − hq, hq),
 # the colour and not its square blended into the second moment.  m2_of_squared_history: hq = h² (the interpolated colour squared instead
@@ -85,15 +93,21 @@ def clamp(t):
 
 class TemporalMomentsF64:
     def __init__(self, width, height, feedback=False, misread=None):
-        assert misread is None or misread in MISREADINGS or (feedback and misread in FEEDBACK_MISREADINGS), misread
+        plain = misread in temporal_f64.COUNTS_MISREADINGS  # a wrong reading of §4.23's plain rules: the inner reference's
+        assert misread is None or misread in MISREADINGS + COUNTS_MISREADINGS or plain or (feedback and misread in FEEDBACK_MISREADINGS), misread
         self.width, self.height, self.track, self.misread = width, height, feedback, misread
-        self.inner = temporal_f64.TemporalF64(width, height)
+        self.inner = temporal_f64.TemporalF64(width, height, misread=misread if plain else None)
         self.state = None  # dict: m2, Em2 (h, w, 3); W2, EW (h, w); m1, Em1 (h, w, 3; a feedback handle's)
         self.last_spatial = None  # (h, w) bool: the pixels whose variance the last step took from the spatial estimate
 
     @property
     def last_static(self):
         return self.inner.last_static
+
+    @property
+    def last_passthrough(self):
+        """The pixels whose colour, length and W2 the last step took by selection (no history: c, n, 1)."""
+        return self.inner.last_passthrough
 
     def reset(self):
         self.inner.reset()
@@ -137,7 +151,13 @@ class TemporalMomentsF64:
         # ---- step 1: §4.15's colour and length, from §4.15's reference ----------------------------------------------------------
         had = self.inner.has_history
         S = self.state
-        c_out, _, N_out, (bc, _, bN), ex = self.inner.step(rgb, np.zeros((h, w, 3)), index, normal, point, camera, spp, bound=True, **plain)
+        counts = np.ndim(spp) != 0 and not mis("count_shared_over_the_frame")
+        cnt = np.asarray(spp).reshape(h, w) if counts else None
+        if self.inner.misread:  # (no bound is asked of a misreading)
+            c_out, _, N_out = self.inner.step(rgb, np.zeros((h, w, 3)), index, normal, point, camera, spp, **plain)
+            bc, bN, ex = np.zeros((h, w, 3)), np.zeros((h, w)), np.zeros((h, w), bool)
+        else:
+            c_out, _, N_out, (bc, _, bN), ex = self.inner.step(rgb, np.zeros((h, w, 3)), index, normal, point, camera, spp, bound=True, **plain)
         Ec = bc / 2
         T = self.inner.taps if had else None
         z3, z1 = np.zeros((h, w, 3)), np.zeros((h, w))
@@ -179,6 +199,20 @@ class TemporalMomentsF64:
                 else:
                     W2_b = k * k * hWb + al * al
                 EW_b = hWb * dk2 + k * k * EhW + da2 + U * W2_b
+                if counts:
+                    # §4.23: history found and n = 0 — m2_out = hq (δhq), W2_out = hW (δhW), selected on the VALUE: c may be a NaN
+                    kept = cnt == 0
+                    if not mis("m2_from_input_at_zero_count"):
+                        m2_b, Em2_b = np.where(kept[..., None], hq, m2_b), np.where(kept[..., None], Ehq, Em2_b)
+                    else:
+                        m2_b, Em2_b = np.where(kept[..., None], cc, m2_b), np.where(kept[..., None], U * cc, Em2_b)
+                    if mis("w2_reset_at_zero_count"):
+                        W2_b = np.where(kept, 1.0, W2_b)
+                    elif mis("w2_blended_at_zero_count"):
+                        am = np.float64(np.float32({**temporal_f64.DEFAULTS, **plain}["alpha_min"]))
+                        W2_b = np.where(kept, (1 - am) * (1 - am) * hWb + am * am, W2_b)
+                    else:
+                        W2_b, EW_b = np.where(kept, hWb, W2_b), np.where(kept, EhW, EW_b)
                 m2_o, Em2 = np.where(h3, m2_b, m2_o), np.where(h3, Em2_b, Em2)
                 W2_o, EW, hW = np.where(has, W2_b, W2_o), np.where(has, EW_b, EW), np.where(has, hWb, hW)
                 if self.track:
@@ -219,14 +253,17 @@ class TemporalMomentsF64:
             vt, Evt = np.where(h3, clamp(q), VCAP), np.where(h3, Evt, 0.0)
 
         # ---- step 4: the spatial estimate over the current frame ----------------------------------------------------------------
-        vs, Evs, nnear = self._spatial(mis, c, c_out, idx, n, cm, mt, W2_o, EW)
+        vs, Evs, nnear = self._spatial(mis, c, c_out, idx, n, cm, mt, W2_o, EW, cnt)
 
         # ---- step 5: selection -----------------------------------------------------------------------------------------------------
         spatial = hit & ((hW if mis("w2_of_history_selects") else W2_o) > wm)
         s3 = spatial[..., None]
         v_out = np.where(hit[..., None], np.where(s3, vs, vt), VCAP if mis("background_gets_the_cap") else 0.0)
         Ev = np.where(hit[..., None], np.where(s3, Evs, Evt), 0.0)
-        wnear = hit & (EW > 0) & (np.abs(W2_o - wm) <= 2 * EW)
+        # (.. unless the estimate the reference selected has no finite bound in any channel: nothing is held to it then — with
+        # w2_max = 1 a W2_out within its margin of 1 is exactly that case, den <= 2δden — and nothing needs excluding; the pixel
+        # stays in the comparison, where only a NaN can fail)
+        wnear = hit & (EW > 0) & (np.abs(W2_o - wm) <= 2 * EW) & np.isfinite(Ev).any(axis=-1)
         vex = ex | wnear | ((spatial | wnear) & nnear)
 
         self.state = dict(m2=m2_o, Em2=Em2, W2=W2_o, EW=EW, m1=m1_o, Em1=Em1)
@@ -236,10 +273,12 @@ class TemporalMomentsF64:
             res += ((bc, 2 * Ev, bN, 2 * EW), (ex, vex))
         return res
 
-    def _spatial(self, mis, c, c_out, idx, n, cm, mt, W2_o, EW):
+    def _spatial(self, mis, c, c_out, idx, n, cm, mt, W2_o, EW, cnt=None):
         """§4.16 step 4 for every pixel (the caller selects): vs, its bound, and the mask of the pixels with a 7x7 normal test inside
-        its doubled margin."""
+        its doubled margin.  With per-pixel counts `cnt` (§4.23) a position is counted only if it was sampled, the centre too."""
         h, w = self.height, self.width
+        sampled = np.ones((h, w), bool) if cnt is None else cnt > 0
+        sp = np.pad(sampled, 3, constant_values=True)  # (outside the frame `inside_p` decides)
         R = 2 if mis("spatial_window_5x5") else 3
         clamped = mis("spatial_edge_clamped_in")
         pad = lambda a: np.pad(a, [(3, 3), (3, 3)] + [(0, 0)] * (a.ndim - 2), mode="edge" if clamped else "constant")  # noqa: E731
@@ -257,6 +296,9 @@ class TemporalMomentsF64:
                 dn = np.sum(nq * n, axis=-1)
                 same = inside_p[sl] if mis("spatial_ignores_index") else inside_p[sl] & (iq == idx)
                 acc = same & (centre or mis("spatial_ignores_normals") or (dn >= cm))
+                if cnt is not None and not (mis("centre_counted_without_samples") if centre else mis("neighbourhood_counts_unsampled")):
+                    acc = acc & sp[sl]
+                    same = same & sp[sl]  # (an unsampled position's normal test decides nothing)
                 if not centre:
                     nnear |= same & (np.abs(dn - cm) <= 2 * 3 * U * np.sum(np.abs(nq * n), axis=-1))
                 a3 = acc[..., None]
