@@ -1150,6 +1150,41 @@ int rayz_hip_temporal_get_resampling(RayzTemporal* tm, uint32_t* mode);
 int rayz_hip_temporal_set_background(RayzTemporal* tm, uint32_t mode);
 int rayz_hip_temporal_get_background(RayzTemporal* tm, uint32_t* mode);
 
+/* ---- temporal accumulation, clip mode: the history's colour clamped to the current frame's neighbourhood ----
+ * BUILD-DEFINED, additive within ABI 5, opt-in: a handle starts in RAYZ_TEMPORAL_CLIP_OFF, where every step is what it was, bit
+ * for bit.  A step accepts a history pixel by geometry alone; nothing compares its colour with the frame it is blended into, so
+ * stale radiance that passes every geometric test stays.  In RAYZ_TEMPORAL_CLIP_VARIANCE a MOVING step clamps, per channel, the
+ * gathered history mean of a pixel that found history to mu +- gamma*sd before the blend, where mu and sd are the mean and the
+ * unbiased sample deviation of the CURRENT frame over the pixel's 7x7 neighbourhood on the same surface — §4.16 step 4's taps,
+ * acceptance and sums — wherever that neighbourhood has at least min_taps pixels.  In RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE a pixel
+ * with index < 0 is clipped too, against the misses of its neighbourhood.  In moments mode the history's second moment of a
+ * clipped channel moves with the mean and keeps its spread about it, and a pixel that also takes the spatial estimate uses the
+ * same sums.  A static step, a first frame and a pixel without history are the OFF step bit for bit: a still camera keeps
+ * converging to the running mean.  gamma = +inf never clips (the OFF step bit for bit); gamma = 0 replaces the history by mu.
+ * What it does not do: the history length, W2 and the plain step's carried variance ignore the clip.
+ * The history's layout does not change and the handle gains no device state, so the mode may be changed between any two steps,
+ * with or without history.  The arithmetic is a contract (§4.28), restated by tests/temporal_clip_mirror.cpp.
+ * params_or_null: NULL takes the defaults below; both are used as f32.
+ * d_clipped_or_null: DEVICE memory, height*width bytes, which the caller keeps allocated until another call replaces it (NULL:
+ * none).  EVERY later step of the handle, in either mode, writes one byte per pixel there: 1 where the clip changed any channel of
+ * the pixel's colour history — by as little as one ulp — and 0 elsewhere; a step that runs no clip kernel clears it on its own
+ * stream.  A step refuses a d_clipped that equals one of its outputs or the handle's d_taken with RAYZ_ERR_BAD_ARG.
+ * Limits of this version, all RAYZ_ERR_STATE: a handle that tracks feedback or resamples cubically refuses set_clip(VARIANCE),
+ * and a VARIANCE handle refuses rayz_hip_temporal_track_feedback and set_resampling(CUBIC); a VARIANCE handle refuses
+ * rayz_hip_temporal_step_counts and _step_moments_counts.
+ * RAYZ_ERR_BAD_ARG (checked before the handle): a mode that is neither constant; gamma not >= 0 (+inf is allowed, a NaN is not);
+ * min_taps outside [2, 49].  RAYZ_ERR_STATE: a bad handle. */
+#define RAYZ_TEMPORAL_CLIP_OFF      0u   /* default: every section as it is */
+#define RAYZ_TEMPORAL_CLIP_VARIANCE 1u
+#define RAYZ_TEMPORAL_CLIP_DEFAULT_GAMMA    1.0   /* PROVISIONAL: parameters, not contract */
+#define RAYZ_TEMPORAL_CLIP_DEFAULT_MIN_TAPS 4.0
+typedef struct RayzTemporalClipParams {
+    double gamma;    /* >= 0: the half-width of the box in sample deviations */
+    double min_taps; /* in [2, 49]: below this many accepted neighbours the history is not clipped */
+} RayzTemporalClipParams; /* used as f32 */
+int rayz_hip_temporal_set_clip(RayzTemporal* tm, uint32_t mode, const RayzTemporalClipParams* params_or_null, uint8_t* d_clipped_or_null);
+int rayz_hip_temporal_get_clip(RayzTemporal* tm, uint32_t* mode, RayzTemporalClipParams* params_or_null);
+
 #ifdef __cplusplus
 }
 #endif

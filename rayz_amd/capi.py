@@ -56,6 +56,9 @@ TEMPORAL_RESAMPLE_BILINEAR, TEMPORAL_RESAMPLE_CUBIC = 0, 1  # RAYZ_TEMPORAL_RESA
 TEMPORAL_RESAMPLING = {"bilinear": TEMPORAL_RESAMPLE_BILINEAR, "cubic": TEMPORAL_RESAMPLE_CUBIC}
 TEMPORAL_BACKGROUND_INPUT, TEMPORAL_BACKGROUND_ACCUMULATE = 0, 1  # RAYZ_TEMPORAL_BACKGROUND_* 
 TEMPORAL_BACKGROUND = {"input": TEMPORAL_BACKGROUND_INPUT, "accumulate": TEMPORAL_BACKGROUND_ACCUMULATE}
+TEMPORAL_CLIP_OFF, TEMPORAL_CLIP_VARIANCE = 0, 1  # RAYZ_TEMPORAL_CLIP_* 
+TEMPORAL_CLIP = {"off": TEMPORAL_CLIP_OFF, "variance": TEMPORAL_CLIP_VARIANCE}
+TEMPORAL_CLIP_DEFAULTS = {"gamma": 1.0, "min_taps": 4.0}  # RAYZ_TEMPORAL_CLIP_DEFAULT_*
 
 D3 = C.c_double * 3
 
@@ -165,6 +168,10 @@ class TemporalMomentsParams(C.Structure):
     _fields_ = [("w2_max", C.c_double), ("min_taps", C.c_double)]
 
 
+class TemporalClipParams(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("min_taps", C.c_double)]
+
+
 assert C.sizeof(Texture) == 48 and C.sizeof(Material) == 24 and C.sizeof(Sphere) == 64 and C.sizeof(Triangle) == 80
 assert C.sizeof(SceneDesc) == 48
 assert C.sizeof(CameraDesc) == 152 and C.sizeof(RenderParams) == 56 and C.sizeof(RenderStats) == 40
@@ -174,6 +181,7 @@ assert C.sizeof(UpscaleParams) == 24
 assert C.sizeof(ChainParams) == 16 and C.sizeof(ChainOutputs) == 24
 assert C.sizeof(SampledParams) == 8 and C.sizeof(SampledOutputs) == 32
 assert C.sizeof(AdaptiveSummary) == 40 and C.sizeof(TemporalParams) == 32 and C.sizeof(TemporalMomentsParams) == 16
+assert C.sizeof(TemporalClipParams) == 16
 
 # every symbol include/rayz_hip.h declares: (name, restype, argtypes)
 PROTOTYPES = [
@@ -323,6 +331,8 @@ PROTOTYPES = [
     ("rayz_hip_temporal_get_resampling", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("rayz_hip_temporal_set_background", C.c_int, [C.c_void_p, C.c_uint32]),
     ("rayz_hip_temporal_get_background", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("rayz_hip_temporal_set_clip", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(TemporalClipParams), C.c_void_p]),
+    ("rayz_hip_temporal_get_clip", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(TemporalClipParams)]),
 ]
 
 

@@ -1,7 +1,8 @@
 // temporal.hpp — temporal accumulation's handle (rayz_hip_temporal_*; the kernel and its launch:
 // temporal_kernel.hpp; what it shares with the denoiser's handle: frame_handle.hpp; the moments mode: temporal_moments.hpp) and
 // the one procedure of a step of either kind, temporal_run_step; the background mode's host part and calls (§4.27); the choice of a
-// plain step's kernel, temporal_launch_plain (the counts, background and cubic kernels: temporal_modes_kernel.hpp).
+// plain step's kernel, temporal_launch_plain (the counts, background, cubic and clip kernels: temporal_modes_kernel.hpp); the clip
+// mode's calls (§4.28).
 // Included by rayz_hip.hip; of the renderer it needs the device contexts only.
 #pragma once
 
@@ -22,6 +23,9 @@ struct RayzTemporal : FrameHandle<2 * 4, 3> {
     uint32_t resampling = RAYZ_TEMPORAL_RESAMPLE_BILINEAR; // rayz_hip_temporal_set_resampling (§4.26): how a moving step fetches the colour history
     uint8_t* taken = nullptr; // .. and the caller's device bytes every step writes (1: the pixel took the cubic path), or NULL
     uint32_t background = RAYZ_TEMPORAL_BACKGROUND_INPUT; // rayz_hip_temporal_set_background (§4.27): whether a pixel with id < 0 gathers history
+    uint32_t clip = RAYZ_TEMPORAL_CLIP_OFF; // rayz_hip_temporal_set_clip (§4.28): whether a moving step clamps the colour history ..
+    RayzTemporalClipParams clip_params{RAYZ_TEMPORAL_CLIP_DEFAULT_GAMMA, RAYZ_TEMPORAL_CLIP_DEFAULT_MIN_TAPS}; // .. to what box ..
+    uint8_t* clipped = nullptr; // .. and the caller's device bytes every step writes (1: a channel was clipped), or NULL
 };
 
 namespace {
@@ -70,6 +74,17 @@ void temporal_background_matrix(const RayzCameraDesc* prev, const RayzCameraDesc
 void temporal_background_args(const RayzTemporal* tm, const RayzCameraDesc* cam, bool is_static, float* G) {
     std::memset(G, 0, 9 * sizeof(float));
     if (tm->has_history && !is_static) temporal_background_matrix(&tm->cam, cam, G);
+}
+
+// §4.28: does this step of the handle run a clip kernel?  Only a moving step with history of a VARIANCE handle does (which is no
+// counts step, and whose handle neither tracks feedback nor resamples cubically: all refused before).
+bool temporal_clips(const RayzTemporal* tm, bool is_static) {
+    return tm->clip == RAYZ_TEMPORAL_CLIP_VARIANCE && tm->has_history && !is_static;
+}
+
+// .. and what its kernel takes of the handle.
+TemporalClip temporal_clip_args(const RayzTemporal* tm) {
+    return TemporalClip{(float)tm->clip_params.gamma, (float)tm->clip_params.min_taps, tm->clipped};
 }
 
 // The checks both kinds of step make of the parameters and the sample count ..
@@ -144,9 +159,15 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
         return fail(RAYZ_ERR_STATE, "a temporal handle that tracks feedback takes no counts step (its first moment has no rule for a pixel without samples)");
     if (counts && tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
         return fail(RAYZ_ERR_STATE, "a temporal handle in cubic resampling mode takes no counts step (rayz_hip_temporal_set_resampling back to bilinear first)");
+    if (counts && tm->clip == RAYZ_TEMPORAL_CLIP_VARIANCE)
+        return fail(RAYZ_ERR_STATE, "a temporal handle in variance clip mode takes no counts step (rayz_hip_temporal_set_clip back to off first)");
     if (tm->taken)
         for (const void* o : {(const void*)d_out, (const void*)d_var_out, (const void*)d_len_out, (const void*)d_w2_out})
             if (o == (const void*)tm->taken) return fail(RAYZ_ERR_BAD_ARG, "temporal: the handle's d_taken is also an output of the step");
+    if (tm->clipped)
+        for (const void* o : {(const void*)d_out, (const void*)d_var_out, (const void*)d_len_out, (const void*)d_w2_out, (const void*)tm->taken})
+            if (o == (const void*)tm->clipped)
+                return fail(RAYZ_ERR_BAD_ARG, "temporal: the handle's d_clipped is also an output of the step or its d_taken");
     hipStream_t st;
     RAYZ_TRY(frame_handle_stream(tm, stream_arg, st));
     DeviceScope scope(tm->device);
@@ -158,6 +179,8 @@ int temporal_run_step(RayzTemporal* tm, bool moments, const RayzTemporalParams& 
     // (§4.26: only the cubic kernels write the taken bytes themselves; every other step took the sixteen taps nowhere)
     const bool cubic = tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static;
     if (tm->taken && !cubic) HIP_TRY(hipMemsetAsync(tm->taken, 0, (size_t)tm->width * tm->height, st));
+    // (§4.28: only the clip kernels write the clipped bytes themselves; every other step clipped nothing)
+    if (tm->clipped && !temporal_clips(tm, is_static)) HIP_TRY(hipMemsetAsync(tm->clipped, 0, (size_t)tm->width * tm->height, st));
     launch(st, a, is_static);
     RAYZ_TRY(frame_handle_launched(tm, 1, st));
     temporal_stepped(tm, cam, M, from);
@@ -180,6 +203,13 @@ void temporal_launch_plain(hipStream_t st, const RayzTemporal* tm, const RayzCam
                            const uint32_t* d_counts) {
     const bool bg = tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE;
     const bool cubic = tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC && !is_static;
+    if (temporal_clips(tm, is_static)) { // (§4.28: the moving step only; neither a counts nor a cubic step)
+        TemporalClipArgs c{{a, {}, nullptr, nullptr}, temporal_clip_args(tm)};
+        if (bg) temporal_background_args(tm, cam, is_static, c.m.G);
+        hipLaunchKernelGGL(bg ? rayz_dev_clip::clip_plain_kernel<true> : rayz_dev_clip::clip_plain_kernel<false>, denoise_grid(a.width, a.height),
+                           dim3(256), 0, st, c);
+        return;
+    }
     if (!bg && !d_counts && !cubic)
         return temporal_launch_step(st, temporal_step_kernel<true>, temporal_step_kernel<false>, is_static, a, a.width, a.height);
     TemporalModeArgs m{a, {}, d_counts, tm->taken};
@@ -218,6 +248,8 @@ int temporal_set_resampling(RayzTemporal* tm, uint32_t mode, uint8_t* d_taken) {
         return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle that tracks feedback has no cubic mode (its raw first moment has no resampling rule)");
     if (mode == RAYZ_TEMPORAL_RESAMPLE_CUBIC && tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE)
         return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle that accumulates the background has no cubic mode (rayz_hip_temporal_set_background back to input first)");
+    if (mode == RAYZ_TEMPORAL_RESAMPLE_CUBIC && tm->clip == RAYZ_TEMPORAL_CLIP_VARIANCE)
+        return fail(RAYZ_ERR_STATE, "temporal set_resampling: a handle in variance clip mode has no cubic mode (rayz_hip_temporal_set_clip back to off first)");
     tm->resampling = mode, tm->taken = d_taken;
     return RAYZ_OK;
 }
@@ -244,6 +276,29 @@ int temporal_set_background(RayzTemporal* tm, uint32_t mode) {
 int temporal_get_background(RayzTemporal* tm, uint32_t* mode) {
     RAYZ_TRY(frame_handle_check(tm));
     if (mode) *mode = tm->background;
+    return RAYZ_OK;
+}
+
+// §4.28's mode, its parameters and the clipped bytes.  The mode and the parameters are arguments and are checked before the handle.
+int temporal_set_clip(RayzTemporal* tm, uint32_t mode, const RayzTemporalClipParams* params, uint8_t* d_clipped) {
+    if (mode != RAYZ_TEMPORAL_CLIP_OFF && mode != RAYZ_TEMPORAL_CLIP_VARIANCE)
+        return fail(RAYZ_ERR_BAD_ARG, "temporal clip mode %u: must be RAYZ_TEMPORAL_CLIP_OFF or _VARIANCE", mode);
+    const RayzTemporalClipParams p = params ? *params : RayzTemporalClipParams{RAYZ_TEMPORAL_CLIP_DEFAULT_GAMMA, RAYZ_TEMPORAL_CLIP_DEFAULT_MIN_TAPS};
+    if (!(p.gamma >= 0)) return fail(RAYZ_ERR_BAD_ARG, "temporal clip gamma %g: must be at least 0 (+inf never clips)", p.gamma);
+    if (!(p.min_taps >= 2 && p.min_taps <= 49)) return fail(RAYZ_ERR_BAD_ARG, "temporal clip min_taps %g: must lie in [2, 49]", p.min_taps);
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode == RAYZ_TEMPORAL_CLIP_VARIANCE && tm->feedback)
+        return fail(RAYZ_ERR_STATE, "temporal set_clip: a handle that tracks feedback has no clip mode (its raw first moment has no clip rule)");
+    if (mode == RAYZ_TEMPORAL_CLIP_VARIANCE && tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
+        return fail(RAYZ_ERR_STATE, "temporal set_clip: a handle in cubic resampling mode has no clip mode (rayz_hip_temporal_set_resampling back to bilinear first)");
+    tm->clip = mode, tm->clip_params = p, tm->clipped = d_clipped;
+    return RAYZ_OK;
+}
+
+int temporal_get_clip(RayzTemporal* tm, uint32_t* mode, RayzTemporalClipParams* params) {
+    RAYZ_TRY(frame_handle_check(tm));
+    if (mode) *mode = tm->clip;
+    if (params) *params = tm->clip_params;
     return RAYZ_OK;
 }
 
@@ -302,6 +357,14 @@ int rayz_hip_temporal_set_background(RayzTemporal* tm, uint32_t mode) {
 
 int rayz_hip_temporal_get_background(RayzTemporal* tm, uint32_t* mode) {
     return guarded([&] { return temporal_get_background(tm, mode); });
+}
+
+int rayz_hip_temporal_set_clip(RayzTemporal* tm, uint32_t mode, const RayzTemporalClipParams* params_or_null, uint8_t* d_clipped_or_null) {
+    return guarded([&] { return temporal_set_clip(tm, mode, params_or_null, d_clipped_or_null); });
+}
+
+int rayz_hip_temporal_get_clip(RayzTemporal* tm, uint32_t* mode, RayzTemporalClipParams* params_or_null) {
+    return guarded([&] { return temporal_get_clip(tm, mode, params_or_null); });
 }
 
 int rayz_hip_temporal_reset(RayzTemporal* tm) {

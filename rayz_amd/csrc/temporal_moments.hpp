@@ -1,8 +1,8 @@
 // temporal_moments.hpp — the moments mode of temporal accumulation's handle (rayz_hip_temporal_track_moments, _step_moments;
 // DESIGN.md §4.16; the kernel: temporal_moments_kernel.hpp; the handle and what both kinds of step share — temporal_run_step, the
 // step's procedure —: temporal.hpp; the launch: temporal_kernel.hpp), its feedback mode (rayz_hip_temporal_track_feedback,
-// _feedback; §4.17; temporal_feedback_kernel.hpp) and the choice of a moments step's kernel, temporal_launch_moments (the counts
-// and background kernels: temporal_modes_kernel.hpp; the cubic one: temporal_cubic_kernel.hpp).
+// _feedback; §4.17; temporal_feedback_kernel.hpp) and the choice of a moments step's kernel, temporal_launch_moments (the counts,
+// background and clip kernels: temporal_modes_kernel.hpp; the cubic one: temporal_cubic_kernel.hpp).
 // Included by rayz_hip.hip after temporal.hpp.
 #pragma once
 
@@ -33,6 +33,8 @@ int temporal_track_feedback(RayzTemporal* tm) {
     if (!tm->moments) return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is not in moments mode (rayz_hip_temporal_track_moments first)");
     if (tm->resampling == RAYZ_TEMPORAL_RESAMPLE_CUBIC)
         return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is in cubic resampling mode (rayz_hip_temporal_set_resampling back to bilinear first)");
+    if (tm->clip == RAYZ_TEMPORAL_CLIP_VARIANCE)
+        return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle is in variance clip mode (rayz_hip_temporal_set_clip back to off first)");
     if (tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE)
         return fail(RAYZ_ERR_STATE, "temporal track_feedback: the handle accumulates the background (rayz_hip_temporal_set_background back to input first)");
     if (tm->has_history)
@@ -64,7 +66,12 @@ void temporal_launch_moments(hipStream_t st, const RayzTemporal* tm, const RayzC
                              const uint32_t* d_counts) {
     const uint32_t w = a.t.width, h = a.t.height;
     const bool bg = tm->background == RAYZ_TEMPORAL_BACKGROUND_ACCUMULATE;
-    if (bg || d_counts) {
+    if (temporal_clips(tm, is_static)) { // (§4.28: the moving step only; neither a counts, a cubic nor a feedback step)
+        TemporalMomentsClipArgs c{{a, {}, nullptr}, temporal_clip_args(tm)};
+        if (bg) temporal_background_args(tm, cam, is_static, c.m.G);
+        hipLaunchKernelGGL(bg ? rayz_dev_clip::clip_moments_kernel<true> : rayz_dev_clip::clip_moments_kernel<false>, denoise_grid(w, h), dim3(256),
+                           0, st, c);
+    } else if (bg || d_counts) {
         TemporalMomentsModeArgs m{a, {}, d_counts};
         if (bg) temporal_background_args(tm, cam, is_static, m.G);
         void (*still)(TemporalMomentsModeArgs) = rayz_dev_counts::temporal_counts_moments_kernel<true>;

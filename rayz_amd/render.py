@@ -1057,12 +1057,15 @@ class Temporal(_Handle):
     steps fetch the colour history with the 4x4 Catmull-Rom kernel where all sixteen history pixels are the same surface, and
     bilinearly elsewhere (`set_resampling`, §4.26); the default "bilinear" is §4.15 as it is.  `background` "accumulate": pixels
     whose centre ray misses the scene gather history too, reprojected by the view's turn alone (`set_background`, §4.27); the
-    default "input" passes them through."""
+    default "input" passes them through.  `clip` "variance": a moving step clamps the history's colour to mean ± `clip_gamma` sample
+    deviations of the current frame's 7x7 neighbourhood on the same surface before it blends (`set_clip`, §4.28; `clip_gamma` and
+    `clip_min_taps` None: capi.TEMPORAL_CLIP_DEFAULTS); the default "off" compares no colours."""
 
     _destroy = "rayz_hip_temporal_destroy"  # (waits for the handle's last step)
 
     def __init__(self, width: int, height: int, device: int | None = None, moments: bool = False, feedback: bool = False,
-                 resampling: str = "bilinear", background: str = "input"):
+                 resampling: str = "bilinear", background: str = "input", clip: str = "off", clip_gamma: float | None = None,
+                 clip_min_taps: float | None = None):
         self._lib = capi.load()
         self._h = C.c_void_p()
         self.width, self.height = int(width), int(height)
@@ -1071,6 +1074,8 @@ class Temporal(_Handle):
         self._device = device if device is not None else _default_device
         self._inflight = None  # the tensors of the last step: kept alive until the next step or close() (the kernel may still use them)
         self._taken = None  # the uint8 (height, width) tensor the library writes at every step (set_resampling), or None
+        self._clipped = None  # .. and the one of set_clip
+        self._clip_mode = "off"  # what set_clip last set: what `_counts` looks at (the library refuses such a step itself)
         if feedback and not moments:
             self.close()
             raise ValueError("feedback=True needs moments=True: only a moments handle tracks feedback")
@@ -1091,6 +1096,10 @@ class Temporal(_Handle):
                 self.set_resampling(resampling)
             if background != "input":
                 self.set_background(background)
+            if clip not in capi.TEMPORAL_CLIP:
+                raise ValueError(f"clip must be one of {sorted(capi.TEMPORAL_CLIP)}, got {clip!r}")
+            if clip != "off" or clip_gamma is not None or clip_min_taps is not None:
+                self.set_clip(clip, clip_gamma, clip_min_taps)
         except Exception:
             self.close()
             raise
@@ -1153,6 +1162,57 @@ class Temporal(_Handle):
         capi.check(self._lib, self._lib.rayz_hip_temporal_get_background(self._h, C.byref(mode)), "rayz_hip_temporal_get_background")
         return {v: k for k, v in capi.TEMPORAL_BACKGROUND.items()}[mode.value]
 
+    def set_clip(self, clip: str, gamma: float | None = None, min_taps: float | None = None, clipped=False) -> None:
+        """Whether moving steps clip the colour history from now on (`rayz_hip_temporal_set_clip`): "off", or
+        "variance" — a pixel that found history clamps its history's colour, per channel, to mean ± `gamma` sample deviations of
+        the current frame over its 7x7 neighbourhood on the same surface (for a background pixel of an "accumulate" handle: over
+        the neighbourhood's misses), where that has at least `min_taps` pixels; a moments handle moves the second moment with it.
+        Static steps, first frames and pixels without history are unchanged.  `gamma` >= 0 (inf never clips) and `min_taps` in
+        [2, 49]; None: capi.TEMPORAL_CLIP_DEFAULTS.  May be changed between any two steps.  `clipped`: True for a new uint8
+        (height, width) tensor on the handle's device that every later step writes — 1 where the clip changed a channel of the
+        pixel's colour history — or such a tensor (`Temporal.clipped`); False for none.  Limits: a handle that tracks feedback or
+        is in "cubic" resampling mode has no clip mode, and a "variance" handle takes no counts tensor as spp."""
+        import torch
+
+        if clip not in capi.TEMPORAL_CLIP:
+            raise ValueError(f"clip must be one of {sorted(capi.TEMPORAL_CLIP)}, got {clip!r}")
+        prm = capi.TemporalClipParams(capi.TEMPORAL_CLIP_DEFAULTS["gamma"] if gamma is None else float(gamma),
+                                      capi.TEMPORAL_CLIP_DEFAULTS["min_taps"] if min_taps is None else float(min_taps))
+        if clipped is True:
+            clipped = torch.empty((self.height, self.width), dtype=torch.uint8, device=torch.device("cuda", self._device))
+        elif clipped is False or clipped is None:
+            clipped = None
+        else:
+            _check_tensor("clipped", clipped, torch.uint8, (self.height, self.width), self._device, "the temporal handle")
+        capi.check(self._lib, self._lib.rayz_hip_temporal_set_clip(self._h, capi.TEMPORAL_CLIP[clip], C.byref(prm),
+                                                                   C.c_void_p(clipped.data_ptr() if clipped is not None else None)),
+                   "rayz_hip_temporal_set_clip")
+        self._clip_mode = clip
+        self._clipped = clipped  # (every later step writes it and keeps it in _inflight, as the taken bytes)
+
+    def _get_clip(self):
+        mode, prm = C.c_uint32(), capi.TemporalClipParams()
+        capi.check(self._lib, self._lib.rayz_hip_temporal_get_clip(self._h, C.byref(mode), C.byref(prm)), "rayz_hip_temporal_get_clip")
+        return mode.value, prm
+
+    @property
+    def clip(self) -> str:
+        """"off" or "variance": the handle's clip mode (`rayz_hip_temporal_get_clip`)."""
+        mode, _ = self._get_clip()
+        return next(k for k, v in capi.TEMPORAL_CLIP.items() if v == mode)
+
+    @property
+    def clip_params(self) -> dict:
+        """{"gamma": .., "min_taps": ..}: the clip's parameters as the handle holds them (`rayz_hip_temporal_get_clip`)."""
+        _, prm = self._get_clip()
+        return {"gamma": prm.gamma, "min_taps": prm.min_taps}
+
+    @property
+    def clipped(self):
+        """The uint8 (height, width) tensor `set_clip(..., clipped=...)` named, holding the last step's bytes once that step has
+        finished: 1 where the clip changed a channel of the pixel's colour history.  None: no such tensor."""
+        return self._clipped
+
     @property
     def taken(self):
         """The uint8 (height, width) tensor `set_resampling(..., taken=...)` named, holding the last step's bytes once that step has
@@ -1203,6 +1263,8 @@ class Temporal(_Handle):
             return None
         if self.resampling == "cubic":
             raise ValueError('a handle in "cubic" resampling mode takes no counts tensor as spp (set_resampling("bilinear") first)')
+        if self._clip_mode == "variance":
+            raise ValueError('a handle in "variance" clip mode takes no counts tensor as spp (set_clip("off") first)')
         _check_tensor("spp", spp, torch.int32, (self.height, self.width), self._device, "the temporal handle")
         if int(spp.min()) < 0:
             raise ValueError("spp holds a negative sample count")
@@ -1230,7 +1292,7 @@ class Temporal(_Handle):
                                       C.c_void_p(var_out.data_ptr()), C.c_void_p(length.data_ptr() if length is not None else None),
                                       C.c_void_p(stream or None))
         capi.check(self._lib, rc, name)
-        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length, counts, self._taken)  # (the step writes the taken bytes too)
+        self._inflight = (rgb, var_rgb, gbuffer, out, var_out, length, counts, self._taken, self._clipped)  # (the step writes the taken and clipped bytes too)
         return (out, var_out) if length is None else (out, var_out, length)
 
     def step_moments(self, rgb, gbuffer: "QueryResult", camera: capi.CameraDesc, spp, out=None, var_out=None, length=False,
@@ -1266,7 +1328,7 @@ class Temporal(_Handle):
                                       C.c_void_p(length.data_ptr() if length is not None else None),
                                       C.c_void_p(w2.data_ptr() if w2 is not None else None), C.c_void_p(stream or None))
         capi.check(self._lib, rc, name)
-        self._inflight = (rgb, gbuffer, out, var_out, length, w2, counts, self._taken)
+        self._inflight = (rgb, gbuffer, out, var_out, length, w2, counts, self._taken, self._clipped)
         return (out, var_out) + tuple(t for t in (length, w2) if t is not None)
 
     def reset(self) -> None:

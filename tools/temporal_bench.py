@@ -82,7 +82,20 @@ alternating in one process on the same frames; the input mode runs the kernels i
     the hit pixels' parts of it — and the share of background pixels that found history with their mean history length.
     --motion, --pan and --config as for --cubic.
 
-    python tools/temporal_bench.py --background [--config 3] [--motion pan|orbit] [--pan 2.5] [--cost-only] [the switches above]"""
+    python tools/temporal_bench.py --background [--config 3] [--motion pan|orbit] [--pan 2.5] [--cost-only] [the switches above]
+
+--clip measures the clip mode (rayz_hip_temporal_set_clip) beside the OFF mode, the two alternating in one
+process on the same frames; the OFF mode runs the kernels it always ran and is the yardstick.
+(a) Cost.  The MOVED step (the only one the mode changes) of a plain and of a moments handle, with the background passed through
+    and accumulated, OFF against VARIANCE at the defaults with the clipped bytes written, by the handles' own HIP events, each
+    beside a device copy of the step's compulsory bytes (204 / 208 B per pixel; + 1 with the map), the ratio variance / off, and
+    beside them the moments step's FIRST frame, which stages its tile in every workgroup too.
+(b) Quality.  Per frame, MSE against the --ref-spp frame of the moments step alone and of the step + `run_guided`, on one-chunk
+    frames, OFF against VARIANCE with gamma 0.5, 1, 2 and +inf (which must equal OFF), in both background modes — over the whole
+    frame, and split into the background pixels' and the hit pixels' parts of it — and the share of pixels clipped.
+    --motion, --pan and --config as for --cubic.
+
+    python tools/temporal_bench.py --clip [--config 3] [--motion pan|orbit] [--pan 2.5] [--cost-only] [the switches above]"""
 import argparse
 import json
 import os
@@ -807,6 +820,150 @@ def main_background(args):
             json.dump(res, f, indent=1)
 
 
+CLIP_GAMMAS = (0.5, 1.0, 2.0, float("inf"))
+
+
+def main_clip(args):
+    """--clip: see the module docstring."""
+    render.init(0)
+    t = tracer.randomBouncing(args.width, seed=42) if args.config == 2 else tracer.randomBouncing(args.width, -50, 50, seed=42)
+    t.samples_per_px, t.max_bounces = args.spp, 50
+    t.set_gpu(render_seed=1, traversal=capi.TRAVERSAL_BVH, chunk_spp=0)
+    sd, cam, p = t.scene_desc(), t.camera_desc(), t.params()
+    p.tmin = 1e-3
+    w, h = p.width, p.height
+    n = w * h
+    assert args.spp <= 16, "--clip wants an spp of at most 16: one automatic chunk"
+    ds = render.DeviceScene(sd)
+    move = (lambda k: orbited(cam, args.pan * k, w, h)) if args.motion == "orbit" else (lambda k: panned(cam, args.pan * k))
+    res = {"mode": "clip", "config": args.config, "motion": args.motion, "size": f"{w}x{h}", "frames": args.frames,
+           "px_per_frame": args.pan, "spp": args.spp, "ref_spp": args.ref_spp, "reps": args.reps}
+    seq = []
+    for k in range(args.frames if not args.cost_only else 2):
+        c = move(k)
+        q = capi.RenderParams.from_buffer_copy(p)
+        q.seed, q.chunk_spp = 1000 + k, 0
+        one = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        ds.render_into(c, q, one.data_ptr())
+        ds.sync()
+        g = ds.gbuffer(c, p)
+        ds.query_sync()
+        ref = None
+        if not args.cost_only:
+            q.samples_per_px, q.seed = args.ref_spp, 7
+            ref = torch.empty_like(one)
+            torch.cuda.synchronize()
+            ds.render_into(c, q, ref.data_ptr())
+            ds.sync()
+        seq.append((c, one, g, ref))
+        print(f"frame {k}: {args.spp} spp in one chunk, background {float((g.index < 0).float().mean()):.4f} of the pixels"
+              + ("" if ref is None else f", reference {args.ref_spp} spp"), flush=True)
+    var = torch.full((h, w, 3), 1e-3, dtype=torch.float32, device="cuda")  # (the plain step's cost does not depend on the variance's values)
+    out, vout = torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+    clipped = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+
+    # ---- (a) cost: the moved step, OFF and VARIANCE alternating; and the moments step's first frame ------------------------------
+    res["cost"] = {}
+    clips = ("off", "variance")
+    handles = {(kind, bg, clip): render.Temporal(w, h, moments=kind == "moments", background=bg)
+               for kind in ("plain", "moments") for bg in ("input", "accumulate") for clip in clips}
+    for (kind, bg, clip), tm in handles.items():
+        tm.set_clip(clip, clipped=clipped if clip == "variance" else False)
+
+    def steps(kind, tm, frames):
+        tm.reset()
+        for c, one, g, _ in frames:
+            if kind == "plain":
+                tm.step(one, var, g, c, args.spp, out=out, var_out=vout)
+            else:
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout)
+
+    ms = {k: [] for k in handles}
+    first = []
+    for r in range(args.warmup + args.reps):
+        for (kind, bg, clip), tm in handles.items():
+            steps(kind, tm, seq[:2])
+            x = tm.timing()
+            if r >= args.warmup:
+                ms[(kind, bg, clip)].append(x)
+        tm = handles[("moments", "input", "off")]
+        steps("moments", tm, seq[:1])
+        x = tm.timing()
+        if r >= args.warmup:
+            first.append(x)
+    for kind, nbytes in (("plain", STEP_BYTES), ("moments", MOMENTS_STEP_BYTES)):
+        for bg in ("input", "accumulate"):
+            med = {clip: statistics.median(ms[(kind, bg, clip)]) for clip in clips}
+            for clip in clips:
+                per_pixel = nbytes + (1 if clip == "variance" else 0)  # (the variance handles here write the clipped bytes)
+                cp = copy_ms(n * per_pixel // 2, args.reps, args.warmup)
+                v = ms[(kind, bg, clip)]
+                share = None
+                if clip == "variance":
+                    steps(kind, handles[(kind, bg, clip)], seq[:2])
+                    torch.cuda.synchronize()
+                    share = float(clipped.float().mean())
+                res["cost"][f"{kind} {bg} {clip}"] = {"ms": med[clip], "min": min(v), "max": max(v), "bytes_per_pixel": per_pixel, "copy_ms": cp[0],
+                                                      "copy_min": cp[1], "copy_max": cp[2], "ratio_to_copy": med[clip] / cp[0],
+                                                      "ratio_to_off": med[clip] / med["off"], "clipped_share": share}
+                print(f"{kind:7s} moved step, background {bg:10s}, clip {clip:8s}: {med[clip]:.4f} ms [{min(v):.4f}, {max(v):.4f}] = "
+                      f"{med[clip] / cp[0]:.2f} x the copy of its {per_pixel} B per pixel ({cp[0]:.4f} ms [{cp[1]:.4f}, {cp[2]:.4f}]), "
+                      f"{med[clip] / med['off']:.3f} x the off mode" + ("" if share is None else f"; {share:.4f} of the pixels clipped"), flush=True)
+    cp = copy_ms(n * MOMENTS_STEP_BYTES // 2, args.reps, args.warmup)
+    fm = statistics.median(first)
+    res["cost"]["moments first frame"] = {"ms": fm, "min": min(first), "max": max(first), "copy_ms": cp[0], "ratio_to_copy": fm / cp[0]}
+    print(f"moments FIRST frame (stages in every workgroup): {fm:.4f} ms [{min(first):.4f}, {max(first):.4f}] = {fm / cp[0]:.2f} x the copy of its "
+          f"{MOMENTS_STEP_BYTES} B per pixel ({cp[0]:.4f} ms)", flush=True)
+    for tm in handles.values():
+        tm.close()
+
+    # ---- (b) quality: moments handles on the one-chunk frames ---------------------------------------------------------------------
+    if not args.cost_only:
+        dn = render.Denoiser(w, h)
+        den = torch.empty_like(out)
+        res["rows"] = []
+        names = ["off"] + [f"g{g_}" for g_ in CLIP_GAMMAS]
+        tms = {}
+        for bg in ("input", "accumulate"):
+            tms[(bg, "off")] = render.Temporal(w, h, moments=True, background=bg)
+            for g_ in CLIP_GAMMAS:
+                tms[(bg, f"g{g_}")] = render.Temporal(w, h, moments=True, background=bg, clip="variance", clip_gamma=g_)
+                tms[(bg, f"g{g_}")].set_clip("variance", g_, clipped=clipped)
+        for k, (c, one, g, ref) in enumerate(seq):
+            bgm = g.index < 0
+
+            def mse2(a):
+                err = ((a.double() - ref.double()) ** 2).mean(dim=2)
+                return [float(err.mean()), float(err[bgm].mean()) if bool(bgm.any()) else 0.0, float(err[~bgm].mean())]
+
+            row = {"frame": k, "raw": mse2(one), "share_background": float(bgm.float().mean())}
+            for (bg, name), tm in tms.items():
+                tm.step_moments(one, g, c, args.spp, out=out, var_out=vout)
+                dn.run_guided(out, vout, g, out=den)
+                torch.cuda.synchronize()
+                row[f"temporal_{bg}_{name}"], row[f"temporal_guided_{bg}_{name}"] = mse2(out), mse2(den)
+                if name != "off":
+                    row[f"clipped_{bg}_{name}"] = float(clipped.float().mean())
+            res["rows"].append(row)
+            whole = row["raw"][0]  # every figure as a share of the WHOLE frame's raw MSE, as --background prints them
+            sb = row["share_background"]
+            part = lambda key: "/".join(f"{x:.4f}" for x in (row[key][0] / whole, row[key][1] * sb / whole, row[key][2] * (1 - sb) / whole))  # noqa: E731
+            for bg in ("input", "accumulate"):
+                print(f"frame {k:2d} {bg:10s}: MSE / raw of the frame (all/background's part/hit pixels' part): "
+                      + "; ".join(f"{name} {part(f'temporal_{bg}_{name}')} +guided {part(f'temporal_guided_{bg}_{name}')}"
+                                  + ("" if name == "off" else f" clipped {row[f'clipped_{bg}_{name}']:.4f}") for name in names), flush=True)
+        print(f"raw MSE of the last frame (all | background | hit): {row['raw']}; background share {row['share_background']:.4f}", flush=True)
+        for tm in tms.values():
+            tm.close()
+        dn.close()
+    ds.close()
+    print(json.dumps(res), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=16)
@@ -824,7 +981,8 @@ def main():
     ap.add_argument("--counts", action="store_true", help="measure the counts step (DESIGN.md §4.23) beside the scalar steps")
     ap.add_argument("--cubic", action="store_true", help="measure the cubic resampling mode (DESIGN.md §4.26) beside the bilinear one")
     ap.add_argument("--background", action="store_true", help="measure the background mode (DESIGN.md §4.27) beside the input mode")
-    ap.add_argument("--cost-only", action="store_true", help="--cubic, --background: the cost part alone (two frames, no references)")
+    ap.add_argument("--clip", action="store_true", help="measure the clip mode (DESIGN.md §4.28) beside the off mode")
+    ap.add_argument("--cost-only", action="store_true", help="--cubic, --background, --clip: the cost part alone (two frames, no references)")
     ap.add_argument("--config", type=int, default=3, choices=(2, 3), help="--cubic: BASELINE config 2 (grid [-11, 11)) or 3 (grid [-50, 50))")
     ap.add_argument("--motion", default="pan", choices=("pan", "orbit"),
                     help="--cubic: pan (px_origin moved along px_du by --pan pixels per frame) or orbit (look_from turned about the focus point by --pan "
@@ -832,6 +990,8 @@ def main():
     ap.add_argument("--lib-label", default=None, help="--cubic: what to call --lib's build in the output")
     ap.add_argument("--lib", default=None, help="--cubic: load this build of librayz_hip.so (an older one: its bilinear step alone is timed)")
     args = ap.parse_args()
+    if args.clip:
+        return main_clip(args)
     if args.background:
         return main_background(args)
     if args.cubic:
